@@ -6,10 +6,14 @@ at sample_root^2 spp into HBM, then (N>1) one RCCL all_gather assembles the fram
 fixed as N grows ("strong" scaling: the image is tiled across the GPUs, as the north star states).
 Sample tables and the scene are resident in HBM before the timed region (they are the inputs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--root 128] [--scene demo2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--root 128] [--scene demo2] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  A plain run sets up, warms up, times the K
+steps and prints the headline (value, ms_per_step, step breakdown, launch configuration).  `--full` adds everything else
+the line used to carry: the second context (ctx_create_*, reference_equivalent_*, vs_baseline), the frame's copy to the
+host, a measured HBM copy, the statistics pass and the roofline, and at N = 1 the RCCL and C-ABI probes and the CPU
+baselines.  `--dump-outputs DIR` writes the frame of the last timed step to DIR/frame.npy ([H][W][3] float64).
 """
 import argparse
 import json
@@ -66,12 +70,20 @@ def parse():
                     help="ONE process driving --gpus N devices through the C ABI's multi-GPU entry (flux_multi_*: per-device contexts, one "
                          "launch per device, ncclAllGather from RCCL's C API) instead of N torch.distributed ranks: what a compiled "
                          "embedder (the reference's Rust host, the C++ `flux --split sets`) runs.  Prints the same kind of line.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: context creation and the reference-equivalent span, the "
+                         "frame's copy to the host, a device copy's bandwidth, the statistics pass and roofline, and at N = 1 the "
+                         "RCCL / C-ABI probes and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame the timed path returned in its last step to DIR/frame.npy ([H][W][3] float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-rccl-probe", action="store_true",
-                    help="skip the world-size-1 RCCL child after the timed region (profiling passes: a second GPU process under "
-                         "the rocprofv3 preload would put its kernels into the counter files)")
-    ap.add_argument("--cpu-root", type=int, default=None, help="sample_root of the bounded CPU-baseline sample")
+                    help="with --full: skip the world-size-1 RCCL child after the timed region (profiling passes: a second GPU "
+                         "process under the rocprofv3 preload would put its kernels into the counter files)")
+    ap.add_argument("--cpu-root", type=int, default=None, help="with --full: sample_root of the bounded CPU-baseline sample")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     scene, root = CONFIGS[a.config if a.config is not None else 4]
     a.scene = a.scene or scene
     a.root = a.root or root
@@ -148,6 +160,14 @@ def load_profile(scene_label, kernel_name):
             d["file"] = os.path.basename(path)
             return d
     return None
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: what a caller of the timed path receives, the assembled frame of the last timed step ([H][W][3] f64,
+    11.5 MB at 800x600).  The inputs are fixed by the arguments (scene, spp, depth, seed), so two builds compare pixel for pixel."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float64))
 
 
 def rccl_probe(frame_bytes):
@@ -317,7 +337,11 @@ def abi_multi_main(a):
             m.render_frame_device()
             spans.append(m.timing())
         elapsed = time.perf_counter() - t0
+        # the timed steps leave their frame on device 0; this call renders the same inputs once more into host memory (the
+        # frame is deterministic: repeated frames are bit-equal, checked by the multi_abi probe and tests/test_gpu_multi.py)
         frame = m.render_frame()
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, frame)
         info = m.info()
         plan = m.rank_renderer(0).launch_plan(num_sets=len(range(0, W, a.gpus))) if info["shard"] == flux_amd.SHARD_SETS else \
             m.rank_renderer(0).launch_plan(num_rows=len(range(0, H, a.gpus)))
@@ -362,6 +386,13 @@ def main():
         if rank == 0:
             print(f"bench.py: --gpus {a.gpus} but launched with WORLD_SIZE {world}; using {world}", file=sys.stderr)
         a.gpus = world
+    # RCCL prints a version banner to STDOUT when a rank's communicator comes up; stdout carries the ONE JSON line, so in a
+    # multi-rank run file descriptor 1 points at stderr and the line goes to a copy of the original stdout
+    line_out = sys.stdout
+    if world > 1:
+        sys.stdout.flush()
+        line_out = os.fdopen(os.dup(1), "w")
+        os.dup2(2, 1)
 
     import torch
     import torch.distributed as dist
@@ -414,16 +445,19 @@ def main():
     torch.cuda.synchronize()
     t_create_cold = time.perf_counter() - t0
     create_cold = r.create_timing()
-    # ... and a SECOND, identical context beside it: what Scene::from_data + Camera::new (workers.rs:46-54) cost a running worker,
-    # i.e. what the reference's timer (manager.rs:145 -> 170) spans for every job.  Created, timed, destroyed.
-    t0 = time.perf_counter()
-    r2 = flux_amd.Renderer(sd, cfg, seed=a.seed, device=local_rank, set_share=share)
-    torch.cuda.synchronize()
-    t_create = time.perf_counter() - t0
-    create_warm = r2.create_timing()
-    r2.close()
-    del r2
-    phase(rank, world, f"ctx created ({t_create_cold * 1e3:.0f} ms the process's first, {t_create * 1e3:.1f} ms a second one)")
+    # ... and (--full) a SECOND, identical context beside it: what Scene::from_data + Camera::new (workers.rs:46-54) cost a running
+    # worker, i.e. what the reference's timer (manager.rs:145 -> 170) spans for every job.  Created, timed, destroyed.
+    if a.full:
+        t0 = time.perf_counter()
+        r2 = flux_amd.Renderer(sd, cfg, seed=a.seed, device=local_rank, set_share=share)
+        torch.cuda.synchronize()
+        t_create = time.perf_counter() - t0
+        create_warm = r2.create_timing()
+        r2.close()
+        del r2
+        phase(rank, world, f"ctx created ({t_create_cold * 1e3:.0f} ms the process's first, {t_create * 1e3:.1f} ms a second one)")
+    else:
+        phase(rank, world, f"ctx created ({t_create_cold * 1e3:.0f} ms)")
     r.set_kernel(a.kernel)
     r.set_math(flux_amd.MATH_FAST if a.math == "fast" else flux_amd.MATH_STRICT)
     if use_sets:
@@ -480,16 +514,20 @@ def main():
               for j, name in ((1, "render"), (2, "all_gather"), (3, "reassembly"), (4, "launch_overhead_ms"))}
 
     # the frame's way to the host (the reference-equivalent span ends with the image in host memory, manager.rs:316-324): one
-    # device-to-host copy of the assembled frame into pageable memory, timed on rank 0 (untimed extra)
-    t0 = time.perf_counter()
-    frame_host = frame.cpu()
-    t_d2h = time.perf_counter() - t0
-    del frame_host
+    # device-to-host copy of the assembled frame into pageable memory, timed on rank 0 (untimed extra, --full); it is also the
+    # copy --dump-outputs writes
+    if a.full or (a.dump_outputs and rank == 0):
+        t0 = time.perf_counter()
+        frame_host = frame.cpu()
+        t_d2h = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, frame_host.numpy())
+        del frame_host
 
     # what HBM delivers on THIS device ("report against both" the 8 TB/s spec and a measured copy): a 1 GiB
-    # device-to-device copy, read + write bytes, best of 5 (untimed extra)
+    # device-to-device copy, read + write bytes, best of 5 (untimed extra, --full)
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and a.full:
         src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -504,20 +542,21 @@ def main():
         copy_gbs = 2.0 * src.numel() * 4 / (best * 1e-3) / 1e9
         del src, dst
 
-    # exact path statistics of THIS rank's share (untimed extra pass) -> algorithmic bytes
-    r.enable_stats(True)
-    r.stats(reset=True)
-    sh.render(fn)
-    torch.cuda.synchronize()
-    st = r.stats(reset=True)
-    r.enable_stats(False)
-    phase(rank, world, "statistics pass done")
-    stt = torch.tensor([st["samples"], st["matte_bounces"], st["segments"], st["glossy_bounces"], st["bvh_nodes"],
-                        st["tris_tested"], st["misses"]], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(stt, op=dist.ReduceOp.SUM)
-    tot_samples, tot_matte, tot_segments, tot_glossy, tot_nodes, tot_tris, tot_miss = [float(x) for x in stt]
-    bvh = r.bvh_info()
+    # exact path statistics of THIS rank's share (untimed extra pass, --full) -> algorithmic bytes
+    if a.full:
+        r.enable_stats(True)
+        r.stats(reset=True)
+        sh.render(fn)
+        torch.cuda.synchronize()
+        st = r.stats(reset=True)
+        r.enable_stats(False)
+        phase(rank, world, "statistics pass done")
+        stt = torch.tensor([st["samples"], st["matte_bounces"], st["segments"], st["glossy_bounces"], st["bvh_nodes"],
+                            st["tris_tested"], st["misses"]], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(stt, op=dist.ReduceOp.SUM)
+        tot_samples, tot_matte, tot_segments, tot_glossy, tot_nodes, tot_tris, tot_miss = [float(x) for x in stt]
+        bvh = r.bvh_info()
     # the kernel the timed call launched: asked of the library's launch planner for exactly that call (never re-derived here)
     plan = r.launch_plan(num_sets=sh.count) if use_sets else r.launch_plan(num_rows=sh.count)
     kernel_name = {flux_amd._lib.PLAN_STATIC: "render_static_kernel", flux_amd._lib.PLAN_REFILL: "render_refill_kernel",
@@ -526,56 +565,8 @@ def main():
 
     if rank == 0:
         samples = W * H * n * n
-        assert int(tot_samples) == samples, (tot_samples, samples)
         finite = bool(torch.isfinite(frame).all())
-        mbar = tot_matte / tot_samples
-        gbar = tot_glossy / tot_samples
-        # pixel 16 B + lens 16 B + 24 B per Matte bounce, plus (triangle scenes) the BVH nodes visited
-        # and triangles tested at their laid-out sizes (64 B / 128 B).  (As laid out here a glossy bounce also reads 24 B
-        # of tabulated lobe factors: reported beside it, not counted in `achieved`.)
-        table_bytes = 32.0 + 24.0 * mbar
-        # as laid out for the kernel that ran: 64-B 4-wide nodes and 128-B leaf records holding one or two triangles (counted
-        # per triangle test at 64 B when the record is a quad's) for render_bvh4_kernel; 32-B nodes (two 16-B gathers of a
-        # DevNodeQ) + 80 B of a DevTri for the binary-tree kernel; the inline walk of the other kernels reads DevNode / DevTri
-        if plan["kernel"] == flux_amd._lib.PLAN_BVH4:
-            tri_b = bvh["leaf_record_bytes"] * bvh["leaf_records"] / max(bvh["triangles"], 1)
-            bvh_bytes = (tot_nodes * bvh["wide_node_bytes"] + tot_tris * tri_b) / tot_samples
-        else:
-            bvh_bytes = (tot_nodes * bvh["node_bytes"] + tot_tris * bvh["tri_bytes"]) / tot_samples
-        bytes_per_sample = table_bytes + bvh_bytes
-        # the dominant kernel's launch on rank 0 covers samples/world camera paths + its share of the framebuffer
-        samples_launch = samples / world
-        alg_bytes_launch = samples_launch * bytes_per_sample + (H * W / world) * 24.0
-        alg_gbs = alg_bytes_launch / (kernel_ms_max * 1e-3) / 1e9
         workload = f"{scene_label} {W}x{H} at {n * n} spp (sample_root {n}), depth {a.depth}, seed {a.seed}"
-        prof = load_profile(scene_label, kernel_name)
-        # counters of the committed rocprofv3 PMC passes of this scene + kernel, carried per sample (NOT measured in this
-        # run: `from_committed_profile`)
-        scale = samples_launch / prof["samples_per_launch"] if prof else None
-        l2_miss = None
-        if prof:
-            l2_miss = prof.get("l2_miss_bytes_per_launch") or prof.get("hbm_bytes_per_launch")  # (the key's name before round 3)
-        traffic = l2_miss * scale if l2_miss else None
-        traffic_gbs = traffic / (kernel_ms_max * 1e-3) / 1e9 if traffic else None
-        # ONE basis for `achieved` / `frac`: the algorithmic bytes of SURVEY.md 8(d).  Where they exceed what HBM could
-        # deliver (config 5: every node / triangle record a lane reads, served by L1 / L2 / Infinity Cache) no HBM fraction is
-        # claimed: frac is null.  The PMC figure is published beside it for what it is -- the bytes that left the L2s towards
-        # the fabric (FETCH_SIZE x 2 + WRITE_SIZE: one 128-B line per miss, tallied at 64 B, also for divergent 16-B gathers;
-        # Infinity-Cache hits INCLUDED: profiles/r03_gather_calibration.json), an upper bound on HBM bytes.  gfx950 exposes no
-        # DRAM-side counter (profiles/r03_experiments/rocprofv3_counter_names_gfx950.txt), so hbm_bytes is null.
-        if alg_gbs <= HBM_PEAK_GBS:
-            achieved, basis = alg_gbs, "algorithmic bytes (SURVEY.md 8d) / kernel time"
-        else:
-            achieved, basis = None, (f"the algorithmic figure ({alg_gbs:.0f} GB/s) exceeds the HBM peak: the records are served by "
-                                     "L1 / L2 / Infinity Cache, and no counter on gfx950 separates HBM from Infinity-Cache traffic "
-                                     "(l2_miss_traffic_gbs is an upper bound on the HBM rate); no HBM fraction is claimed")
-        valu_insts = prof["valu_insts_per_launch"] * scale if prof and prof.get("valu_insts_per_launch") else None
-        # VALU issue ceiling: 256 CU x 4 SIMD wave-instructions per (mean cycles per instruction of THIS kernel's mix) at the
-        # nominal 2.4 GHz -- 614 G/s at 4 cycles each, 632 G/s for the split kernel's measured mix
-        # ... from the committed profile's own class counters when it has them (scripts/valu_classes.sh + summarize_profile.py), else
-        # the round-5 figures above
-        issue_cycles = (prof or {}).get("issue_cycles_per_inst") or ISSUE_CYCLES_PER_INST.get(kernel_name, 4.1)
-        issue_peak = 256 * 4 * NOMINAL_CLOCK_HZ / issue_cycles
         out = {
             "metric": (f"Msamples/sec on {a.scene}.yml (fixed spp)" if not a.scene.startswith("hf:") else
                        f"Msamples/sec on the procedural {a.scene[3:]} height field in the demo2 set (fixed spp)"),
@@ -587,14 +578,6 @@ def main():
             "ms_per_step": round(elapsed_max / a.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong",
-            "vs_baseline": (round(samples * a.steps / elapsed_max / 1e6 / PUBLISHED_MSAMPLES_S, 1)
-                            if a.scene == "demo2" and n == 128 else None),
-            # the one published run (README.md:1: 1479.9 s on "44 cores") is quoted for 16384 spp, but demo.png carries the per-pixel
-            # variance of a 65536-spp render of this estimator (tests/test_gpu_ref16.py::test_variance_profile):
-            # the published time may belong to a 4x larger job, and vs_baseline would then be 4x too high
-            "published_run_note": ("vs_baseline divides by README.md's 1479.9 s for '16384 spp'; demo.png's variance matches 65536 spp "
-                                   "(test_variance_profile), so that run may have been 4x this job" if a.scene == "demo2" and n == 128
-                                   else None),
             "dtype": "f64",
             "data": "synthetic",
             "config": {"workload": workload, "scene": scene_label, "kernel": kernel_name.replace("render_", "").replace("_kernel", ""),
@@ -613,98 +596,158 @@ def main():
                                   "note": "HIP events on the launch stream, mean over steps; render / all_gather / reassembly at the top "
                                           "level are the max over ranks; launch_overhead_ms = a rank's wall time per step minus its three "
                                           "event spans (host-side launch path, event gaps, the barrier wait for slower ranks)"},
-            "roofline": {"bound": "hbm", "achieved": None if achieved is None else round(achieved, 3), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": None if achieved is None else round(achieved / HBM_PEAK_GBS, 6),
-                         "traffic": traffic, "basis": basis,
-                         "traffic_is": ("L2-miss bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, rocprofv3 PMC, separate passes): they "
-                                        "include Infinity-Cache hits, so this is an UPPER bound on HBM bytes"),
-                         "l2_miss_bytes": traffic, "hbm_bytes": None,
-                         "hbm_bytes_note": "gfx950 / rocprofv3 7.2 expose no DRAM-side counter (TCC_EA0_RDREQ_DRAM counts the same "
-                                           "requests warm and cold: profiles/r03_gather_calibration.json)",
-                         "from_committed_profile": prof is not None,
-                         "from_committed_profile_fields": ["traffic", "l2_miss_bytes", "l2_miss_traffic_gbs", "fp64_issue_frac",
-                                                           "valu_busy_frac", "lanes_active_frac", "useful_valu_frac"],
-                         "measured_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
-                         "frac_of_measured_copy": (None if achieved is None or not copy_gbs else
-                                                   round(achieved / copy_gbs, 6)),
-                         "algorithmic_gbs": round(alg_gbs, 3),
-                         "l2_miss_traffic_gbs": None if traffic_gbs is None else round(traffic_gbs, 3),
-                         "profile": prof["file"] if prof else None,
-                         "kernel": kernel_name,
-                         "kernel_ms": round(kernel_ms_max, 3), "samples_per_launch": samples_launch,
-                         "bytes_per_sample": round(bytes_per_sample, 3),
-                         "bytes_per_sample_as_laid_out": round(bytes_per_sample + 24.0 * gbar, 3),
-                         # what actually bounds the analytic kernels: VALU issue (f64, packed f32, compares, e64 selects: 4+ cycles of
-                         # a SIMD each; plain 32-bit arithmetic and moves 2.4) -- instruction counts from the committed PMC profile
-                         "fp64_issue_frac": (None if valu_insts is None else
-                                             round(valu_insts / (kernel_ms_max * 1e-3) / issue_peak, 4)),
-                         "issue_cycles_per_inst": issue_cycles,
-                         "issue_cycles_from": ("the committed profile's dynamic class counters" if (prof or {}).get("issue_cycles_per_inst")
-                                               else "round 5's class mix (bench.py ISSUE_CYCLES_PER_INST)"),
-                         "valu_classes_per_64_samples": (prof or {}).get("valu_classes_per_64_samples"),
-                         "issue_note": "fp64_issue_frac = VALU instructions/s x mean cycles per instruction of this kernel's class mix "
-                                       "(profiles/r05_valu_issue.json) / (1024 SIMDs x 2.4 GHz; the render kernels run at 2.38 GHz, "
-                                       "scripts/kernel_clock.sh): the fraction of cycles in which the VALU issues.  valu_busy_frac (SQ_ACTIVE_INST_VALU x 4 "
-                                       "/ cycles) charges every plain instruction 4 cycles and overstates by the two-cycle share",
-                         "valu_busy_frac": prof.get("valu_busy_frac") if prof else None,
-                         "lanes_active_frac": prof.get("lanes_active_frac") if prof else None,
-                         "useful_valu_frac": (None if valu_insts is None or bvh["triangles"] or a.scene != "demo2" else
-                                              round(USEFUL_LANE_OPS_PER_SEGMENT * tot_segments / world / (64.0 * valu_insts), 4)),
-                         "matte_bounces_per_sample": round(mbar, 5),
-                         "segments_per_sample": round(tot_segments / tot_samples, 5),
-                         "glossy_bounces_per_sample": round(gbar, 5),
-                         "bvh_nodes_per_sample": round(tot_nodes / tot_samples, 3),
-                         "tris_tested_per_sample": round(tot_tris / tot_samples, 3),
-                         "misses": int(tot_miss),
-                         "note": "FP64 path tracer: analytic shapes live in SGPRs; the sample tables (and, for triangle "
-                                 "scenes, BVH nodes/triangles) are the only streamed data; bytes are the algorithmic figure, "
-                                 "not inflated; with the set-grouped pixel order nearly all table bytes are served by the XCD "
-                                 "L2s (`traffic`: what reached the memory side).  The analytic kernels are VALU-issue bound "
-                                 "(valu_busy_frac); lanes_active_frac = SQ_THREAD_CYCLES_VALU / (64 SQ_ACTIVE_INST_VALU); "
-                                 "useful_valu_frac = model lane-operations (DESIGN.md section 4) / issued lane slots"},
-            # the job as the reference times it (manager.rs:145 -> 170: Scene::from_data + Camera::new incl. MasterSampleSets::new,
-            # workers.rs:46-54, then the render, then the rows in host memory): a running worker's context creation (the SECOND
-            # context of this process) + one frame + the frame's copy to the host.  `_cold_s`: the same with the process's FIRST
-            # context, whose creation also pays the HIP runtime's one-time initialisation.
-            "ctx_create_ms": round(t_create * 1e3, 2),
-            "ctx_create_breakdown_ms": {k: round(v, 3) for k, v in create_warm.items()},
-            "ctx_create_cold_ms": round(t_create_cold * 1e3, 1),
-            "ctx_create_cold_breakdown_ms": {k: round(v, 3) for k, v in create_cold.items()},
-            "ctx_create_note": "flux_ctx_create_timing: host = validation + scene records (+ BVH build), runtime = HIP device initialisation, "
-                               "alloc / upload / tables (MasterSampleSets::new on the device) / free / other; cold = the process's first "
-                               "context (runtime + first-copy / first-launch set-up land in it), ctx_create_ms = a second context",
-            "frame_d2h_ms": round(t_d2h * 1e3, 3),
-            "reference_equivalent_s": round(t_create + elapsed_max / a.steps + t_d2h, 4),
-            "reference_equivalent_cold_s": round(t_create_cold + elapsed_max / a.steps + t_d2h, 4),
             "build_id": (flux_amd._lib.lib.flux_build_id() or b"").decode(),
+            "full": a.full,
         }
-        out["reference_equivalent_msamples_s"] = round(samples / out["reference_equivalent_s"] / 1e6, 1)
-        if out["vs_baseline"] is not None:
-            # the published 1479.9 s spans table construction + render + gather: compared on the same span
-            out["vs_baseline"] = round(samples / out["reference_equivalent_s"] / 1e6 / PUBLISHED_MSAMPLES_S, 1)
-            out["vs_baseline_span"] = ("reference-equivalent (context creation of a running worker + one frame + the frame's copy to "
-                                       "the host) against README.md's 1479.9 s, which spans the same steps; value / 5.314 would be "
-                                       f"{round(samples * a.steps / elapsed_max / 1e6 / PUBLISHED_MSAMPLES_S, 1)}")
-        prof_kernels = (prof or {}).get("build_id", "")
-        out["roofline"]["profile_build_id"] = prof_kernels or None
-        out["roofline"]["profile_head"] = (prof or {}).get("git_head")
-        same = bool(prof_kernels) and prof_kernels.split("kernels:")[-1] == out["build_id"].split("kernels:")[-1]
-        out["roofline"]["profile_matches_build"] = same if prof else None
-        if prof and not same:
-            out["roofline"]["profile_warning"] = ("the committed PMC profile was taken from another build of the kernels: the "
-                                                  "from_committed_profile fields describe THAT binary")
-        if world == 1 and not a.no_rccl_probe:
-            out["rccl_probe"] = rccl_probe(int(sh.local.numel() * 8))
-            out["multi_abi"] = multi_abi_probe(flux_amd, sd, cfg, a, frame)
-        if world == 1 and not a.no_cpu_baseline:
-            if a.scene.startswith("hf:"):
-                # the CPU checker scans every triangle per ray (it DEFINES what the BVH must reproduce): ~5 ms per ray on
-                # a 1M-triangle mesh, so no bounded sample of this workload is meaningful; the headline line carries it
-                out["cpu_baseline"] = None
+        if a.full:
+            assert int(tot_samples) == samples, (tot_samples, samples)
+            mbar = tot_matte / tot_samples
+            gbar = tot_glossy / tot_samples
+            # pixel 16 B + lens 16 B + 24 B per Matte bounce, plus (triangle scenes) the BVH nodes visited
+            # and triangles tested at their laid-out sizes (64 B / 128 B).  (As laid out here a glossy bounce also reads 24 B
+            # of tabulated lobe factors: reported beside it, not counted in `achieved`.)
+            table_bytes = 32.0 + 24.0 * mbar
+            # as laid out for the kernel that ran: 64-B 4-wide nodes and 128-B leaf records holding one or two triangles (counted
+            # per triangle test at 64 B when the record is a quad's) for render_bvh4_kernel; 32-B nodes (two 16-B gathers of a
+            # DevNodeQ) + 80 B of a DevTri for the binary-tree kernel; the inline walk of the other kernels reads DevNode / DevTri
+            if plan["kernel"] == flux_amd._lib.PLAN_BVH4:
+                tri_b = bvh["leaf_record_bytes"] * bvh["leaf_records"] / max(bvh["triangles"], 1)
+                bvh_bytes = (tot_nodes * bvh["wide_node_bytes"] + tot_tris * tri_b) / tot_samples
             else:
-                out["cpu_baseline"] = cpu_baseline(sd, a.depth, a.seed, a.cpu_root)
-                out["cpu_baseline"]["single_thread"] = cpu_single_thread(a.depth, a.seed)
-        print(json.dumps(out), flush=True)
+                bvh_bytes = (tot_nodes * bvh["node_bytes"] + tot_tris * bvh["tri_bytes"]) / tot_samples
+            bytes_per_sample = table_bytes + bvh_bytes
+            # the dominant kernel's launch on rank 0 covers samples/world camera paths + its share of the framebuffer
+            samples_launch = samples / world
+            alg_bytes_launch = samples_launch * bytes_per_sample + (H * W / world) * 24.0
+            alg_gbs = alg_bytes_launch / (kernel_ms_max * 1e-3) / 1e9
+            prof = load_profile(scene_label, kernel_name)
+            # counters of the committed rocprofv3 PMC passes of this scene + kernel, carried per sample (NOT measured in this
+            # run: `from_committed_profile`)
+            scale = samples_launch / prof["samples_per_launch"] if prof else None
+            l2_miss = None
+            if prof:
+                l2_miss = prof.get("l2_miss_bytes_per_launch") or prof.get("hbm_bytes_per_launch")  # (the key's name before round 3)
+            traffic = l2_miss * scale if l2_miss else None
+            traffic_gbs = traffic / (kernel_ms_max * 1e-3) / 1e9 if traffic else None
+            # ONE basis for `achieved` / `frac`: the algorithmic bytes of SURVEY.md 8(d).  Where they exceed what HBM could
+            # deliver (config 5: every node / triangle record a lane reads, served by L1 / L2 / Infinity Cache) no HBM fraction is
+            # claimed: frac is null.  The PMC figure is published beside it for what it is -- the bytes that left the L2s towards
+            # the fabric (FETCH_SIZE x 2 + WRITE_SIZE: one 128-B line per miss, tallied at 64 B, also for divergent 16-B gathers;
+            # Infinity-Cache hits INCLUDED: profiles/r03_gather_calibration.json), an upper bound on HBM bytes.  gfx950 exposes no
+            # DRAM-side counter (profiles/r03_experiments/rocprofv3_counter_names_gfx950.txt), so hbm_bytes is null.
+            if alg_gbs <= HBM_PEAK_GBS:
+                achieved, basis = alg_gbs, "algorithmic bytes (SURVEY.md 8d) / kernel time"
+            else:
+                achieved, basis = None, (f"the algorithmic figure ({alg_gbs:.0f} GB/s) exceeds the HBM peak: the records are served by "
+                                         "L1 / L2 / Infinity Cache, and no counter on gfx950 separates HBM from Infinity-Cache traffic "
+                                         "(l2_miss_traffic_gbs is an upper bound on the HBM rate); no HBM fraction is claimed")
+            valu_insts = prof["valu_insts_per_launch"] * scale if prof and prof.get("valu_insts_per_launch") else None
+            # VALU issue ceiling: 256 CU x 4 SIMD wave-instructions per (mean cycles per instruction of THIS kernel's mix) at the
+            # nominal 2.4 GHz -- 614 G/s at 4 cycles each, 632 G/s for the split kernel's measured mix
+            # ... from the committed profile's own class counters when it has them (scripts/valu_classes.sh + summarize_profile.py), else
+            # the round-5 figures above
+            issue_cycles = (prof or {}).get("issue_cycles_per_inst") or ISSUE_CYCLES_PER_INST.get(kernel_name, 4.1)
+            issue_peak = 256 * 4 * NOMINAL_CLOCK_HZ / issue_cycles
+            out.update({
+                "vs_baseline": (round(samples * a.steps / elapsed_max / 1e6 / PUBLISHED_MSAMPLES_S, 1)
+                                if a.scene == "demo2" and n == 128 else None),
+                # the one published run (README.md:1: 1479.9 s on "44 cores") is quoted for 16384 spp, but demo.png carries the per-pixel
+                # variance of a 65536-spp render of this estimator (tests/test_gpu_ref16.py::test_variance_profile):
+                # the published time may belong to a 4x larger job, and vs_baseline would then be 4x too high
+                "published_run_note": ("vs_baseline divides by README.md's 1479.9 s for '16384 spp'; demo.png's variance matches 65536 spp "
+                                       "(test_variance_profile), so that run may have been 4x this job" if a.scene == "demo2" and n == 128
+                                       else None),
+                "roofline": {"bound": "hbm", "achieved": None if achieved is None else round(achieved, 3), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": None if achieved is None else round(achieved / HBM_PEAK_GBS, 6),
+                             "traffic": traffic, "basis": basis,
+                             "traffic_is": ("L2-miss bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, rocprofv3 PMC, separate passes): they "
+                                            "include Infinity-Cache hits, so this is an UPPER bound on HBM bytes"),
+                             "l2_miss_bytes": traffic, "hbm_bytes": None,
+                             "hbm_bytes_note": "gfx950 / rocprofv3 7.2 expose no DRAM-side counter (TCC_EA0_RDREQ_DRAM counts the same "
+                                               "requests warm and cold: profiles/r03_gather_calibration.json)",
+                             "from_committed_profile": prof is not None,
+                             "from_committed_profile_fields": ["traffic", "l2_miss_bytes", "l2_miss_traffic_gbs", "fp64_issue_frac",
+                                                               "valu_busy_frac", "lanes_active_frac", "useful_valu_frac"],
+                             "measured_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
+                             "frac_of_measured_copy": (None if achieved is None or not copy_gbs else
+                                                       round(achieved / copy_gbs, 6)),
+                             "algorithmic_gbs": round(alg_gbs, 3),
+                             "l2_miss_traffic_gbs": None if traffic_gbs is None else round(traffic_gbs, 3),
+                             "profile": prof["file"] if prof else None,
+                             "kernel": kernel_name,
+                             "kernel_ms": round(kernel_ms_max, 3), "samples_per_launch": samples_launch,
+                             "bytes_per_sample": round(bytes_per_sample, 3),
+                             "bytes_per_sample_as_laid_out": round(bytes_per_sample + 24.0 * gbar, 3),
+                             # what actually bounds the analytic kernels: VALU issue (f64, packed f32, compares, e64 selects: 4+ cycles of
+                             # a SIMD each; plain 32-bit arithmetic and moves 2.4) -- instruction counts from the committed PMC profile
+                             "fp64_issue_frac": (None if valu_insts is None else
+                                                 round(valu_insts / (kernel_ms_max * 1e-3) / issue_peak, 4)),
+                             "issue_cycles_per_inst": issue_cycles,
+                             "issue_cycles_from": ("the committed profile's dynamic class counters" if (prof or {}).get("issue_cycles_per_inst")
+                                                   else "round 5's class mix (bench.py ISSUE_CYCLES_PER_INST)"),
+                             "valu_classes_per_64_samples": (prof or {}).get("valu_classes_per_64_samples"),
+                             "issue_note": "fp64_issue_frac = VALU instructions/s x mean cycles per instruction of this kernel's class mix "
+                                           "(profiles/r05_valu_issue.json) / (1024 SIMDs x 2.4 GHz; the render kernels run at 2.38 GHz, "
+                                           "scripts/kernel_clock.sh): the fraction of cycles in which the VALU issues.  valu_busy_frac (SQ_ACTIVE_INST_VALU x 4 "
+                                           "/ cycles) charges every plain instruction 4 cycles and overstates by the two-cycle share",
+                             "valu_busy_frac": prof.get("valu_busy_frac") if prof else None,
+                             "lanes_active_frac": prof.get("lanes_active_frac") if prof else None,
+                             "useful_valu_frac": (None if valu_insts is None or bvh["triangles"] or a.scene != "demo2" else
+                                                  round(USEFUL_LANE_OPS_PER_SEGMENT * tot_segments / world / (64.0 * valu_insts), 4)),
+                             "matte_bounces_per_sample": round(mbar, 5),
+                             "segments_per_sample": round(tot_segments / tot_samples, 5),
+                             "glossy_bounces_per_sample": round(gbar, 5),
+                             "bvh_nodes_per_sample": round(tot_nodes / tot_samples, 3),
+                             "tris_tested_per_sample": round(tot_tris / tot_samples, 3),
+                             "misses": int(tot_miss),
+                             "note": "FP64 path tracer: analytic shapes live in SGPRs; the sample tables (and, for triangle "
+                                     "scenes, BVH nodes/triangles) are the only streamed data; bytes are the algorithmic figure, "
+                                     "not inflated; with the set-grouped pixel order nearly all table bytes are served by the XCD "
+                                     "L2s (`traffic`: what reached the memory side).  The analytic kernels are VALU-issue bound "
+                                     "(valu_busy_frac); lanes_active_frac = SQ_THREAD_CYCLES_VALU / (64 SQ_ACTIVE_INST_VALU); "
+                                     "useful_valu_frac = model lane-operations (DESIGN.md section 4) / issued lane slots"},
+                # the job as the reference times it (manager.rs:145 -> 170: Scene::from_data + Camera::new incl. MasterSampleSets::new,
+                # workers.rs:46-54, then the render, then the rows in host memory): a running worker's context creation (the SECOND
+                # context of this process) + one frame + the frame's copy to the host.  `_cold_s`: the same with the process's FIRST
+                # context, whose creation also pays the HIP runtime's one-time initialisation.
+                "ctx_create_ms": round(t_create * 1e3, 2),
+                "ctx_create_breakdown_ms": {k: round(v, 3) for k, v in create_warm.items()},
+                "ctx_create_cold_ms": round(t_create_cold * 1e3, 1),
+                "ctx_create_cold_breakdown_ms": {k: round(v, 3) for k, v in create_cold.items()},
+                "ctx_create_note": "flux_ctx_create_timing: host = validation + scene records (+ BVH build), runtime = HIP device initialisation, "
+                                   "alloc / upload / tables (MasterSampleSets::new on the device) / free / other; cold = the process's first "
+                                   "context (runtime + first-copy / first-launch set-up land in it), ctx_create_ms = a second context",
+                "frame_d2h_ms": round(t_d2h * 1e3, 3),
+                "reference_equivalent_s": round(t_create + elapsed_max / a.steps + t_d2h, 4),
+                "reference_equivalent_cold_s": round(t_create_cold + elapsed_max / a.steps + t_d2h, 4),
+            })
+            out["reference_equivalent_msamples_s"] = round(samples / out["reference_equivalent_s"] / 1e6, 1)
+            if out["vs_baseline"] is not None:
+                # the published 1479.9 s spans table construction + render + gather: compared on the same span
+                out["vs_baseline"] = round(samples / out["reference_equivalent_s"] / 1e6 / PUBLISHED_MSAMPLES_S, 1)
+                out["vs_baseline_span"] = ("reference-equivalent (context creation of a running worker + one frame + the frame's copy to "
+                                           "the host) against README.md's 1479.9 s, which spans the same steps; value / 5.314 would be "
+                                           f"{round(samples * a.steps / elapsed_max / 1e6 / PUBLISHED_MSAMPLES_S, 1)}")
+            prof_kernels = (prof or {}).get("build_id", "")
+            out["roofline"]["profile_build_id"] = prof_kernels or None
+            out["roofline"]["profile_head"] = (prof or {}).get("git_head")
+            same = bool(prof_kernels) and prof_kernels.split("kernels:")[-1] == out["build_id"].split("kernels:")[-1]
+            out["roofline"]["profile_matches_build"] = same if prof else None
+            if prof and not same:
+                out["roofline"]["profile_warning"] = ("the committed PMC profile was taken from another build of the kernels: the "
+                                                      "from_committed_profile fields describe THAT binary")
+            if world == 1 and not a.no_rccl_probe:
+                out["rccl_probe"] = rccl_probe(int(sh.local.numel() * 8))
+                out["multi_abi"] = multi_abi_probe(flux_amd, sd, cfg, a, frame)
+            if world == 1 and not a.no_cpu_baseline:
+                if a.scene.startswith("hf:"):
+                    # the CPU checker scans every triangle per ray (it DEFINES what the BVH must reproduce): ~5 ms per ray on
+                    # a 1M-triangle mesh, so no bounded sample of this workload is meaningful; the headline line carries it
+                    out["cpu_baseline"] = None
+                else:
+                    out["cpu_baseline"] = cpu_baseline(sd, a.depth, a.seed, a.cpu_root)
+                    out["cpu_baseline"]["single_thread"] = cpu_single_thread(a.depth, a.seed)
+        print(json.dumps(out), file=line_out, flush=True)
     r.close()
     if world > 1:
         dist.barrier()

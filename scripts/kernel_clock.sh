@@ -6,7 +6,7 @@ set -uo pipefail
 TAG=${1:-r05}; shift || true
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; export TMPDIR=/tmp; cd "$REPO" || exit 1
 OUT="$REPO/gpurun_out/clock_$TAG"; mkdir -p "$OUT" || exit 1
-rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d "$OUT/pmc" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-rccl-probe "$@" > "$OUT/bench.json" 2> "$OUT/err.log" || { tail -5 "$OUT/err.log"; exit 1; }
+rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d "$OUT/pmc" -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-rccl-probe "$@" > "$OUT/bench.json" 2> "$OUT/err.log" || { tail -5 "$OUT/err.log"; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys
 out = sys.argv[1]

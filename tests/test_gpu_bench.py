@@ -1,20 +1,21 @@
-"""bench.py's contract on the GPU box: one JSON line with BASELINE.json's metric, the roofline and cpu_baseline objects, the
-N = 1 RCCL probe -- run once on a small configuration (BASELINE config 2: demo1 @256 spp) in a child process."""
+"""bench.py's contract on the GPU box: one JSON line with BASELINE.json's metric; with --full also the roofline and cpu_baseline
+objects and the N = 1 RCCL probe -- run on a small configuration (BASELINE config 2: demo1 @256 spp) in a child process."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, max_abs_diff
 
 pytestmark = pytest.mark.gpu
 
 
 def test_bench_line_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "2", "--warmup", "1", "--cpu-root", "8"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "2", "--warmup", "1", "--cpu-root", "8",
+                        "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                      # exactly ONE line on stdout
@@ -49,6 +50,31 @@ def test_bench_line_contract():
     assert d["roofline"]["profile_matches_build"] in (True, False, None)
 
 
+def test_bench_plain_line_and_dumped_frame(flux, demo1, tmp_path):
+    """A plain run (no --full) times the steps and prints the headline only; --dump-outputs writes the frame of the last timed
+    step, which is the frame of the same inputs rendered by the library directly."""
+    out_dir = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+              "step_breakdown_ms"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Msamples/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 1000.0 and d["ms_per_step"] > 0 and "demo1" in d["metric"] and d["full"] is False
+    assert abs(d["value"] - 800 * 600 * 256 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"]
+    for k in ("roofline", "cpu_baseline", "rccl_probe", "multi_abi", "ctx_create_ms", "vs_baseline"):  # --full only
+        assert k not in d, k
+    frame = np.load(out_dir / "frame.npy")
+    assert frame.shape == (600, 800, 3) and frame.dtype == np.float64 and np.isfinite(frame).all()
+    with flux.Renderer(demo1, flux.JobConfiguration(16, 5, 50), seed=1) as r:
+        want = r.render_frame()
+    assert max_abs_diff(frame, want) < 1e-9
+
+
 @pytest.mark.parametrize("shard", ["sets", "rows"])
 def test_bench_multi_rank_branch_rehearsal(shard):
     """bench.py's N > 1 branch (the reference's fan-out and gather: fluxcore/src/manager.rs:156-162, 316-324), kept alive in
@@ -60,7 +86,7 @@ def test_bench_multi_rank_branch_rehearsal(shard):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "3", "--steps", "2", "--warmup", "1",
-                        "--shard", shard], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--shard", shard, "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]            # rank 0 prints, once
