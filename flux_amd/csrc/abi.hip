@@ -186,8 +186,10 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
                     (unsigned long long)scene->num_shapes);
     for (uint64_t i = 0; i < scene->num_shapes; i++) {
         const flux_shape &s = scene->shapes[i];
-        if (s.kind != FLUX_SHAPE_SPHERE && s.kind != FLUX_SHAPE_PLANE)
+        if (s.kind != FLUX_SHAPE_SPHERE && s.kind != FLUX_SHAPE_PLANE && s.kind != FLUX_SHAPE_DISK)
             return fail(FLUX_E_INVALID, "shape %llu: unknown kind %d", (unsigned long long)i, s.kind);
+        if (s.kind == FLUX_SHAPE_DISK && !(std::isfinite(s.radius) && s.radius >= 0.0))
+            return fail(FLUX_E_INVALID, "shape %llu: disk radius must be finite and >= 0, got %g", (unsigned long long)i, s.radius);
         if (s.material.kind < FLUX_MAT_MATTE || s.material.kind > FLUX_MAT_GLOSSY)
             return fail(FLUX_E_INVALID, "shape %llu: unknown material kind %d", (unsigned long long)i,
                         s.material.kind);
@@ -260,17 +262,22 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
             d.c1x = s.p[0] + s.radius;
             d.c1y = s.p[1] + s.radius;
             d.c1z = s.p[2] + s.radius;
-        } else {
+        } else {  // plane, disk: the normal as given
             d.c0x = s.n[0];
             d.c0y = s.n[1];
             d.c0z = s.n[2];
+            if (s.kind == FLUX_SHAPE_DISK) {
+                d.radius = s.radius;
+                d.rr = s.radius * s.radius;
+            }
         }
         fill_material(mats[i], s.material);
     }
-    // FAST path layout of the same shapes: scan records (spheres, planes) + hit records in scan order
+    // FAST path layout of the same shapes: scan records (spheres, planes, disks) + hit records in scan order
     std::vector<flux::DevScanSphere> fsph;
     std::vector<flux::DevScanPlane> fpln;
-    std::vector<flux::DevHitRec> frec_s, frec_p;
+    std::vector<flux::DevScanDisk> fdsk;
+    std::vector<flux::DevHitRec> frec_s, frec_p, frec_d;
     for (size_t i = 0; i < ns; i++) {
         const flux::DevShape &d = shapes[i];
         const flux::DevMaterial &m = mats[i];
@@ -285,13 +292,20 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
         r.ax = m.kind == flux::kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
         r.az = m.kind == flux::kMatMatte ? 0.0071 : 0.00764;
         r.shape_kind = d.kind; r.mat_kind = m.kind; r.orig_id = (int32_t)i;
-        // spheres: |(hit - centre) / radius| = 1 to rounding; planes use the stored normal as is (shapes.rs:135-152)
+        // spheres: |(hit - centre) / radius| = 1 to rounding; planes and disks use the stored normal as is (shapes.rs:135-152)
         r.unit_normal = d.kind == flux::kShapeSphere ||
                         std::fabs((d.c0x * d.c0x + d.c0y * d.c0y + d.c0z * d.c0z) - 1.0) <= 4.0 * 2.220446049250313e-16;
         if (d.kind == flux::kShapeSphere) {
             r.cx = d.px; r.cy = d.py; r.cz = d.pz; r.inv_rad = d.inv_rad;
             fsph.push_back(flux::DevScanSphere{d.px, d.py, d.pz, d.rr});
             frec_s.push_back(r);
+        } else if (d.kind == flux::kShapeDisk) {
+            r.cx = d.c0x; r.cy = d.c0y; r.cz = d.c0z;
+            flux::DevScanDisk dk;
+            std::memset(&dk, 0, sizeof(dk));
+            dk.px = d.px; dk.py = d.py; dk.pz = d.pz; dk.nx = d.c0x; dk.ny = d.c0y; dk.nz = d.c0z; dk.id = (int32_t)i; dk.rr = d.rr;
+            fdsk.push_back(dk);
+            frec_d.push_back(r);
         } else {
             r.cx = d.c0x; r.cy = d.c0y; r.cz = d.c0z;
             flux::DevScanPlane pl;
@@ -352,7 +366,10 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
     // its ray-generation step: x - half_w for every column, (H - row) - half_h for every row -- the same two IEEE operations the
     // kernels perform, done once here
     const size_t fs_px_off = (fs_ss_off + fs_ss_bytes + 127) & ~(size_t)127;
-    std::vector<unsigned char> fscene(fs_px_off + ((size_t)c->W + c->H) * sizeof(double), 0);
+    // the disks' scan records last (+1: as the other scan records, one past the end stays addressable)
+    const size_t fs_dsk_off = (fs_px_off + ((size_t)c->W + c->H) * sizeof(double) + 127) & ~(size_t)127;
+    std::vector<unsigned char> fscene(fs_dsk_off + (fdsk.size() + 1) * sizeof(flux::DevScanDisk), 0);
+    if (!fdsk.empty()) std::memcpy(fscene.data() + fs_dsk_off, fdsk.data(), fdsk.size() * sizeof(flux::DevScanDisk));
     {
         double *pxc = reinterpret_cast<double *>(fscene.data() + fs_px_off);
         const double half_w = (double)c->W * 0.5, half_h = (double)c->H * 0.5;
@@ -368,6 +385,9 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
     if (!frec_p.empty())
         std::memcpy(fscene.data() + fs_sph_bytes + fs_pln_bytes + frec_s.size() * sizeof(flux::DevHitRec), frec_p.data(),
                     frec_p.size() * sizeof(flux::DevHitRec));
+    if (!frec_d.empty())
+        std::memcpy(fscene.data() + fs_sph_bytes + fs_pln_bytes + (frec_s.size() + frec_p.size()) * sizeof(flux::DevHitRec), frec_d.data(),
+                    frec_d.size() * sizeof(flux::DevHitRec));
 
     // extension: meshes -> triangle records (hit order: after all shapes) + BVH
     std::vector<flux::DevTri> tris((size_t)total_tris);
@@ -616,6 +636,7 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
                     : nullptr;
     rp.sshapes = reinterpret_cast<const flux::DevShape *>(c->d_fscene + fs_ss_off);
     rp.pxc = reinterpret_cast<const double *>(c->d_fscene + fs_px_off);
+    rp.fdsk = reinterpret_cast<const flux::DevScanDisk *>(c->d_fscene + fs_dsk_off);
     rp.fwx = rp.focal * rp.Wx;  // trace.rs:96-98's focal_distance * w, one product per frame instead of per wave
     rp.fwy = rp.focal * rp.Wy;
     rp.fwz = rp.focal * rp.Wz;
@@ -628,6 +649,8 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
     rp.slot_stride = 1;
     rp.glossy_long = 0;
     for (const flux::DevHitRec &hr : frec_p)
+        if (!hr.unit_normal) rp.glossy_long = 1;
+    for (const flux::DevHitRec &hr : frec_d)  // a disk's normal is a plane's: the same rule
         if (!hr.unit_normal) rp.glossy_long = 1;
     rp.n_uni = n_uni;
     rp.uni_idx[0] = uni_idx[0];
@@ -679,6 +702,8 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
         if (!(std::fabs(sp.px) < 1e3 && std::fabs(sp.py) < 1e3 && std::fabs(sp.pz) < 1e3 && sp.rr < 1e6)) rp.self_skip = 0;
     rp.n_sph = (int32_t)fsph.size();
     rp.n_pln = (int32_t)fpln.size();
+    rp.n_dsk = (int32_t)fdsk.size();
+    rp.pad_dsk = 0;
     lap(FLUX_CREATE_MS_UPLOAD);
     laps[FLUX_CREATE_MS_TOTAL] = 0.0;
     for (int k = 1; k < FLUX_CREATE_TIMING_WORDS; k++) laps[FLUX_CREATE_MS_TOTAL] += laps[k];  // (the parts sum to the total by construction)

@@ -42,6 +42,7 @@ constexpr double kInvPi = 1.0 / kPi;                   // constants.rs:5
 
 constexpr int kShapeSphere = 0;
 constexpr int kShapePlane = 1;
+constexpr int kShapeDisk = 2;  // extension: Plane::hit bounded to |q - centre|^2 <= rr (include/flux_abi.h FLUX_SHAPE_DISK)
 constexpr int kMatMatte = 0;
 constexpr int kMatEmissive = 1;
 constexpr int kMatReflective = 2;
@@ -50,9 +51,9 @@ constexpr int kMatGlossy = 3;
 // One shape, 128 B.  The shape loop index is wave-uniform, so these are
 // fetched with scalar loads (s_load_dwordx8/x16) and live in SGPRs.
 struct DevShape {
-    double px, py, pz;     // sphere centre | plane point
-    double rr;             // radius*radius (shapes.rs:179 recomputes it per ray); first 32 B = sphere quadratic
-    double c0x, c0y, c0z;  // sphere AABB corner0 (Sphere::new, shapes.rs:154-169) | plane normal
+    double px, py, pz;     // sphere centre | plane point | disk centre
+    double rr;             // radius*radius (shapes.rs:179 recomputes it per ray); first 32 B = sphere quadratic.  Disk: its r^2
+    double c0x, c0y, c0z;  // sphere AABB corner0 (Sphere::new, shapes.rs:154-169) | plane / disk normal
     double radius;         // sphere radius
     double c1x, c1y, c1z;  // sphere AABB corner1
     double inv;            // invert_val: -1 if `invert` else +1 (shapes.rs:181)
@@ -105,10 +106,18 @@ struct DevScanPlane {   // 64 B
     double pad1;
 };
 static_assert(sizeof(DevScanPlane) == 64, "DevScanPlane layout");
+struct DevScanDisk {    // 64 B: a DevScanPlane with r^2 in its pad (extension, kShapeDisk)
+    double px, py, pz;  // centre
+    double nx, ny, nz;  // normal as stored (never flipped / normalised, as the plane's)
+    int32_t id;         // index in YAML order (tie-break)
+    int32_t pad0;
+    double rr;          // radius^2: a hit needs |q - centre|^2 <= rr, q the hit point
+};
+static_assert(sizeof(DevScanDisk) == 64, "DevScanDisk layout");
 // Everything Scene::shade needs about the winning shape, fetched in ONE per-lane batch (6 x 16 B) after
-// the scan instead of a chain of dependent loads.  Indexed in scan order: spheres, then planes.
+// the scan instead of a chain of dependent loads.  Indexed in scan order: spheres, then planes, then disks.
 struct DevHitRec {      // 96 B
-    double cx, cy, cz;  // sphere centre | plane normal
+    double cx, cy, cz;  // sphere centre | plane / disk normal
     double inv_rad;     // sphere: invert_val / radius
     // Emissive: the emitted radiance color * power (materials.rs:45).  Every other material: the FAST bounce weight f (n.wi)/pdf in
     // its closed form -- f / INV_PI for Matte (f = diffuse_color kd INV_PI, brdf.rs:30: the same two IEEE multiplications the kernels
@@ -180,7 +189,7 @@ struct RenderParams {
     // FAST path scene (same shapes as `shapes`/`mats`)
     const DevScanSphere *fsph;
     const DevScanPlane *fpln;
-    const DevHitRec *frec;  // [n_sph + n_pln]
+    const DevHitRec *frec;  // [n_sph + n_pln + n_dsk]
     const DevScanSphere32 *fsph32;  // [n_sph] f32 candidate-filter records, or nullptr (a coordinate beyond f32's safe range)
     const DevShape *sshapes;        // [n_sph] the spheres' STRICT records in scan order (pad0 = YAML index): STRICT's candidates
     int32_t n_sph, n_pln;
@@ -230,6 +239,9 @@ struct RenderParams {
     // flux_math_coeffs.h kExp2Poly, for the glossy lobe's 2^x: read with two scalar loads where the
     // literals cost 24 s_mov_b32 per evaluation
     double exp2c[12];
+    // extension: disks (kShapeDisk), scanned after the planes with the same wave-uniform loop; hit records n_sph + n_pln + j
+    const DevScanDisk *fdsk;
+    int32_t n_dsk, pad_dsk;
 };
 
 }  // namespace flux

@@ -329,6 +329,25 @@ __device__ __forceinline__ void bvh_traverse(const RenderParams &P, const Ray &r
     }
 }
 
+// ---- disks (extension, include/flux_abi.h FLUX_SHAPE_DISK) ----
+// Plane::hit's t (shapes.rs:135-152: the same operands in the same order), a hit iff t > T_MIN and the hit point q lies in the closed
+// disk, |q - centre|^2 <= r^2.  q is formed as shade_hit forms the next segment's origin from (o, t, d) -- o + t d per component, one
+// FMA each in FAST (contract(fast) fuses shade_hit's expression the same way), a product and a sum in STRICT -- so a path that is
+// declared to hit the disk continues from a point that passed the test.  A non-finite t is never a hit: q is then infinite or NaN
+// and fails the compare (rr is finite: abi.hip).
+__device__ __forceinline__ bool disk_hit(const DevScanDisk &S, const Ray &r, double tmin, double &t) {
+    const double num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
+    const double den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
+    t = num / den;
+#if FLUX_FAST
+    const double qx = __builtin_fma(t, r.dx, r.ox), qy = __builtin_fma(t, r.dy, r.oy), qz = __builtin_fma(t, r.dz, r.oz);
+#else
+    const double qx = r.ox + t * r.dx, qy = r.oy + t * r.dy, qz = r.oz + t * r.dz;
+#endif
+    const double ex = qx - S.px, ey = qy - S.py, ez = qz - S.pz;
+    return t > tmin && ex * ex + ey * ey + ez * ez <= S.rr;
+}
+
 // ---- the conservative f32 sphere filter (flux_device.h DevScanSphere32), shared by FAST's scan and -- round 5 -- STRICT's ----
 // Only a SUPERSET of the spheres a ray can hit comes out of it; the exact f64 test of the arithmetic in use decides every hit
 // afterwards.  The ray's side of the test: u, o.u, 2 o and o.o (1 - 8e-6) in f32, each splatted into a pair.  (The records hold the
@@ -450,8 +469,24 @@ __device__ __forceinline__ double sphere_hb(double tx, double ty, double tz, dou
     return __builtin_fma(tz, uz, __builtin_fma(ty, uy, tx * ux));
 }
 
-// FAST: nearest analytic shape (spheres, planes) of Scene::hit.  `best` = winning HIT RECORD index
-// (scan order: spheres, then planes) or -1; `tb` its distance.
+// Disks after the planes (FAST scans and the split kernel's primary scan): wave-uniform, operands in scalar registers, one scalar compare
+// when the scene has none.  The general guarded update (`tb` means something only beside best >= 0: the first plane's peeled form leaves
+// it as it comes under ENV_SHORT), and an equal t decided by the YAML index, not by scan order -- a disk listed before a coplanar plane
+// still wins the tie.  `best` = hit record index (disk j: n_sph + n_pln + j), `best_id` its YAML index.
+__device__ __forceinline__ void scan_disks(const RenderParams &P, const Ray &r, double tmin, int &best, int &best_id, double &tb) {
+    for (int j = 0; j < P.n_dsk; ++j) {
+        const DevScanDisk &S = P.fdsk[j];
+        double t;
+        if (disk_hit(S, r, tmin, t) && (best < 0 || t < tb || (t == tb && S.id < best_id))) {
+            best = P.n_sph + P.n_pln + j;
+            best_id = S.id;
+            tb = t;
+        }
+    }
+}
+
+// FAST: nearest analytic shape (spheres, planes, disks) of Scene::hit.  `best` = winning HIT RECORD index
+// (scan order: spheres, then planes, then disks) or -1; `tb` its distance.
 template <bool ENV_SHORT = false, bool LDS_SCENE = false, bool MAX32 = false, bool TYP = false, int ZF = -1>
 __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ray &r, int self, int &best, double &tb,
                                                  long long *lap = nullptr, const char *fsph_lds = nullptr) {
@@ -489,6 +524,9 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
             tb = t;
         }
     }
+    // (TYP: the launch takes that instantiation only for a scene without disks -- the loop, even never entered, cost the split kernel
+    // 1.2 % on demo2 in code it moved around)
+    if (!TYP) scan_disks(P, r, tmin, best, best_id, tb);
     // Spheres, phase 1: wave-uniform index, operands in SGPRs, all lanes active -- only the half-b
     // discriminant of Sphere::hit (shapes.rs:176-184 with b = 2 hb along the unit direction: disc/4a = hb_u^2 - c)
     // plus the "sphere entirely behind the origin" rejection (c > 0 and hb > 0 => both roots negative).
@@ -504,7 +542,7 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
     // and is taken as the unit direction as it stands, as phase A of the split kernel does for primaries:
     // no rsqrt, no scaling (one wave-uniform branch).
     // TYP (the split kernel's instantiation for the usual scene, chosen by the launch: no non-unit plane normal, the self-skip rule in
-    // force, ONE `invert` sphere and it is an Emissive environment): the scene's flags are compile-time constants here -- each was a
+    // force, ONE `invert` sphere and it is an Emissive environment, no disk): the scene's flags are compile-time constants here -- each was a
     // scalar load, a compare and a branch per pass, with the other side's code behind it
     const bool p_unit_dirs = TYP ? true : P.unit_dirs != 0;
     const bool p_env_short = TYP ? true : P.env_short != 0;
@@ -606,7 +644,7 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
                     if (!(t > tmin)) t = (-hb + e) * rs;  // shapes.rs:201
                     if (t > tmin) {
                         // min_by + Hit::compare: smaller t wins; equal t keeps the lower YAML index.  Spheres come in
-                        // YAML order among themselves, so only a plane can hold an equal t with a higher index.
+                        // YAML order among themselves, so only a plane or a disk can hold an equal t with a higher index.
                         // (Flat -- no nested `if`s, the equal-t rule behind a vote -- was measured: three scalar instructions and two
                         // branches less per trip for one more compare, +0.4 % slower: profiles/r06_experiments/ab_m17_m18_m19_r06x.log.)
                         bool take = best < 0 || t < tb;
@@ -744,6 +782,11 @@ __device__ __forceinline__ int scene_hit(const RenderParams &P, const Ray &r, in
             double t = num / den;
             if (t > kTMin) consider(t, S.id, -1, best, bslot, tb);
         }
+        for (int j = 0; j < P.n_dsk; ++j) {  // disks (extension): consider() applies the tie rule by YAML index
+            const DevScanDisk &S = P.fdsk[j];
+            double t;
+            if (disk_hit(S, r, kTMin, t)) consider(t, S.id, -1, best, bslot, tb);
+        }
         // the filter's ray: unit direction (2-ulp reciprocal square root: it only feeds the conservative test), o.o
         const double rs = fastmath::frsqrt(a);
         const double ux = r.dx * rs, uy = r.dy * rs, uz = r.dz * rs;
@@ -812,12 +855,17 @@ __device__ __forceinline__ int scene_hit(const RenderParams &P, const Ray &r, in
                 const double t0 = __builtin_fmax(tx_min, __builtin_fmax(ty_min, tz_min));
                 const double t1 = __builtin_fmin(tx_max, __builtin_fmin(ty_max, tz_max));
                 if (t0 < t1 && t1 > kTMin && !__builtin_isunordered(tz_min, tz_max)) cand |= 1u << k;
-            } else {
+            } else if (S.kind == kShapePlane) {
                 // Plane::hit: shapes.rs:135-152 (normal stored in c0)
                 double num = (S.px - r.ox) * S.c0x + (S.py - r.oy) * S.c0y + (S.pz - r.oz) * S.c0z;
                 double den = r.dx * S.c0x + r.dy * S.c0y + r.dz * S.c0z;
                 double t = num / den;
                 if (t > kTMin) consider(t, base + k, -1, best, bslot, tb);
+            } else {
+                // disk (extension): centre in p, normal in c0, r^2 in rr
+                const DevScanDisk D = {S.px, S.py, S.pz, S.c0x, S.c0y, S.c0z, base + k, 0, S.rr};
+                double t;
+                if (disk_hit(D, r, kTMin, t)) consider(t, base + k, -1, best, bslot, tb);
             }
         }
         while (cand) {
@@ -1763,8 +1811,9 @@ __device__ __forceinline__ void pixel_sphere_mask(const RenderParams &P, int row
     }
 }
 
-// Scene::hit for a primary ray against the pixel's candidates: planes as in scan_shapes_fast, then the exact sphere
+// Scene::hit for a primary ray against the pixel's candidates: planes and disks as in scan_shapes_fast, then the exact sphere
 // test (shapes.rs:176-214 along the unit direction) with the sphere record in SGPRs and a wave-uniform trip count.
+template <bool TYP>
 __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const Ray &r, unsigned long long cand_mask,
                                                     unsigned long long in_mask, double in_t0, bool valid, unsigned long long valid_m,
                                                     int &best, double &tb) {
@@ -1794,6 +1843,7 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
             tb = t;
         }
     }
+    if (!TYP) scan_disks(P, r, tmin, best, best_id, tb);  // (TYP: a scene without disks, as in scan_shapes_fast)
     // a primary direction is normalize(...) (trace.rs:44-51): already the unit direction the quadratic is solved along
     const double rs = 1.0, ux = r.dx, uy = r.dy, uz = r.dz, len = 1.0;
     const bool zflat = r.dz == 0.0, any_zflat = any64(zflat);  // box_z_nan_miss, as in scan_shapes_fast
@@ -1851,17 +1901,17 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
     const uint32_t K = blockDim.x >> 6, sub = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t s_lo = (uint32_t)((uint64_t)N * sub / K), s_hi = (uint32_t)((uint64_t)N * (sub + 1) / K);
     // (the scene records FIRST, at an LDS address the compiler knows; the queues behind them)
-    const size_t scene_lds_bytes = (size_t)(P.n_sph + P.n_pln) * sizeof(DevHitRec) + (size_t)P.n_sph * sizeof(DevScanSphere);
+    const size_t scene_lds_bytes = (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec) + (size_t)P.n_sph * sizeof(DevScanSphere);
     double *q = lds_stack + scene_lds_bytes / 8 + (size_t)sub * (kQueueBytesPerWave / 8);  // this wave's queue: [field][slot]
     int *qi = reinterpret_cast<int *>(q + kQueueDoubles * 64);
     // The scene's hit records (96 B per shape) and scan spheres (32 B) copied into the block's LDS behind the queues: the per-lane gathers
     // of the shading step and of the candidate loop -- dependent loads in the middle of a pass, ~600 cycles each from the L2 -- become
     // LDS reads (~100).  The launch plan reserves the bytes (plan_render_impl: the split kernel serves scenes whose records fit 16 KiB).
     const char *const frec_lds = reinterpret_cast<const char *>(lds_stack);
-    const char *const fsph_lds = frec_lds + (size_t)(P.n_sph + P.n_pln) * sizeof(DevHitRec);
+    const char *const fsph_lds = frec_lds + (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec);
     {
         uint32_t *dst = reinterpret_cast<uint32_t *>(const_cast<char *>(frec_lds));
-        const uint32_t nrec_w = (uint32_t)(P.n_sph + P.n_pln) * (uint32_t)(sizeof(DevHitRec) / 4), nsph_w = (uint32_t)P.n_sph * 8u;
+        const uint32_t nrec_w = (uint32_t)(P.n_sph + P.n_pln + P.n_dsk) * (uint32_t)(sizeof(DevHitRec) / 4), nsph_w = (uint32_t)P.n_sph * 8u;
         const uint32_t *src_r = reinterpret_cast<const uint32_t *>(P.frec), *src_s = reinterpret_cast<const uint32_t *>(P.fsph);
         for (uint32_t w = (uint32_t)tid; w < nrec_w; w += blockDim.x) dst[w] = src_r[w];
         for (uint32_t w = (uint32_t)tid; w < nsph_w; w += blockDim.x) dst[nrec_w + w] = src_s[w];
@@ -1982,7 +2032,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 }
                 int hit = -1;
                 double t = 0.0;
-                scan_shapes_primary(P, pa.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
+                scan_shapes_primary<TYP>(P, pa.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
                 if (valid) {
                     double Lr, Lg, Lb;
                     FLUX_CENSUS(P, 2);
@@ -2550,11 +2600,11 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_BVH4) void render_bvh4
     // step's dependent gathers -- triangle record -> material record, hit record, a sphere record per candidate -- lose an L2 round trip
     // (LDS_SCENE: the launch plan chose this instantiation and reserved the bytes -- small analytic sets only, plan_render_impl)
     const char *const frec_lds = reinterpret_cast<const char *>(lds_stack) + (size_t)(P.bvh4_stack > 0 ? P.bvh4_stack : 1) * kEntry;
-    const char *const mats_lds = frec_lds + (size_t)(P.n_sph + P.n_pln) * sizeof(DevHitRec);
+    const char *const mats_lds = frec_lds + (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec);
     const char *const fsph_lds = mats_lds + (size_t)P.n_mats * sizeof(DevMaterial);
     if constexpr (LDS_SCENE) {
         uint32_t *dst = reinterpret_cast<uint32_t *>(const_cast<char *>(frec_lds));
-        const uint32_t n1 = (uint32_t)(P.n_sph + P.n_pln) * (uint32_t)(sizeof(DevHitRec) / 4), n2 = (uint32_t)P.n_mats * (uint32_t)(sizeof(DevMaterial) / 4),
+        const uint32_t n1 = (uint32_t)(P.n_sph + P.n_pln + P.n_dsk) * (uint32_t)(sizeof(DevHitRec) / 4), n2 = (uint32_t)P.n_mats * (uint32_t)(sizeof(DevMaterial) / 4),
                        n3 = (uint32_t)P.n_sph * 8u;
         const uint32_t *s1 = reinterpret_cast<const uint32_t *>(P.frec), *s2 = reinterpret_cast<const uint32_t *>(P.mats),
                        *s3 = reinterpret_cast<const uint32_t *>(P.fsph);
@@ -2939,7 +2989,7 @@ static LaunchPlan plan_render_impl(const RenderParams &p, int variant) {
         size_t lds4 = (size_t)(p.bvh4_stack > 0 ? p.bvh4_stack : 1) * 64 * sizeof(int);
         // the analytic set's records + the materials in LDS behind the stack (round 5) while they are small: a one-wave block must stay
         // within the 6 LDS granules (7 680 B) that 5 waves/SIMD leave it, and the copy is made once per pixel
-        const size_t scene4 = (size_t)(p.n_sph + p.n_pln) * sizeof(DevHitRec) + (size_t)p.n_mats * sizeof(DevMaterial) +
+        const size_t scene4 = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_mats * sizeof(DevMaterial) +
                               (size_t)p.n_sph * sizeof(DevScanSphere);
         const bool lds_scene4 = lds4 + scene4 <= 7680;
         if (lds_scene4) lds4 += scene4;
@@ -2958,7 +3008,7 @@ static LaunchPlan plan_render_impl(const RenderParams &p, int variant) {
     // serves scenes whose records fit 16 KiB there (64 spheres -- the pixel mask's width -- leave room for 85 planes, demo2's 12 for 154;
     // until round 6 the rule was "at most 16 planes", and a seventeenth sent the scene to the refill kernel); larger analytic scenes
     // take the refill kernel, which reads the records from global memory (the launch plan says which)
-    const size_t scene_lds = (size_t)(p.n_sph + p.n_pln) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
+    const size_t scene_lds = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
     if (variant == FLUX_KERNEL_SPLIT && !tris && p.n_sph <= 64 && scene_lds <= 16384) {
         L.kernel = 2;
         L.block = block;
@@ -2998,7 +3048,8 @@ static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStre
     }
     if (L.kernel == 4) {
         // the usual analytic set beside the mesh (scan_shapes_fast's TYP / MAX32: constants of the instantiation)
-        const bool typ = L.lds_scene && p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.n_uni == 1 && p.fsph32 != nullptr;
+        const bool typ = L.lds_scene && p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.n_uni == 1 && p.fsph32 != nullptr &&
+                         p.n_dsk == 0;
         if (typ) {
             if (stats) render_bvh4_kernel<true, true, true><<<g, b, lds, stream>>>(p);
             else render_bvh4_kernel<false, true, true><<<g, b, lds, stream>>>(p);
@@ -3014,7 +3065,9 @@ static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStre
     if (L.kernel == 2) {
         const bool max32 = p.n_sph <= 32;  // (one group of the sphere filter: scan_shapes_fast's MAX32)
         // the usual scene (scan_shapes_fast's TYP: these five values become constants of the instantiation)
-        const bool typ = max32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 && p.fsph32 != nullptr;
+        // (and no disks: the instantiation leaves their loop out)
+        const bool typ = max32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 && p.fsph32 != nullptr &&
+                         p.n_dsk == 0;
         if (stats && typ) render_split_kernel<true, true, true><<<g, b, lds, stream>>>(p);
         else if (stats && max32) render_split_kernel<true, true, false><<<g, b, lds, stream>>>(p);
         else if (stats) render_split_kernel<true, false, false><<<g, b, lds, stream>>>(p);

@@ -4,6 +4,7 @@
 #include <random>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -87,7 +88,13 @@ ShapeData shape(const Node &n, const std::string &what) {
     if (tag == "Plane")
         return PlaneData{vec3(req(*b, "point", w), w + ".point"), vec3(req(*b, "normal", w), w + ".normal"),
                          material(req(*b, "material", w), w + ".material")};
-    bad(what + ": unknown variant `" + tag + "`, expected one of `Sphere`, `Plane`");
+    if (tag == "Disk") {  // extension (flux_host.hpp DiskData)
+        const double radius = num(req(*b, "radius", w), w + ".radius");
+        if (!(std::isfinite(radius) && radius >= 0.0)) bad(w + ".radius: expected a finite number >= 0");
+        return DiskData{vec3(req(*b, "center", w), w + ".center"), vec3(req(*b, "normal", w), w + ".normal"), radius,
+                        material(req(*b, "material", w), w + ".material")};
+    }
+    bad(what + ": unknown variant `" + tag + "`, expected one of `Sphere`, `Plane`, `Disk`");
 }
 
 SceneData scene_from_node(const Node &d) {
@@ -178,6 +185,12 @@ AbiScene::AbiScene(const SceneData &sd) : name(sd.scene_name) {
             fs.p[0] = p->point.x; fs.p[1] = p->point.y; fs.p[2] = p->point.z;
             fs.n[0] = p->normal.x; fs.n[1] = p->normal.y; fs.n[2] = p->normal.z;
             fs.material = to_abi(p->material);
+        } else if (auto k = std::get_if<DiskData>(&sd.shapes[i])) {
+            fs.kind = FLUX_SHAPE_DISK;
+            fs.p[0] = k->center.x; fs.p[1] = k->center.y; fs.p[2] = k->center.z;
+            fs.n[0] = k->normal.x; fs.n[1] = k->normal.y; fs.n[2] = k->normal.z;
+            fs.radius = k->radius;
+            fs.material = to_abi(k->material);
         }
     }
     desc.scene_name = name.c_str();

@@ -45,7 +45,9 @@ using MaterialData = std::variant<MatteData, EmissiveData, ReflectiveData, Gloss
 
 struct SphereData { Vec3 center; double radius = 0; MaterialData material; bool invert = false; };
 struct PlaneData { Vec3 point, normal; MaterialData material; };
-using ShapeData = std::variant<SphereData, PlaneData>;
+// extension (include/flux_abi.h FLUX_SHAPE_DISK): a closed disk; a reference node cannot decode it
+struct DiskData { Vec3 center, normal; double radius = 0; MaterialData material; };
+using ShapeData = std::variant<SphereData, PlaneData, DiskData>;
 
 struct CameraSettings { Vec3 eye, look_at, up; };
 struct CameraData { double zoom_factor = 1, view_plane_distance = 0, focal_distance = 0, lens_radius = 0; };

@@ -94,16 +94,27 @@ void enc_shape(Encoder &e, const ShapeData &s) {  // scene.rs:71-74, shapes.rs:1
         enc_material(e, sp->material);
         e.key("invert");
         e.boolean(sp->invert);
-    } else {
-        const auto &pl = std::get<PlaneData>(s);
+    } else if (auto *pl = std::get_if<PlaneData>(&s)) {
         e.text("Plane");
         e.map(3);
         e.key("point");
-        enc_vec3(e, pl.point);
+        enc_vec3(e, pl->point);
         e.key("normal");
-        enc_vec3(e, pl.normal);
+        enc_vec3(e, pl->normal);
         e.key("material");
-        enc_material(e, pl.material);
+        enc_material(e, pl->material);
+    } else {  // extension: externally tagged like the others; a reference node rejects the unknown variant
+        const auto &dk = std::get<DiskData>(s);
+        e.text("Disk");
+        e.map(4);
+        e.key("center");
+        enc_vec3(e, dk.center);
+        e.key("normal");
+        enc_vec3(e, dk.normal);
+        e.key("radius");
+        e.real(dk.radius);
+        e.key("material");
+        enc_material(e, dk.material);
     }
 }
 
@@ -406,6 +417,19 @@ bool dec_shape(Decoder &d, ShapeData &s) {
             if (!read_struct(d, [&](const std::string &k) {
                     if (k == "point") return dec_vec3(d, v.point);
                     if (k == "normal") return dec_vec3(d, v.normal);
+                    if (k == "material") return dec_material(d, v.material);
+                    return d.skip();
+                }))
+                return false;
+            s = v;
+            return true;
+        }
+        if (name == "Disk") {
+            DiskData v;
+            if (!read_struct(d, [&](const std::string &k) {
+                    if (k == "center") return dec_vec3(d, v.center);
+                    if (k == "normal") return dec_vec3(d, v.normal);
+                    if (k == "radius") return d.read_number(v.radius);
                     if (k == "material") return dec_material(d, v.material);
                     return d.skip();
                 }))

@@ -16,6 +16,8 @@ and unknown variants are errors.
 from dataclasses import dataclass, field
 from typing import List, Sequence, Tuple, Union
 
+import math
+
 import yaml
 
 from . import _lib
@@ -95,7 +97,19 @@ class PlaneData:  # shapes.rs:33-37
     material: MaterialData
 
 
-ShapeData = Union[SphereData, PlaneData]  # scene.rs:71-74
+@dataclass
+class DiskData:
+    """Extension (absent in the reference: scene.rs:71-74 has Sphere | Plane): a closed disk, the finite area light.  YAML:
+        - Disk: {center: [x, y, z], normal: [x, y, z], radius: r, material: {...}}
+    Plane::hit bounded to |hit - center| <= radius; the normal is used as given (never normalised or flipped) and emission is
+    one-sided as for every shape (it lights the side its normal points to).  Ties: YAML index among the analytic shapes."""
+    center: Vec3
+    normal: Vec3
+    radius: float
+    material: MaterialData
+
+
+ShapeData = Union[SphereData, PlaneData, DiskData]  # scene.rs:71-74 + the Disk extension
 
 
 @dataclass
@@ -295,6 +309,11 @@ class SceneDesc:
                 fs.kind = _lib.SHAPE_PLANE
                 fs.p[:] = s.point
                 fs.n[:] = s.normal
+            elif isinstance(s, DiskData):
+                fs.kind = _lib.SHAPE_DISK
+                fs.p[:] = s.center
+                fs.n[:] = s.normal
+                fs.radius = s.radius
             else:
                 raise TypeError(f"not a ShapeData: {s!r}")
             fs.material = material_to_abi(s.material)
@@ -354,10 +373,23 @@ def mesh_from_yaml(tag, b, what):
 _shape_from_yaml_reference = shape_from_yaml
 
 
-def shape_from_yaml(m, what="shape"):  # noqa: F811  (extends the reference enum with Mesh / Triangle)
+def disk_from_yaml(b, what):
+    w = f"{what}.Disk"
+    radius = _num(b, "radius", w)
+    if not (math.isfinite(radius) and radius >= 0.0):
+        raise SceneError(f"{w}.radius: expected a finite number >= 0, got {radius!r}")
+    return DiskData(_vec3(_req(b, "center", w), w + ".center"), _vec3(_req(b, "normal", w), w + ".normal"), radius,
+                    material_from_yaml(_req(b, "material", w), w + ".material"))
+
+
+def shape_from_yaml(m, what="shape"):  # noqa: F811  (extends the reference enum with Disk / Mesh / Triangle)
     tag, b = _single_variant(m, what)
     if tag in ("Mesh", "Triangle"):
         return mesh_from_yaml(tag, b, what)
+    if tag == "Disk":
+        return disk_from_yaml(b, what)
+    if tag not in ("Sphere", "Plane"):
+        raise SceneError(f"{what}: unknown variant `{tag}`, expected one of `Sphere`, `Plane`, `Disk`, `Mesh`, `Triangle`")
     return _shape_from_yaml_reference(m, what)
 
 

@@ -44,6 +44,10 @@ extern "C" {
 /* ShapeData variants: fluxcore/src/scene.rs:71-74 */
 #define FLUX_SHAPE_SPHERE 0
 #define FLUX_SHAPE_PLANE 1
+/* EXTENSION (absent in the reference; its TODO.md asks for a finite area light): a closed disk, see flux_shape.
+ * Added without an ABI version bump: a library that predates it rejects kind 2 in flux_ctx_create with
+ * FLUX_E_INVALID ("unknown kind"), which is how a client detects support. */
+#define FLUX_SHAPE_DISK 2
 
 /* MaterialData variants: fluxcore/src/shapes.rs:42-47 */
 #define FLUX_MAT_MATTE 0       /* MatteData            shapes.rs:52-56 */
@@ -68,7 +72,13 @@ typedef struct flux_material {
 
 /* ShapeData (scene.rs:71-74) = SphereData (shapes.rs:18-23) | PlaneData
  * (shapes.rs:33-37).  sphere: p = center, radius, invert.  plane: p = point,
- * n = normal (used as given: never normalised or flipped, shapes.rs:135-152). */
+ * n = normal (used as given: never normalised or flipped, shapes.rs:135-152).
+ * disk (extension, FLUX_SHAPE_DISK): p = centre, n = normal, radius (`invert` ignored).
+ * Plane::hit's t = ((p - o).n) / (d.n), a hit iff t > T_MIN and the hit point q
+ * (the next segment's origin) has |q - p|^2 <= radius^2; a non-finite t is a miss.
+ * Two-sided, normal as given (as the plane's); it emits towards -n only
+ * (materials.rs:44).  radius must be finite and >= 0 (0: a degenerate disk),
+ * else flux_ctx_create returns FLUX_E_INVALID.  Ties: YAML index, as every shape. */
 typedef struct flux_shape {
     int32_t kind;
     int32_t invert;
