@@ -34,6 +34,9 @@
 //
 // The loop body (render_body.inc) is compiled twice: STRICT under `#pragma clang fp contract(off)` with the
 // reference's operation order, FAST under contract(fast) with flux_math.h (see render_body.inc's header).
+#include <algorithm>
+#include <cstdlib>
+
 #include "flux_device.h"
 #include "flux_tables.h"
 #include "flux_math.h"

@@ -1107,6 +1107,30 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
     p.r.dz = wi.z;
 }
 
+// The fields of an analytic shape's hit (shapes.rs:140-146,191-197) from its record: gathered per lane, one batch of independent
+// loads (DevHitRec) instead of shape -> kind -> fields -> material chains.  Returns the shape's material index.  One copy, shared by
+// the shading step (shade_hit_fast) and the split kernel's bounce of a parked hit (bounce_parked_hit), so that both form the normal
+// from the same operands with the same operations.
+template <bool LDS_SCENE>
+__device__ __forceinline__ int analytic_hit_fields(const RenderParams &P, const Ray &r, int hit, double t, const char *frec_lds, V3 &n,
+                                                   int &kind, bool &unit_n, bool &convex, double &fr, double &fg, double &fb,
+                                                   double &m_inv_e1, double &ax, double &az) {
+    (void)frec_lds;
+    const DevHitRec R = *reinterpret_cast<const DevHitRec *>((LDS_SCENE ? frec_lds : reinterpret_cast<const char *>(P.frec)) +
+                                                              (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
+    kind = R.mat_kind;
+    unit_n = R.unit_normal != 0;
+    fr = R.fr; fg = R.fg; fb = R.fb; m_inv_e1 = R.inv_e1;
+    ax = R.ax; az = R.az;
+    // sphere: (temp + t d) * invert_val / radius with invert_val/radius in one rounding; plane: stored normal
+    const V3 ns = mk(((r.ox - R.cx) + t * r.dx) * R.inv_rad, ((r.oy - R.cy) + t * r.dy) * R.inv_rad,
+                     ((r.oz - R.cz) + t * r.dz) * R.inv_rad);
+    const bool sph = R.shape_kind == kShapeSphere;
+    n = mk(sph ? ns.x : R.cx, sph ? ns.y : R.cy, sph ? ns.z : R.cz);
+    convex = sph && R.inv_rad > 0.0;
+    return R.orig_id;  // a shape's material has the shape's index
+}
+
 // FAST, in two phases.  Phase 1, every lane of the shading step: what was hit, and the two ways a path ENDS (a miss, an emitter)
 // as values.  Phase 2, the lanes that bounce: the lobe code and the ONLY update of the loop-carried path state, under one plain
 // `if` that follows the join of phase 1.  Written with early returns (as the reference's match arms suggest, and as round 1-3 had
@@ -1114,7 +1138,9 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
 // state for the next pass gets defined -- as a copy of the old one -- where the ways part, i.e. while the old one is still
 // needed: two register sets for the state and ~14 v_mov_b64 into and out of them on every way through, every pass.  The empty asm
 // keeps the compiler from threading `bounce` back into phase 1 (it is 1 on exactly one way into the join).
-template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false>
+// BOUNCE = false (the split kernel's phase B with its hit queue): phase 1 only -- the hit is classified, a continuing path's state is
+// left as it was and its bounce runs later from the parked hit (bounce_parked_hit).
+template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false, bool BOUNCE = true>
 __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, int slot, double t,
                                                double &Lr, double &Lg, double &Lb, Stats &st, int cz, const char *frec_lds = nullptr) {
     (void)frec_lds;  // LDS_SCENE: the block's LDS copy of the hit records
@@ -1146,19 +1172,7 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
             ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
             az = kind == kMatMatte ? 0.0071 : 0.00764;
         } else {
-            const DevHitRec R = *reinterpret_cast<const DevHitRec *>((LDS_SCENE ? frec_lds : reinterpret_cast<const char *>(P.frec)) +
-                                                                      (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
-            kind = R.mat_kind;
-            p.mat = R.orig_id;  // a shape's material has the shape's index
-            unit_n = R.unit_normal != 0;
-            fr = R.fr; fg = R.fg; fb = R.fb; m_inv_e1 = R.inv_e1;
-            ax = R.ax; az = R.az;
-            // sphere: (temp + t d) * invert_val / radius with invert_val/radius in one rounding; plane: stored normal
-            const V3 ns = mk(((p.r.ox - R.cx) + t * d.x) * R.inv_rad, ((p.r.oy - R.cy) + t * d.y) * R.inv_rad,
-                             ((p.r.oz - R.cz) + t * d.z) * R.inv_rad);
-            const bool sph = R.shape_kind == kShapeSphere;
-            n = mk(sph ? ns.x : R.cx, sph ? ns.y : R.cy, sph ? ns.z : R.cz);
-            convex = sph && R.inv_rad > 0.0;
+            p.mat = analytic_hit_fields<LDS_SCENE>(P, p.r, hit, t, frec_lds, n, kind, unit_n, convex, fr, fg, fb, m_inv_e1, ax, az);
         }
         if (kind == kMatEmissive) {  // materials.rs:41-50
             if (STATS) st.c[5]++;
@@ -1179,11 +1193,27 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
         }
     }
     asm("" : "+v"(bounce));
-    if (bounce) {
+    if (BOUNCE && bounce) {
         fast_bounce<STATS, TRIS, TYP, FIRST>(P, p, set, i, hit, slot, t, n, d, pt, kind, fr, fg, fb, m_inv_e1, ax, az, unit_n, convex, is_tri, st,
                                             cz);
     }
     return bounce != 0;
+}
+
+// The other half of shade_hit_fast for a hit the split kernel parked in its hit queue (an analytic shape, records in LDS): the
+// bounce from (o, d, t, hit) -- p.r holds the segment (o, d) --, with the operands and operations of the shading step that
+// classified it (analytic_hit_fields, pt = o + t d, fast_bounce): the path's next ray is bit for bit the one the step would have made.
+template <bool STATS, bool TYP>
+__device__ __forceinline__ void bounce_parked_hit(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, double t, Stats &st,
+                                                  int cz, const char *frec_lds) {
+    const V3 d = mk(p.r.dx, p.r.dy, p.r.dz);
+    const V3 pt = mk(p.r.ox + t * d.x, p.r.oy + t * d.y, p.r.oz + t * d.z);
+    V3 n;
+    int kind;
+    bool unit_n, convex;
+    double fr, fg, fb, m_inv_e1, ax, az;
+    p.mat = analytic_hit_fields<true>(P, p.r, hit, t, frec_lds, n, kind, unit_n, convex, fr, fg, fb, m_inv_e1, ax, az);
+    fast_bounce<STATS, false, TYP, false>(P, p, set, i, hit, -1, t, n, d, pt, kind, fr, fg, fb, m_inv_e1, ax, az, unit_n, convex, false, st, cz);
 }
 #endif
 
@@ -1757,6 +1787,28 @@ constexpr int kQueueSq = 0;
 constexpr int kQueueDoubles = 9 + kQueueSq;
 constexpr int kQueueBytesPerWave = (kQueueDoubles * 64) * 8 + 2 * 64 * 4;         // + sample index, Path::self (int)
 
+// The hit queue (plan_render_impl chooses C per scene): C slots per wave, structure of arrays [field][slot] as above.
+// Phase B only CLASSIFIES its hits; a continuing hit is parked here -- the segment o d and its hit distance t (8 B each), the hit-record
+// index and the depth (one int), the sample index (int) and the path's throughput -- and its bounce runs later, in a pass whose free
+// lanes take a full batch of parked hits at once (bounce_parked_hit), instead of under the sparse mask of the scan's survivors.
+// The throughput is kept either as three doubles (FLUX_HITQ_LIST=0: 88 B a slot) or as the list of the path's earlier bounce records,
+// `bits` per bounce in one int (FLUX_HITQ_LIST=1, the default: 68 B a slot): without long-form glossy weights (P.glossy_long) a bounce
+// of an analytic shape multiplies the throughput by its record's (fr, fg, fb) and nothing else, so the product recomputed front to back from the block's LDS copy of the records is bit
+// for bit the running one.  Every decision of the pass loop is a count (wave-uniform), so frames stay bit-reproducible.
+#ifndef FLUX_HITQ_LIST
+#define FLUX_HITQ_LIST 1
+#endif
+#ifndef FLUX_HITQ_MIN_TAKE
+// H, the parked hits a wave waits for before a pass takes them instead of starting 64 more samples, is C - 64 (at most 64): phase A
+// runs while the queue has room for its 64 continuations.  Below this H the bounce batches are too thin to pay for the queue
+// (demo2 @16384 spp, C = 110: H 46 159.2, 40 162.9, 32 171.0, 24 182.3, 16 200.9 ms; the ray queue 172.0 ms), and the scene keeps
+// the ray queue.
+#define FLUX_HITQ_MIN_TAKE 32
+#endif
+constexpr int kHitQDoubles = FLUX_HITQ_LIST ? 7 : 10;                  // o d t (+ tr tg tb)
+constexpr int kHitQInts = FLUX_HITQ_LIST ? 3 : 2;                      // hit | depth << 16, sample index (+ bounce list)
+constexpr int kHitQBytesPerSlot = kHitQDoubles * 8 + kHitQInts * 4;    // 68 | 88
+
 // The spheres a primary ray of pixel (row, col) can hit: a conservative wave-uniform mask (bit = scan index).
 // Every primary ray starts on the lens, |o - eye| <= R = lens_radius (to_poisson_disc maps into the unit disc,
 // lib.rs:144-182), and passes through the point Fp = eye + x k U + y k V - f W of the focal plane (trace.rs:44-51:
@@ -1888,8 +1940,15 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
     }
 }
 
-template <bool STATS, bool MAX32, bool TYP>
-__global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void render_split_kernel(const RenderParams P0) {
+// HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
+// bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see plan_render_impl): the 64-entry ray queue and phase B's
+// bounce at once, in the lanes that continue.
+template <bool STATS, bool MAX32, bool TYP, bool HQ = false>
+__global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void render_split_kernel(const RenderParams P0, int hq_cap, int hq_th,
+                                                                                                  int hq_bits) {
+    (void)hq_cap;
+    (void)hq_th;
+    (void)hq_bits;
     const RenderParams &P = P0;  // (inside the pass loop: shadowed by the re-read view)
     extern __shared__ double lds_stack[];
     __shared__ double part[FLUX_MAX_WAVES_PER_PIXEL][3];  // per-wave totals of the pixel (K > 1)
@@ -1902,8 +1961,8 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
     const uint32_t s_lo = (uint32_t)((uint64_t)N * sub / K), s_hi = (uint32_t)((uint64_t)N * (sub + 1) / K);
     // (the scene records FIRST, at an LDS address the compiler knows; the queues behind them)
     const size_t scene_lds_bytes = (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec) + (size_t)P.n_sph * sizeof(DevScanSphere);
-    double *q = lds_stack + scene_lds_bytes / 8 + (size_t)sub * (kQueueBytesPerWave / 8);  // this wave's queue: [field][slot]
-    int *qi = reinterpret_cast<int *>(q + kQueueDoubles * 64);
+    double *q = lds_stack + scene_lds_bytes / 8 + (size_t)sub * (HQ ? (size_t)hq_cap * kHitQBytesPerSlot / 8 : kQueueBytesPerWave / 8);
+    int *qi = reinterpret_cast<int *>(q + (HQ ? (size_t)kHitQDoubles * hq_cap : (size_t)kQueueDoubles * 64));  // this wave's queue: [field][slot]
     // The scene's hit records (96 B per shape) and scan spheres (32 B) copied into the block's LDS behind the queues: the per-lane gathers
     // of the shading step and of the candidate loop -- dependent loads in the middle of a pass, ~600 cycles each from the L2 -- become
     // LDS reads (~100).  The launch plan reserves the bytes (plan_render_impl: the split kernel serves scenes whose records fit 16 KiB).
@@ -1928,7 +1987,185 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
 
     Stats st = {};
     double sr = 0.0, sg = 0.0, sb = 0.0;
-    if (wave_on) {
+    if (HQ && wave_on) {
+        unsigned long long cand_mask, in_mask;
+        double in_t0;
+        pixel_sphere_mask(P, row, col, lane, cand_mask, in_mask, in_t0);
+        const uint32_t C = (uint32_t)hq_cap, H = (uint32_t)hq_th;
+        const uint32_t bmask = (1u << hq_bits) - 1u;
+        const DevHitRec *const recs = reinterpret_cast<const DevHitRec *>(frec_lds);
+        uint32_t next = s_lo;  // wave-uniform cursor: first unstarted sample of this wave's slice
+        uint32_t nhit = 0;     // wave-uniform: parked hits, in slots C-1, C-2, ... (the newest at C - nhit)
+        constexpr int kDeadDepth = 0x7fffffff;  // (as in the loop below: "no path" kept in the depth)
+        // Every lane is free at the top of a pass: the scan of the pass before ended or parked each of its paths.  So no path state is
+        // carried from pass to pass -- only the sums, the statistics and the two counts.
+        for (;;) {
+            const RenderParams &P = relaunder_params(next + nhit);  // kernel arguments re-read per pass (see relaunder_params)
+            uint32_t set_p = set;
+            unsigned long long cand_p = cand_mask, in_p = in_mask;
+            asm("" : "+s"(set_p) : "s"(next));
+            asm("" : "+s"(cand_p), "+s"(in_p) : "s"(next));
+            Path p;
+            path_begin(p);
+            p.depth = kDeadDepth;
+            p.sq = make_double2(0.5, 0.5);
+            uint32_t i = 0;
+            uint32_t ml = 0;  // FLUX_HITQ_LIST: the records of the path's bounces so far, entry k at bit k * hq_bits
+            // ---- phase A, while fewer than H hits are parked and the queue has room for all 64 continuations: samples next .. next+63,
+            //      their continuing paths stay in their lanes
+            const bool run_a = next < s_hi && nhit < H && nhit + 64u <= C;
+            if (run_a) {
+                FLUX_TRIP(P, 12);
+                FLUX_CENSUS(P, 0);
+                const uint32_t ia = next + lane;
+                const bool valid = ia < s_hi;
+                const unsigned long long valid_m = ballot64(ia < s_hi);
+                next = (s_hi - next) > 64u ? next + 64u : s_hi;
+                bool cont = false;
+                const double2 *pix = set_rows_of(P, set_p).pix;
+                const double2 *disc = set_rows_of(P, set_p).disc;
+                const char *pxc_b = reinterpret_cast<const char *>(P.pxc);
+                const PixelConsts PX = PixelConsts{*reinterpret_cast<const double *>(pxc_b + ((uint32_t)col << 3)),
+                                                   *reinterpret_cast<const double *>(pxc_b + ((uint32_t)(P.img_w + row) << 3)), P.fwx, P.fwy, P.fwz};
+                {
+                    const uint32_t ic = ia < s_hi ? ia : s_hi - 1u;  // (lanes past the slice's end: see the loop below)
+                    p.sq = gather_global_d2(pix, ic << 4);
+                    p.r = primary_ray_px(P, PX, p.sq, gather_global_d2(disc, ic << 4));
+                    if (STATS && valid) {
+                        st.c[0]++;
+                        st.c[1]++;
+                    }
+                }
+                int hit = -1;
+                double t = 0.0;
+                scan_shapes_primary<TYP>(P, p.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
+                p.depth = 1;
+                if (valid) {
+                    double Lr, Lg, Lb;
+                    FLUX_CENSUS(P, 2);
+                    cont = shade_hit_fast<STATS, false, true, TYP, true>(P, p, set_p, ia, hit, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
+                    if (cont && p.depth > P.max_depth) {  // scene.rs:164-165 on entry to the next level
+                        cont = false;
+                        Lr = Lg = Lb = 0.0;
+                        if (STATS) st.c[7]++;
+                    }
+                    if (!cont) {
+                        fold_path(p, nullptr, 0, Lr, Lg, Lb);
+                        sr += Lr;  // trace.rs:82
+                        sg += Lg;
+                        sb += Lb;
+                    }
+                }
+                i = ia;
+                ml = (uint32_t)hit;
+                if (!cont) p.depth = kDeadDepth;
+            }
+            // ---- free lanes take parked hits, newest first, and bounce them: when phase A did not run (H of them are parked, the
+            //      queue is full, or the slice is used up), or when H of them fill free lanes phase A left, or when phase A cannot run
+            //      again
+            if (nhit) {
+                const unsigned long long freemask = ballot64(p.depth == kDeadDepth);
+                const uint32_t nfree = (uint32_t)__popcll(freemask);
+                const uint32_t take = nfree < nhit ? nfree : nhit;
+                if (!run_a || take >= H || !(next < s_hi && nhit + 64u <= C)) {
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(freemask >> 32),
+                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)freemask, 0u));
+                    if (p.depth == kDeadDepth && rank < take) {
+                        FLUX_CENSUS(P, 15);
+                        const uint32_t slot = C - nhit + rank;
+                        p.r.ox = q[0 * C + slot];
+                        p.r.oy = q[1 * C + slot];
+                        p.r.oz = q[2 * C + slot];
+                        p.r.dx = q[3 * C + slot];
+                        p.r.dy = q[4 * C + slot];
+                        p.r.dz = q[5 * C + slot];
+                        const double t = q[6 * C + slot];
+                        const int hd = qi[slot];
+                        i = (uint32_t)qi[C + slot];
+                        const int hit = hd & 0xffff;
+                        p.depth = hd >> 16;
+                        if (FLUX_HITQ_LIST) {
+                            // the throughput, front to back as fast_bounce formed it (the first bounce's weight, then one product per bounce)
+                            ml = (uint32_t)qi[2 * C + slot];
+                            const DevHitRec &R0 = recs[ml & bmask];
+                            p.tr = R0.fr;
+                            p.tg = R0.fg;
+                            p.tb = R0.fb;
+                            for (int k = 1; k < p.depth - 1; ++k) {
+                                const DevHitRec &Rk = recs[(ml >> (k * hq_bits)) & bmask];
+                                p.tr *= Rk.fr;
+                                p.tg *= Rk.fg;
+                                p.tb *= Rk.fb;
+                            }
+                            ml |= (uint32_t)hit << ((p.depth - 1) * hq_bits);
+                        } else {
+                            p.tr = q[7 * C + slot];
+                            p.tg = q[8 * C + slot];
+                            p.tb = q[9 * C + slot];
+                        }
+                        bounce_parked_hit<STATS, TYP>(P, p, set_p, i, hit, t, st, 6, frec_lds);
+                    }
+                    nhit -= take;
+                }
+            }
+            // the way out: nothing parked, the slice used up and no lane live (the scalar test first, as below)
+            if (__builtin_expect((nhit | (s_hi - next)) == 0u, 0)) {
+                if (!any64(p.depth != kDeadDepth)) break;
+            }
+            // ---- phase B: Scene::hit and the first half of Scene::shade (scene.rs:162-172) for every live lane; a path that ends is
+            //      added to the lane's sums, a path that continues is parked
+            FLUX_TRIP(P, 10);
+            const bool live = p.depth != kDeadDepth;
+            const bool trace = p.depth <= P.max_depth;  // (live, and) scene.rs:164-165: a path beyond the depth limit ends with L = 0
+            double Lr = 0.0, Lg = 0.0, Lb = 0.0;
+            bool cont = false;
+            int hit = -1;
+            double t = 0.0;
+            if (trace) {
+                FLUX_CENSUS(P, 3);
+                if (STATS) st.c[1]++;
+                const float ofx = (float)p.r.ox, ofy = (float)p.r.oy, ofz = (float)p.r.oz;
+                const float oo32 = __builtin_fmaf(ofz, ofz, __builtin_fmaf(ofy, ofy, ofx * ofx));
+                if (__builtin_expect((ballot64(p.r.dz == 0.0) | ballot64(!(oo32 < 0.999e6f))) != 0ull, 0))
+                    scan_shapes_fast<true, true, MAX32, TYP, 1>(P, p.r, p.self, hit, t, nullptr, fsph_lds);
+                else
+                    scan_shapes_fast<true, true, MAX32, TYP, 0>(P, p.r, p.self, hit, t, nullptr, fsph_lds);
+                cont = shade_hit_fast<STATS, false, true, TYP, false, false>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds);
+            }
+            if (live && !cont) {
+                if (STATS && !trace) st.c[7]++;
+                fold_path(p, nullptr, 0, Lr, Lg, Lb);
+                sr += Lr;
+                sg += Lg;
+                sb += Lb;
+            }
+            const unsigned long long pmask = ballot64(cont);
+            if (cont) {
+                // (room: the queue held at most C - 64 hits when this pass's phase A ran, and a pass without it parks no more paths
+                // than it took from the queue)
+                const uint32_t slot = C - 1u - nhit - __builtin_amdgcn_mbcnt_hi((uint32_t)(pmask >> 32),
+                                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)pmask, 0u));
+                q[0 * C + slot] = p.r.ox;
+                q[1 * C + slot] = p.r.oy;
+                q[2 * C + slot] = p.r.oz;
+                q[3 * C + slot] = p.r.dx;
+                q[4 * C + slot] = p.r.dy;
+                q[5 * C + slot] = p.r.dz;
+                q[6 * C + slot] = t;
+                qi[slot] = hit | (p.depth << 16);
+                qi[C + slot] = (int)i;
+                if (FLUX_HITQ_LIST) {
+                    qi[2 * C + slot] = (int)ml;
+                } else {
+                    q[7 * C + slot] = p.tr;
+                    q[8 * C + slot] = p.tg;
+                    q[9 * C + slot] = p.tb;
+                }
+            }
+            nhit += (uint32_t)__popcll(pmask);
+        }
+    }
+    if (!HQ && wave_on) {
         unsigned long long cand_mask, in_mask;
         double in_t0;
         pixel_sphere_mask(P, row, col, lane, cand_mask, in_mask, in_t0);
@@ -2950,9 +3187,18 @@ static hipError_t launch_shade_rays_impl(const RenderParams &p, const double *d_
     return hipGetLastError();
 }
 
+#if FLUX_FAST
+// the usual scene of the split kernel (scan_shapes_fast's TYP: these values become constants of the instantiation; and no disks: the
+// instantiation leaves their loop out)
+static bool split_typ(const RenderParams &p) {
+    return p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 &&
+           p.fsph32 != nullptr && p.n_dsk == 0;
+}
+#endif
+
 // Which kernel a render call runs (flux_tables.h LaunchPlan): decided HERE, once.
 static LaunchPlan plan_render_impl(const RenderParams &p, int variant) {
-    LaunchPlan L = {-1, 64, 0, 0, 1, 0};
+    LaunchPlan L = {-1, 64, 0, 0, 1, 0, 0, 0, 0};
     const uint32_t N = p.nsamp;
     const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
     if (npix == 0 || p.set_count <= 0) return L;
@@ -3014,6 +3260,29 @@ static LaunchPlan plan_render_impl(const RenderParams &p, int variant) {
         L.block = block;
         L.waves_per_pixel = K;
         L.lds = (size_t)kQueueBytesPerWave * K + scene_lds;
+        // The hit queue: as many slots as the LDS leaves a wave at FLUX_WPE_SPLIT waves/SIMD -- the CU's 128 granules of
+        // 1280 B shared by 4 * FLUX_WPE_SPLIT / K blocks, less the scene copy and the 96 B of `part` (demo2, K = 4: 25 granules, 7 568 B
+        // a wave, 110 slots of 68 B; H = 46).  A scene that leaves fewer than 64 + H slots (H at least FLUX_HITQ_MIN_TAKE), or whose bounce list does not fit 32 bits or does
+        // not give the throughput back exactly (long-form glossy weights: P.glossy_long), keeps the ray queue and the immediate bounce.
+        // C depends on the scene only through the size of its records, so a disk in place of a plane changes no lane a sample runs in.
+        // FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT override C (at most what fits) and H.
+        if (!FLUX_HITQ_LIST || p.glossy_long == 0) {
+            const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
+            const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
+            uint32_t cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
+            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_CAP")) cap = std::min(cap, (uint32_t)std::max(0, std::atoi(e)) & ~1u);
+            uint32_t th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
+            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
+            int bits = 1;
+            while ((1 << bits) < p.n_sph + p.n_pln + p.n_dsk) ++bits;
+            const bool list_fits = !FLUX_HITQ_LIST || bits * p.max_depth <= 32;
+            if (cap >= 64u + th && list_fits) {
+                L.hq_cap = (int)cap;
+                L.hq_th = (int)th;
+                L.hq_bits = bits;
+                L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
+            }
+        }
         return L;
     }
 #endif
@@ -3064,16 +3333,20 @@ static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStre
     }
     if (L.kernel == 2) {
         const bool max32 = p.n_sph <= 32;  // (one group of the sphere filter: scan_shapes_fast's MAX32)
-        // the usual scene (scan_shapes_fast's TYP: these five values become constants of the instantiation)
-        // (and no disks: the instantiation leaves their loop out)
-        const bool typ = max32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 && p.fsph32 != nullptr &&
-                         p.n_dsk == 0;
-        if (stats && typ) render_split_kernel<true, true, true><<<g, b, lds, stream>>>(p);
-        else if (stats && max32) render_split_kernel<true, true, false><<<g, b, lds, stream>>>(p);
-        else if (stats) render_split_kernel<true, false, false><<<g, b, lds, stream>>>(p);
-        else if (typ) render_split_kernel<false, true, true><<<g, b, lds, stream>>>(p);
-        else if (max32) render_split_kernel<false, true, false><<<g, b, lds, stream>>>(p);
-        else render_split_kernel<false, false, false><<<g, b, lds, stream>>>(p);
+        const bool typ = split_typ(p);
+        const int c = L.hq_cap, h = L.hq_th, bits = L.hq_bits;
+#define FLUX_LAUNCH_SPLIT(HQ)                                                                                      \
+    do {                                                                                                           \
+        if (stats && typ) render_split_kernel<true, true, true, HQ><<<g, b, lds, stream>>>(p, c, h, bits);         \
+        else if (stats && max32) render_split_kernel<true, true, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits); \
+        else if (stats) render_split_kernel<true, false, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits);         \
+        else if (typ) render_split_kernel<false, true, true, HQ><<<g, b, lds, stream>>>(p, c, h, bits);            \
+        else if (max32) render_split_kernel<false, true, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits);         \
+        else render_split_kernel<false, false, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits);                   \
+    } while (0)
+        if (L.hq_cap > 0) FLUX_LAUNCH_SPLIT(true);
+        else FLUX_LAUNCH_SPLIT(false);
+#undef FLUX_LAUNCH_SPLIT
         return hipGetLastError();
     }
 #endif

@@ -1,0 +1,143 @@
+"""The split kernel's hit queue (render_body.inc, kHitQBytesPerSlot): phase B parks its continuing hits in LDS and bounces them in
+batches.  Each sample's arithmetic is the immediate bounce's, so against the refill and static kernels the path statistics are
+identical and the images equal to the summation order (1e-12); decisions are counts, so frames are bit-reproducible and independent
+of how they are sharded.  FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT (read by the launch plan) reach the small queues and the
+one-hit batches a default plan does not choose.
+"""
+import copy
+
+import numpy as np
+import pytest
+
+from conftest import small_scene
+
+pytestmark = pytest.mark.gpu
+
+SLOT = 68            # bytes per slot (the bounce-list format)
+RAY_QUEUE = 5120     # bytes per wave of the 64-entry ray queue (the immediate bounce)
+REC, SPH = 96, 32    # DevHitRec, DevScanSphere
+
+# (C, H): None = the plan's own choice; the smallest queue (64 + 2: a pass's 64 continuations and room to spare), one-hit batches;
+# a middling one; the largest a one-wave block holds for demo2 (86 slots)
+QUEUES = [None, (66, 1), (80, 16), (86, 22)]
+
+
+def _scene_lds(flux, sd):
+    n_sph = sum(isinstance(s, flux.SphereData) for s in sd.shapes)
+    return len(sd.shapes) * REC + n_sph * SPH
+
+
+def _plane_to_disk(flux, sd, radius=1e3):
+    s = copy.deepcopy(sd)
+    for i, sh in enumerate(s.shapes):
+        if isinstance(sh, flux.PlaneData):
+            s.shapes[i] = flux.DiskData(sh.point, sh.normal, radius, sh.material)
+    return s
+
+
+@pytest.fixture
+def queue(monkeypatch):
+    def set_queue(q):
+        if q is None:
+            monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
+            monkeypatch.delenv("FLUX_SPLIT_HITQ_TAKE_AT", raising=False)
+        else:
+            monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", str(q[0]))
+            monkeypatch.setenv("FLUX_SPLIT_HITQ_TAKE_AT", str(q[1]))
+    yield set_queue
+    set_queue(None)
+
+
+def _render(flux, sd, n, kernel, seed=1):
+    with flux.Renderer(sd, flux.JobConfiguration(n, 5, 50), seed=seed) as r:
+        r.set_kernel(kernel)
+        r.enable_stats(True)
+        r.stats(reset=True)
+        img = r.render_frame()
+        return img, r.stats(), r.launch_plan()
+
+
+def _scenes(flux, demo1, demo2):
+    return {"demo1": small_scene(demo1, 40, 30), "demo2": small_scene(demo2, 40, 30),
+            "disk": _plane_to_disk(flux, small_scene(demo2, 40, 30))}
+
+
+def test_headline_plan_holds_110_slots(flux, demo2):
+    """demo2 at 16384 spp (K = 4): 25 LDS granules per block at 5 waves/SIMD, less the scene copy and `part`: 110 slots a wave."""
+    sd = small_scene(demo2, 8, 6)
+    with flux.Renderer(sd, flux.JobConfiguration(128, 5, 50), seed=1) as r:
+        r.set_kernel(flux.KERNEL_DEFAULT)
+        plan = r.launch_plan()
+    assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == 4
+    assert plan["lds"] == 110 * SLOT * 4 + _scene_lds(flux, sd)
+    assert plan["lds"] + 96 <= 25 * 1280
+
+
+@pytest.mark.parametrize("q", QUEUES)
+@pytest.mark.parametrize("n", [2, 4, 8, 16, 32])
+@pytest.mark.parametrize("scene", ["demo1", "demo2", "disk"])
+def test_split_equals_refill_and_static(flux, demo1, demo2, queue, scene, n, q):
+    sd = _scenes(flux, demo1, demo2)[scene]
+    want, ws, _ = _render(flux, sd, n, flux.KERNEL_REFILL)
+    stat, ss, _ = _render(flux, sd, n, flux.KERNEL_STATIC)
+    queue(q)
+    got, gs, plan = _render(flux, sd, n, flux.KERNEL_SPLIT)
+    if n * n >= 64:
+        assert plan["kernel"] == flux._lib.PLAN_SPLIT
+        if q is not None:  # the override reaches the kernel: the hit queue's LDS, not the ray queue's
+            assert plan["lds"] == q[0] * SLOT * plan["waves_per_pixel"] + _scene_lds(flux, sd)
+    assert gs == ws == ss, (gs, ws, ss)
+    assert np.abs(got - want).max() <= 1e-12
+    assert np.abs(got - stat).max() <= 1e-12
+
+
+@pytest.mark.parametrize("q", [(66, 1), (86, 22)])
+@pytest.mark.parametrize("scene,n", [("demo1", 16), ("demo2", 16), ("demo2", 32)])
+def test_split_against_the_oracle(flux, oracle_mod, demo1, demo2, queue, scene, n, q):
+    sd = _scenes(flux, demo1, demo2)[scene]
+    want_o = oracle_mod.Oracle(sd, flux.JobConfiguration(n, 5, 50), seed=1)
+    want = want_o.render_frame(threads=8)
+    queue(q)
+    got, gs, _ = _render(flux, sd, n, flux.KERNEL_SPLIT)
+    assert np.abs(got - want).max() < 1e-4
+    o_stats = want_o.stats()
+    assert {k: gs[k] for k in o_stats} == o_stats
+
+
+@pytest.mark.parametrize("q", [None, (66, 1), (86, 22)])
+def test_determinism_and_row_bands(flux, demo2, queue, q):
+    sd = small_scene(demo2, 40, 30)
+    queue(q)
+    with flux.Renderer(sd, flux.JobConfiguration(32, 5, 50), seed=2) as r:
+        r.set_kernel(flux.KERNEL_SPLIT)
+        a = r.render_frame()
+        assert np.array_equal(a, r.render_frame())
+        for lo, hi in ((0, 0), (3, 9), (10, 29)):
+            assert np.array_equal(r.render_rows(lo, hi), a[lo:hi + 1])
+
+
+@pytest.mark.parametrize("q", [None, (66, 1), (86, 22)])
+@pytest.mark.parametrize("n", [16, 32])
+def test_plane_and_disk_bit_equal(flux, demo1, demo2, queue, n, q):
+    queue(q)
+    for name in ("demo1", "demo2"):
+        plane = small_scene(demo1 if name == "demo1" else demo2, 40, 30)
+        a, sa, pa = _render(flux, plane, n, flux.KERNEL_SPLIT)
+        b, sb, pb = _render(flux, _plane_to_disk(flux, plane), n, flux.KERNEL_SPLIT)
+        assert pa["lds"] == pb["lds"]
+        assert sa == sb and np.array_equal(a, b), (name, n)
+
+
+def test_records_that_leave_no_room_fall_back(flux, demo2):
+    """96 extra planes far below the floor: 13 KiB of records leave a 4-wave block (16384 spp) fewer than 96 slots a wave, so the
+    kernel keeps the ray queue and bounces at once -- with the same statistics and image as the refill kernel."""
+    base = small_scene(demo2, 4, 3)
+    sd = copy.deepcopy(base)
+    for k in range(96):
+        sd.shapes.append(flux.PlaneData((0.0, -1e4 - k, 0.0), (0.0, 1.0, 0.0), base.shapes[-1].material))
+    lds = _scene_lds(flux, sd)
+    assert lds <= 16384
+    got, gs, plan = _render(flux, sd, 128, flux.KERNEL_SPLIT)
+    assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["lds"] == RAY_QUEUE * plan["waves_per_pixel"] + lds
+    want, ws, _ = _render(flux, sd, 128, flux.KERNEL_REFILL)
+    assert gs == ws and np.abs(got - want).max() <= 1e-12
