@@ -15,6 +15,7 @@ FLUX_OK = 0
 E_INVALID, E_DEVICE, E_NOMEM, E_IO = -1, -2, -3, -4
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_DISK = 0, 1, 2  # SHAPE_DISK: extension (include/flux_abi.h FLUX_SHAPE_DISK)
 MAT_MATTE, MAT_EMISSIVE, MAT_REFLECTIVE, MAT_GLOSSY = 0, 1, 2, 3
+MAT_DIELECTRIC = 4  # extension (include/flux_abi.h FLUX_MAT_DIELECTRIC)
 KERNEL_DEFAULT, KERNEL_STATIC, KERNEL_REFILL, KERNEL_SPLIT = 0, 1, 2, 3
 MATH_FAST, MATH_STRICT = 0, 1
 SAMPLER_REGULAR, SAMPLER_JITTERED, SAMPLER_MULTI_JITTERED, SAMPLER_CORRELATED_MULTI_JITTERED = 0, 1, 2, 3

@@ -131,6 +131,17 @@ static void fill_material(flux::DevMaterial &dm, const flux_material &m) {
     dm.exp_parity = 0;
     if (std::isfinite(m.exponent) && std::floor(m.exponent) == m.exponent)
         dm.exp_parity = (std::fabs(m.exponent) >= 9007199254740992.0 || std::fmod(m.exponent, 2.0) == 0.0) ? 1 : 2;
+    if (m.kind == FLUX_MAT_DIELECTRIC) {
+        // the transmitted bounce's weight as given; the refraction index where a Glossy material keeps 1 / (exponent + 1)
+        // (flux_device.h DevMaterial)
+        dm.exponent = 0.0;
+        dm.inv_e1 = m.k;
+        dm.exp_parity = 0;
+        dm.fr = m.color[0];
+        dm.fg = m.color[1];
+        dm.fb = m.color[2];
+        return;
+    }
     double f[3];
     for (int ch = 0; ch < 3; ch++) {
         f[ch] = m.color[ch] * m.k;
@@ -190,17 +201,23 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
             return fail(FLUX_E_INVALID, "shape %llu: unknown kind %d", (unsigned long long)i, s.kind);
         if (s.kind == FLUX_SHAPE_DISK && !(std::isfinite(s.radius) && s.radius >= 0.0))
             return fail(FLUX_E_INVALID, "shape %llu: disk radius must be finite and >= 0, got %g", (unsigned long long)i, s.radius);
-        if (s.material.kind < FLUX_MAT_MATTE || s.material.kind > FLUX_MAT_GLOSSY)
+        if (s.material.kind < FLUX_MAT_MATTE || s.material.kind > FLUX_MAT_DIELECTRIC)
             return fail(FLUX_E_INVALID, "shape %llu: unknown material kind %d", (unsigned long long)i,
                         s.material.kind);
+        if (s.material.kind == FLUX_MAT_DIELECTRIC && !(std::isfinite(s.material.k) && s.material.k > 0.0))
+            return fail(FLUX_E_INVALID, "shape %llu: dielectric refraction index must be finite and > 0, got %g", (unsigned long long)i,
+                        s.material.k);
     }
     if (scene->num_meshes > 0 && !scene->meshes)
         return fail(FLUX_E_INVALID, "num_meshes > 0 but meshes is null");
     uint64_t total_tris = 0;
     for (uint64_t m = 0; m < scene->num_meshes; m++) {
         const flux_mesh &me = scene->meshes[m];
-        if (me.material.kind < FLUX_MAT_MATTE || me.material.kind > FLUX_MAT_GLOSSY)
+        if (me.material.kind < FLUX_MAT_MATTE || me.material.kind > FLUX_MAT_DIELECTRIC)
             return fail(FLUX_E_INVALID, "mesh %llu: unknown material kind %d", (unsigned long long)m, me.material.kind);
+        if (me.material.kind == FLUX_MAT_DIELECTRIC && !(std::isfinite(me.material.k) && me.material.k > 0.0))
+            return fail(FLUX_E_INVALID, "mesh %llu: dielectric refraction index must be finite and > 0, got %g", (unsigned long long)m,
+                        me.material.k);
         if (me.num_triangles && (!me.vertices || !me.indices))
             return fail(FLUX_E_INVALID, "mesh %llu: null vertices/indices", (unsigned long long)m);
         for (uint64_t k = 0; k < 3 * me.num_triangles; k++)
@@ -703,7 +720,9 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
     rp.n_sph = (int32_t)fsph.size();
     rp.n_pln = (int32_t)fpln.size();
     rp.n_dsk = (int32_t)fdsk.size();
-    rp.pad_dsk = 0;
+    rp.has_diel = 0;
+    for (const flux::DevMaterial &m : mats)
+        if (m.kind == flux::kMatDielectric) rp.has_diel = 1;
     lap(FLUX_CREATE_MS_UPLOAD);
     laps[FLUX_CREATE_MS_TOTAL] = 0.0;
     for (int k = 1; k < FLUX_CREATE_TIMING_WORDS; k++) laps[FLUX_CREATE_MS_TOTAL] += laps[k];  // (the parts sum to the total by construction)

@@ -47,6 +47,7 @@ constexpr int kMatMatte = 0;
 constexpr int kMatEmissive = 1;
 constexpr int kMatReflective = 2;
 constexpr int kMatGlossy = 3;
+constexpr int kMatDielectric = 4;  // extension: Fresnel-sampled glass (include/flux_abi.h FLUX_MAT_DIELECTRIC)
 
 // One shape, 128 B.  The shape loop index is wave-uniform, so these are
 // fetched with scalar loads (s_load_dwordx8/x16) and live in SGPRs.
@@ -72,7 +73,7 @@ struct DevMaterial {
     // (brdf.rs:45,76) -- per-material constants the reference recomputes per hit.
     double fr, fg, fb;
     double exponent;  // Glossy reflect_exponent
-    double inv_e1;    // 1/(exponent+1) (samplers/src/lib.rs:136)
+    double inv_e1;    // 1/(exponent+1) (samplers/src/lib.rs:136).  Dielectric: its refraction index (fr, fg, fb: transmit_color)
     int32_t kind;
     int32_t exp_parity;  // Glossy exponent: 1 even integer, 2 odd integer, 0 not integral (powf of a negative base)
     double pad1[2];
@@ -123,7 +124,8 @@ struct DevHitRec {      // 96 B
     // its closed form -- f / INV_PI for Matte (f = diffuse_color kd INV_PI, brdf.rs:30: the same two IEEE multiplications the kernels
     // performed per bounce until round 6, done once on the host), f itself for Reflective / Glossy (DevMaterial keeps the plain f)
     double fr, fg, fb;
-    double inv_e1;      // Glossy: 1 / (exponent + 1); the exponent itself and its parity: DevMaterial (mats[orig_id]), long-form lobes only
+    double inv_e1;      // Glossy: 1 / (exponent + 1); the exponent itself and its parity: DevMaterial (mats[orig_id]), long-form lobes only.
+                        // Dielectric: its refraction index (fr, fg, fb: the transmitted bounce's weight)
     int32_t shape_kind, mat_kind;
     int32_t orig_id;      // index in YAML order (the tie rule's key; also the shape's material index)
     int32_t unit_normal;  // 1: the hit normal has length 1 to rounding (every sphere; a plane whose stored normal does)
@@ -241,7 +243,10 @@ struct RenderParams {
     double exp2c[12];
     // extension: disks (kShapeDisk), scanned after the planes with the same wave-uniform loop; hit records n_sph + n_pln + j
     const DevScanDisk *fdsk;
-    int32_t n_dsk, pad_dsk;
+    int32_t n_dsk;
+    // extension: 1 = some shape or mesh is a Dielectric (kMatDielectric).  The kernels' dielectric branch sits behind this uniform
+    // flag, and the launch keeps such a scene out of the TYP instantiations and the split kernel's hit queue (plan_render_impl)
+    int32_t has_diel;
 };
 
 }  // namespace flux

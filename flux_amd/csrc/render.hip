@@ -94,6 +94,7 @@ static_assert(FLUX_BVH4_EARLY_AT >= FLUX_BVH_REFILL_AT,
 // The loop itself lives in render_body.inc and is compiled twice (see its header): the STRICT
 // arithmetic (reference operation order, no contraction) and the FAST arithmetic (FMA + flux_math.h).
 #define FLUX_FAST 0
+#define FLUX_DIEL 1  // (STRICT: the dielectric branch sits behind RenderParams::has_diel, render_body.inc fast_bounce / shade_hit)
 #define FLUX_WPE FLUX_WAVES_PER_EU
 #define FLUX_WPE_WIDE FLUX_WAVES_PER_EU
 #pragma clang fp contract(off)
@@ -103,6 +104,7 @@ namespace strict {
 }  // namespace strict
 }  // namespace flux
 #undef FLUX_FAST
+#undef FLUX_DIEL
 #undef FLUX_WPE
 #undef FLUX_WPE_WIDE
 
@@ -110,11 +112,23 @@ namespace strict {
 #define FLUX_WPE FLUX_WAVES_PER_EU_FAST
 #define FLUX_WPE_WIDE FLUX_WAVES_PER_EU_FAST_WIDE
 #pragma clang fp contract(fast)
+#define FLUX_DIEL 0
 namespace flux {
 namespace fast {
 #include "render_body.inc"
 }  // namespace fast
 }  // namespace flux
+#undef FLUX_DIEL
+// ... and a third time for the scenes that have a Dielectric (RenderParams::has_diel): the same kernels with the
+// dielectric lobe in fast_bounce.  The copy above, which every other scene runs, is compiled without it, so under contract(fast)
+// the fusion decisions in its lobe code are the ones it made before the material existed.
+#define FLUX_DIEL 1
+namespace flux {
+namespace fast_diel {
+#include "render_body.inc"
+}  // namespace fast_diel
+}  // namespace flux
+#undef FLUX_DIEL
 // FAST glossy-lobe factors of every pixel sample (RenderParams::gloss), compiled with the FAST arithmetic
 // so that the table holds bit for bit what to_unit_hemi would compute inline.
 namespace flux {
@@ -145,17 +159,20 @@ namespace flux {
 
 hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream) {
     if (math == FLUX_MATH_STRICT) return strict::launch_render_impl(p, variant, stream);
+    if (p.has_diel) return fast_diel::launch_render_impl(p, variant, stream);
     return fast::launch_render_impl(p, variant, stream);
 }
 
 // the kernel, grid and LDS launch_render would pick (host-side budget check, flux_ctx_launch_plan)
 LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
-    return math == FLUX_MATH_STRICT ? strict::plan_render_impl(p, variant) : fast::plan_render_impl(p, variant);
+    return math == FLUX_MATH_STRICT ? strict::plan_render_impl(p, variant)
+                                    : p.has_diel ? fast_diel::plan_render_impl(p, variant) : fast::plan_render_impl(p, variant);
 }
 
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream) {
     if (math == FLUX_MATH_STRICT) return strict::launch_shade_rays_impl(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
+    if (p.has_diel) return fast_diel::launch_shade_rays_impl(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
     return fast::launch_shade_rays_impl(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
 }
 

@@ -79,7 +79,8 @@ __device__ __forceinline__ const DevSetRows &set_rows_of(const RenderParams &P, 
 }
 
 // -DFLUX_DEBUG_TRIPS (experiment builds, scripts/): wave-level trip counts of the loop sections, added by the first
-// active lane to the reserved statistics slots 10..15 (stats must be enabled); never in the product build.
+// active lane to the statistics slots 10..15 (stats must be enabled) -- on top of the dielectric counters in 10 and 11, which
+// such a build does not keep apart; never in the product build.
 #ifndef FLUX_TRIP_DEFINED
 #define FLUX_TRIP_DEFINED
 #ifdef FLUX_DEBUG_TRIPS
@@ -231,7 +232,7 @@ __device__ __forceinline__ PixelConsts pixel_consts(const RenderParams &P, int r
 
 // path statistics (STATS builds only)
 struct Stats {
-    unsigned c[10];
+    unsigned c[12];  // [10] / [11]: dielectric reflections / transmissions (include/flux_abi.h flux_ctx_stats)
 };
 
 // ---- extension: triangles (no reference counterpart; DESIGN.md "Triangles and the BVH") ----------
@@ -933,6 +934,40 @@ __device__ __forceinline__ V3 to_unit_hemi(double2 p, double inv_e1) {
 #endif
 }
 
+// ---- dielectric (extension, include/flux_abi.h FLUX_MAT_DIELECTRIC; DESIGN.md §5c) ----
+// One bounce of the spec in the order it is written: n the shading normal the other materials use, d the segment's direction, ri the
+// refraction index, u the z of hemi_sets[set][depth-1][sample].  Returns true for a reflection (weight 1; total internal reflection
+// included), false for a transmission (weight transmit_color); wi the new direction, a unit vector to rounding.  STRICT: IEEE
+// division and square root, no contraction; FAST: the same operations under contract(fast).
+__device__ __forceinline__ bool dielectric_dir(V3 n, V3 d, double ri, double u, V3 &wi) {
+    const double ln = sqrt(n.x * n.x + n.y * n.y + n.z * n.z), ld = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
+    const V3 nh = mk(n.x / ln, n.y / ln, n.z / ln), dh = mk(d.x / ld, d.y / ld, d.z / ld);
+    double c = -(dh.x * nh.x + dh.y * nh.y + dh.z * nh.z);
+    double eta = ri;
+    V3 m = nh;
+    if (!(c > 0.0)) {  // arriving from the inside (the side the normal points away from)
+        eta = 1.0 / ri;
+        m = mk(-nh.x, -nh.y, -nh.z);
+        c = -c;
+    }
+    const double k = 1.0 - (1.0 - c * c) / (eta * eta);
+    double F = 1.0, ct = 0.0;  // k < 0: total internal reflection
+    if (!(k < 0.0)) {
+        ct = sqrt(k);
+        const double rs = (c - eta * ct) / (c + eta * ct);
+        const double rp = (eta * c - ct) / (eta * c + ct);
+        F = (rs * rs + rp * rp) / 2.0;
+    }
+    if (u <= F) {
+        const double c2 = 2.0 * c;
+        wi = mk(dh.x + c2 * m.x, dh.y + c2 * m.y, dh.z + c2 * m.z);
+        return true;
+    }
+    const double a = c / eta - ct;
+    wi = mk(dh.x / eta + a * m.x, dh.y / eta + a * m.y, dh.z / eta + a * m.z);
+    return false;
+}
+
 // Per-lane path state.
 struct Path {
     Ray r;
@@ -992,86 +1027,106 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
     double scale = 1.0;
     const bool matte = kind == kMatMatte;
     FLUX_CENSUS(P, 6 + cz);  // the lobe code: every lane whose path continues
-    V3 w = n;
-    if (!matte) {  // Reflective::path_shade materials.rs:56-72: r = -wo + n (n.wo) 2, wo = -d
-        const double ndotwo = -dot(n, d);
-        w = mk(d.x + n.x * ndotwo * 2.0, d.y + n.y * ndotwo * 2.0, d.z + n.z * ndotwo * 2.0);
-    }
-    if (kind == kMatReflective) {  // PerfectSpecular::sample_f brdf.rs:38-46
-        if (STATS) st.c[4]++;
-        wi = w;
-    } else {
-        double hx, hy, hz;
-        if (matte) {
-            FLUX_CENSUS(P, 7 + cz);
-            if (STATS) st.c[2]++;
-            const size_t N = P.nsamp;
-            // wave-uniform base (this pixel's set) + 32-bit per-lane byte offset -> saddr + voffset addressing
-            // analytic kernels: the set's rows from the context's DevSetRows record, one scalar load instead of a 64-bit multiply-add chain
-            // (a scalar instruction costs the issue-bound loop a third of a VALU instruction); the mesh kernels keep the arithmetic
-            // (their shading step is rare and the extra dependent load measured +0.5 % there)
-            const char *hbase = !TRIS ? reinterpret_cast<const char *>(set_rows_of(P, set).hemi)
-                                                         : reinterpret_cast<const char *>(P.hemi + (size_t)set * P.max_depth * N * 4);
-            const uint32_t hoff = ((uint32_t)(p.depth - 1) * (uint32_t)N + i) * 32u;
-            const double2 hxy = gather_global_d2(hbase, hoff);
-            hx = hxy.x;
-            hy = hxy.y;
-            hz = gather_global<double>(hbase, hoff + 16u);
-            if (TRIS && is_tri) scale = 1.0 / kInvPi;  // (n.wi) / ((n.wi) INV_PI); an analytic shape's record holds the product already
+    // The dielectric branch exists only in the FAST copy that serves scenes with a dielectric (FLUX_DIEL: render.hip's third
+    // inclusion of this file, chosen by RenderParams::has_diel) and, there, outside TYP (the launch never picks it for such a scene).
+    // The copy every other scene runs is compiled without it, so its code -- and, under contract(fast), every fusion decision of the
+    // lobe code -- is the one it had before the material existed.
+#if FLUX_DIEL
+    if (!TYP && kind == kMatDielectric) {  // extension: DESIGN.md §5c
+        // u: the hemi sample the Matte lobe reads at this depth (hemi_sets' z), addressed as there
+        const char *hbase = !TRIS ? reinterpret_cast<const char *>(set_rows_of(P, set).hemi)
+                                  : reinterpret_cast<const char *>(P.hemi + (size_t)set * P.max_depth * P.nsamp * 4);
+        const double u = gather_global<double>(hbase, ((uint32_t)(p.depth - 1) * P.nsamp + i) * 32u + 16u);
+        if (dielectric_dir(n, d, m_inv_e1, u, wi)) {  // reflected: weight 1; transmitted: transmit_color, (fr, fg, fb) as loaded
+            if (STATS) st.c[10]++;
+            fr = fg = fb = 1.0;
         } else {
-            FLUX_CENSUS(P, 8 + cz);
-            if (STATS) st.c[3]++;
-            // to_unit_hemi(pixel sample, exponent) (brdf.rs:64, lib.rs:133-142) with its sample-only factors read
-            // from the table (RenderParams::gloss): cos_theta = (1-y)^(1/(e+1)) = exp2(log2(1-y)/(e+1))
-            const char *gbase = !TRIS ? reinterpret_cast<const char *>(set_rows_of(P, set).gloss)
-                                                         : reinterpret_cast<const char *>(P.gloss + (size_t)set * P.nsamp * 4);
-            const double2 cs = gather_global_d2(gbase, i * 32u);
-            const double cos_theta = fastmath::fexp2_tab(m_inv_e1 * gather_global<double>(gbase, i * 32u + 16u), P.exp2c);   // 1 - y > 0 for every sample (y < 1)
-            const double sin_theta = fastmath::fsqrt(1.0 - cos_theta * cos_theta);
-            hx = sin_theta * cs.x;
-            hy = sin_theta * cs.y;
-            hz = cos_theta;
+            if (STATS) st.c[11]++;
         }
-        const V3 b1 = normalize(cross(mk(ax, 1.0, az), w));
-        const V3 b2 = cross(b1, w);
-        const double c1 = matte ? hy : hx, c2 = matte ? hx : hy;
-        const V3 q = mk(c1 * b1.x + c2 * b2.x, c1 * b1.y + c2 * b2.y, c1 * b1.z + c2 * b2.z);
-        const V3 hw = mk(hz * w.x, hz * w.y, hz * w.z);
-        const V3 wi0 = mk(q.x + hw.x, q.y + hw.y, q.z + hw.z);
-        if (matte) {
-            // brdf.rs:26 normalises wi; with a unit normal the frame (b2, b1, w) is orthonormal and h is a unit vector, so
-            // |wi0| = 1 to a few ulp already and the division changes nothing above rounding (as in to_unit_hemi): it is
-            // kept for the hits whose normal is NOT unit (a plane stored with a non-unit normal)
-            wi = wi0;
-            if (p_glossy_long) {  // the scene's flag (abi.hip): a scalar compare instead of a vote of the wave on `!unit_n`
-                const V3 wn = normalize(wi0);
-                wi = unit_n ? wi0 : wn;
+    } else
+#endif
+    {
+        V3 w = n;
+        if (!matte) {  // Reflective::path_shade materials.rs:56-72: r = -wo + n (n.wo) 2, wo = -d
+            const double ndotwo = -dot(n, d);
+            w = mk(d.x + n.x * ndotwo * 2.0, d.y + n.y * ndotwo * 2.0, d.z + n.z * ndotwo * 2.0);
+        }
+        if (kind == kMatReflective) {  // PerfectSpecular::sample_f brdf.rs:38-46
+            if (STATS) st.c[4]++;
+            wi = w;
+        } else {
+            double hx, hy, hz;
+            if (matte) {
+                FLUX_CENSUS(P, 7 + cz);
+                if (STATS) st.c[2]++;
+                const size_t N = P.nsamp;
+                // wave-uniform base (this pixel's set) + 32-bit per-lane byte offset -> saddr + voffset addressing
+                // analytic kernels: the set's rows from the context's DevSetRows record, one scalar load instead of a 64-bit multiply-add chain
+                // (a scalar instruction costs the issue-bound loop a third of a VALU instruction); the mesh kernels keep the arithmetic
+                // (their shading step is rare and the extra dependent load measured +0.5 % there)
+                const char *hbase = !TRIS ? reinterpret_cast<const char *>(set_rows_of(P, set).hemi)
+                                                             : reinterpret_cast<const char *>(P.hemi + (size_t)set * P.max_depth * N * 4);
+                const uint32_t hoff = ((uint32_t)(p.depth - 1) * (uint32_t)N + i) * 32u;
+                const double2 hxy = gather_global_d2(hbase, hoff);
+                hx = hxy.x;
+                hy = hxy.y;
+                hz = gather_global<double>(hbase, hoff + 16u);
+                if (TRIS && is_tri) scale = 1.0 / kInvPi;  // (n.wi) / ((n.wi) INV_PI); an analytic shape's record holds the product already
+            } else {
+                FLUX_CENSUS(P, 8 + cz);
+                if (STATS) st.c[3]++;
+                // to_unit_hemi(pixel sample, exponent) (brdf.rs:64, lib.rs:133-142) with its sample-only factors read
+                // from the table (RenderParams::gloss): cos_theta = (1-y)^(1/(e+1)) = exp2(log2(1-y)/(e+1))
+                const char *gbase = !TRIS ? reinterpret_cast<const char *>(set_rows_of(P, set).gloss)
+                                                             : reinterpret_cast<const char *>(P.gloss + (size_t)set * P.nsamp * 4);
+                const double2 cs = gather_global_d2(gbase, i * 32u);
+                const double cos_theta = fastmath::fexp2_tab(m_inv_e1 * gather_global<double>(gbase, i * 32u + 16u), P.exp2c);   // 1 - y > 0 for every sample (y < 1)
+                const double sin_theta = fastmath::fsqrt(1.0 - cos_theta * cos_theta);
+                hx = sin_theta * cs.x;
+                hy = sin_theta * cs.y;
+                hz = cos_theta;
             }
-        } else {  // brdf.rs:67-69: below the surface -> (-hx) u - hy v + hz w
-            const bool below = dot(n, wi0) < 0.0;
-            wi = wi0;
-            if (ballot64(below) != 0ull)  // (the mirrored direction and its six selects only in a wave that has such a lane)
-                wi = mk(below ? hw.x - q.x : wi0.x, below ? hw.y - q.y : wi0.y, below ? hw.z - q.z : wi0.z);
-            // The closed-form weight cs ks is the long form's value whenever the lobe (r.wi)^e is finite and non-zero.
-            // r.wi = hz |r|^2 and |r| = |d| for a unit normal, so it can only under- or overflow after a specular bounce off
-            // a NON-unit normal.  A scene that has one (a plane stored with a non-unit normal: P.glossy_long, uniform for the
-            // whole launch) takes the reference's long form (brdf.rs:73-76, materials.rs:69-70) for every glossy bounce and
-            // so gets its NaN (0 * inf) or subnormal-degraded weights; every other scene skips this with one scalar branch.
-            if (p_glossy_long) {
-                const double rdotwi = dot(w, wi), ndotwi = dot(n, wi);
-                const DevMaterial &Ml = P.mats[is_tri ? P.tris[slot].mat : P.frec[hit].orig_id];  // (a shape's material has the shape's index)
-                const double e = Ml.exponent;
-                const int parity = Ml.exp_parity;
-                // powf: negative base -> +|x|^e for an even integral e, -|x|^e for an odd one, NaN otherwise
-                double lobe = fastmath::fpow_pos(fabs(rdotwi), e);
-                if (e == 0.0) lobe = 1.0;
-                if (rdotwi < 0.0) lobe = parity == 1 ? lobe : (parity == 2 ? -lobe : __builtin_nan(""));
-                if (rdotwi != rdotwi) lobe = rdotwi;
-                const double pdf = lobe * ndotwi;
-                fr *= lobe;  // f = cs ks lobe (brdf.rs:75)
-                fg *= lobe;
-                fb *= lobe;
-                scale = ndotwi / pdf;
+            const V3 b1 = normalize(cross(mk(ax, 1.0, az), w));
+            const V3 b2 = cross(b1, w);
+            const double c1 = matte ? hy : hx, c2 = matte ? hx : hy;
+            const V3 q = mk(c1 * b1.x + c2 * b2.x, c1 * b1.y + c2 * b2.y, c1 * b1.z + c2 * b2.z);
+            const V3 hw = mk(hz * w.x, hz * w.y, hz * w.z);
+            const V3 wi0 = mk(q.x + hw.x, q.y + hw.y, q.z + hw.z);
+            if (matte) {
+                // brdf.rs:26 normalises wi; with a unit normal the frame (b2, b1, w) is orthonormal and h is a unit vector, so
+                // |wi0| = 1 to a few ulp already and the division changes nothing above rounding (as in to_unit_hemi): it is
+                // kept for the hits whose normal is NOT unit (a plane stored with a non-unit normal)
+                wi = wi0;
+                if (p_glossy_long) {  // the scene's flag (abi.hip): a scalar compare instead of a vote of the wave on `!unit_n`
+                    const V3 wn = normalize(wi0);
+                    wi = unit_n ? wi0 : wn;
+                }
+            } else {  // brdf.rs:67-69: below the surface -> (-hx) u - hy v + hz w
+                const bool below = dot(n, wi0) < 0.0;
+                wi = wi0;
+                if (ballot64(below) != 0ull)  // (the mirrored direction and its six selects only in a wave that has such a lane)
+                    wi = mk(below ? hw.x - q.x : wi0.x, below ? hw.y - q.y : wi0.y, below ? hw.z - q.z : wi0.z);
+                // The closed-form weight cs ks is the long form's value whenever the lobe (r.wi)^e is finite and non-zero.
+                // r.wi = hz |r|^2 and |r| = |d| for a unit normal, so it can only under- or overflow after a specular bounce off
+                // a NON-unit normal.  A scene that has one (a plane stored with a non-unit normal: P.glossy_long, uniform for the
+                // whole launch) takes the reference's long form (brdf.rs:73-76, materials.rs:69-70) for every glossy bounce and
+                // so gets its NaN (0 * inf) or subnormal-degraded weights; every other scene skips this with one scalar branch.
+                if (p_glossy_long) {
+                    const double rdotwi = dot(w, wi), ndotwi = dot(n, wi);
+                    const DevMaterial &Ml = P.mats[is_tri ? P.tris[slot].mat : P.frec[hit].orig_id];  // (a shape's material has the shape's index)
+                    const double e = Ml.exponent;
+                    const int parity = Ml.exp_parity;
+                    // powf: negative base -> +|x|^e for an even integral e, -|x|^e for an odd one, NaN otherwise
+                    double lobe = fastmath::fpow_pos(fabs(rdotwi), e);
+                    if (e == 0.0) lobe = 1.0;
+                    if (rdotwi < 0.0) lobe = parity == 1 ? lobe : (parity == 2 ? -lobe : __builtin_nan(""));
+                    if (rdotwi != rdotwi) lobe = rdotwi;
+                    const double pdf = lobe * ndotwi;
+                    fr *= lobe;  // f = cs ks lobe (brdf.rs:75)
+                    fg *= lobe;
+                    fb *= lobe;
+                    scale = ndotwi / pdf;
+                }
             }
         }
     }
@@ -1324,60 +1379,73 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
     V3 wi;
     double scale;  // (n . wi) / pdf
     const bool matte = kind == kMatMatte;
-    V3 w = n;
-    if (!matte) {
-        // Reflective::path_shade materials.rs:56-72; wo = -d, so -wo = d exactly
-        const V3 wo = mk(d.x * -1.0, d.y * -1.0, d.z * -1.0);
-        const double ndotwo = dot(n, wo);
-        w = mk(-wo.x + n.x * ndotwo * 2.0, -wo.y + n.y * ndotwo * 2.0, -wo.z + n.z * ndotwo * 2.0);  // r
-    }
-    if (kind == kMatReflective) {  // PerfectSpecular::sample_f brdf.rs:38-46
-        if (STATS) st.c[4]++;
-        wi = w;
-        const double pdf = dot(n, wi);
-        scale = dot(n, wi) / pdf;
-    } else {
-        double hx, hy, hz;
-        if (matte) {  // materials.rs:18-34 + Lambertian::sample_f brdf.rs:19-31
-            if (STATS) st.c[2]++;
-            const size_t N = P.nsamp;
-            const double *hp = P.hemi + (((size_t)set * P.max_depth + (p.depth - 1)) * N + i) * 4;
-            const double2 hxy = *reinterpret_cast<const double2 *>(hp);
-            hx = hxy.x;
-            hy = hxy.y;
-            hz = hp[2];
-        } else {  // GlossySpecular::sample_f brdf.rs:54-79
-            if (STATS) st.c[3]++;
-            FLUX_STAGE();
-            const V3 h = to_unit_hemi(p.sq, m_inv_e1);
-            FLUX_STAGE();
-            hx = h.x;
-            hy = h.y;
-            hz = h.z;
-        }
-        const double ax = matte ? 0.0034 : 0.00424, az = matte ? 0.0071 : 0.00764;
-        const V3 b1 = normalize(cross(mk(ax, 1.0, az), w));
-        const V3 b2 = cross(b1, w);
-        const double c1 = matte ? hy : hx, c2 = matte ? hx : hy;  // the coefficients of b1 and b2
-        const V3 q = mk(c1 * b1.x + c2 * b2.x, c1 * b1.y + c2 * b2.y, c1 * b1.z + c2 * b2.z);
-        const V3 hw = mk(hz * w.x, hz * w.y, hz * w.z);
-        const V3 wi0 = mk(q.x + hw.x, q.y + hw.y, q.z + hw.z);
-        if (matte) {
-            wi = normalize(wi0);  // brdf.rs:26
-            const double ndotwi = dot(n, wi);
-            const double pdf = ndotwi * kInvPi;
-            scale = ndotwi / pdf;
+    // (STRICT: one copy for every scene, the branch behind the scene's uniform flag -- without contraction the code around it computes
+    // the same bits whatever shape the branch gives the control flow)
+    if (P.has_diel != 0 && kind == kMatDielectric) {  // extension: DESIGN.md §5c -- the entry (1, 1, 1, 1) or (transmit_color, 1)
+        const double *hp = P.hemi + (((size_t)set * P.max_depth + (p.depth - 1)) * P.nsamp + i) * 4;
+        if (dielectric_dir(n, d, m_inv_e1, hp[2], wi)) {
+            if (STATS) st.c[10]++;
+            fr = fg = fb = 1.0;
         } else {
-            // brdf.rs:67-69: below the surface -> (u (-hx) - v hy) + w hz = (-q) + hw (a negated sum is the sum of the negated
-            // terms, exactly)
-            const bool below = dot(n, wi0) < 0.0;
-            wi = mk(below ? hw.x - q.x : wi0.x, below ? hw.y - q.y : wi0.y, below ? hw.z - q.z : wi0.z);
-            const double lobe = pow(dot(w, wi), m_exponent);
-            const double pdf = lobe * dot(n, wi);
-            fr = fr * lobe;
-            fg = fg * lobe;
-            fb = fb * lobe;
+            if (STATS) st.c[11]++;
+        }
+        scale = 1.0;
+    } else {
+        V3 w = n;
+        if (!matte) {
+            // Reflective::path_shade materials.rs:56-72; wo = -d, so -wo = d exactly
+            const V3 wo = mk(d.x * -1.0, d.y * -1.0, d.z * -1.0);
+            const double ndotwo = dot(n, wo);
+            w = mk(-wo.x + n.x * ndotwo * 2.0, -wo.y + n.y * ndotwo * 2.0, -wo.z + n.z * ndotwo * 2.0);  // r
+        }
+        if (kind == kMatReflective) {  // PerfectSpecular::sample_f brdf.rs:38-46
+            if (STATS) st.c[4]++;
+            wi = w;
+            const double pdf = dot(n, wi);
             scale = dot(n, wi) / pdf;
+        } else {
+            double hx, hy, hz;
+            if (matte) {  // materials.rs:18-34 + Lambertian::sample_f brdf.rs:19-31
+                if (STATS) st.c[2]++;
+                const size_t N = P.nsamp;
+                const double *hp = P.hemi + (((size_t)set * P.max_depth + (p.depth - 1)) * N + i) * 4;
+                const double2 hxy = *reinterpret_cast<const double2 *>(hp);
+                hx = hxy.x;
+                hy = hxy.y;
+                hz = hp[2];
+            } else {  // GlossySpecular::sample_f brdf.rs:54-79
+                if (STATS) st.c[3]++;
+                FLUX_STAGE();
+                const V3 h = to_unit_hemi(p.sq, m_inv_e1);
+                FLUX_STAGE();
+                hx = h.x;
+                hy = h.y;
+                hz = h.z;
+            }
+            const double ax = matte ? 0.0034 : 0.00424, az = matte ? 0.0071 : 0.00764;
+            const V3 b1 = normalize(cross(mk(ax, 1.0, az), w));
+            const V3 b2 = cross(b1, w);
+            const double c1 = matte ? hy : hx, c2 = matte ? hx : hy;  // the coefficients of b1 and b2
+            const V3 q = mk(c1 * b1.x + c2 * b2.x, c1 * b1.y + c2 * b2.y, c1 * b1.z + c2 * b2.z);
+            const V3 hw = mk(hz * w.x, hz * w.y, hz * w.z);
+            const V3 wi0 = mk(q.x + hw.x, q.y + hw.y, q.z + hw.z);
+            if (matte) {
+                wi = normalize(wi0);  // brdf.rs:26
+                const double ndotwi = dot(n, wi);
+                const double pdf = ndotwi * kInvPi;
+                scale = ndotwi / pdf;
+            } else {
+                // brdf.rs:67-69: below the surface -> (u (-hx) - v hy) + w hz = (-q) + hw (a negated sum is the sum of the negated
+                // terms, exactly)
+                const bool below = dot(n, wi0) < 0.0;
+                wi = mk(below ? hw.x - q.x : wi0.x, below ? hw.y - q.y : wi0.y, below ? hw.z - q.z : wi0.z);
+                const double lobe = pow(dot(w, wi), m_exponent);
+                const double pdf = lobe * dot(n, wi);
+                fr = fr * lobe;
+                fg = fg * lobe;
+                fb = fb * lobe;
+                scale = dot(n, wi) / pdf;
+            }
         }
     }
     // record (f, s); child ray starts at the hit point (materials.rs:26-29,65-68)
@@ -1512,7 +1580,7 @@ __device__ __forceinline__ void finish_pixel(const RenderParams &P, bool lane_on
 template <bool STATS>
 __device__ __forceinline__ void flush_stats(const RenderParams &P, Stats &st, uint32_t lane) {
     if (!STATS) return;
-    for (int c = 0; c < 10; ++c) {
+    for (int c = 0; c < 12; ++c) {
         unsigned v = st.c[c];
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0 && v) atomicAdd(P.stats + c, (unsigned long long)v);
@@ -3188,11 +3256,11 @@ static hipError_t launch_shade_rays_impl(const RenderParams &p, const double *d_
 }
 
 #if FLUX_FAST
-// the usual scene of the split kernel (scan_shapes_fast's TYP: these values become constants of the instantiation; and no disks: the
-// instantiation leaves their loop out)
+// the usual scene of the split kernel (scan_shapes_fast's TYP: these values become constants of the instantiation; and no disks and no
+// dielectrics: the instantiation leaves their loop and their lobe out)
 static bool split_typ(const RenderParams &p) {
     return p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 &&
-           p.fsph32 != nullptr && p.n_dsk == 0;
+           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0;
 }
 #endif
 
@@ -3266,7 +3334,9 @@ static LaunchPlan plan_render_impl(const RenderParams &p, int variant) {
         // not give the throughput back exactly (long-form glossy weights: P.glossy_long), keeps the ray queue and the immediate bounce.
         // C depends on the scene only through the size of its records, so a disk in place of a plane changes no lane a sample runs in.
         // FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT override C (at most what fits) and H.
-        if (!FLUX_HITQ_LIST || p.glossy_long == 0) {
+        // A scene with a dielectric keeps the ray queue too: a dielectric bounce's weight depends on the branch it took, which its hit
+        // record does not tell (DESIGN.md §5c).
+        if ((!FLUX_HITQ_LIST || p.glossy_long == 0) && p.has_diel == 0) {
             const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
             const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
             uint32_t cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
@@ -3318,7 +3388,7 @@ static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStre
     if (L.kernel == 4) {
         // the usual analytic set beside the mesh (scan_shapes_fast's TYP / MAX32: constants of the instantiation)
         const bool typ = L.lds_scene && p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.n_uni == 1 && p.fsph32 != nullptr &&
-                         p.n_dsk == 0;
+                         p.n_dsk == 0 && p.has_diel == 0;
         if (typ) {
             if (stats) render_bvh4_kernel<true, true, true><<<g, b, lds, stream>>>(p);
             else render_bvh4_kernel<false, true, true><<<g, b, lds, stream>>>(p);

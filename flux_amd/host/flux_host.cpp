@@ -76,7 +76,12 @@ MaterialData material(const Node &n, const std::string &what) {
         return GlossyReflectiveData{num(req(*b, "reflect_amount", w), w + ".reflect_amount"),
                                     color(req(*b, "reflect_color", w), w + ".reflect_color"),
                                     num(req(*b, "reflect_exponent", w), w + ".reflect_exponent")};
-    bad(what + ": unknown variant `" + tag + "`, expected one of `Matte`, `Emissive`, `Reflective`, `GlossyReflective`");
+    if (tag == "Dielectric") {  // extension (flux_host.hpp DielectricData)
+        const double ri = num(req(*b, "refraction_index", w), w + ".refraction_index");
+        if (!(std::isfinite(ri) && ri > 0.0)) bad(w + ".refraction_index: expected a finite number > 0");
+        return DielectricData{ri, color(req(*b, "transmit_color", w), w + ".transmit_color")};
+    }
+    bad(what + ": unknown variant `" + tag + "`, expected one of `Matte`, `Emissive`, `Reflective`, `GlossyReflective`, `Dielectric`");
 }
 
 ShapeData shape(const Node &n, const std::string &what) {
@@ -147,6 +152,10 @@ flux_material to_abi(const MaterialData &m) {
         set3(o.color, p->reflect_color);
         o.k = p->reflect_amount;
         o.exponent = p->reflect_exponent;
+    } else if (auto p = std::get_if<DielectricData>(&m)) {
+        o.kind = FLUX_MAT_DIELECTRIC;
+        set3(o.color, p->transmit_color);
+        o.k = p->refraction_index;
     }
     return o;
 }

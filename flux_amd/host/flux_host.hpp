@@ -41,7 +41,9 @@ struct MatteData { Color diffuse_color, ambient_color; double diffuse_coefficien
 struct EmissiveData { Color color; double power = 0; };
 struct ReflectiveData { double reflect_amount = 0; Color reflect_color; };
 struct GlossyReflectiveData { double reflect_amount = 0; Color reflect_color; double reflect_exponent = 0; };
-using MaterialData = std::variant<MatteData, EmissiveData, ReflectiveData, GlossyReflectiveData>;
+// extension (include/flux_abi.h FLUX_MAT_DIELECTRIC): Fresnel-sampled glass; a reference node cannot decode it
+struct DielectricData { double refraction_index = 1; Color transmit_color; };
+using MaterialData = std::variant<MatteData, EmissiveData, ReflectiveData, GlossyReflectiveData, DielectricData>;
 
 struct SphereData { Vec3 center; double radius = 0; MaterialData material; bool invert = false; };
 struct PlaneData { Vec3 point, normal; MaterialData material; };

@@ -68,16 +68,23 @@ void enc_material(Encoder &e, const MaterialData &m) {  // shapes.rs:42-81
         e.real(c->reflect_amount);
         e.key("reflect_color");
         enc_color(e, c->reflect_color);
-    } else {
-        const auto &g = std::get<GlossyReflectiveData>(m);
+    } else if (auto *g = std::get_if<GlossyReflectiveData>(&m)) {
         e.text("GlossyReflective");
         e.map(3);
         e.key("reflect_amount");
-        e.real(g.reflect_amount);
+        e.real(g->reflect_amount);
         e.key("reflect_color");
-        enc_color(e, g.reflect_color);
+        enc_color(e, g->reflect_color);
         e.key("reflect_exponent");
-        e.real(g.reflect_exponent);
+        e.real(g->reflect_exponent);
+    } else {  // extension: externally tagged like the others; a reference node rejects the unknown variant
+        const auto &dl = std::get<DielectricData>(m);
+        e.text("Dielectric");
+        e.map(2);
+        e.key("refraction_index");
+        e.real(dl.refraction_index);
+        e.key("transmit_color");
+        enc_color(e, dl.transmit_color);
     }
 }
 
@@ -386,6 +393,17 @@ bool dec_material(Decoder &d, MaterialData &m) {
                     if (k == "reflect_amount") return d.read_number(v.reflect_amount);
                     if (k == "reflect_color") return dec_color(d, v.reflect_color);
                     if (k == "reflect_exponent") return d.read_number(v.reflect_exponent);
+                    return d.skip();
+                }))
+                return false;
+            m = v;
+            return true;
+        }
+        if (name == "Dielectric") {  // extension
+            DielectricData v;
+            if (!read_struct(d, [&](const std::string &k) {
+                    if (k == "refraction_index") return d.read_number(v.refraction_index);
+                    if (k == "transmit_color") return dec_color(d, v.transmit_color);
                     return d.skip();
                 }))
                 return false;

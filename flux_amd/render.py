@@ -14,7 +14,8 @@ from . import _lib
 from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult
 
 STAT_NAMES = ("samples", "segments", "matte_bounces", "glossy_bounces", "specular_bounces",
-              "emissive_hits", "misses", "depth_exhausted", "bvh_nodes", "tris_tested")
+              "emissive_hits", "misses", "depth_exhausted", "bvh_nodes", "tris_tested",
+              "dielectric_reflections", "dielectric_transmissions")
 
 
 class Renderer:
@@ -169,8 +170,8 @@ class Renderer:
         return dict(zip(STAT_NAMES, [int(x) for x in buf]))
 
     def stats_raw(self) -> list:
-        """All FLUX_NUM_STATS slots (slots 10.. are reserved: 0 in the product build; experiment builds with
-        -DFLUX_DEBUG_TRIPS count loop trips there, scripts/trip_counts.py)."""
+        """All FLUX_NUM_STATS slots (10 and 11 count dielectric bounces, 12.. are reserved: 0 in the product build;
+        experiment builds with -DFLUX_DEBUG_TRIPS count loop trips in 10.., scripts/trip_counts.py)."""
         buf = (C.c_uint64 * _lib.NUM_STATS)()
         _lib.check(_lib.lib.flux_ctx_stats(self._handle(), buf, 0))
         return [int(x) for x in buf]

@@ -79,7 +79,17 @@ class GlossyReflectiveData:  # shapes.rs:77-81
     reflect_exponent: float
 
 
-MaterialData = Union[MatteData, EmissiveData, ReflectiveData, GlossyReflectiveData]  # shapes.rs:42-47
+@dataclass
+class DielectricData:
+    """Extension (absent in the reference: shapes.rs:42-47 has four materials): Fresnel-sampled glass.  YAML:
+        Dielectric: {refraction_index: 1.5, transmit_color: [1, 1, 1]}
+    refraction_index (finite, > 0) is the index of the medium on the side the normal points AWAY from, the other side's being 1.
+    Each hit reflects with the Fresnel probability F (weight 1) or transmits (weight transmit_color); DESIGN.md §5c."""
+    refraction_index: float
+    transmit_color: Vec3
+
+
+MaterialData = Union[MatteData, EmissiveData, ReflectiveData, GlossyReflectiveData, DielectricData]  # shapes.rs:42-47 + Dielectric
 
 
 @dataclass
@@ -186,8 +196,13 @@ def material_from_yaml(m, what="material") -> MaterialData:
         return GlossyReflectiveData(_num(b, "reflect_amount", w),
                                     _vec3(_req(b, "reflect_color", w), w + ".reflect_color"),
                                     _num(b, "reflect_exponent", w))
+    if tag == "Dielectric":  # extension
+        ri = _num(b, "refraction_index", w)
+        if not (math.isfinite(ri) and ri > 0.0):
+            raise SceneError(f"{w}.refraction_index: expected a finite number > 0, got {ri!r}")
+        return DielectricData(ri, _vec3(_req(b, "transmit_color", w), w + ".transmit_color"))
     raise SceneError(f"{what}: unknown variant `{tag}`, expected one of "
-                     "`Matte`, `Emissive`, `Reflective`, `GlossyReflective`")
+                     "`Matte`, `Emissive`, `Reflective`, `GlossyReflective`, `Dielectric`")
 
 
 def shape_from_yaml(m, what="shape") -> ShapeData:
@@ -271,6 +286,10 @@ def material_to_abi(m: MaterialData) -> _lib.FluxMaterial:
         out.color[:] = m.reflect_color
         out.k = m.reflect_amount
         out.exponent = m.reflect_exponent
+    elif isinstance(m, DielectricData):
+        out.kind = _lib.MAT_DIELECTRIC
+        out.color[:] = m.transmit_color
+        out.k = m.refraction_index
     else:
         raise TypeError(f"not a MaterialData: {m!r}")
     return out

@@ -54,13 +54,26 @@ extern "C" {
 #define FLUX_MAT_EMISSIVE 1    /* EmissiveData         shapes.rs:61-64 */
 #define FLUX_MAT_REFLECTIVE 2  /* ReflectiveData       shapes.rs:69-72 */
 #define FLUX_MAT_GLOSSY 3      /* GlossyReflectiveData shapes.rs:77-81 */
+/* EXTENSION (absent in the reference): Fresnel-sampled glass, see flux_material.  Added without an ABI version
+ * bump: a library that predates it rejects kind 4 in flux_ctx_create with FLUX_E_INVALID ("unknown material
+ * kind"), which is how a client detects support. */
+#define FLUX_MAT_DIELECTRIC 4
 
 /* MaterialData (shapes.rs:42-81) flattened:
  *   Matte     : color = diffuse_color, ambient = ambient_color (parsed but
  *               unused by path_shade, materials.rs:18-34), k = diffuse_coefficient
  *   Emissive  : color, k = power
  *   Reflective: color = reflect_color, k = reflect_amount
- *   Glossy    : color = reflect_color, k = reflect_amount, exponent = reflect_exponent */
+ *   Glossy    : color = reflect_color, k = reflect_amount, exponent = reflect_exponent
+ *   Dielectric (extension, FLUX_MAT_DIELECTRIC): color = transmit_color, k = refraction_index
+ *               (finite and > 0, else flux_ctx_create returns FLUX_E_INVALID); ambient and exponent
+ *               are ignored.  Allowed on every shape and mesh.  A hit with shading normal n (as for
+ *               the other materials), n^ = n/|n|, d^ = d/|d|, c = -d^.n^: from outside (c > 0)
+ *               eta = k, m = n^; else eta = 1/k, m = -n^, c = -c.  F = 1 if 1 - (1 - c^2)/eta^2 < 0
+ *               (total internal reflection), else the unpolarised Fresnel reflectance.  With u the
+ *               z of hemi_sets[set][depth-1][sample]: u <= F reflects, wi = d^ + 2c m, weight 1;
+ *               otherwise wi = d^/eta + (c/eta - c_t) m, weight color.  No emission, no ambient
+ *               term, no eta^2 radiance factor.  DESIGN.md section 5c. */
 typedef struct flux_material {
     int32_t kind;
     int32_t reserved;
@@ -260,7 +273,10 @@ double flux_ctx_last_kernel_ms(flux_ctx *ctx);
  * [0] samples, [1] ray segments, [2] Matte bounces, [3] glossy bounces,
  * [4] perfect-specular bounces, [5] emissive terminations, [6] misses,
  * [7] depth-exhausted paths, [8] BVH nodes visited, [9] triangles tested,
- * [10..15] reserved (0). */
+ * [10] dielectric reflections (total internal reflection included), [11] dielectric
+ * transmissions (both 0 for a scene without FLUX_MAT_DIELECTRIC), [12..15] reserved (0).
+ * Experiment builds with -DFLUX_DEBUG_TRIPS (never the product) write loop trip counts into
+ * slots 10..15, over the dielectric counters. */
 #define FLUX_NUM_STATS 16
 int flux_ctx_enable_stats(flux_ctx *ctx, int on);
 int flux_ctx_stats(flux_ctx *ctx, uint64_t out[FLUX_NUM_STATS], int reset);
