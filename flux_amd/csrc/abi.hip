@@ -12,11 +12,11 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <algorithm>
 #include <cstdlib>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/flux_abi.h"
@@ -102,523 +102,193 @@ static void free_ctx(flux_ctx *c) {
     (void)hipFree(c->d_tris);
     (void)hipFree(c->d_nodes);
     (void)hipFree(c->d_nodesq);
-    (void)hipFree(c->d_nodes4);
-    (void)hipFree(c->d_leaves);
+    (void)hipFree(c->d_arena);
     (void)hipFree(c->d_out);
     delete c;
 }
 
 void flux_ctx_destroy(flux_ctx *ctx) { free_ctx(ctx); }
 
-static void normalize3(const double in[3], double out[3]) {
-    double len = std::sqrt(in[0] * in[0] + in[1] * in[1] + in[2] * in[2]);
-    out[0] = in[0] / len;
-    out[1] = in[1] / len;
-    out[2] = in[2] / len;
-}
-static void cross3(const double a[3], const double b[3], double o[3]) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
+}  // extern "C"
+
+namespace flux {
+
+// a material's kind and, for a Dielectric, its refraction index; `what` and `i` name its owner ("shape 3", "mesh 0")
+static int validate_material(const flux_material &m, const char *what, uint64_t i) {
+    if (m.kind < FLUX_MAT_MATTE || m.kind > FLUX_MAT_DIELECTRIC)
+        return fail(FLUX_E_INVALID, "%s %llu: unknown material kind %d", what, (unsigned long long)i, m.kind);
+    if (m.kind == FLUX_MAT_DIELECTRIC && !(std::isfinite(m.k) && m.k > 0.0))
+        return fail(FLUX_E_INVALID, "%s %llu: dielectric refraction index must be finite and > 0, got %g", what, (unsigned long long)i, m.k);
+    return FLUX_OK;
 }
 
-// material_from_data (scene.rs:87-125) + the per-material constants of brdf.rs:30,45,76 / materials.rs:45
-static void fill_material(flux::DevMaterial &dm, const flux_material &m) {
-    dm.kind = m.kind;
-    dm.exponent = m.exponent;
-    dm.inv_e1 = 1.0 / (m.exponent + 1.0);
-    // powf(negative, e): +|x|^e for an even integral e, -|x|^e for an odd one, NaN otherwise
-    dm.exp_parity = 0;
-    if (std::isfinite(m.exponent) && std::floor(m.exponent) == m.exponent)
-        dm.exp_parity = (std::fabs(m.exponent) >= 9007199254740992.0 || std::fmod(m.exponent, 2.0) == 0.0) ? 1 : 2;
-    if (m.kind == FLUX_MAT_DIELECTRIC) {
-        // the transmitted bounce's weight as given; the refraction index where a Glossy material keeps 1 / (exponent + 1)
-        // (flux_device.h DevMaterial)
-        dm.exponent = 0.0;
-        dm.inv_e1 = m.k;
-        dm.exp_parity = 0;
-        dm.fr = m.color[0];
-        dm.fg = m.color[1];
-        dm.fb = m.color[2];
-        return;
-    }
-    double f[3];
-    for (int ch = 0; ch < 3; ch++) {
-        f[ch] = m.color[ch] * m.k;
-        if (m.kind == FLUX_MAT_MATTE) f[ch] = f[ch] * flux::kInvPi;  // brdf.rs:30
-    }
-    dm.fr = f[0];
-    dm.fg = f[1];
-    dm.fb = f[2];
-}
-
-int flux_ctx_create(const flux_scene_desc *scene, const flux_job_cfg *cfg, uint64_t seed, int device,
-                    flux_ctx **out) {
-    return flux_ctx_create_sets(scene, cfg, seed, device, 0, 1, out);
-}
-
-int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, uint64_t seed, int device,
-                         uint64_t first_set, uint64_t set_stride, flux_ctx **out) {
-    if (!scene || !cfg || !out) return fail(FLUX_E_INVALID, "flux_ctx_create: null argument");
-    *out = nullptr;
-    // where the wall time of this call goes (flux_ctx_create_timing): lap(k) books the time since the previous lap under word k
-    double laps[FLUX_CREATE_TIMING_WORDS] = {};
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](int k) {
-        const auto now = std::chrono::steady_clock::now();
-        laps[k] += std::chrono::duration<double, std::milli>(now - t_last).count();
-        t_last = now;
-    };
+int validate_job(const flux_scene_desc &scene, const flux_job_cfg &cfg, uint64_t first_set, uint64_t set_stride) {
     if (set_stride < 1 || first_set >= set_stride)
         return fail(FLUX_E_INVALID, "sample-set share: need set_stride >= 1 and first_set < set_stride, got %llu / %llu",
                     (unsigned long long)first_set, (unsigned long long)set_stride);
     if (set_stride > 0xffffffffull)  // stored as 32-bit (SetRange); first_set < set_stride is then in range too
         return fail(FLUX_E_INVALID, "sample-set share: set_stride %llu exceeds 2^32 - 1", (unsigned long long)set_stride);
-    if (cfg->sample_root < 1 || cfg->sample_root > 4096)
-        return fail(FLUX_E_INVALID, "sample_root must be in [1,4096], got %llu",
-                    (unsigned long long)cfg->sample_root);
-    if (cfg->max_trace_depth < 1 || cfg->max_trace_depth > 256)
-        return fail(FLUX_E_INVALID, "max_trace_depth must be in [1,256], got %llu",
-                    (unsigned long long)cfg->max_trace_depth);
+    if (cfg.sample_root < 1 || cfg.sample_root > 4096)
+        return fail(FLUX_E_INVALID, "sample_root must be in [1,4096], got %llu", (unsigned long long)cfg.sample_root);
+    if (cfg.max_trace_depth < 1 || cfg.max_trace_depth > 256)
+        return fail(FLUX_E_INVALID, "max_trace_depth must be in [1,256], got %llu", (unsigned long long)cfg.max_trace_depth);
     // the render kernels address a pixel's Lambertian samples with a 32-bit byte offset from the set's base:
     // max_trace_depth * sample_root^2 * 32 B must stay below 4 GiB (the table of even ONE narrow image row would
     // otherwise be enormous: this only excludes e.g. sample_root 4096 with depth >= 8)
-    if ((uint64_t)cfg->max_trace_depth * cfg->sample_root * cfg->sample_root * 32ull >= (1ull << 32))
+    if ((uint64_t)cfg.max_trace_depth * cfg.sample_root * cfg.sample_root * 32ull >= (1ull << 32))
         return fail(FLUX_E_INVALID, "max_trace_depth * sample_root^2 = %llu is too large (limit 2^27 = 134217728)",
-                    (unsigned long long)(cfg->max_trace_depth * cfg->sample_root * cfg->sample_root));
-    if (scene->image_width < 1 || scene->image_height < 1 || scene->image_width > 65535 ||
-        scene->image_height > (1u << 20))
-        return fail(FLUX_E_INVALID, "image size %llux%llu out of range",
-                    (unsigned long long)scene->image_width, (unsigned long long)scene->image_height);
-    if (scene->num_shapes > 0 && !scene->shapes)
-        return fail(FLUX_E_INVALID, "num_shapes > 0 but shapes is null");
-    if (scene->num_shapes > 4096)
-        return fail(FLUX_E_INVALID, "flat shape list limited to 4096 shapes, got %llu",
-                    (unsigned long long)scene->num_shapes);
-    for (uint64_t i = 0; i < scene->num_shapes; i++) {
-        const flux_shape &s = scene->shapes[i];
+                    (unsigned long long)(cfg.max_trace_depth * cfg.sample_root * cfg.sample_root));
+    if (scene.image_width < 1 || scene.image_height < 1 || scene.image_width > 65535 || scene.image_height > (1u << 20))
+        return fail(FLUX_E_INVALID, "image size %llux%llu out of range", (unsigned long long)scene.image_width,
+                    (unsigned long long)scene.image_height);
+    if (scene.num_shapes > 0 && !scene.shapes) return fail(FLUX_E_INVALID, "num_shapes > 0 but shapes is null");
+    if (scene.num_shapes > 4096)
+        return fail(FLUX_E_INVALID, "flat shape list limited to 4096 shapes, got %llu", (unsigned long long)scene.num_shapes);
+    for (uint64_t i = 0; i < scene.num_shapes; i++) {
+        const flux_shape &s = scene.shapes[i];
         if (s.kind != FLUX_SHAPE_SPHERE && s.kind != FLUX_SHAPE_PLANE && s.kind != FLUX_SHAPE_DISK)
             return fail(FLUX_E_INVALID, "shape %llu: unknown kind %d", (unsigned long long)i, s.kind);
         if (s.kind == FLUX_SHAPE_DISK && !(std::isfinite(s.radius) && s.radius >= 0.0))
             return fail(FLUX_E_INVALID, "shape %llu: disk radius must be finite and >= 0, got %g", (unsigned long long)i, s.radius);
-        if (s.material.kind < FLUX_MAT_MATTE || s.material.kind > FLUX_MAT_DIELECTRIC)
-            return fail(FLUX_E_INVALID, "shape %llu: unknown material kind %d", (unsigned long long)i,
-                        s.material.kind);
-        if (s.material.kind == FLUX_MAT_DIELECTRIC && !(std::isfinite(s.material.k) && s.material.k > 0.0))
-            return fail(FLUX_E_INVALID, "shape %llu: dielectric refraction index must be finite and > 0, got %g", (unsigned long long)i,
-                        s.material.k);
+        if (int rc = validate_material(s.material, "shape", i)) return rc;
     }
-    if (scene->num_meshes > 0 && !scene->meshes)
-        return fail(FLUX_E_INVALID, "num_meshes > 0 but meshes is null");
+    if (scene.num_meshes > 0 && !scene.meshes) return fail(FLUX_E_INVALID, "num_meshes > 0 but meshes is null");
     uint64_t total_tris = 0;
-    for (uint64_t m = 0; m < scene->num_meshes; m++) {
-        const flux_mesh &me = scene->meshes[m];
-        if (me.material.kind < FLUX_MAT_MATTE || me.material.kind > FLUX_MAT_DIELECTRIC)
-            return fail(FLUX_E_INVALID, "mesh %llu: unknown material kind %d", (unsigned long long)m, me.material.kind);
-        if (me.material.kind == FLUX_MAT_DIELECTRIC && !(std::isfinite(me.material.k) && me.material.k > 0.0))
-            return fail(FLUX_E_INVALID, "mesh %llu: dielectric refraction index must be finite and > 0, got %g", (unsigned long long)m,
-                        me.material.k);
+    for (uint64_t m = 0; m < scene.num_meshes; m++) {
+        const flux_mesh &me = scene.meshes[m];
+        if (int rc = validate_material(me.material, "mesh", m)) return rc;
         if (me.num_triangles && (!me.vertices || !me.indices))
             return fail(FLUX_E_INVALID, "mesh %llu: null vertices/indices", (unsigned long long)m);
         for (uint64_t k = 0; k < 3 * me.num_triangles; k++)
             if (me.indices[k] >= me.num_vertices)
-                return fail(FLUX_E_INVALID, "mesh %llu: vertex index %u out of range (%llu vertices)",
-                            (unsigned long long)m, me.indices[k], (unsigned long long)me.num_vertices);
+                return fail(FLUX_E_INVALID, "mesh %llu: vertex index %u out of range (%llu vertices)", (unsigned long long)m,
+                            me.indices[k], (unsigned long long)me.num_vertices);
         total_tris += me.num_triangles;
     }
     if (total_tris >= (1ull << 27))  // leaf references pack (first << 3 | count) into 31 bits
         return fail(FLUX_E_INVALID, "too many triangles: %llu", (unsigned long long)total_tris);
-    lap(FLUX_CREATE_MS_HOST);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(FLUX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
+    return FLUX_OK;
+}
 
+int build_host(const flux_scene_desc &scene, HostScene &host) {
+    std::string error;
+    const int rc = build_host_scene(scene, host, error);
+    return rc == FLUX_OK ? rc : fail(rc, "%s", error.c_str());
+}
+
+namespace {
+struct FreeCtx {
+    void operator()(flux_ctx *c) const { free_ctx(c); }
+};
+}  // namespace
+
+int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int device, uint64_t first_set, uint64_t set_stride,
+           CreateLaps &laps, flux_ctx **out) {
+    *out = nullptr;
     DeviceGuard guard(device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", device);
     (void)hipFree(nullptr);  // the runtime's lazy per-device initialisation, booked under its own word (zero once the process has used the device)
-    lap(FLUX_CREATE_MS_RUNTIME);
+    laps.lap(FLUX_CREATE_MS_RUNTIME);
 
-    flux_ctx *c = new (std::nothrow) flux_ctx();
-    if (!c) return fail(FLUX_E_NOMEM, "host allocation failed");
+    std::unique_ptr<flux_ctx, FreeCtx> c(new flux_ctx());
     c->device = device;
     c->seed = seed;
-    c->n = (uint32_t)cfg->sample_root;
+    c->n = (uint32_t)cfg.sample_root;
     c->N = c->n * c->n;
-    c->D = (uint32_t)cfg->max_trace_depth;
-    c->W = (uint32_t)scene->image_width;
-    c->H = (uint32_t)scene->image_height;
-    c->S = c->W;  // workers.rs:50: num_sets = image_width
+    c->D = (uint32_t)cfg.max_trace_depth;
+    c->W = (uint32_t)h.rp.img_w;
+    c->H = (uint32_t)h.rp.img_h;
+    c->S = h.rp.num_sets;
     // the sets this context holds tables for: all of them, or one rank's share of a set-sharded render
     c->sets.first = (uint32_t)first_set;
     c->sets.stride = (uint32_t)set_stride;
     c->sets.count = first_set < c->S ? (uint32_t)((c->S - first_set + set_stride - 1) / set_stride) : 0u;
-
-    // ---- Scene::from_data: per-shape constants -------------------------------
-    const size_t ns = (size_t)scene->num_shapes;
-    std::vector<flux::DevShape> shapes(ns ? ns : 1);
-    std::vector<flux::DevMaterial> mats(ns + (size_t)scene->num_meshes + 1);
-    std::memset(shapes.data(), 0, shapes.size() * sizeof(flux::DevShape));
-    std::memset(mats.data(), 0, mats.size() * sizeof(flux::DevMaterial));
-    for (size_t i = 0; i < ns; i++) {
-        const flux_shape &s = scene->shapes[i];
-        flux::DevShape &d = shapes[i];
-        d.kind = s.kind;
-        d.px = s.p[0];
-        d.py = s.p[1];
-        d.pz = s.p[2];
-        if (s.kind == FLUX_SHAPE_SPHERE) {
-            d.radius = s.radius;
-            d.rr = s.radius * s.radius;
-            d.inv = s.invert ? -1.0 : 1.0;
-            d.inv_rad = d.inv / s.radius;
-            // Sphere::new: shapes.rs:154-169
-            d.c0x = s.p[0] - s.radius;
-            d.c0y = s.p[1] - s.radius;
-            d.c0z = s.p[2] - s.radius;
-            d.c1x = s.p[0] + s.radius;
-            d.c1y = s.p[1] + s.radius;
-            d.c1z = s.p[2] + s.radius;
-        } else {  // plane, disk: the normal as given
-            d.c0x = s.n[0];
-            d.c0y = s.n[1];
-            d.c0z = s.n[2];
-            if (s.kind == FLUX_SHAPE_DISK) {
-                d.radius = s.radius;
-                d.rr = s.radius * s.radius;
-            }
-        }
-        fill_material(mats[i], s.material);
-    }
-    // FAST path layout of the same shapes: scan records (spheres, planes, disks) + hit records in scan order
-    std::vector<flux::DevScanSphere> fsph;
-    std::vector<flux::DevScanPlane> fpln;
-    std::vector<flux::DevScanDisk> fdsk;
-    std::vector<flux::DevHitRec> frec_s, frec_p, frec_d;
-    for (size_t i = 0; i < ns; i++) {
-        const flux::DevShape &d = shapes[i];
-        const flux::DevMaterial &m = mats[i];
-        flux::DevHitRec r;
-        std::memset(&r, 0, sizeof(r));
-        // (the FAST bounce weight: flux_device.h DevHitRec; the product is the one the kernels formed per bounce, `fr * scale`)
-        const double wsc = m.kind == flux::kMatMatte ? 1.0 / flux::kInvPi : 1.0;
-        r.fr = m.kind == flux::kMatMatte ? m.fr * wsc : m.fr;
-        r.fg = m.kind == flux::kMatMatte ? m.fg * wsc : m.fg;
-        r.fb = m.kind == flux::kMatMatte ? m.fb * wsc : m.fb;
-        r.inv_e1 = m.inv_e1;
-        r.ax = m.kind == flux::kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
-        r.az = m.kind == flux::kMatMatte ? 0.0071 : 0.00764;
-        r.shape_kind = d.kind; r.mat_kind = m.kind; r.orig_id = (int32_t)i;
-        // spheres: |(hit - centre) / radius| = 1 to rounding; planes and disks use the stored normal as is (shapes.rs:135-152)
-        r.unit_normal = d.kind == flux::kShapeSphere ||
-                        std::fabs((d.c0x * d.c0x + d.c0y * d.c0y + d.c0z * d.c0z) - 1.0) <= 4.0 * 2.220446049250313e-16;
-        if (d.kind == flux::kShapeSphere) {
-            r.cx = d.px; r.cy = d.py; r.cz = d.pz; r.inv_rad = d.inv_rad;
-            fsph.push_back(flux::DevScanSphere{d.px, d.py, d.pz, d.rr});
-            frec_s.push_back(r);
-        } else if (d.kind == flux::kShapeDisk) {
-            r.cx = d.c0x; r.cy = d.c0y; r.cz = d.c0z;
-            flux::DevScanDisk dk;
-            std::memset(&dk, 0, sizeof(dk));
-            dk.px = d.px; dk.py = d.py; dk.pz = d.pz; dk.nx = d.c0x; dk.ny = d.c0y; dk.nz = d.c0z; dk.id = (int32_t)i; dk.rr = d.rr;
-            fdsk.push_back(dk);
-            frec_d.push_back(r);
-        } else {
-            r.cx = d.c0x; r.cy = d.c0y; r.cz = d.c0z;
-            flux::DevScanPlane pl;
-            std::memset(&pl, 0, sizeof(pl));
-            pl.px = d.px; pl.py = d.py; pl.pz = d.pz; pl.nx = d.c0x; pl.ny = d.c0y; pl.nz = d.c0z; pl.id = (int32_t)i;
-            fpln.push_back(pl);
-            frec_p.push_back(r);
-        }
-    }
-    const size_t fs_sph_bytes = (fsph.size() + 1) * sizeof(flux::DevScanSphere);  // +1: the scan reads one record ahead
-    const size_t fs_pln_bytes = (fpln.size() + 1) * sizeof(flux::DevScanPlane);
-    const size_t fs_rec_bytes = (ns + 1) * sizeof(flux::DevHitRec);
-    // f32 records of the conservative candidate filter (flux_device.h DevScanSphere32): valid while every magnitude
-    // stays far inside f32's range (squares are formed), else the f64 filter is used
-    std::vector<flux::DevScanSphere32> fsph32((fsph.size() + 1) / 2);
-    std::memset(fsph32.data(), 0, fsph32.size() * sizeof(flux::DevScanSphere32));
-    bool filter32_ok = true;
-    for (size_t k = 0; k < fsph.size(); k++) {
-        const flux::DevScanSphere &sp = fsph[k];
-        const double pp = sp.px * sp.px + sp.py * sp.py + sp.pz * sp.pz;
-        if (!(pp < 1e30) || !(sp.rr < 1e30)) filter32_ok = false;
-    }
-    // `invert` spheres (environments: nearly every ray is inside and hits them) are tested for all lanes together with
-    // scalar operands instead of through every lane's candidate list (render_body.inc scan_shapes_fast): up to two,
-    // given a filter record that never passes (c = 3e38: "entirely behind the origin" or dq < 0)
-    int n_uni = 0, uni_idx[2] = {0, 0};
-    if (filter32_ok)
-        for (size_t k = 0; k < fsph.size() && n_uni < FLUX_UNI_SPHERES; k++)
-            if (frec_s[k].inv_rad < 0.0) uni_idx[n_uni++] = (int)k;
-    for (size_t k = 0; k < fsph.size(); k++) {
-        const flux::DevScanSphere &sp = fsph[k];
-        const double pp = sp.px * sp.px + sp.py * sp.py + sp.pz * sp.pz;
-        const double ppr = (pp - sp.rr) - 8e-6 * (pp + sp.rr) - 1e-30;
-        float f = (float)ppr;
-        if ((double)f > ppr) f = std::nextafterf(f, -INFINITY);  // rounded down: the bias is never reduced
-        flux::DevScanSphere32 &d = fsph32[k / 2];
-        d.px[k & 1] = -(float)sp.px;  // the NEGATED centre (flux_device.h DevScanSphere32)
-        d.py[k & 1] = -(float)sp.py;
-        d.pz[k & 1] = -(float)sp.pz;
-        d.ppr[k & 1] = f;
-        if ((n_uni > 0 && uni_idx[0] == (int)k) || (n_uni > 1 && uni_idx[1] == (int)k)) {
-            d.px[k & 1] = d.py[k & 1] = d.pz[k & 1] = 0.0f;
-            d.ppr[k & 1] = 3.0e38f;
-        }
-    }
-    const size_t fs_s32_bytes = (fsph32.size() + 4) * sizeof(flux::DevScanSphere32);  // +4 pairs: the filter loads whole groups of 8 spheres
-    // STRICT's sphere records in SCAN order (round 5: its scan takes its candidates from the same f32 filter, whose bit k is scan
-    // sphere k): the DevShape as it is, with the YAML index -- the tie rule's key -- in pad0
-    std::vector<flux::DevShape> sshapes;
-    for (size_t i = 0; i < ns; i++)
-        if (shapes[i].kind == flux::kShapeSphere) {
-            sshapes.push_back(shapes[i]);
-            sshapes.back().pad0 = (int32_t)i;
-        }
-    const size_t fs_ss_off = (fs_sph_bytes + fs_pln_bytes + fs_rec_bytes + fs_s32_bytes + 127) & ~(size_t)127;
-    const size_t fs_ss_bytes = (sshapes.size() + 1) * sizeof(flux::DevShape);
-    // The split kernel's per-pixel constants of the primary ray (trace.rs:56-57, 93-94) as two tables a wave reads with scalar loads in
-    // its ray-generation step: x - half_w for every column, (H - row) - half_h for every row -- the same two IEEE operations the
-    // kernels perform, done once here
-    const size_t fs_px_off = (fs_ss_off + fs_ss_bytes + 127) & ~(size_t)127;
-    // the disks' scan records last (+1: as the other scan records, one past the end stays addressable)
-    const size_t fs_dsk_off = (fs_px_off + ((size_t)c->W + c->H) * sizeof(double) + 127) & ~(size_t)127;
-    std::vector<unsigned char> fscene(fs_dsk_off + (fdsk.size() + 1) * sizeof(flux::DevScanDisk), 0);
-    if (!fdsk.empty()) std::memcpy(fscene.data() + fs_dsk_off, fdsk.data(), fdsk.size() * sizeof(flux::DevScanDisk));
-    {
-        double *pxc = reinterpret_cast<double *>(fscene.data() + fs_px_off);
-        const double half_w = (double)c->W * 0.5, half_h = (double)c->H * 0.5;
-        for (uint32_t x = 0; x < c->W; x++) pxc[x] = (double)(int32_t)x - half_w;
-        for (uint32_t y = 0; y < c->H; y++) pxc[c->W + y] = (double)((int32_t)c->H - (int32_t)y) - half_h;
-    }
-    if (!sshapes.empty()) std::memcpy(fscene.data() + fs_ss_off, sshapes.data(), sshapes.size() * sizeof(flux::DevShape));
-    if (!fsph32.empty())
-        std::memcpy(fscene.data() + fs_sph_bytes + fs_pln_bytes + fs_rec_bytes, fsph32.data(), fsph32.size() * sizeof(flux::DevScanSphere32));
-    if (!fsph.empty()) std::memcpy(fscene.data(), fsph.data(), fsph.size() * sizeof(flux::DevScanSphere));
-    if (!fpln.empty()) std::memcpy(fscene.data() + fs_sph_bytes, fpln.data(), fpln.size() * sizeof(flux::DevScanPlane));
-    if (!frec_s.empty()) std::memcpy(fscene.data() + fs_sph_bytes + fs_pln_bytes, frec_s.data(), frec_s.size() * sizeof(flux::DevHitRec));
-    if (!frec_p.empty())
-        std::memcpy(fscene.data() + fs_sph_bytes + fs_pln_bytes + frec_s.size() * sizeof(flux::DevHitRec), frec_p.data(),
-                    frec_p.size() * sizeof(flux::DevHitRec));
-    if (!frec_d.empty())
-        std::memcpy(fscene.data() + fs_sph_bytes + fs_pln_bytes + (frec_s.size() + frec_p.size()) * sizeof(flux::DevHitRec), frec_d.data(),
-                    frec_d.size() * sizeof(flux::DevHitRec));
-
-    // extension: meshes -> triangle records (hit order: after all shapes) + BVH
-    std::vector<flux::DevTri> tris((size_t)total_tris);
-    std::vector<flux::DevNode> nodes;
-    {
-        // one record per triangle: edges, the geometric normal (a square root and three divisions each).  A million of them take
-        // tens of milliseconds on one core, so large meshes are dealt to threads by index range (FLUX_BUILD_THREADS, as for the BVH)
-        std::vector<size_t> first((size_t)scene->num_meshes + 1, 0);
-        for (uint64_t m = 0; m < scene->num_meshes; m++) {
-            fill_material(mats[ns + (size_t)m], scene->meshes[m].material);
-            first[(size_t)m + 1] = first[(size_t)m] + (size_t)scene->meshes[m].num_triangles;
-        }
-        auto make = [&](size_t lo, size_t hi) {
-            size_t m = 0;
-            for (size_t g = lo; g < hi; g++) {
-                while (g >= first[m + 1]) m++;
-                const flux_mesh &me = scene->meshes[m];
-                const size_t k = g - first[m];
-                const double *a = me.vertices + 3 * (size_t)me.indices[3 * k];
-                const double *b = me.vertices + 3 * (size_t)me.indices[3 * k + 1];
-                const double *d = me.vertices + 3 * (size_t)me.indices[3 * k + 2];
-                flux::DevTri t;
-                std::memset(&t, 0, sizeof(t));
-                t.v0x = a[0]; t.v0y = a[1]; t.v0z = a[2];
-                t.e1x = b[0] - a[0]; t.e1y = b[1] - a[1]; t.e1z = b[2] - a[2];
-                t.e2x = d[0] - a[0]; t.e2y = d[1] - a[1]; t.e2z = d[2] - a[2];
-                const double e1[3] = {t.e1x, t.e1y, t.e1z}, e2[3] = {t.e2x, t.e2y, t.e2z};
-                double nn[3], nu[3];
-                cross3(e1, e2, nn);
-                if (nn[0] == 0.0 && nn[1] == 0.0 && nn[2] == 0.0) {
-                    // a triangle whose e1 x e2 is exactly zero (repeated or exactly collinear vertices) has no surface:
-                    // clearing the edges makes Moeller-Trumbore's det exactly 0, so it is never hit (and never NaN)
-                    t.e1x = t.e1y = t.e1z = t.e2x = t.e2y = t.e2z = 0.0;
-                    nu[0] = nu[1] = nu[2] = 0.0;
-                } else {
-                    normalize3(nn, nu);
-                }
-                t.nx = nu[0]; t.ny = nu[1]; t.nz = nu[2];
-                t.id = (int32_t)(ns + g);
-                t.mat = (int32_t)(ns + m);
-                tris[g] = t;
-            }
-        };
-        unsigned threads = std::thread::hardware_concurrency();
-        if (const char *env = std::getenv("FLUX_BUILD_THREADS")) threads = (unsigned)std::max(1, std::atoi(env));
-        threads = std::min(std::max(threads, 1u), 16u);
-        const size_t n = tris.size();
-        if (threads > 1 && n >= 65536) {
-            std::vector<std::thread> pool;
-            for (unsigned t = 0; t < threads; t++) pool.emplace_back(make, n * t / threads, n * (t + 1) / threads);
-            for (std::thread &t : pool) t.join();
-        } else {
-            make(0, n);
-        }
-    }
-    // the traversal addresses node and triangle records by 32-bit byte offsets from their bases (render_body.inc)
-    if (tris.size() * sizeof(flux::DevTri) >= (1ull << 32)) {
-        int code = fail(FLUX_E_INVALID, "%zu triangles exceed the %llu a context can hold", tris.size(),
-                        (unsigned long long)((1ull << 32) / sizeof(flux::DevTri)));
-        delete c;
-        return code;
-    }
-    std::vector<flux::DevNodeQ> nodesq;
-    // the FAST traversal kernel's layout: 4-wide nodes + leaf records (flux_bvh.h)
-    std::vector<flux::DevNode4Q> nodes4;
-    std::vector<flux::DevLeafRec> leafrecs;
-    flux::build_bvh(tris, nodes, c->bvh);
-    if (!flux::quantize_bvh(nodes, nodesq, c->bvh)) {
-        int code = fail(FLUX_E_INVALID, "BVH quantisation lost containment (mesh coordinates beyond the 16-bit grid's reach)");
-        delete c;
-        return code;
-    }
-    // round 5: nodes and leaf records in ONE arena of 64-B units, a node's children contiguous (flux_bvh.h DevNode4A); an
-    // arena beyond the 26-bit unit index comes back empty and the mesh is walked by the binary tree's kernel
-    std::vector<flux::DevNode4A> arena;
-    flux::build_wide_arena(nodes, nodesq, tris, arena, c->bvh);
-    if (nodes4.size() * sizeof(flux::DevNode4Q) >= (1ull << 32) || leafrecs.size() * sizeof(flux::DevLeafRec) >= (1ull << 32) ||
-        leafrecs.size() >= (1ull << 28)) {
-        int code = fail(FLUX_E_INVALID, "mesh too large for the traversal kernel's 32-bit record offsets");
-        delete c;
-        return code;
-    }
-    if (c->bvh.max_depth > (uint64_t)flux::kBvhMaxDepth) {
-        int code = fail(FLUX_E_INVALID, "BVH depth %llu exceeds %d (degenerate mesh)",
-                        (unsigned long long)c->bvh.max_depth, flux::kBvhMaxDepth);
-        delete c;
-        return code;
+    c->bvh = h.bvh;
+    for (int a = 0; a < 3; a++) {
+        c->U[a] = h.U[a];
+        c->V[a] = h.V[a];
+        c->Wv[a] = h.W[a];
     }
 
-    // ---- CameraBasis::new: scene.rs:28-35 --------------------------------------
-    double em[3] = {scene->eye[0] - scene->look_at[0], scene->eye[1] - scene->look_at[1],
-                    scene->eye[2] - scene->look_at[2]};
-    double upxw[3];
-    normalize3(em, c->Wv);
-    cross3(scene->up, c->Wv, upxw);
-    normalize3(upxw, c->U);
-    cross3(c->Wv, c->U, c->V);
-
-    flux::RenderParams &rp = c->rp;
-    rp.ex = scene->eye[0];
-    rp.ey = scene->eye[1];
-    rp.ez = scene->eye[2];
-    rp.Ux = c->U[0];
-    rp.Uy = c->U[1];
-    rp.Uz = c->U[2];
-    rp.Vx = c->V[0];
-    rp.Vy = c->V[1];
-    rp.Vz = c->V[2];
-    rp.Wx = c->Wv[0];
-    rp.Wy = c->Wv[1];
-    rp.Wz = c->Wv[2];
-    rp.aps = scene->pixel_size / scene->zoom_factor;                  // trace.rs:60
-    rp.half_w = (double)c->W * 0.5;                                   // trace.rs:57
-    rp.half_h = (double)c->H * 0.5;                                   // trace.rs:56
-    rp.factor = scene->focal_distance / scene->view_plane_distance;   // trace.rs:45
-    rp.focal = scene->focal_distance;
-    rp.lens_radius = scene->lens_radius;
-    rp.bgr = scene->background[0];
-    rp.bgg = scene->background[1];
-    rp.bgb = scene->background[2];
-    rp.pixel_denom = 1.0 / (double)((uint64_t)c->n * c->n);           // trace.rs:59
-    rp.img_w = (int32_t)c->W;
-    rp.img_h = (int32_t)c->H;
-    rp.n_shapes = (int32_t)ns;
-    rp.max_depth = (int32_t)c->D;
-    rp.nsamp = c->N;
-    rp.num_sets = c->S;
-
-    lap(FLUX_CREATE_MS_HOST);
-    // ---- HBM allocations ------------------------------------------------------
+    // ---- HBM allocations and uploads -------------------------------------------
     const size_t own = c->sets.count ? c->sets.count : 1;  // a share past the last set holds nothing (allocate one slot)
     const size_t pix_bytes = own * c->N * sizeof(double2);
-    const size_t hemi_bytes = own * c->D * c->N * flux::kHemiDoubles * sizeof(double);
+    const size_t hemi_bytes = own * c->D * c->N * kHemiDoubles * sizeof(double);
     const size_t perm_bytes = (size_t)c->H * c->S * sizeof(int32_t);
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) {
+    auto alloc = [&](auto **p, size_t bytes) {
         if (e != hipSuccess) return;
-        lap(FLUX_CREATE_MS_UPLOAD);
-        e = hipMalloc(p, bytes);
+        laps.lap(FLUX_CREATE_MS_UPLOAD);
+        e = hipMalloc((void **)p, bytes);
         if (e == hipSuccess) c->device_bytes += bytes;
-        lap(FLUX_CREATE_MS_ALLOC);
+        laps.lap(FLUX_CREATE_MS_ALLOC);
     };
-    alloc((void **)&c->d_shapes, shapes.size() * sizeof(flux::DevShape));
-    // the materials, followed by their bounce weights {f * (n.wi)/pdf in FAST's closed form: f / INV_PI for Matte, f otherwise; pad}
-    // of 32 B each (render_bvh4_kernel keeps a path's material indices and multiplies the weights when the path ends)
-    std::vector<double> wtab(mats.size() * 4, 0.0);
-    for (size_t k = 0; k < mats.size(); k++) {
-        const double sc = mats[k].kind == flux::kMatMatte ? 1.0 / flux::kInvPi : 1.0;
-        wtab[4 * k] = mats[k].fr * sc;
-        wtab[4 * k + 1] = mats[k].fg * sc;
-        wtab[4 * k + 2] = mats[k].fb * sc;
+    auto copy = [&](void *dst, const auto &v) {
+        if (e == hipSuccess) e = hipMemcpy(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
+    };
+    auto alloc_copy = [&](auto **p, const auto &v) {
+        alloc(p, v.size() * sizeof(v[0]));
+        copy(*p, v);
+    };
+    alloc_copy(&c->d_shapes, h.shapes);
+    // the materials, followed by their bounce weights (render_bvh4_kernel)
+    alloc(&c->d_mats, h.mats.size() * sizeof(DevMaterial) + h.wtab.size() * sizeof(double));
+    copy(c->d_mats, h.mats);
+    copy(c->d_mats + h.mats.size(), h.wtab);
+    alloc_copy(&c->d_fscene, h.fscene);
+    alloc(&c->d_pix, pix_bytes);
+    alloc(&c->d_disc, pix_bytes);
+    alloc(&c->d_hemi, hemi_bytes);
+    alloc(&c->d_gloss, pix_bytes * 2);
+    alloc(&c->d_setrows, own * sizeof(DevSetRows));
+    alloc(&c->d_rowperm, perm_bytes);
+    alloc(&c->d_invperm, perm_bytes);
+    alloc(&c->d_stats, FLUX_NUM_STATS * sizeof(unsigned long long));
+    if (!h.tris.empty()) {
+        alloc_copy(&c->d_tris, h.tris);
+        alloc_copy(&c->d_nodes, h.nodes);
+        alloc_copy(&c->d_nodesq, h.nodesq);
+        if (!h.arena.empty()) alloc_copy(&c->d_arena, h.arena);
     }
-    alloc((void **)&c->d_mats, mats.size() * sizeof(flux::DevMaterial) + wtab.size() * sizeof(double));
-    alloc((void **)&c->d_fscene, fscene.size());
-    alloc((void **)&c->d_pix, pix_bytes);
-    alloc((void **)&c->d_disc, pix_bytes);
-    alloc((void **)&c->d_hemi, hemi_bytes);
-    alloc((void **)&c->d_gloss, pix_bytes * 2);
-    alloc((void **)&c->d_setrows, own * sizeof(flux::DevSetRows));
-    alloc((void **)&c->d_rowperm, perm_bytes);
-    alloc((void **)&c->d_invperm, perm_bytes);
-    alloc((void **)&c->d_stats, FLUX_NUM_STATS * sizeof(unsigned long long));
-    if (!tris.empty()) {
-        alloc((void **)&c->d_tris, tris.size() * sizeof(flux::DevTri));
-        alloc((void **)&c->d_nodes, nodes.size() * sizeof(flux::DevNode));
-        if (e == hipSuccess) e = hipMemcpy(c->d_tris, tris.data(), tris.size() * sizeof(flux::DevTri), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(c->d_nodes, nodes.data(), nodes.size() * sizeof(flux::DevNode), hipMemcpyHostToDevice);
-        alloc((void **)&c->d_nodesq, nodesq.size() * sizeof(flux::DevNodeQ));
-        if (e == hipSuccess) e = hipMemcpy(c->d_nodesq, nodesq.data(), nodesq.size() * sizeof(flux::DevNodeQ), hipMemcpyHostToDevice);
-        if (!arena.empty()) {
-            alloc((void **)&c->d_nodes4, arena.size() * sizeof(flux::DevNode4A));
-            if (e == hipSuccess) e = hipMemcpy(c->d_nodes4, arena.data(), arena.size() * sizeof(flux::DevNode4A), hipMemcpyHostToDevice);
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpy(c->d_shapes, shapes.data(), shapes.size() * sizeof(flux::DevShape), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->d_mats, mats.data(), mats.size() * sizeof(flux::DevMaterial), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->d_mats + mats.size(), wtab.data(), wtab.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->d_fscene, fscene.data(), fscene.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(c->d_stats, 0, FLUX_NUM_STATS * sizeof(unsigned long long));
-    lap(FLUX_CREATE_MS_UPLOAD);
+    laps.lap(FLUX_CREATE_MS_UPLOAD);
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-    lap(FLUX_CREATE_MS_OTHER);
+    laps.lap(FLUX_CREATE_MS_OTHER);
     // ---- MasterSampleSets::new on the device (sampling.rs:13-33) --------------
     double tab_ms[3] = {0, 0, 0};
     if (e == hipSuccess)
-        e = flux::generate_tables(seed, c->S, c->sets, c->D, c->n, c->H, c->d_pix, c->d_disc, c->d_hemi, c->d_rowperm, c->d_invperm, nullptr, tab_ms);
+        e = generate_tables(seed, c->S, c->sets, c->D, c->n, c->H, c->d_pix, c->d_disc, c->d_hemi, c->d_rowperm, c->d_invperm, nullptr, tab_ms);
     if (e == hipSuccess) {
-        e = flux::generate_gloss_table(c->d_pix, (size_t)c->sets.count * c->N, c->d_gloss, nullptr);
+        e = generate_gloss_table(c->d_pix, (size_t)c->sets.count * c->N, c->d_gloss, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
-    lap(FLUX_CREATE_MS_TABLES);
+    laps.lap(FLUX_CREATE_MS_TABLES);
     // the generator's scratch (the permutations of every grid: 262 MB at 16384 spp) is allocation, not table work
-    laps[FLUX_CREATE_MS_TABLES] -= tab_ms[0] + tab_ms[2];
-    laps[FLUX_CREATE_MS_ALLOC] += tab_ms[0];
-    laps[FLUX_CREATE_MS_FREE] += tab_ms[2];
+    laps.ms[FLUX_CREATE_MS_TABLES] -= tab_ms[0] + tab_ms[2];
+    laps.ms[FLUX_CREATE_MS_ALLOC] += tab_ms[0];
+    laps.ms[FLUX_CREATE_MS_FREE] += tab_ms[2];
+    // where each held set's rows of the sample tables start: one 32-B record per slot, so that a kernel forms a table address with one
+    // scalar load instead of a 64-bit multiply-add chain per table and pass (render_body.inc FLUX_SET_ROWS)
     if (e == hipSuccess) {
-        // where each held set's rows of the sample tables start: one 32-B record per slot, so that a kernel forms a table address with one
-        // scalar load instead of a 64-bit multiply-add chain per table and pass (render_body.inc FLUX_SET_ROWS)
-        std::vector<flux::DevSetRows> rows(own);
+        std::vector<DevSetRows> rows(own);
         for (size_t m = 0; m < own; m++) {
             rows[m].pix = c->d_pix + m * c->N;
             rows[m].disc = c->d_disc + m * c->N;
-            rows[m].hemi = c->d_hemi + m * c->D * c->N * flux::kHemiDoubles;
-            rows[m].gloss = c->d_gloss ? c->d_gloss + m * c->N * 4 : nullptr;
+            rows[m].hemi = c->d_hemi + m * c->D * c->N * kHemiDoubles;
+            rows[m].gloss = c->d_gloss + m * c->N * 4;
         }
-        e = hipMemcpy(c->d_setrows, rows.data(), own * sizeof(flux::DevSetRows), hipMemcpyHostToDevice);
+        copy(c->d_setrows, rows);
     }
-    if (e != hipSuccess) {
-        int code = fail(e == hipErrorOutOfMemory ? FLUX_E_NOMEM : FLUX_E_DEVICE, "flux_ctx_create: %s",
-                        hipGetErrorString(e));
-        free_ctx(c);
-        return code;
-    }
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? FLUX_E_NOMEM : FLUX_E_DEVICE, "flux_ctx_create: %s", hipGetErrorString(e));
+
+    // ---- RenderParams: the host scene's fields, pointed into this device's copies ----
+    RenderParams &rp = c->rp;
+    rp = h.rp;
+    rp.pixel_denom = 1.0 / (double)((uint64_t)c->n * c->n);  // trace.rs:59
+    rp.max_depth = (int32_t)c->D;
+    rp.nsamp = c->N;
     rp.shapes = c->d_shapes;
     rp.mats = c->d_mats;
     rp.pix = c->d_pix;
@@ -626,109 +296,59 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
     rp.hemi = c->d_hemi;
     rp.gloss = c->d_gloss;
     rp.set_rows = c->d_setrows;
-    for (int k = 0; k < 12; k++) rp.exp2c[k] = flux::fastmath::kExp2Poly[k];
     rp.rowperm = c->d_rowperm;
     rp.invperm = c->d_invperm;
-    rp.stats = nullptr;
+    for (int k = 0; k < 12; k++) rp.exp2c[k] = fastmath::kExp2Poly[k];
     rp.tris = c->d_tris;
     rp.nodes = c->d_nodes;
-    rp.n_tris = (int32_t)tris.size();
-    rp.bvh_stack = (int32_t)c->bvh.max_depth;
     rp.nodesq = c->d_nodesq;
-    rp.nodes4 = c->d_nodes4;
-    rp.leaves = c->d_leaves;
-    rp.bvh4_stack = (int32_t)c->bvh.wide_stack;
-    rp.n_mats = (int32_t)mats.size();
-    rp.mat_bits = 1;
-    while ((size_t)1 << rp.mat_bits < mats.size()) rp.mat_bits++;
-    for (int a = 0; a < 3; a++) {
-        rp.bvh_qmin[a] = c->bvh.qmin[a];
-        rp.bvh_qstep[a] = c->bvh.qstep[a];
-    }
-    rp.fsph = reinterpret_cast<const flux::DevScanSphere *>(c->d_fscene);
-    rp.fpln = reinterpret_cast<const flux::DevScanPlane *>(c->d_fscene + fs_sph_bytes);
-    rp.frec = reinterpret_cast<const flux::DevHitRec *>(c->d_fscene + fs_sph_bytes + fs_pln_bytes);
-    rp.fsph32 = filter32_ok
-                    ? reinterpret_cast<const flux::DevScanSphere32 *>(c->d_fscene + fs_sph_bytes + fs_pln_bytes + fs_rec_bytes)
-                    : nullptr;
-    rp.sshapes = reinterpret_cast<const flux::DevShape *>(c->d_fscene + fs_ss_off);
-    rp.pxc = reinterpret_cast<const double *>(c->d_fscene + fs_px_off);
-    rp.fdsk = reinterpret_cast<const flux::DevScanDisk *>(c->d_fscene + fs_dsk_off);
-    rp.fwx = rp.focal * rp.Wx;  // trace.rs:96-98's focal_distance * w, one product per frame instead of per wave
-    rp.fwy = rp.focal * rp.Wy;
-    rp.fwz = rp.focal * rp.Wz;
-    rp.bvh_mag = c->bvh.mag;
-    rp.set_first = 0;
-    rp.set_stride = 1;
-    rp.set_count = (int32_t)c->S;
-    rp.out_by_set = 0;
-    rp.slot_first = 0;
-    rp.slot_stride = 1;
-    rp.glossy_long = 0;
-    for (const flux::DevHitRec &hr : frec_p)
-        if (!hr.unit_normal) rp.glossy_long = 1;
-    for (const flux::DevHitRec &hr : frec_d)  // a disk's normal is a plane's: the same rule
-        if (!hr.unit_normal) rp.glossy_long = 1;
-    rp.n_uni = n_uni;
-    rp.uni_idx[0] = uni_idx[0];
-    rp.uni_idx[1] = uni_idx[1];
-    rp.unit_dirs = rp.glossy_long ? 0 : 1;
-    rp.self_skip = rp.glossy_long ? 0 : 1;
-    {   // the environment shortcut (flux_device.h env_short): exactly one `invert` sphere, Emissive, of ordinary size
-        int inverted = 0;
-        for (const flux::DevHitRec &hr : frec_s)
-            if (hr.inv_rad < 0.0) inverted++;
-        rp.env_short = 0;
-        rp.pad_env = 0;
-        rp.env_radius = 0.0;
-        if (n_uni == 1 && inverted == 1 && frec_s[uni_idx[0]].mat_kind == flux::kMatEmissive) {
-            const double rad = std::sqrt(fsph[uni_idx[0]].rr);
-            if (rad > 1e-3 && rad < 1e6) {
-                rp.env_short = 1;
-                rp.env_radius = rad * (1.0 + 1e-12);  // never below the true radius: it bounds the exit distance from above
-            }
-        }
-    }
-    rp.t_min = flux::kTMin;
-    rp.env_deep = -(4.0 * flux::kTMin) * rp.env_radius;  // (the kernels' own expression, evaluated once)
-    rp.env_px = rp.env_py = rp.env_pz = rp.env_rr = 0.0;
-    rp.env_eps = 1e-9;
-    if (n_uni == 1) {
-        const flux::DevScanSphere &es = fsph[uni_idx[0]];
-        rp.env_px = es.px; rp.env_py = es.py; rp.env_pz = es.pz; rp.env_rr = es.rr;
-    }
-    {   // the filter's group walk for at most 32 spheres (render_body.inc sphere_filter32: the same arithmetic, done once)
-        rp.f32_half = nullptr;
-        rp.f32_top = rp.fsph32;
-        rp.f32_groups = 0;
-        rp.f32_valid = fsph.size() >= 32 ? 0xffffffffu : (1u << fsph.size()) - 1u;
-        if (rp.fsph32 != nullptr && fsph.size() <= 32) {
-            int pairs = ((int)fsph.size() + 1) >> 1;
-            const int rem = pairs & 3;
-            if (rem == 1 || rem == 2) {
-                rp.f32_half = rp.fsph32 + (pairs - rem);
-                pairs -= rem;
-            } else if (rem == 3) {
-                pairs += 1;  // its fourth pair is padding (zeros)
-            }
-            rp.f32_groups = pairs / 4;
-            rp.f32_top = rp.fsph32 + pairs;
-        }
-    }
-    for (const flux::DevScanSphere &sp : fsph)
-        if (!(std::fabs(sp.px) < 1e3 && std::fabs(sp.py) < 1e3 && std::fabs(sp.pz) < 1e3 && sp.rr < 1e6)) rp.self_skip = 0;
-    rp.n_sph = (int32_t)fsph.size();
-    rp.n_pln = (int32_t)fpln.size();
-    rp.n_dsk = (int32_t)fdsk.size();
-    rp.has_diel = 0;
-    for (const flux::DevMaterial &m : mats)
-        if (m.kind == flux::kMatDielectric) rp.has_diel = 1;
-    lap(FLUX_CREATE_MS_UPLOAD);
-    laps[FLUX_CREATE_MS_TOTAL] = 0.0;
-    for (int k = 1; k < FLUX_CREATE_TIMING_WORDS; k++) laps[FLUX_CREATE_MS_TOTAL] += laps[k];  // (the parts sum to the total by construction)
-    for (int k = 0; k < FLUX_CREATE_TIMING_WORDS; k++) c->create_ms[k] = laps[k];
-    *out = c;
+    rp.nodes4 = reinterpret_cast<const DevNode4Q *>(c->d_arena);  // (the arena's kernel reads it as DevNode4A)
+    const unsigned char *fs = c->d_fscene;
+    rp.fsph = reinterpret_cast<const DevScanSphere *>(fs + h.fs.sph);
+    rp.fpln = reinterpret_cast<const DevScanPlane *>(fs + h.fs.pln);
+    rp.frec = reinterpret_cast<const DevHitRec *>(fs + h.fs.rec);
+    rp.fsph32 = h.filter32 ? reinterpret_cast<const DevScanSphere32 *>(fs + h.fs.s32) : nullptr;
+    rp.f32_half = rp.fsph32 && h.f32_half >= 0 ? rp.fsph32 + h.f32_half : nullptr;
+    rp.f32_top = rp.fsph32 ? rp.fsph32 + h.f32_top : nullptr;
+    rp.sshapes = reinterpret_cast<const DevShape *>(fs + h.fs.ss);
+    rp.pxc = reinterpret_cast<const double *>(fs + h.fs.pxc);
+    rp.fdsk = reinterpret_cast<const DevScanDisk *>(fs + h.fs.dsk);
+    laps.lap(FLUX_CREATE_MS_UPLOAD);
+    laps.ms[FLUX_CREATE_MS_TOTAL] = 0.0;
+    for (int k = 1; k < FLUX_CREATE_TIMING_WORDS; k++) laps.ms[FLUX_CREATE_MS_TOTAL] += laps.ms[k];  // (the parts sum to the total by construction)
+    for (int k = 0; k < FLUX_CREATE_TIMING_WORDS; k++) c->create_ms[k] = laps.ms[k];
+    *out = c.release();
     return FLUX_OK;
+}
+
+}  // namespace flux
+
+extern "C" {
+
+int flux_ctx_create(const flux_scene_desc *scene, const flux_job_cfg *cfg, uint64_t seed, int device,
+                    flux_ctx **out) {
+    return flux_ctx_create_sets(scene, cfg, seed, device, 0, 1, out);
+}
+
+// validation (before the device check: a CPU-only machine still reports a bad job as such) -> device check -> host build -> upload
+int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, uint64_t seed, int device,
+                         uint64_t first_set, uint64_t set_stride, flux_ctx **out) {
+    if (!scene || !cfg || !out) return fail(FLUX_E_INVALID, "flux_ctx_create: null argument");
+    *out = nullptr;
+    flux::CreateLaps laps;
+    if (int rc = flux::validate_job(*scene, *cfg, first_set, set_stride)) return rc;
+    laps.lap(FLUX_CREATE_MS_HOST);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(FLUX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
+    laps.lap(FLUX_CREATE_MS_RUNTIME);
+    return flux::no_throw([&] {
+        flux::HostScene host;
+        if (int rc = flux::build_host(*scene, host)) return rc;
+        laps.lap(FLUX_CREATE_MS_HOST);
+        return flux::upload(host, *cfg, seed, device, first_set, set_stride, laps, out);
+    });
 }
 
 static bool holds_all_sets(const flux_ctx *c) { return c->sets.stride == 1 && c->sets.first == 0; }

@@ -5,6 +5,7 @@
 // f32 so that the device slab test never rejects a box whose triangle the f64 Moeller-Trumbore test
 // would accept.  The traversal must return exactly the brute-force nearest hit (lowest id on ties).
 #include "flux_bvh.h"
+#include "joining_thread.h"
 
 #include <algorithm>
 #include <array>
@@ -13,6 +14,7 @@
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
+#include <exception>
 #include <functional>
 #include <limits>
 #include <thread>
@@ -192,17 +194,22 @@ struct Builder {
         info.max_depth = std::max<uint64_t>(info.max_depth, (uint64_t)depth + 1);
         const uint32_t m = split(b, e, depth);
         const uint32_t rb[2] = {b, m}, re[2] = {m, e};
-        std::thread left;
         std::vector<DevNode> left_nodes;
         BvhInfo left_info;
         Box left_box;
+        std::exception_ptr left_error;  // what the left builder threw, rethrown here once it has been joined
+        JoiningThread left;             // (declared last: joined before what it writes goes out of scope)
         const bool forked = fork > 0 && (m - b) >= 4096u && (m - b) > (uint32_t)kBvhLeafSize && (e - m) > (uint32_t)kBvhLeafSize;
         if (forked)
-            left = std::thread([&, this] {
-                Builder L{prims, left_nodes, pad, left_info};
-                left_box = L.range_box(b, m);
-                left_nodes.reserve((m - b) / 2 + 4);
-                L.build_inner(b, m, depth + 1, fork - 1);
+            left = JoiningThread([&, this] {
+                try {
+                    Builder L{prims, left_nodes, pad, left_info};
+                    left_box = L.range_box(b, m);
+                    left_nodes.reserve((m - b) / 2 + 4);
+                    L.build_inner(b, m, depth + 1, fork - 1);
+                } catch (...) {
+                    left_error = std::current_exception();
+                }
             });
         for (int side = forked ? 1 : 0; side < 2; side++) {
             const uint32_t cnt = re[side] - rb[side];
@@ -228,6 +235,7 @@ struct Builder {
         }
         if (forked) {
             left.join();
+            if (left_error) std::rethrow_exception(left_error);
             const int32_t off = (int32_t)nodes.size();
             for (DevNode N : left_nodes) {
                 if (N.child0 >= 0) N.child0 += off;

@@ -3,17 +3,45 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <new>
 #include <string>
+#include <system_error>
 
 #include "../../include/flux_abi.h"
 #include "flux_device.h"
 #include "flux_tables.h"
+#include "scene_build.h"
 
 namespace flux {
 
 // message of the calling thread's last failed call (flux_last_error); fail() sets it and returns `code`
 extern thread_local std::string g_last_error;
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// Runs f() and returns its FLUX code.  What it throws becomes a code instead of unwinding through the C ABI: a failed host
+// allocation or thread creation is FLUX_E_NOMEM.
+template <class F> int no_throw(F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        return fail(FLUX_E_NOMEM, "host allocation failed");
+    } catch (const std::system_error &e) {
+        return fail(FLUX_E_NOMEM, "%s", e.what());
+    }
+}
+
+// Where the wall time of a context's creation goes (flux_ctx_create_timing): lap(k) books the time since the previous lap under
+// word k.  A context of flux_multi_create starts with the shared host build already booked under HOST.
+struct CreateLaps {
+    double ms[FLUX_CREATE_TIMING_WORDS] = {};
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void lap(int k) {
+        const auto now = std::chrono::steady_clock::now();
+        ms[k] += std::chrono::duration<double, std::milli>(now - last).count();
+        last = now;
+    }
+};
 
 struct DeviceGuard {
     int prev = -1;
@@ -26,6 +54,14 @@ struct DeviceGuard {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+// The three phases of context creation (abi.hip): the job's checks, which need no device; the host scene build (scene_build.h),
+// its failures reported through fail(); the device half, which makes the context on `device` for the sample sets first_set +
+// k * set_stride and books its time from RUNTIME on.
+int validate_job(const flux_scene_desc &scene, const flux_job_cfg &cfg, uint64_t first_set, uint64_t set_stride);
+int build_host(const flux_scene_desc &scene, HostScene &host);
+int upload(const HostScene &host, const flux_job_cfg &cfg, uint64_t seed, int device, uint64_t first_set, uint64_t set_stride,
+           CreateLaps &laps, flux_ctx **out);
 
 }  // namespace flux
 
@@ -45,7 +81,7 @@ struct flux_ctx {
     flux::SetRange sets{0, 1, 0};  // sets with tables in this context (all S unless created by flux_ctx_create_sets)
     flux::DevShape *d_shapes = nullptr;
     flux::DevMaterial *d_mats = nullptr;
-    unsigned char *d_fscene = nullptr;  // FAST path: scan spheres | scan planes | hit records | f32 filter spheres
+    unsigned char *d_fscene = nullptr;  // the FAST scene image, regions as HostScene::fs lays them out (scene_build.h)
     double2 *d_pix = nullptr, *d_disc = nullptr;
     double *d_hemi = nullptr;
     double *d_gloss = nullptr;  // FAST glossy-lobe factors of pixel_sets
@@ -56,8 +92,7 @@ struct flux_ctx {
     // extension: triangle meshes
     flux::DevTri *d_tris = nullptr;
     flux::DevNode *d_nodes = nullptr;
-    flux::DevNode4Q *d_nodes4 = nullptr;
-    flux::DevLeafRec *d_leaves = nullptr;
+    flux::DevNode4A *d_arena = nullptr;  // the 4-wide tree of the FAST traversal kernel (RenderParams::nodes4), or nullptr
     flux::DevNodeQ *d_nodesq = nullptr;
     flux::BvhInfo bvh{};
     int traversal = FLUX_TRAVERSE_BVH;
@@ -70,6 +105,6 @@ struct flux_ctx {
     bool timed = false;
     uint64_t device_bytes = 0;
     double U[3], V[3], Wv[3];
-    // where flux_ctx_create's wall time went (flux_ctx_create_timing), milliseconds
+    // where flux_ctx_create's wall time went (flux_ctx_create_timing, CreateLaps), milliseconds
     double create_ms[FLUX_CREATE_TIMING_WORDS] = {};
 };

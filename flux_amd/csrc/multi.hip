@@ -21,13 +21,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "flux_ctx.h"
+#include "joining_thread.h"
 
 using flux::DeviceGuard;
 using flux::fail;
@@ -184,6 +185,9 @@ void free_multi(flux_multi *m) {
     }
     delete m;  // (the communicators stay in the process-wide cache)
 }
+struct FreeMulti {
+    void operator()(flux_multi *m) const { free_multi(m); }
+};
 
 // the frame on devices[0]; when out_rgb != nullptr also copied to the host
 int render_frame(flux_multi *m, double *out_rgb) {
@@ -316,118 +320,124 @@ int flux_multi_create(const flux_scene_desc *scene, const flux_job_cfg *cfg, uin
         std::lock_guard<std::mutex> lk(g_rccl_mu);
         if (!rccl_load(err)) return fail(FLUX_E_DEVICE, "%s", err.c_str());
     }
-    flux_multi *m = new (std::nothrow) flux_multi();
-    if (!m) return fail(FLUX_E_NOMEM, "host allocation failed");
-    m->shard = shard;
-    m->loopback = loopback;
-    m->ranks.resize(G);
-    for (uint32_t g = 0; g < G; g++) m->ranks[g].device = devices[g];
+    return flux::no_throw([&] {
+        std::unique_ptr<flux_multi, FreeMulti> m(new flux_multi());
+        m->shard = shard;
+        m->loopback = loopback;
+        m->ranks.resize(G);
+        for (uint32_t g = 0; g < G; g++) m->ranks[g].device = devices[g];
 
-    // communicators: from the cache, or created on a thread of their own while the contexts come up
-    const std::vector<int> key(devices, devices + G);
-    std::vector<ncclComm_t> comms;
-    std::string comm_err;
-    double comm_ms = 0;
-    std::thread comm_thread;
-    if (loopback) {
-        comms.assign(G, nullptr);
-    } else {
-        std::lock_guard<std::mutex> lk(g_rccl_mu);
-        auto it = g_comms.find(key);
-        if (it != g_comms.end()) {
-            comms = it->second;
-            m->comms_cached = true;
+        // communicators: from the cache, or created on a thread of their own while the contexts come up
+        const std::vector<int> key(devices, devices + G);
+        std::vector<ncclComm_t> comms;
+        std::string comm_err;
+        bool comm_nomem = false;
+        double comm_ms = 0;
+        if (loopback) {
+            comms.assign(G, nullptr);
+        } else {
+            std::lock_guard<std::mutex> lk(g_rccl_mu);
+            auto it = g_comms.find(key);
+            if (it != g_comms.end()) {
+                comms = it->second;
+                m->comms_cached = true;
+            }
+            (void)g_rccl.GetVersion(&m->rccl_version);
         }
-        (void)g_rccl.GetVersion(&m->rccl_version);
-    }
-    if (!m->comms_cached && !loopback)
-        comm_thread = std::thread([&] {
-            const auto tc = std::chrono::steady_clock::now();
-            std::vector<ncclComm_t> cs(G, nullptr);
-            const ncclResult_t r = g_rccl.CommInitAll(cs.data(), (int)G, key.data());
-            if (r != ncclSuccess)
-                comm_err = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r);
-            else
-                comms = cs;
-            comm_ms = ms_since(tc);
-        });
-    // fan-out of the job (manager.rs:156-162): Scene::from_data + Camera::new per device, concurrently
-    std::vector<std::thread> th;
-    for (uint32_t g = 0; g < G; g++)
-        th.emplace_back([&, g] {
+        flux::JoiningThread comm_thread;
+        if (!m->comms_cached && !loopback)
+            comm_thread = flux::JoiningThread([&] {
+                const auto tc = std::chrono::steady_clock::now();
+                try {
+                    std::vector<ncclComm_t> cs(G, nullptr);
+                    const ncclResult_t r = g_rccl.CommInitAll(cs.data(), (int)G, key.data());
+                    if (r != ncclSuccess)
+                        comm_err = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r);
+                    else
+                        comms.swap(cs);
+                } catch (const std::bad_alloc &) {
+                    comm_nomem = true;
+                }
+                comm_ms = ms_since(tc);
+            });
+        // Scene::from_data + Camera::new once, on this thread (the job is the same for every device: manager.rs:156-162); then
+        // every device uploads the same host scene, concurrently.  Each rank's HOST word is this build: its context waited for it.
+        const auto th0 = std::chrono::steady_clock::now();
+        flux::HostScene host;
+        int host_rc = flux::validate_job(*scene, *cfg, 0, shard == FLUX_SHARD_SETS ? G : 1);
+        if (host_rc == FLUX_OK) host_rc = flux::build_host(*scene, host);
+        const double host_ms = ms_since(th0);
+        std::vector<flux::JoiningThread> th;
+        for (uint32_t g = 0; g < G && host_rc == FLUX_OK; g++)
+            th.emplace_back([&, g] {
+                Rank &rk = m->ranks[g];
+                const auto tc = std::chrono::steady_clock::now();
+                flux::CreateLaps laps;
+                laps.ms[FLUX_CREATE_MS_HOST] = host_ms;
+                const bool sets = shard == FLUX_SHARD_SETS;
+                rk.rc = flux::no_throw([&] { return flux::upload(host, *cfg, seed, rk.device, sets ? g : 0, sets ? G : 1, laps, &rk.ctx); });
+                if (rk.rc != FLUX_OK) rk.error = flux_last_error();
+                rk.create_ms = host_ms + ms_since(tc);
+            });
+        for (flux::JoiningThread &t : th) t.join();
+        comm_thread.join();
+        if (!m->comms_cached && !loopback && comm_err.empty() && !comm_nomem) {
+            std::lock_guard<std::mutex> lk(g_rccl_mu);
+            auto ins = g_comms.emplace(key, comms);
+            if (!ins.second) {  // another thread created the same list meanwhile: keep the cached ones, drop ours
+                for (ncclComm_t c : comms) (void)g_rccl.CommDestroy(c);
+                comms = ins.first->second;
+            }
+        }
+        if (host_rc != FLUX_OK) return host_rc;  // (its message is this thread's flux_last_error already)
+        for (uint32_t g = 0; g < G; g++)
+            if (m->ranks[g].rc != FLUX_OK) return fail(m->ranks[g].rc, "device %d: %s", m->ranks[g].device, m->ranks[g].error.c_str());
+        if (comm_nomem) return fail(FLUX_E_NOMEM, "ncclCommInitAll: host allocation failed");
+        if (!comm_err.empty()) return fail(FLUX_E_DEVICE, "%s", comm_err.c_str());
+        m->W = m->ranks[0].ctx->W;
+        m->H = m->ranks[0].ctx->H;
+        m->S = m->ranks[0].ctx->S;
+        if (shard == FLUX_SHARD_SETS) {
+            m->per_rank = (m->S + G - 1) / G;
+            m->share_doubles = (size_t)m->H * m->per_rank * 3;
+        } else {
+            m->per_rank = (m->H + G - 1) / G;
+            m->share_doubles = (size_t)m->per_rank * m->W * 3;
+        }
+        hipError_t e = hipSuccess;
+        for (uint32_t g = 0; g < G && e == hipSuccess; g++) {
             Rank &rk = m->ranks[g];
-            const auto tc = std::chrono::steady_clock::now();
-            rk.rc = shard == FLUX_SHARD_SETS ? flux_ctx_create_sets(scene, cfg, seed, rk.device, g, G, &rk.ctx)
-                                             : flux_ctx_create(scene, cfg, seed, rk.device, &rk.ctx);
-            if (rk.rc != FLUX_OK) rk.error = flux_last_error();
-            rk.create_ms = ms_since(tc);
-        });
-    for (std::thread &t : th) t.join();
-    if (comm_thread.joinable()) comm_thread.join();
-    if (!m->comms_cached && !loopback && comm_err.empty()) {
-        std::lock_guard<std::mutex> lk(g_rccl_mu);
-        auto ins = g_comms.emplace(key, comms);
-        if (!ins.second) {  // another thread created the same list meanwhile: keep the cached ones, drop ours
-            for (ncclComm_t c : comms) (void)g_rccl.CommDestroy(c);
-            comms = ins.first->second;
+            rk.comm = comms[g];
+            const uint64_t total = shard == FLUX_SHARD_SETS ? m->S : m->H;
+            rk.count = g < total ? (total - g + G - 1) / G : 0;
+            DeviceGuard dg(rk.device);
+            e = hipStreamCreateWithFlags(&rk.stream, hipStreamNonBlocking);
+            const size_t share_bytes = m->share_doubles * sizeof(double);
+            if (e == hipSuccess) e = hipMalloc((void **)&rk.d_share, share_bytes);
+            if (e == hipSuccess) e = hipMemset(rk.d_share, 0, share_bytes);  // padding stays zero (image.rs:55-59 writes never-received rows as zeros)
+            if (e == hipSuccess) e = hipMalloc((void **)&rk.d_gathered, share_bytes * G);
+            m->buffer_bytes += share_bytes * (G + 1);
+            if (e == hipSuccess && shard == FLUX_SHARD_SETS && rk.count && rk.count != m->per_rank) {
+                e = hipMalloc((void **)&rk.d_render, (size_t)m->H * rk.count * 24);
+                m->buffer_bytes += (size_t)m->H * rk.count * 24;
+            }
+            if (e == hipSuccess) e = hipDeviceSynchronize();
         }
-    }
-    for (uint32_t g = 0; g < G; g++)
-        if (m->ranks[g].rc != FLUX_OK) {
-            const int rc = fail(m->ranks[g].rc, "device %d: %s", m->ranks[g].device, m->ranks[g].error.c_str());
-            free_multi(m);
-            return rc;
+        if (e == hipSuccess) {
+            DeviceGuard dg(m->ranks[0].device);
+            e = hipMalloc((void **)&m->d_frame, (size_t)m->H * m->W * 24);
+            m->buffer_bytes += (size_t)m->H * m->W * 24;
+            for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&m->ev[k]);
         }
-    if (!comm_err.empty()) {
-        free_multi(m);
-        return fail(FLUX_E_DEVICE, "%s", comm_err.c_str());
-    }
-    m->W = m->ranks[0].ctx->W;
-    m->H = m->ranks[0].ctx->H;
-    m->S = m->ranks[0].ctx->S;
-    if (shard == FLUX_SHARD_SETS) {
-        m->per_rank = (m->S + G - 1) / G;
-        m->share_doubles = (size_t)m->H * m->per_rank * 3;
-    } else {
-        m->per_rank = (m->H + G - 1) / G;
-        m->share_doubles = (size_t)m->per_rank * m->W * 3;
-    }
-    hipError_t e = hipSuccess;
-    for (uint32_t g = 0; g < G && e == hipSuccess; g++) {
-        Rank &rk = m->ranks[g];
-        rk.comm = comms[g];
-        const uint64_t total = shard == FLUX_SHARD_SETS ? m->S : m->H;
-        rk.count = g < total ? (total - g + G - 1) / G : 0;
-        DeviceGuard dg(rk.device);
-        e = hipStreamCreateWithFlags(&rk.stream, hipStreamNonBlocking);
-        const size_t share_bytes = m->share_doubles * sizeof(double);
-        if (e == hipSuccess) e = hipMalloc((void **)&rk.d_share, share_bytes);
-        if (e == hipSuccess) e = hipMemset(rk.d_share, 0, share_bytes);  // padding stays zero (image.rs:55-59 writes never-received rows as zeros)
-        if (e == hipSuccess) e = hipMalloc((void **)&rk.d_gathered, share_bytes * G);
-        m->buffer_bytes += share_bytes * (G + 1);
-        if (e == hipSuccess && shard == FLUX_SHARD_SETS && rk.count && rk.count != m->per_rank) {
-            e = hipMalloc((void **)&rk.d_render, (size_t)m->H * rk.count * 24);
-            m->buffer_bytes += (size_t)m->H * rk.count * 24;
-        }
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess) {
-        DeviceGuard dg(m->ranks[0].device);
-        e = hipMalloc((void **)&m->d_frame, (size_t)m->H * m->W * 24);
-        m->buffer_bytes += (size_t)m->H * m->W * 24;
-        for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&m->ev[k]);
-    }
-    if (e != hipSuccess) {
-        const int rc = fail(e == hipErrorOutOfMemory ? FLUX_E_NOMEM : FLUX_E_DEVICE, "flux_multi_create: %s", hipGetErrorString(e));
-        free_multi(m);
-        return rc;
-    }
-    m->timing[0] = ms_since(t0);
-    for (const Rank &rk : m->ranks)
-        if (rk.create_ms > m->timing[1]) m->timing[1] = rk.create_ms;
-    m->timing[2] = comm_ms;
-    *out = m;
-    return FLUX_OK;
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? FLUX_E_NOMEM : FLUX_E_DEVICE, "flux_multi_create: %s", hipGetErrorString(e));
+        m->timing[0] = ms_since(t0);
+        for (const Rank &rk : m->ranks)
+            if (rk.create_ms > m->timing[1]) m->timing[1] = rk.create_ms;
+        m->timing[2] = comm_ms;
+        *out = m.release();
+        return FLUX_OK;
+    });
 }
 
 void flux_multi_destroy(flux_multi *m) { free_multi(m); }

@@ -1,0 +1,53 @@
+// scene_build.h -- the host half of context creation: everything a context's scene buffers and RenderParams hold that depends on
+// the scene alone, built once on the host (abi.hip uploads it to one device, multi.hip to each of its devices).  Plain C++: no HIP
+// call and no device, so a CPU-only test can build and inspect it (tests/scene_build_selftest.cpp).
+#pragma once
+#include <cstddef>
+#include <string>
+#include <vector>
+
+#include "../../include/flux_abi.h"
+#include "flux_device.h"
+
+namespace flux {
+
+// Where each region of the FAST scene image starts, in bytes from its base.  fscene_layout() computes it once; the host build
+// fills the image by it and the upload points RenderParams::fsph .. fdsk into the device copy by it.
+struct FsceneLayout {
+    size_t sph = 0;    // DevScanSphere[n_sph + 1] (+1: the scan reads one record ahead)
+    size_t pln = 0;    // DevScanPlane[n_pln + 1]
+    size_t rec = 0;    // DevHitRec[n_shapes + 1]: spheres, planes, disks
+    size_t s32 = 0;    // DevScanSphere32[(n_sph + 1) / 2 + 4] (+4 pairs: the filter loads whole groups of 8 spheres)
+    size_t ss = 0;     // DevShape[n_sph + 1], 128-B aligned: STRICT's spheres in scan order
+    size_t pxc = 0;    // double[W + H], 128-B aligned: the primary ray's per-column and per-row constants
+    size_t dsk = 0;    // DevScanDisk[n_dsk + 1], 128-B aligned
+    size_t bytes = 0;  // the whole image
+};
+FsceneLayout fscene_layout(size_t n_sph, size_t n_pln, size_t n_dsk, size_t n_shapes, uint32_t W, uint32_t H);
+
+struct HostScene {
+    std::vector<DevShape> shapes;   // one record at least
+    std::vector<DevMaterial> mats;  // the shapes', then the meshes', then one unused record
+    std::vector<double> wtab;       // behind the materials on the device: per material {its FAST bounce weight; 0}
+    FsceneLayout fs;
+    std::vector<unsigned char> fscene;
+    // meshes (all empty without triangles)
+    std::vector<DevTri> tris;
+    std::vector<DevNode> nodes;
+    std::vector<DevNodeQ> nodesq;
+    std::vector<DevNode4A> arena;  // empty when the arena exceeds its 26-bit unit index: the binary tree's kernel walks the mesh
+    BvhInfo bvh;
+    double U[3] = {}, V[3] = {}, W[3] = {};  // CameraBasis::new (scene.rs:28-35)
+    // every field of RenderParams the scene decides.  The pointers stay null here; the upload sets them, f32_half and f32_top from
+    // the pair indices below.
+    RenderParams rp{};
+    bool filter32 = false;  // fsph32 is usable (else RenderParams::fsph32 and f32_top are null)
+    int f32_half = -1;      // RenderParams::f32_half = fsph32 + f32_half, null when -1
+    int f32_top = 0;        // RenderParams::f32_top = fsph32 + f32_top
+};
+
+// `scene` as validate_job (abi.hip) passed it.  Returns FLUX_OK, or FLUX_E_INVALID with the message in `error` (too many triangles
+// for a context, or a mesh the BVH cannot hold).  Host allocation failures and thread creation throw.
+int build_host_scene(const flux_scene_desc &scene, HostScene &out, std::string &error);
+
+}  // namespace flux

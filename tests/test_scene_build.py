@@ -1,0 +1,115 @@
+"""The host half of context creation (flux_amd/csrc/scene_build.cpp) checked on the CPU: tests/scene_build_selftest.cpp builds the
+records, the FAST scene image, the mesh's triangles and trees and the scene-derived RenderParams of four shipped scenes and a
+height field, and this test pins the SHA-256 of every buffer.  The digests are the bytes the kernels read: a change to any of
+them changes what a context uploads."""
+import hashlib
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT, SCENES
+
+BUFFERS = ("shapes", "mats", "fscene", "tris", "nodes", "nodesq", "arena", "scalars")
+SCENE_NAMES = ("demo1", "demo2", "disk_light", "glass", "heightfield")
+
+DIGESTS = {
+    "demo1.arena": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo1.fscene": "44a7ad117428bdf2d150bb1c08426a4e677d8e046ea209404c26b91d7a01384c",
+    "demo1.mats": "bb4a57006db7100f93b01c20997bd96af88fa19e2590a3079cfebe51788f8188",
+    "demo1.nodes": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo1.nodesq": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo1.scalars": "913a85df95c3b455156d048976386062c8ecc26bda14b291e4ac6b65d768d8a4",
+    "demo1.shapes": "1f9a67127ec6577b5994cc74e38149a6b5e72795330c7c06f06f1f40e5a2f217",
+    "demo1.tris": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo2.arena": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo2.fscene": "8f53b6c44df12e2b3d77c267a0092f9e8fe31418f75bd913fa22560f3836475d",
+    "demo2.mats": "6df6d78ad23cfb337685d9eb030d01079f3f9c32dc95bcce45d92f17b09756ca",
+    "demo2.nodes": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo2.nodesq": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "demo2.scalars": "22936df35a0fe7b3f986e644337988282a68ce53c7d44e77fe45c36c8d5389af",
+    "demo2.shapes": "db278296bd9ce8d1ecc7f739f4f3e3f52c7204369990d7a3c47c74a514251238",
+    "demo2.tris": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "disk_light.arena": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "disk_light.fscene": "a94b1a6bc3f70869a304fc6a8fd44982904cfc0c2b04e4a015cbd8c528e2e262",
+    "disk_light.mats": "6df6d78ad23cfb337685d9eb030d01079f3f9c32dc95bcce45d92f17b09756ca",
+    "disk_light.nodes": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "disk_light.nodesq": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "disk_light.scalars": "9faa7e7c7d0da08ca00bda6973319d82b8673edf7029152f56ed23da6d5663c6",
+    "disk_light.shapes": "a5b0e1869bee7d678a6b80fe0308d9a878dc2e21d250f42ce11f686ca915f887",
+    "disk_light.tris": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "glass.arena": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "glass.fscene": "a5732247d4dae5aa0fbae2384b218f36070b1be2443630092c6f710858030d1c",
+    "glass.mats": "8311ec99579711c08d35d9569898bcb0548e38d89549159929c6d1fd0649c87b",
+    "glass.nodes": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "glass.nodesq": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "glass.scalars": "5fd87304288088934ca3decd4cb6811aaa693460e5c75521357c4f3b51e889eb",
+    "glass.shapes": "db278296bd9ce8d1ecc7f739f4f3e3f52c7204369990d7a3c47c74a514251238",
+    "glass.tris": "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855",
+    "heightfield.arena": "fdad34fc17314c27a22c0c7f68121fd733472e3401f16c59d32eef744139c70a",
+    "heightfield.fscene": "44a7ad117428bdf2d150bb1c08426a4e677d8e046ea209404c26b91d7a01384c",
+    "heightfield.mats": "1a9eb1d0dc5931b3b7b5afd5b67a3b4d92e6eee3ea48e458214c356c0bf5fe99",
+    "heightfield.nodes": "24cc7e9e897e98e350a95285fa00c108837cf3ba510ab9ccac4b30629d527b57",
+    "heightfield.nodesq": "2b246b05689b6ce6804f9c17cbf0747633dec19cffd2d6441066ef1f2cc084c6",
+    "heightfield.scalars": "cce1abccf3ead8acf421db2cf2fc3ae7eb6c8ae19f46d045e86804c4462c68a3",
+    "heightfield.shapes": "1f9a67127ec6577b5994cc74e38149a6b5e72795330c7c06f06f1f40e5a2f217",
+    "heightfield.tris": "0e011d18a8dff082ab7e97d085a68aeb8819c396fed86ecb00352d35604e02b0",
+}
+
+
+@pytest.fixture(scope="module")
+def selftest(tmp_path_factory):
+    from flux_amd import build
+    build.build_hip()
+    exe = str(tmp_path_factory.mktemp("scene_build") / "scene_build_selftest")
+    host = os.path.join(ROOT, "flux_amd", "host")
+    csrc = os.path.join(ROOT, "flux_amd", "csrc")
+    # host-only clang: plain g++ cannot compile flux_device.h's ext_vector_type records; -ffp-contract=off as the library's
+    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
+                    "-I/opt/rocm/include", "-pthread", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "scene_build_selftest.cpp"),
+                    os.path.join(csrc, "scene_build.cpp"), os.path.join(csrc, "bvh.cpp")] +
+                   [os.path.join(host, s) for s in build.HOST_SOURCES] +
+                   ["-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"),
+                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    return exe
+
+
+def _run(exe, out_dir, threads=None):
+    env = dict(os.environ)
+    env.pop("FLUX_BUILD_THREADS", None)
+    if threads is not None:
+        env["FLUX_BUILD_THREADS"] = str(threads)
+    os.makedirs(out_dir, exist_ok=True)
+    out = subprocess.run([exe, SCENES, str(out_dir)], capture_output=True, text=True, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    digests = {}
+    for scene in SCENE_NAMES:
+        for buf in BUFFERS:
+            ext = "txt" if buf == "scalars" else "bin"
+            with open(os.path.join(out_dir, f"{scene}.{buf}.{ext}"), "rb") as f:
+                digests[f"{scene}.{buf}"] = hashlib.sha256(f.read()).hexdigest()
+    return out.stdout, digests
+
+
+@pytest.fixture(scope="module")
+def default_run(selftest, tmp_path_factory):
+    return _run(selftest, tmp_path_factory.mktemp("default"))
+
+
+def test_selftest_checks(default_run):
+    stdout, _ = default_run
+    for name in ("unit normal", "non-unit plane normal", "sphere beyond 1e3", "one emissive invert sphere", "two invert spheres",
+                 "group walk", "no f32 filter") + tuple(f"dump {s}" for s in SCENE_NAMES):
+        assert f"ok {name}" in stdout
+    assert "all ok" in stdout
+
+
+def test_buffers_are_pinned(default_run):
+    _, digests = default_run
+    assert digests == DIGESTS
+
+
+def test_mesh_is_the_same_with_one_thread(selftest, default_run, tmp_path):
+    _, digests = _run(selftest, tmp_path, threads=1)
+    assert {k: v for k, v in digests.items() if k.startswith("heightfield.")} == \
+           {k: v for k, v in default_run[1].items() if k.startswith("heightfield.")}
