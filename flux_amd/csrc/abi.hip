@@ -367,15 +367,14 @@ static bool holds_all_sets(const flux_ctx *c) { return c->sets.stride == 1 && c-
 // (a function of the JOB alone -- max_trace_depth and the mesh's BVH depth --, not of flux_ctx_set_traversal: the arithmetic a scene
 // is rendered with must not flip with a test hook; a brute-force traversal leaves the BVH stack's bytes unused)
 static bool strict_fits_lds(const flux_ctx *ctx) {
-    const size_t stack = (size_t)ctx->D * 4 * 64 * sizeof(double);
-    const size_t bvh = ctx->rp.n_tris > 0 ? (size_t)ctx->bvh.max_depth * 64 * sizeof(int) : 0;
-    return stack + bvh + 512 <= 64 * 1024;  // (the smallest block the planner can choose: one wave; plan_render_impl)
+    // (the smallest block the planner can choose: one wave; launch_plan.cpp plan_render)
+    return flux::lane_stacks_lds(FLUX_MATH_STRICT, ctx->D, ctx->rp.n_tris > 0, (size_t)ctx->bvh.max_depth, 64) + 512 <= 64 * 1024;
 }
 static int effective_math(const flux_ctx *ctx) {
     return (ctx->math == FLUX_MATH_FAST && ctx->rp.glossy_long && strict_fits_lds(ctx)) ? FLUX_MATH_STRICT : ctx->math;
 }
 
-// LDS one block of the kernel about to be launched needs: asked of the launch plan itself (render_body.inc plan_render_impl:
+// LDS one block of the kernel about to be launched needs: asked of the launch plan itself (launch_plan.cpp plan_render:
 // STRICT keeps the (f,s) recursion stack, 4 doubles per level per lane; mesh scenes the BVH traversal stack, one int per
 // level per lane -- 64 lanes in the FAST state-machine kernel, the block's in the others --; the split kernel its path
 // queues), plus the few static words of the refill / split kernels.  64 KiB per block is the launch limit.
@@ -391,12 +390,10 @@ static int check_lds_budget(const flux_ctx *ctx, const flux::RenderParams &p, co
                     ctx->math == FLUX_MATH_STRICT ? "FLUX_MATH_FAST or a smaller max_trace_depth" : "a smaller max_trace_depth");
     return FLUX_OK;
 }
-// flux_debug_shade: 64-thread blocks, STRICT recursion stack + per-lane BVH stack (render_body.inc launch_shade_rays_impl)
+// flux_debug_shade: 64-thread blocks, STRICT recursion stack + per-lane BVH stack (launch_plan.cpp shade_rays_lds)
 static int check_lds_budget_rays(const flux_ctx *ctx, const flux::RenderParams &p) {
-    const size_t strict = effective_math(ctx) == FLUX_MATH_STRICT ? (size_t)ctx->D * 4 * 64 * sizeof(double) : 0;
-    const size_t stack = p.n_tris > 0 ? (size_t)p.bvh_stack * 64 * sizeof(int) : 0;
-    if (strict + stack > 64 * 1024)
-        return fail(FLUX_E_INVALID, "flux_debug_shade: %zu B of LDS per block exceed the 64 KiB limit", strict + stack);
+    const size_t lds = flux::shade_rays_lds(p, effective_math(ctx));
+    if (lds > 64 * 1024) return fail(FLUX_E_INVALID, "flux_debug_shade: %zu B of LDS per block exceed the 64 KiB limit", lds);
     return FLUX_OK;
 }
 

@@ -245,7 +245,7 @@ struct RenderParams {
     const DevScanDisk *fdsk;
     int32_t n_dsk;
     // extension: 1 = some shape or mesh is a Dielectric (kMatDielectric).  The kernels' dielectric branch sits behind this uniform
-    // flag, and the launch keeps such a scene out of the TYP instantiations and the split kernel's hit queue (plan_render_impl)
+    // flag, and the launch keeps such a scene out of the TYP instantiations and the split kernel's hit queue (launch_plan.cpp plan_render)
     int32_t has_diel;
 };
 

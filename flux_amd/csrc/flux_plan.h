@@ -1,0 +1,69 @@
+// flux_plan.h -- the launch planner (launch_plan.cpp) and what it shares with the render kernels (render.hip): the tunables that
+// size a launch and the LDS layout of the split kernel's queues.  Both sides read these numbers from here, so a -D override
+// (scripts/sweep_variants.py) reaches the kernels and the plan alike.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "flux_device.h"
+
+// Block size of the static and BVH kernels: measured on demo2 at 1024 spp (refill kernel): 256 threads x 2 waves/SIMD 88.6 ms;
+// 256 x 3 71.7 ms; 64 x 3 70.7 ms; 256 x 4 83.0 ms (spills).  Waves never cooperate, so one wave per block lets the LDS stack of a
+// finished wave be reused at once.
+#ifndef FLUX_BLOCK_THREADS
+#define FLUX_BLOCK_THREADS 64
+#endif
+#ifndef FLUX_WPE_SPLIT
+#define FLUX_WPE_SPLIT 5          // waves/SIMD of the split kernel: 96 VGPRs, nothing spilled since round 4 (4 until then: 128 VGPRs); demo2 @16384 spp 250.0 -> 225.4 ms
+#endif
+#ifndef FLUX_HITQ_MIN_TAKE
+// H, the parked hits a wave waits for before a pass takes them instead of starting 64 more samples, is C - 64 (at most 64): phase A
+// runs while the queue has room for its 64 continuations.  Below this H the bounce batches are too thin to pay for the queue
+// (demo2 @16384 spp, C = 110: H 46 159.2, 40 162.9, 32 171.0, 24 182.3, 16 200.9 ms; the ray queue 172.0 ms), and the scene keeps
+// the ray queue.
+#define FLUX_HITQ_MIN_TAKE 32
+#endif
+
+namespace flux {
+
+// The split kernel's ray queue: 64 queued paths per wave, structure of arrays [field][slot]: ox oy oz dx dy dz tr tg tb, then the
+// sample index and Path::self (int)
+constexpr int kQueueDoubles = 9;
+constexpr int kQueueBytesPerWave = (kQueueDoubles * 64) * 8 + 2 * 64 * 4;
+// The hit queue (plan_render chooses C per scene): C slots per wave, [field][slot] as above -- o d t, then hit | depth << 16, the
+// sample index and the bounce list (render_body.inc render_split_kernel): 68 B a slot
+constexpr int kHitQDoubles = 7;
+constexpr int kHitQInts = 3;
+constexpr int kHitQBytesPerSlot = kHitQDoubles * 8 + kHitQInts * 4;
+
+// The copy of render_body.inc a launch runs (render.hip): the STRICT arithmetic, the FAST one, or the FAST one with the dielectric
+// lobe (RenderParams::has_diel)
+enum KernelCopy { kCopyStrict = 0, kCopyFast = 1, kCopyFastDiel = 2 };
+KernelCopy kernel_copy(const RenderParams &p, int math);
+
+// Which kernel launch_render runs for these parameters -- which instantiation, with what block size, grid and dynamic LDS: decided
+// in ONE place (launch_plan.cpp plan_render) and asked from there by the launch itself, by the host's LDS budget check and by
+// flux_ctx_launch_plan / flux_ctx_bvh_info, so that they cannot drift apart.  The launch maps these fields to template arguments.
+struct LaunchPlan {
+    int kernel = -1;  // FLUX_PLAN_* (include/flux_abi.h): 0 static, 1 refill, 2 split, 3 BVH state machine over the binary tree,
+                      // 4 the same over the 4-wide tree; -1 nothing to do
+    unsigned block = 64;
+    uint64_t blocks = 0;
+    size_t lds = 0;                // dynamic LDS per block (the refill / split kernels add 96 B of static LDS)
+    unsigned waves_per_pixel = 1;  // K: waves that share one pixel's samples (1 in the static and BVH kernels)
+    int lds_scene = 0;             // kernel 4: 1 = the instantiation that keeps the analytic set's records and the materials in LDS (`lds` includes them)
+    int hq_cap = 0, hq_th = 0, hq_bits = 0;  // kernel 2: the hit queue's slots per wave (0: none, the ray queue), H, and the bounce list's bits per entry
+    int copy = kCopyFast;          // KernelCopy
+    int tris = 0;                  // kernels 0 and 1: the instantiation with the mesh (TRIS)
+    int typ = 0;                   // kernels 2 and 4: the instantiation for the usual analytic scene (TYP)
+    int max32 = 0;                 // kernel 2: at most 32 spheres, one group of the sphere filter (MAX32)
+};
+LaunchPlan plan_render(const RenderParams &p, int variant, int math);
+
+// LDS of the per-lane stacks of `lanes` lanes: the STRICT (f, s) recursion stack, 4 doubles per level, and the BVH traversal stack,
+// one int per level
+size_t lane_stacks_lds(int math, size_t depth, bool tris, size_t bvh_stack, size_t lanes);
+// flux_debug_shade's kernel: its dynamic LDS (64-lane blocks)
+size_t shade_rays_lds(const RenderParams &p, int math);
+
+}  // namespace flux

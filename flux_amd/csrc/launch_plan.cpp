@@ -1,0 +1,136 @@
+// launch_plan.cpp -- the launch planner: which render kernel instantiation a call runs, with what block, grid and LDS (flux_plan.h).
+// Plain host code, compiled once: render.hip launches what it answers, abi.hip checks its LDS against the limit and reports it
+// (flux_ctx_launch_plan), and tests/scene_build_selftest.cpp pins its answers for the shipped scenes on the CPU.
+#include <algorithm>
+#include <cstdlib>
+
+#include "flux_plan.h"
+#include "../../include/flux_abi.h"
+
+namespace flux {
+
+KernelCopy kernel_copy(const RenderParams &p, int math) {
+    if (math == FLUX_MATH_STRICT) return kCopyStrict;
+    return p.has_diel ? kCopyFastDiel : kCopyFast;
+}
+
+size_t lane_stacks_lds(int math, size_t depth, bool tris, size_t bvh_stack, size_t lanes) {
+    return (math == FLUX_MATH_STRICT ? depth * 4 * lanes * sizeof(double) : 0) + (tris ? bvh_stack * lanes * sizeof(int) : 0);
+}
+
+size_t shade_rays_lds(const RenderParams &p, int math) {
+    return lane_stacks_lds(math, (size_t)p.max_depth, p.n_tris > 0, (size_t)p.bvh_stack, 64);
+}
+
+// The TYP instantiations: scan_shapes_fast's TYP turns these values into constants of the instantiation, and it leaves the disks'
+// loop and the dielectric lobe out.  The split kernel's usual scene ...
+static bool split_typ(const RenderParams &p) {
+    return p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 &&
+           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0;
+}
+// ... and the usual analytic set beside a mesh in render_bvh4_kernel, whose records it keeps in LDS (no environment shortcut there)
+static bool bvh4_typ(const RenderParams &p, bool lds_scene) {
+    return lds_scene && p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.n_uni == 1 &&
+           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0;
+}
+
+LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
+    LaunchPlan L;
+    L.copy = kernel_copy(p, math);
+    const bool fast = L.copy != kCopyStrict;
+    const uint32_t N = p.nsamp;
+    const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
+    if (npix == 0 || p.set_count <= 0) return L;
+    // default: SPLIT from 256 spp (below, a wave's slice is a few 64-sample batches and its drain dominates); SPLIT
+    // itself falls back to REFILL where it does not apply (STRICT arithmetic, meshes, more than 64 spheres)
+    if (variant == FLUX_KERNEL_DEFAULT) variant = N >= 256u ? FLUX_KERNEL_SPLIT : FLUX_KERNEL_REFILL;
+    if (N < 64u) variant = FLUX_KERNEL_STATIC;  // nothing to refill from
+    const uint32_t lpp = N >= 64u ? 64u : N;
+    const uint32_t ppw = 64u / lpp;
+    uint64_t waves = (npix + ppw - 1) / ppw;
+    // grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
+    if (variant != FLUX_KERNEL_STATIC && p.num_sets == (uint32_t)p.img_w)
+        waves = 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows +
+                        ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
+    // refill kernel: K waves per pixel (block = pixel), K from the sample count only
+    unsigned K = 1;  // largest power of two <= min(N / FLUX_MIN_SAMPLES_PER_WAVE, FLUX_MAX_WAVES_PER_PIXEL)
+    if (variant != FLUX_KERNEL_STATIC)
+        while (K * 2u <= (unsigned)FLUX_MAX_WAVES_PER_PIXEL && (uint64_t)K * 2u * FLUX_MIN_SAMPLES_PER_WAVE <= N) K *= 2u;
+    const bool tris = p.n_tris > 0;
+    // STRICT keeps 32 B of recursion stack per level and lane in LDS: fewer waves per pixel where four would not fit the
+    // 64 KiB a block may have (K = 4 holds 7 levels, K = 1 31); still a function of the job alone, never of the sharding
+    if (!fast && variant != FLUX_KERNEL_STATIC)
+        while (K > 1u && lane_stacks_lds(math, (size_t)p.max_depth, tris, (size_t)p.bvh_stack, 64 * K) > 60 * 1024) K /= 2u;
+    const unsigned block = (variant == FLUX_KERNEL_STATIC) ? FLUX_BLOCK_THREADS : 64u * K;
+    const unsigned wpb = (variant == FLUX_KERNEL_STATIC) ? block / 64 : 1u;  // refill: `waves` counts pixel slots
+    L.blocks = (waves + wpb - 1) / wpb;
+    if (fast && variant != FLUX_KERNEL_STATIC && tris && p.bvh_stack > 0) {  // BVH scenes: the traversal state machine
+        L.block = 64;  // one wave per pixel (its launch bounds): `blocks` already counts pixel slots
+        // over the 4-wide tree (kernel 4; 32 stack entries = 8 KiB per wave still allow 5 waves/SIMD) unless its stack would
+        // leave fewer than 3 waves/SIMD: then the binary tree's kernel (kernel 3)
+        size_t lds4 = (size_t)(p.bvh4_stack > 0 ? p.bvh4_stack : 1) * 64 * sizeof(int);
+        // the analytic set's records + the materials in LDS behind the stack (round 5) while they are small: a one-wave block must stay
+        // within the 6 LDS granules (7 680 B) that 5 waves/SIMD leave it, and the copy is made once per pixel
+        const size_t scene4 = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_mats * sizeof(DevMaterial) +
+                              (size_t)p.n_sph * sizeof(DevScanSphere);
+        const bool lds_scene4 = lds4 + scene4 <= 7680;
+        if (lds_scene4) lds4 += scene4;
+        // ... and unless a path's bounces do not fit its 32-bit material list (render_bvh4_kernel: mat_bits per bounce)
+        if (p.nodes4 != nullptr && p.bvh4_stack <= FLUX_BVH_WIDE_MAX_STACK) {
+            L.kernel = 4;
+            L.lds = lds4;
+            L.lds_scene = lds_scene4 ? 1 : 0;
+            L.typ = bvh4_typ(p, lds_scene4) ? 1 : 0;
+        } else {
+            L.kernel = 3;
+            L.lds = (size_t)p.bvh_stack * 64 * sizeof(int);
+        }
+        return L;
+    }
+    // analytic scenes: primary / secondary passes.  The kernel keeps the scene's hit records and scan spheres in the block's LDS, so it
+    // serves scenes whose records fit 16 KiB there (64 spheres -- the pixel mask's width -- leave room for 85 planes, demo2's 12 for 154;
+    // until round 6 the rule was "at most 16 planes", and a seventeenth sent the scene to the refill kernel); larger analytic scenes
+    // take the refill kernel, which reads the records from global memory (the launch plan says which)
+    const size_t scene_lds = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
+    if (fast && variant == FLUX_KERNEL_SPLIT && !tris && p.n_sph <= 64 && scene_lds <= 16384) {
+        L.kernel = 2;
+        L.block = block;
+        L.waves_per_pixel = K;
+        L.lds = (size_t)kQueueBytesPerWave * K + scene_lds;
+        L.typ = split_typ(p) ? 1 : 0;
+        L.max32 = p.n_sph <= 32 ? 1 : 0;
+        // The hit queue: as many slots as the LDS leaves a wave at FLUX_WPE_SPLIT waves/SIMD -- the CU's 128 granules of
+        // 1280 B shared by 4 * FLUX_WPE_SPLIT / K blocks, less the scene copy and the 96 B of `part` (demo2, K = 4: 25 granules, 7 568 B
+        // a wave, 110 slots of 68 B; H = 46).  A scene that leaves fewer than 64 + H slots (H at least FLUX_HITQ_MIN_TAKE), or whose bounce list does not fit 32 bits or does
+        // not give the throughput back exactly (long-form glossy weights: P.glossy_long), keeps the ray queue and the immediate bounce.
+        // C depends on the scene only through the size of its records, so a disk in place of a plane changes no lane a sample runs in.
+        // FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT override C (at most what fits) and H.
+        // A scene with a dielectric keeps the ray queue too: a dielectric bounce's weight depends on the branch it took, which its hit
+        // record does not tell.
+        if (p.glossy_long == 0 && p.has_diel == 0) {
+            const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
+            const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
+            uint32_t cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
+            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_CAP")) cap = std::min(cap, (uint32_t)std::max(0, std::atoi(e)) & ~1u);
+            uint32_t th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
+            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
+            int bits = 1;
+            while ((1 << bits) < p.n_sph + p.n_pln + p.n_dsk) ++bits;
+            if (cap >= 64u + th && bits * p.max_depth <= 32) {
+                L.hq_cap = (int)cap;
+                L.hq_th = (int)th;
+                L.hq_bits = bits;
+                L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
+            }
+        }
+        return L;
+    }
+    L.kernel = variant == FLUX_KERNEL_STATIC ? 0 : 1;
+    L.block = block;
+    L.waves_per_pixel = variant == FLUX_KERNEL_STATIC ? 1 : K;
+    L.lds = lane_stacks_lds(math, (size_t)p.max_depth, tris, (size_t)p.bvh_stack, block);
+    L.tris = tris ? 1 : 0;
+    return L;
+}
+
+}  // namespace flux

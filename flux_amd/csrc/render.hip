@@ -32,12 +32,18 @@
 //    bit-reproducible run to run and independent of how the frame is split), then * 1/n^2, max_to_one, and the
 //    3 doubles are written once.  No atomics.
 //
-// The loop body (render_body.inc) is compiled twice: STRICT under `#pragma clang fp contract(off)` with the
-// reference's operation order, FAST under contract(fast) with flux_math.h (see render_body.inc's header).
-#include <algorithm>
-#include <cstdlib>
-
+// The loop body (render_body.inc) is compiled three times: STRICT under `#pragma clang fp contract(off)` with the
+// reference's operation order, FAST under contract(fast) with flux_math.h (see render_body.inc's header), and FAST again with the
+// dielectric lobe.  Which copy, kernel and instantiation a call runs, with what block, grid and LDS, is the launch plan's decision
+// (launch_plan.cpp plan_render, host code compiled once); launch_render below only maps the plan to a kernel.  The instantiations:
+//  * render_static_kernel<STATS, TRIS>, render_refill_kernel<STATS, TRIS>: every copy;
+//  * render_split_kernel<STATS, MAX32, TYP, HQ>: FAST -- TYP (the usual analytic scene) only with MAX32, and in the copy with the
+//    dielectric lobe neither TYP nor HQ (the hit queue), which the plan never picks for a scene with a dielectric;
+//  * render_bvh_kernel<STATS>, render_bvh4_kernel<STATS, LDS_SCENE, TYP>: FAST -- TYP only with LDS_SCENE, and not in the copy
+//    with the dielectric lobe;
+//  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy.
 #include "flux_device.h"
+#include "flux_plan.h"
 #include "flux_tables.h"
 #include "flux_math.h"
 #include "../../include/flux_abi.h"
@@ -45,14 +51,10 @@
 // Tunables: NUMBERS only (overridable with -D, scripts/sweep_variants.py).  Every either/or of rounds 1-5 -- 45 boolean FLUX_*
 // switches with one shipped value and a measured verdict -- was folded into the code in round 6 (same ISA before and after,
 // profiles/r06_experiments/prune_flags/); the experiments' patches and logs stay under profiles/r0*_experiments/.  What is left
-// here, in flux_device.h (FLUX_UNI_SPHERES, FLUX_BVH_WIDE_MAX_STACK, FLUX_MAX_WAVES_PER_PIXEL, FLUX_MIN_SAMPLES_PER_WAVE) and in
-// bvh.cpp / flux_bvh.h (FLUX_BVH_BINS, FLUX_BVH_COLLAPSE_MODE, FLUX_BVH_LEAF), plus the six -DFLUX_DEBUG_* instrumentation hooks of
-// render_body.inc (never in the product build), is the whole list.
-// Block size: measured on demo2 at 1024 spp (refill kernel): 256 threads x 2 waves/SIMD 88.6 ms; 256 x 3 71.7 ms; 64 x 3 70.7 ms;
-// 256 x 4 83.0 ms (spills).  Waves never cooperate, so one wave per block lets the LDS stack of a finished wave be reused at once.
-#ifndef FLUX_BLOCK_THREADS
-#define FLUX_BLOCK_THREADS 64
-#endif
+// here, in flux_plan.h (FLUX_BLOCK_THREADS, FLUX_WPE_SPLIT, FLUX_HITQ_MIN_TAKE: the ones the launch planner reads too), in flux_device.h
+// (FLUX_UNI_SPHERES, FLUX_BVH_WIDE_MAX_STACK, FLUX_MAX_WAVES_PER_PIXEL, FLUX_MIN_SAMPLES_PER_WAVE) and in bvh.cpp / flux_bvh.h
+// (FLUX_BVH_BINS, FLUX_BVH_COLLAPSE_MODE, FLUX_BVH_LEAF), plus the six -DFLUX_DEBUG_* instrumentation hooks of render_body.inc (never
+// in the product build), is the whole list.
 #ifndef FLUX_WAVES_PER_EU
 #define FLUX_WAVES_PER_EU 3
 #endif
@@ -72,9 +74,6 @@
 // EARLY_AT < REFILL_AT the wave would re-enter the loop on the same counts and never advance
 static_assert(FLUX_BVH4_EARLY_AT >= FLUX_BVH_REFILL_AT,
               "FLUX_BVH4_EARLY_AT must not be below FLUX_BVH_REFILL_AT (render_bvh4_kernel would livelock)");
-#ifndef FLUX_WPE_SPLIT
-#define FLUX_WPE_SPLIT 5          // waves/SIMD of the split kernel: 96 VGPRs, nothing spilled since round 4 (4 until then: 128 VGPRs); demo2 @16384 spp 250.0 -> 225.4 ms
-#endif
 #ifndef FLUX_BVH_LEAF_NUM
 #define FLUX_BVH_LEAF_NUM 2       // binary-tree kernel: the inner-node loop is left once the lanes holding a leaf outweigh the descending ones,
 #define FLUX_BVH_LEAF_DEN 3       //     n_leaf * NUM > n_inner * DEN (swept: 1:1 178.4, 2:3 175.9, 1:2 176.4, 1:3 179.7, 3:2 178.8 ms at 1024 spp)
@@ -157,23 +156,27 @@ hipError_t generate_gloss_table(const double2 *pix, size_t count, double *gloss,
 
 namespace flux {
 
+// the kernel the launch planner names (launch_plan.cpp), in the copy of render_body.inc it names
 hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream) {
-    if (math == FLUX_MATH_STRICT) return strict::launch_render_impl(p, variant, stream);
-    if (p.has_diel) return fast_diel::launch_render_impl(p, variant, stream);
-    return fast::launch_render_impl(p, variant, stream);
-}
-
-// the kernel, grid and LDS launch_render would pick (host-side budget check, flux_ctx_launch_plan)
-LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
-    return math == FLUX_MATH_STRICT ? strict::plan_render_impl(p, variant)
-                                    : p.has_diel ? fast_diel::plan_render_impl(p, variant) : fast::plan_render_impl(p, variant);
+    const LaunchPlan L = plan_render(p, variant, math);
+    if (L.kernel < 0) return hipSuccess;
+    switch (L.copy) {
+        case kCopyStrict: return strict::launch_render_impl(L, p, stream);
+        case kCopyFast: return fast::launch_render_impl(L, p, stream);
+        case kCopyFastDiel: return fast_diel::launch_render_impl(L, p, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream) {
-    if (math == FLUX_MATH_STRICT) return strict::launch_shade_rays_impl(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
-    if (p.has_diel) return fast_diel::launch_shade_rays_impl(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
-    return fast::launch_shade_rays_impl(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
+    const size_t lds = shade_rays_lds(p, math);
+    switch (kernel_copy(p, math)) {
+        case kCopyStrict: return strict::launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
+        case kCopyFast: return fast::launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
+        case kCopyFastDiel: return fast_diel::launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 // ---- flux_math.h under test: out[i] = fn(a[i], b[i]) computed on the device ----------------------

@@ -1848,34 +1848,17 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, TRIS ? FLUX_WPE_WIDE
 // same), so path statistics equal the CPU checker's exactly; the image equals the refill kernel's up to the order in which
 // a pixel's samples are summed (still a fixed order: bit-reproducible, independent of how the frame is sharded).
 // ---------------------------------------------------------------------------
-// a queued path: ox oy oz dx dy dz tr tg tb (+ the pixel sample sqx sqy only in builds without the glossy-lobe table: with it
-// GlossySpecular's re-mapped sample is read from the table by the sample index, and the pixel sample itself is dead after
-// the primary ray)
-constexpr int kQueueSq = 0;
-constexpr int kQueueDoubles = 9 + kQueueSq;
-constexpr int kQueueBytesPerWave = (kQueueDoubles * 64) * 8 + 2 * 64 * 4;         // + sample index, Path::self (int)
-
-// The hit queue (plan_render_impl chooses C per scene): C slots per wave, structure of arrays [field][slot] as above.
+// The two queues' layouts, kQueueBytesPerWave and kHitQBytesPerSlot, are in flux_plan.h: the launch plan reserves their LDS.
+// A queued path: ox oy oz dx dy dz tr tg tb, the sample index and Path::self (GlossySpecular's re-mapped sample is read from the
+// glossy-lobe table by the sample index, so the pixel sample itself is dead after the primary ray).
+// The hit queue (plan_render chooses C per scene): C slots per wave, structure of arrays [field][slot] as above.
 // Phase B only CLASSIFIES its hits; a continuing hit is parked here -- the segment o d and its hit distance t (8 B each), the hit-record
 // index and the depth (one int), the sample index (int) and the path's throughput -- and its bounce runs later, in a pass whose free
 // lanes take a full batch of parked hits at once (bounce_parked_hit), instead of under the sparse mask of the scan's survivors.
-// The throughput is kept either as three doubles (FLUX_HITQ_LIST=0: 88 B a slot) or as the list of the path's earlier bounce records,
-// `bits` per bounce in one int (FLUX_HITQ_LIST=1, the default: 68 B a slot): without long-form glossy weights (P.glossy_long) a bounce
+// The throughput is kept as the list of the path's earlier bounce records, `bits` per bounce in one int (68 B a slot; three doubles,
+// 88 B a slot, was measured slower: DESIGN.md §4, the hit queue): without long-form glossy weights (P.glossy_long) a bounce
 // of an analytic shape multiplies the throughput by its record's (fr, fg, fb) and nothing else, so the product recomputed front to back from the block's LDS copy of the records is bit
 // for bit the running one.  Every decision of the pass loop is a count (wave-uniform), so frames stay bit-reproducible.
-#ifndef FLUX_HITQ_LIST
-#define FLUX_HITQ_LIST 1
-#endif
-#ifndef FLUX_HITQ_MIN_TAKE
-// H, the parked hits a wave waits for before a pass takes them instead of starting 64 more samples, is C - 64 (at most 64): phase A
-// runs while the queue has room for its 64 continuations.  Below this H the bounce batches are too thin to pay for the queue
-// (demo2 @16384 spp, C = 110: H 46 159.2, 40 162.9, 32 171.0, 24 182.3, 16 200.9 ms; the ray queue 172.0 ms), and the scene keeps
-// the ray queue.
-#define FLUX_HITQ_MIN_TAKE 32
-#endif
-constexpr int kHitQDoubles = FLUX_HITQ_LIST ? 7 : 10;                  // o d t (+ tr tg tb)
-constexpr int kHitQInts = FLUX_HITQ_LIST ? 3 : 2;                      // hit | depth << 16, sample index (+ bounce list)
-constexpr int kHitQBytesPerSlot = kHitQDoubles * 8 + kHitQInts * 4;    // 68 | 88
 
 // The spheres a primary ray of pixel (row, col) can hit: a conservative wave-uniform mask (bit = scan index).
 // Every primary ray starts on the lens, |o - eye| <= R = lens_radius (to_poisson_disc maps into the unit disc,
@@ -2009,7 +1992,7 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
 }
 
 // HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
-// bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see plan_render_impl): the 64-entry ray queue and phase B's
+// bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see launch_plan.cpp plan_render): the 64-entry ray queue and phase B's
 // bounce at once, in the lanes that continue.
 template <bool STATS, bool MAX32, bool TYP, bool HQ = false>
 __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void render_split_kernel(const RenderParams P0, int hq_cap, int hq_th,
@@ -2033,7 +2016,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
     int *qi = reinterpret_cast<int *>(q + (HQ ? (size_t)kHitQDoubles * hq_cap : (size_t)kQueueDoubles * 64));  // this wave's queue: [field][slot]
     // The scene's hit records (96 B per shape) and scan spheres (32 B) copied into the block's LDS behind the queues: the per-lane gathers
     // of the shading step and of the candidate loop -- dependent loads in the middle of a pass, ~600 cycles each from the L2 -- become
-    // LDS reads (~100).  The launch plan reserves the bytes (plan_render_impl: the split kernel serves scenes whose records fit 16 KiB).
+    // LDS reads (~100).  The launch plan reserves the bytes (plan_render: the split kernel serves scenes whose records fit 16 KiB).
     const char *const frec_lds = reinterpret_cast<const char *>(lds_stack);
     const char *const fsph_lds = frec_lds + (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec);
     {
@@ -2078,7 +2061,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             p.depth = kDeadDepth;
             p.sq = make_double2(0.5, 0.5);
             uint32_t i = 0;
-            uint32_t ml = 0;  // FLUX_HITQ_LIST: the records of the path's bounces so far, entry k at bit k * hq_bits
+            uint32_t ml = 0;  // the records of the path's bounces so far, entry k at bit k * hq_bits
             // ---- phase A, while fewer than H hits are parked and the queue has room for all 64 continuations: samples next .. next+63,
             //      their continuing paths stay in their lanes
             const bool run_a = next < s_hi && nhit < H && nhit + 64u <= C;
@@ -2152,25 +2135,19 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                         i = (uint32_t)qi[C + slot];
                         const int hit = hd & 0xffff;
                         p.depth = hd >> 16;
-                        if (FLUX_HITQ_LIST) {
-                            // the throughput, front to back as fast_bounce formed it (the first bounce's weight, then one product per bounce)
-                            ml = (uint32_t)qi[2 * C + slot];
-                            const DevHitRec &R0 = recs[ml & bmask];
-                            p.tr = R0.fr;
-                            p.tg = R0.fg;
-                            p.tb = R0.fb;
-                            for (int k = 1; k < p.depth - 1; ++k) {
-                                const DevHitRec &Rk = recs[(ml >> (k * hq_bits)) & bmask];
-                                p.tr *= Rk.fr;
-                                p.tg *= Rk.fg;
-                                p.tb *= Rk.fb;
-                            }
-                            ml |= (uint32_t)hit << ((p.depth - 1) * hq_bits);
-                        } else {
-                            p.tr = q[7 * C + slot];
-                            p.tg = q[8 * C + slot];
-                            p.tb = q[9 * C + slot];
+                        // the throughput, front to back as fast_bounce formed it (the first bounce's weight, then one product per bounce)
+                        ml = (uint32_t)qi[2 * C + slot];
+                        const DevHitRec &R0 = recs[ml & bmask];
+                        p.tr = R0.fr;
+                        p.tg = R0.fg;
+                        p.tb = R0.fb;
+                        for (int k = 1; k < p.depth - 1; ++k) {
+                            const DevHitRec &Rk = recs[(ml >> (k * hq_bits)) & bmask];
+                            p.tr *= Rk.fr;
+                            p.tg *= Rk.fg;
+                            p.tb *= Rk.fb;
                         }
+                        ml |= (uint32_t)hit << ((p.depth - 1) * hq_bits);
                         bounce_parked_hit<STATS, TYP>(P, p, set_p, i, hit, t, st, 6, frec_lds);
                     }
                     nhit -= take;
@@ -2222,13 +2199,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 q[6 * C + slot] = t;
                 qi[slot] = hit | (p.depth << 16);
                 qi[C + slot] = (int)i;
-                if (FLUX_HITQ_LIST) {
-                    qi[2 * C + slot] = (int)ml;
-                } else {
-                    q[7 * C + slot] = p.tr;
-                    q[8 * C + slot] = p.tg;
-                    q[9 * C + slot] = p.tb;
-                }
+                qi[2 * C + slot] = (int)ml;
             }
             nhit += (uint32_t)__popcll(pmask);
         }
@@ -2284,10 +2255,6 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                     p.r.dx = q[3 * 64 + slot];
                     p.r.dy = q[4 * 64 + slot];
                     p.r.dz = q[5 * 64 + slot];
-                    if (kQueueSq) {
-                        p.sq.x = q[9 * 64 + slot];
-                        p.sq.y = q[10 * 64 + slot];
-                    }
                     p.tr = q[6 * 64 + slot];
                     p.tg = q[7 * 64 + slot];
                     p.tb = q[8 * 64 + slot];
@@ -2364,10 +2331,6 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                     q[3 * 64 + slot] = pa.r.dx;
                     q[4 * 64 + slot] = pa.r.dy;
                     q[5 * 64 + slot] = pa.r.dz;
-                    if (kQueueSq) {
-                        q[9 * 64 + slot] = pa.sq.x;
-                        q[10 * 64 + slot] = pa.sq.y;
-                    }
                     q[6 * 64 + slot] = pa.tr;
                     q[7 * 64 + slot] = pa.tg;
                     q[8 * 64 + slot] = pa.tb;
@@ -2903,7 +2866,7 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_BVH4) void render_bvh4
     constexpr int kEntry = 64 * 4;
     // the analytic scene's hit records, the materials and the scan spheres behind the stack (as in render_split_kernel): the shading
     // step's dependent gathers -- triangle record -> material record, hit record, a sphere record per candidate -- lose an L2 round trip
-    // (LDS_SCENE: the launch plan chose this instantiation and reserved the bytes -- small analytic sets only, plan_render_impl)
+    // (LDS_SCENE: the launch plan chose this instantiation and reserved the bytes -- small analytic sets only, plan_render)
     const char *const frec_lds = reinterpret_cast<const char *>(lds_stack) + (size_t)(P.bvh4_stack > 0 ? P.bvh4_stack : 1) * kEntry;
     const char *const mats_lds = frec_lds + (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec);
     const char *const fsph_lds = mats_lds + (size_t)P.n_mats * sizeof(DevMaterial);
@@ -3243,132 +3206,19 @@ __global__ __launch_bounds__(64, 1) void shade_rays_kernel(const RenderParams P,
     out_rgb[3 * k + 2] = Lb;
 }
 
-static hipError_t launch_shade_rays_impl(const RenderParams &p, const double *d_rays, int n, int depth, uint32_t set,
+static hipError_t launch_shade_rays_impl(const RenderParams &p, size_t lds, const double *d_rays, int n, int depth, uint32_t set,
                                          uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    const bool tris = p.n_tris > 0;
-    const size_t lds = (FLUX_FAST ? 0 : (size_t)p.max_depth * 4 * 64 * sizeof(double)) +
-                       (tris ? (size_t)p.bvh_stack * 64 * sizeof(int) : 0);
     const dim3 g((unsigned)((n + 63) / 64)), b(64);
-    if (tris) shade_rays_kernel<true><<<g, b, lds, stream>>>(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t);
+    if (p.n_tris > 0) shade_rays_kernel<true><<<g, b, lds, stream>>>(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t);
     else shade_rays_kernel<false><<<g, b, lds, stream>>>(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t);
     return hipGetLastError();
 }
 
-#if FLUX_FAST
-// the usual scene of the split kernel (scan_shapes_fast's TYP: these values become constants of the instantiation; and no disks and no
-// dielectrics: the instantiation leaves their loop and their lobe out)
-static bool split_typ(const RenderParams &p) {
-    return p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 &&
-           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0;
-}
-#endif
-
-// Which kernel a render call runs (flux_tables.h LaunchPlan): decided HERE, once.
-static LaunchPlan plan_render_impl(const RenderParams &p, int variant) {
-    LaunchPlan L = {-1, 64, 0, 0, 1, 0, 0, 0, 0};
-    const uint32_t N = p.nsamp;
-    const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
-    if (npix == 0 || p.set_count <= 0) return L;
-    // default: SPLIT from 256 spp (below, a wave's slice is a few 64-sample batches and its drain dominates); SPLIT
-    // itself falls back to REFILL where it does not apply (STRICT arithmetic, meshes, more than 64 spheres)
-    if (variant == FLUX_KERNEL_DEFAULT) variant = N >= 256u ? FLUX_KERNEL_SPLIT : FLUX_KERNEL_REFILL;
-    if (N < 64u) variant = FLUX_KERNEL_STATIC;  // nothing to refill from
-    const uint32_t lpp = N >= 64u ? 64u : N;
-    const uint32_t ppw = 64u / lpp;
-    uint64_t waves = (npix + ppw - 1) / ppw;
-    // grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
-    if (variant != FLUX_KERNEL_STATIC && p.num_sets == (uint32_t)p.img_w)
-        waves = 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows +
-                        ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
-    // refill kernel: K waves per pixel (block = pixel), K from the sample count only
-    unsigned K = 1;  // largest power of two <= min(N / FLUX_MIN_SAMPLES_PER_WAVE, FLUX_MAX_WAVES_PER_PIXEL)
-    if (variant != FLUX_KERNEL_STATIC)
-        while (K * 2u <= (unsigned)FLUX_MAX_WAVES_PER_PIXEL && (uint64_t)K * 2u * FLUX_MIN_SAMPLES_PER_WAVE <= N) K *= 2u;
-#if !FLUX_FAST
-    // STRICT keeps 32 B of recursion stack per level and lane in LDS: fewer waves per pixel where four would not fit the
-    // 64 KiB a block may have (K = 4 holds 7 levels, K = 1 31); still a function of the job alone, never of the sharding
-    if (variant != FLUX_KERNEL_STATIC)
-        while (K > 1u && (size_t)p.max_depth * 4 * 64 * K * sizeof(double) + (p.n_tris > 0 ? (size_t)p.bvh_stack * 64 * K * sizeof(int) : 0) > 60 * 1024) K /= 2u;
-#endif
-    const unsigned block = (variant == FLUX_KERNEL_STATIC) ? FLUX_BLOCK_THREADS : 64u * K;
-    const unsigned wpb = (variant == FLUX_KERNEL_STATIC) ? block / 64 : 1u;  // refill: `waves` counts pixel slots
-    L.blocks = (waves + wpb - 1) / wpb;
-    const bool tris = p.n_tris > 0;
-#if FLUX_FAST
-    if (variant != FLUX_KERNEL_STATIC && tris && p.bvh_stack > 0) {  // BVH scenes: the traversal state machine
-        L.block = 64;  // one wave per pixel (its launch bounds): `blocks` already counts pixel slots
-        // over the 4-wide tree (kernel 4; 32 stack entries = 8 KiB per wave still allow 5 waves/SIMD) unless its stack would
-        // leave fewer than 3 waves/SIMD: then the binary tree's kernel (kernel 3)
-        size_t lds4 = (size_t)(p.bvh4_stack > 0 ? p.bvh4_stack : 1) * 64 * sizeof(int);
-        // the analytic set's records + the materials in LDS behind the stack (round 5) while they are small: a one-wave block must stay
-        // within the 6 LDS granules (7 680 B) that 5 waves/SIMD leave it, and the copy is made once per pixel
-        const size_t scene4 = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_mats * sizeof(DevMaterial) +
-                              (size_t)p.n_sph * sizeof(DevScanSphere);
-        const bool lds_scene4 = lds4 + scene4 <= 7680;
-        if (lds_scene4) lds4 += scene4;
-        // ... and unless a path's bounces do not fit its 32-bit material list (render_bvh4_kernel: mat_bits per bounce)
-        if (p.nodes4 != nullptr && p.bvh4_stack <= FLUX_BVH_WIDE_MAX_STACK) {
-            L.kernel = 4;
-            L.lds = lds4;
-            L.lds_scene = lds_scene4 ? 1 : 0;
-        } else {
-            L.kernel = 3;
-            L.lds = (size_t)p.bvh_stack * 64 * sizeof(int);
-        }
-        return L;
-    }
-    // analytic scenes: primary / secondary passes.  The kernel keeps the scene's hit records and scan spheres in the block's LDS, so it
-    // serves scenes whose records fit 16 KiB there (64 spheres -- the pixel mask's width -- leave room for 85 planes, demo2's 12 for 154;
-    // until round 6 the rule was "at most 16 planes", and a seventeenth sent the scene to the refill kernel); larger analytic scenes
-    // take the refill kernel, which reads the records from global memory (the launch plan says which)
-    const size_t scene_lds = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
-    if (variant == FLUX_KERNEL_SPLIT && !tris && p.n_sph <= 64 && scene_lds <= 16384) {
-        L.kernel = 2;
-        L.block = block;
-        L.waves_per_pixel = K;
-        L.lds = (size_t)kQueueBytesPerWave * K + scene_lds;
-        // The hit queue: as many slots as the LDS leaves a wave at FLUX_WPE_SPLIT waves/SIMD -- the CU's 128 granules of
-        // 1280 B shared by 4 * FLUX_WPE_SPLIT / K blocks, less the scene copy and the 96 B of `part` (demo2, K = 4: 25 granules, 7 568 B
-        // a wave, 110 slots of 68 B; H = 46).  A scene that leaves fewer than 64 + H slots (H at least FLUX_HITQ_MIN_TAKE), or whose bounce list does not fit 32 bits or does
-        // not give the throughput back exactly (long-form glossy weights: P.glossy_long), keeps the ray queue and the immediate bounce.
-        // C depends on the scene only through the size of its records, so a disk in place of a plane changes no lane a sample runs in.
-        // FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT override C (at most what fits) and H.
-        // A scene with a dielectric keeps the ray queue too: a dielectric bounce's weight depends on the branch it took, which its hit
-        // record does not tell (DESIGN.md §5c).
-        if ((!FLUX_HITQ_LIST || p.glossy_long == 0) && p.has_diel == 0) {
-            const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
-            const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
-            uint32_t cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
-            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_CAP")) cap = std::min(cap, (uint32_t)std::max(0, std::atoi(e)) & ~1u);
-            uint32_t th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
-            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
-            int bits = 1;
-            while ((1 << bits) < p.n_sph + p.n_pln + p.n_dsk) ++bits;
-            const bool list_fits = !FLUX_HITQ_LIST || bits * p.max_depth <= 32;
-            if (cap >= 64u + th && list_fits) {
-                L.hq_cap = (int)cap;
-                L.hq_th = (int)th;
-                L.hq_bits = bits;
-                L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
-            }
-        }
-        return L;
-    }
-#endif
-    L.kernel = variant == FLUX_KERNEL_STATIC ? 0 : 1;
-    L.block = block;
-    L.waves_per_pixel = variant == FLUX_KERNEL_STATIC ? 1 : K;
-    L.lds = (FLUX_FAST ? 0 : (size_t)p.max_depth * 4 * block * sizeof(double)) +
-            (tris ? (size_t)p.bvh_stack * block * sizeof(int) : 0);
-    return L;
-}
-
-static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStream_t stream) {
-    const LaunchPlan L = plan_render_impl(p, variant);
-    if (L.kernel < 0) return hipSuccess;
+// Runs the kernel the launch plan names (launch_plan.cpp plan_render): its fields become template arguments, nothing is decided here.
+static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p, hipStream_t stream) {
     if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const bool tris = p.n_tris > 0;
+    const bool tris = L.tris != 0;
     const bool stats = p.stats != nullptr;
     const dim3 g((unsigned)L.blocks), b(L.block);
     const size_t lds = L.lds;
@@ -3380,18 +3230,21 @@ static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStre
         else K<false, false><<<g, b, lds, stream>>>(p);                    \
     } while (0)
 #if FLUX_FAST
+    // The copy with the dielectric lobe has no TYP and no hit-queue instantiation: the planner never asks for one for a scene with a
+    // dielectric, and a plan that does is a planner bug.
     if (L.kernel == 3) {
         if (stats) render_bvh_kernel<true><<<g, b, lds, stream>>>(p);
         else render_bvh_kernel<false><<<g, b, lds, stream>>>(p);
         return hipGetLastError();
     }
     if (L.kernel == 4) {
-        // the usual analytic set beside the mesh (scan_shapes_fast's TYP / MAX32: constants of the instantiation)
-        const bool typ = L.lds_scene && p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.n_uni == 1 && p.fsph32 != nullptr &&
-                         p.n_dsk == 0 && p.has_diel == 0;
-        if (typ) {
+        if (L.typ) {
+#if FLUX_DIEL
+            return hipErrorInvalidValue;
+#else
             if (stats) render_bvh4_kernel<true, true, true><<<g, b, lds, stream>>>(p);
             else render_bvh4_kernel<false, true, true><<<g, b, lds, stream>>>(p);
+#endif
         } else if (L.lds_scene) {
             if (stats) render_bvh4_kernel<true, true, false><<<g, b, lds, stream>>>(p);
             else render_bvh4_kernel<false, true, false><<<g, b, lds, stream>>>(p);
@@ -3402,20 +3255,29 @@ static hipError_t launch_render_impl(const RenderParams &p, int variant, hipStre
         return hipGetLastError();
     }
     if (L.kernel == 2) {
-        const bool max32 = p.n_sph <= 32;  // (one group of the sphere filter: scan_shapes_fast's MAX32)
-        const bool typ = split_typ(p);
         const int c = L.hq_cap, h = L.hq_th, bits = L.hq_bits;
-#define FLUX_LAUNCH_SPLIT(HQ)                                                                                      \
-    do {                                                                                                           \
-        if (stats && typ) render_split_kernel<true, true, true, HQ><<<g, b, lds, stream>>>(p, c, h, bits);         \
-        else if (stats && max32) render_split_kernel<true, true, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits); \
-        else if (stats) render_split_kernel<true, false, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits);         \
-        else if (typ) render_split_kernel<false, true, true, HQ><<<g, b, lds, stream>>>(p, c, h, bits);            \
-        else if (max32) render_split_kernel<false, true, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits);         \
-        else render_split_kernel<false, false, false, HQ><<<g, b, lds, stream>>>(p, c, h, bits);                   \
+        const bool hq = L.hq_cap > 0;
+#define FLUX_LAUNCH_SPLIT(MAX32, TYP, HQ)                                                                      \
+    do {                                                                                                       \
+        if (stats) render_split_kernel<true, MAX32, TYP, HQ><<<g, b, lds, stream>>>(p, c, h, bits);            \
+        else render_split_kernel<false, MAX32, TYP, HQ><<<g, b, lds, stream>>>(p, c, h, bits);                 \
     } while (0)
-        if (L.hq_cap > 0) FLUX_LAUNCH_SPLIT(true);
-        else FLUX_LAUNCH_SPLIT(false);
+#if FLUX_DIEL
+        if (L.typ || hq) return hipErrorInvalidValue;
+#else
+        if (L.typ) {
+            if (hq) FLUX_LAUNCH_SPLIT(true, true, true);
+            else FLUX_LAUNCH_SPLIT(true, true, false);
+            return hipGetLastError();
+        }
+        if (hq) {
+            if (L.max32) FLUX_LAUNCH_SPLIT(true, false, true);
+            else FLUX_LAUNCH_SPLIT(false, false, true);
+            return hipGetLastError();
+        }
+#endif
+        if (L.max32) FLUX_LAUNCH_SPLIT(true, false, false);
+        else FLUX_LAUNCH_SPLIT(false, false, false);
 #undef FLUX_LAUNCH_SPLIT
         return hipGetLastError();
     }

@@ -3,14 +3,17 @@
 // For each scene it writes every buffer a context uploads, as <out dir>/<scene>.<buffer>.bin, and every scene-derived scalar as
 // text, <out dir>/<scene>.scalars.txt: the test pins their SHA-256.  The scenes are the shipped ones loaded through the C++ host
 // layer and a generated height field whose triangles need the threaded record pool and the forked BVH build.  Small inline
-// scenes cover each branch of the derived flags.  Prints one "ok <name>" per passed check and "all ok" at the end; exits 1 on
-// the first failure.
+// scenes cover each branch of the derived flags.  It also writes <out dir>/plans.txt: the launch planner's answer (flux_plan.h
+// plan_render: kernel, instantiation, block, grid, LDS) for every scene over a grid of jobs, one line each, which the test pins too.
+// Prints one "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "../flux_amd/csrc/flux_plan.h"
 #include "../flux_amd/csrc/scene_build.h"
 #include "../flux_amd/host/flux_host.hpp"
 
@@ -94,6 +97,44 @@ static int build(const flux_scene_desc &desc, flux::HostScene &h) {
     return rc;
 }
 
+// The launch plans of one scene, as a context would ask for them (abi.hip: rows_params / sets_params, then the traversal hook), over
+// sample roots x kernel variants x arithmetic x traversal x a rows and a sets launch; max_trace_depth 5 (the job default).  Where the
+// upload sets a pointer the planner tests, a placeholder stands in for it.
+static std::string g_plans;
+static void plans(const std::string &name, const flux::HostScene &h, const char *tag) {
+    static const flux::DevScanSphere32 fsph32_placeholder{};
+    static const flux::DevNode4Q nodes4_placeholder{};
+    static const char *kVariant[] = {"default", "static", "refill", "split"};
+    static const char *kTraversal[] = {"bvh", "brute", "binary"};
+    char buf[400];
+    for (const uint32_t root : {4u, 8u, 16u, 128u})
+        for (const int variant : {FLUX_KERNEL_DEFAULT, FLUX_KERNEL_STATIC, FLUX_KERNEL_REFILL, FLUX_KERNEL_SPLIT})
+            for (const int math : {FLUX_MATH_FAST, FLUX_MATH_STRICT})
+                for (const int trav : {FLUX_TRAVERSE_BVH, FLUX_TRAVERSE_BRUTE, FLUX_TRAVERSE_BVH_BINARY})
+                    for (const bool sets : {false, true}) {
+                        flux::RenderParams p = h.rp;
+                        p.max_depth = 5;
+                        p.nsamp = root * root;
+                        p.fsph32 = h.filter32 ? &fsph32_placeholder : nullptr;
+                        p.nodes4 = h.arena.empty() ? nullptr : &nodes4_placeholder;
+                        p.num_rows = p.img_h;
+                        if (sets) {  // the first third of the sets, one rank's share at G = 3
+                            p.set_count = (int32_t)(p.num_sets + 2) / 3;
+                            p.out_by_set = 1;
+                        }
+                        if (trav == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
+                        if (trav == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
+                        const flux::LaunchPlan L = flux::plan_render(p, variant, math);
+                        std::snprintf(buf, sizeof(buf),
+                                      "%s%s root=%u variant=%s math=%s traversal=%s launch=%s kernel=%d copy=%d tris=%d typ=%d max32=%d "
+                                      "lds_scene=%d hq_cap=%d hq_th=%d hq_bits=%d block=%u blocks=%llu lds=%zu K=%u\n",
+                                      name.c_str(), tag, root, kVariant[variant], math == FLUX_MATH_STRICT ? "strict" : "fast",
+                                      kTraversal[trav], sets ? "sets" : "rows", L.kernel, L.copy, L.tris, L.typ, L.max32, L.lds_scene,
+                                      L.hq_cap, L.hq_th, L.hq_bits, L.block, (unsigned long long)L.blocks, L.lds, L.waves_per_pixel);
+                        g_plans += buf;
+                    }
+}
+
 static int dump(const std::string &name, const flux_scene_desc &desc) {
     flux::HostScene h;
     CHECK(build(desc, h) == FLUX_OK);
@@ -105,6 +146,10 @@ static int dump(const std::string &name, const flux_scene_desc &desc) {
     CHECK(write_vec(name + ".shapes.bin", h.shapes) && write_vec(name + ".mats.bin", mats) && write_vec(name + ".fscene.bin", h.fscene) &&
           write_vec(name + ".tris.bin", h.tris) && write_vec(name + ".nodes.bin", h.nodes) && write_vec(name + ".nodesq.bin", h.nodesq) &&
           write_vec(name + ".arena.bin", h.arena) && write_file(name + ".scalars.txt", sc.data(), sc.size()));
+    plans(name, h, "");
+    setenv("FLUX_SPLIT_HITQ_CAP", "0", 1);  // the split kernel without its hit queue
+    plans(name, h, "+hitq_cap0");
+    unsetenv("FLUX_SPLIT_HITQ_CAP");
     std::printf("ok dump %s\n", name.c_str());
     return 0;
 }
@@ -172,6 +217,8 @@ int main(int argc, char **argv) {
         return 2;
     }
     g_out = argv[2];
+    unsetenv("FLUX_SPLIT_HITQ_CAP");  // the planner's test overrides: the plans below are the shipped ones
+    unsetenv("FLUX_SPLIT_HITQ_TAKE_AT");
     for (const char *name : {"demo1", "demo2", "disk_light", "glass"}) {
         const AbiScene abi(scene_from_yaml_file(std::string(argv[1]) + "/" + name + ".yml"));
         if (dump(name, abi.desc)) return 1;
@@ -239,6 +286,8 @@ int main(int argc, char **argv) {
     CHECK(inline_scene(sphere(0, 0, 0, 100, true, true) + sphere(1e16, 1, 0, 1, false), h) == FLUX_OK);
     CHECK(!h.filter32 && h.rp.n_uni == 0 && h.rp.env_short == 0 && h.rp.f32_groups == 0 && h.f32_half == -1 && h.f32_top == 0);
     std::printf("ok no f32 filter\n");
+    CHECK(write_file("plans.txt", g_plans.data(), g_plans.size()));
+    std::printf("ok plans\n");
     std::printf("all ok\n");
     return 0;
 }

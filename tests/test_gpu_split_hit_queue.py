@@ -1,4 +1,4 @@
-"""The split kernel's hit queue (render_body.inc, kHitQBytesPerSlot): phase B parks its continuing hits in LDS and bounces them in
+"""The split kernel's hit queue (render_body.inc; kHitQBytesPerSlot in flux_plan.h): phase B parks its continuing hits in LDS and bounces them in
 batches.  Each sample's arithmetic is the immediate bounce's, so against the refill and static kernels the path statistics are
 identical and the images equal to the summation order (1e-12); decisions are counts, so frames are bit-reproducible and independent
 of how they are sharded.  FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT (read by the launch plan) reach the small queues and the

@@ -1,7 +1,8 @@
 """The host half of context creation (flux_amd/csrc/scene_build.cpp) checked on the CPU: tests/scene_build_selftest.cpp builds the
 records, the FAST scene image, the mesh's triangles and trees and the scene-derived RenderParams of four shipped scenes and a
 height field, and this test pins the SHA-256 of every buffer.  The digests are the bytes the kernels read: a change to any of
-them changes what a context uploads."""
+them changes what a context uploads.  The same program asks the launch planner (flux_amd/csrc/launch_plan.cpp) which kernel
+instantiation, block, grid and LDS each of those scenes gets over a grid of jobs; the table is pinned too."""
 import hashlib
 import os
 import subprocess
@@ -57,6 +58,11 @@ DIGESTS = {
 }
 
 
+# plans.txt: 5 scenes x sample roots 4 / 8 / 16 / 128 x 4 kernel variants x FAST / STRICT x 3 traversals x a rows and a sets launch,
+# then the same under FLUX_SPLIT_HITQ_CAP=0 (one line each)
+PLANS_SHA256 = "12f2966b8918c2997213ead19f3703bc8454ff8affb538bf20b229de6838fa32"
+
+
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
     from flux_amd import build
@@ -76,7 +82,8 @@ def selftest(tmp_path_factory):
 
 def _run(exe, out_dir, threads=None):
     env = dict(os.environ)
-    env.pop("FLUX_BUILD_THREADS", None)
+    for k in ("FLUX_BUILD_THREADS", "FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_HITQ_TAKE_AT"):
+        env.pop(k, None)
     if threads is not None:
         env["FLUX_BUILD_THREADS"] = str(threads)
     os.makedirs(out_dir, exist_ok=True)
@@ -92,14 +99,19 @@ def _run(exe, out_dir, threads=None):
 
 
 @pytest.fixture(scope="module")
-def default_run(selftest, tmp_path_factory):
-    return _run(selftest, tmp_path_factory.mktemp("default"))
+def default_out(tmp_path_factory):
+    return tmp_path_factory.mktemp("default")
+
+
+@pytest.fixture(scope="module")
+def default_run(selftest, default_out):
+    return _run(selftest, default_out)
 
 
 def test_selftest_checks(default_run):
     stdout, _ = default_run
     for name in ("unit normal", "non-unit plane normal", "sphere beyond 1e3", "one emissive invert sphere", "two invert spheres",
-                 "group walk", "no f32 filter") + tuple(f"dump {s}" for s in SCENE_NAMES):
+                 "group walk", "no f32 filter", "plans") + tuple(f"dump {s}" for s in SCENE_NAMES):
         assert f"ok {name}" in stdout
     assert "all ok" in stdout
 
@@ -113,3 +125,38 @@ def test_mesh_is_the_same_with_one_thread(selftest, default_run, tmp_path):
     _, digests = _run(selftest, tmp_path, threads=1)
     assert {k: v for k, v in digests.items() if k.startswith("heightfield.")} == \
            {k: v for k, v in default_run[1].items() if k.startswith("heightfield.")}
+
+
+def _plans(out_dir):
+    rows = {}
+    with open(os.path.join(out_dir, "plans.txt")) as f:
+        for line in f:
+            head, _, rest = line.partition(" kernel=")
+            rows[head] = dict(kv.split("=") for kv in ("kernel=" + rest).split())
+    return rows
+
+
+def test_launch_plans_are_pinned(default_run, default_out):
+    with open(os.path.join(default_out, "plans.txt"), "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == PLANS_SHA256
+    plans = _plans(default_out)
+    assert len(plans) == 5 * 4 * 4 * 2 * 3 * 2 * 2
+
+    def plan(scene, math="fast", traversal="bvh", launch="rows", root=128, variant="default"):
+        return plans[f"{scene} root={root} variant={variant} math={math} traversal={traversal} launch={launch}"]
+
+    # demo2 at 16384 spp: the split kernel, 4 waves per pixel, the hit queue of 110 slots taken at H = 46, the TYP instantiation
+    p = plan("demo2")
+    assert (p["kernel"], p["K"], p["hq_cap"], p["hq_th"], p["typ"], p["max32"], p["copy"]) == ("2", "4", "110", "46", "1", "1", "1")
+    assert plan("demo2+hitq_cap0")["hq_cap"] == "0"
+    # glass: the split kernel with the ray queue, not TYP, in the copy with the dielectric lobe
+    p = plan("glass")
+    assert (p["kernel"], p["hq_cap"], p["typ"], p["copy"]) == ("2", "0", "0", "2")
+    # the height field: the 4-wide tree's kernel, and the binary tree's under FLUX_TRAVERSE_BVH_BINARY
+    assert plan("heightfield")["kernel"] == "4"
+    assert plan("heightfield", traversal="binary")["kernel"] == "3"
+    # demo2 in STRICT: the refill kernel in the STRICT copy
+    p = plan("demo2", math="strict")
+    assert (p["kernel"], p["copy"]) == ("1", "0")
+    # no plan asks the copy with the dielectric lobe for an instantiation it does not compile (TYP, the hit queue)
+    assert all(r["typ"] == "0" and r["hq_cap"] == "0" for r in plans.values() if r["copy"] == "2")
