@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "scene_schema.hpp"
 #include "yaml_lite.hpp"
 
 namespace flux_host {
@@ -17,113 +18,93 @@ using yaml_lite::Node;
 
 [[noreturn]] void bad(const std::string &m) { throw FluxError(FLUX_E_INVALID, m); }
 
-const Node &req(const Node &m, const char *key, const std::string &what) {
-    if (m.kind != Node::Map) bad(what + ": expected a map");
-    const Node *n = m.find(key);
-    if (!n) bad(what + ": missing field `" + key + "`");
-    return *n;
-}
+// serde_yaml::from_reader over the lists of scene_schema.hpp: `n` is the node being read, `path` its dotted path for messages
+struct YamlReader {
+    const Node &n;
+    std::string path;
 
-double num(const Node &n, const std::string &what) {
-    if (n.kind != Node::Scalar) bad(what + ": expected a number");
-    char *end = nullptr;
-    double v = std::strtod(n.scalar.c_str(), &end);
-    if (end == n.scalar.c_str() || *end != '\0') bad(what + ": expected a number, got `" + n.scalar + "`");
-    return v;
-}
+    // the paths below the top level do not start at `scene.` (output_settings.image_width, shapes[3].Sphere.radius)
+    std::string below() const { return path.rfind("scene.", 0) == 0 ? path.substr(6) : path; }
 
-size_t usize(const Node &n, const std::string &what) {
-    double v = num(n, what);
-    if (v < 0 || v != (double)(size_t)v) bad(what + ": expected an unsigned integer");
-    return (size_t)v;
-}
-
-bool boolean(const Node &n, const std::string &what) {
-    if (n.kind == Node::Scalar) {
-        if (n.scalar == "true") return true;
-        if (n.scalar == "false") return false;
+    template <class M> void operator()(const char *key, M &member) {
+        const Node *f = n.find(key);
+        if (!f) bad(below() + ": missing field `" + key + "`");
+        YamlReader{*f, below() + "." + key}.value(member);
     }
-    bad(what + ": expected a boolean");
-}
-
-Vec3 vec3(const Node &n, const std::string &what) {
-    if (n.kind != Node::Seq || n.seq.size() != 3) bad(what + ": expected a sequence of 3 numbers");
-    return Vec3{num(n.seq[0], what), num(n.seq[1], what), num(n.seq[2], what)};
-}
-Color color(const Node &n, const std::string &what) {
-    Vec3 v = vec3(n, what);
-    return Color{v.x, v.y, v.z};
-}
-
-// externally tagged enum: a one-key map
-std::pair<std::string, const Node *> variant(const Node &n, const std::string &what) {
-    if (n.kind != Node::Map || n.map.size() != 1) bad(what + ": expected an externally tagged enum (one-key map)");
-    return {n.map[0].first, &n.map[0].second};
-}
-
-MaterialData material(const Node &n, const std::string &what) {
-    auto [tag, b] = variant(n, what);
-    const std::string w = what + "." + tag;
-    if (tag == "Matte")
-        return MatteData{color(req(*b, "diffuse_color", w), w + ".diffuse_color"),
-                         color(req(*b, "ambient_color", w), w + ".ambient_color"),
-                         num(req(*b, "diffuse_coefficient", w), w + ".diffuse_coefficient")};
-    if (tag == "Emissive") return EmissiveData{color(req(*b, "color", w), w + ".color"), num(req(*b, "power", w), w + ".power")};
-    if (tag == "Reflective")
-        return ReflectiveData{num(req(*b, "reflect_amount", w), w + ".reflect_amount"),
-                              color(req(*b, "reflect_color", w), w + ".reflect_color")};
-    if (tag == "GlossyReflective")
-        return GlossyReflectiveData{num(req(*b, "reflect_amount", w), w + ".reflect_amount"),
-                                    color(req(*b, "reflect_color", w), w + ".reflect_color"),
-                                    num(req(*b, "reflect_exponent", w), w + ".reflect_exponent")};
-    if (tag == "Dielectric") {  // extension (flux_host.hpp DielectricData)
-        const double ri = num(req(*b, "refraction_index", w), w + ".refraction_index");
-        if (!(std::isfinite(ri) && ri > 0.0)) bad(w + ".refraction_index: expected a finite number > 0");
-        return DielectricData{ri, color(req(*b, "transmit_color", w), w + ".transmit_color")};
+    void value(double &v) {
+        if (n.kind != Node::Scalar) bad(path + ": expected a number");
+        char *end = nullptr;
+        v = std::strtod(n.scalar.c_str(), &end);
+        if (end == n.scalar.c_str() || *end != '\0') bad(path + ": expected a number, got `" + n.scalar + "`");
     }
-    bad(what + ": unknown variant `" + tag + "`, expected one of `Matte`, `Emissive`, `Reflective`, `GlossyReflective`, `Dielectric`");
-}
-
-ShapeData shape(const Node &n, const std::string &what) {
-    auto [tag, b] = variant(n, what);
-    const std::string w = what + "." + tag;
-    if (tag == "Sphere")
-        return SphereData{vec3(req(*b, "center", w), w + ".center"), num(req(*b, "radius", w), w + ".radius"),
-                          material(req(*b, "material", w), w + ".material"), boolean(req(*b, "invert", w), w + ".invert")};
-    if (tag == "Plane")
-        return PlaneData{vec3(req(*b, "point", w), w + ".point"), vec3(req(*b, "normal", w), w + ".normal"),
-                         material(req(*b, "material", w), w + ".material")};
-    if (tag == "Disk") {  // extension (flux_host.hpp DiskData)
-        const double radius = num(req(*b, "radius", w), w + ".radius");
-        if (!(std::isfinite(radius) && radius >= 0.0)) bad(w + ".radius: expected a finite number >= 0");
-        return DiskData{vec3(req(*b, "center", w), w + ".center"), vec3(req(*b, "normal", w), w + ".normal"), radius,
-                        material(req(*b, "material", w), w + ".material")};
+    void value(size_t &v) {
+        double d;
+        value(d);
+        if (d < 0 || d != (double)(size_t)d) bad(path + ": expected an unsigned integer");
+        v = (size_t)d;
     }
-    bad(what + ": unknown variant `" + tag + "`, expected one of `Sphere`, `Plane`, `Disk`");
-}
+    void value(bool &v) {
+        if (n.kind != Node::Scalar || (n.scalar != "true" && n.scalar != "false")) bad(path + ": expected a boolean");
+        v = n.scalar == "true";
+    }
+    void value(std::string &s) {
+        if (n.kind != Node::Scalar) bad(path + ": expected a string");
+        s = n.scalar;
+    }
+    void value(Vec3 &v) {
+        if (n.kind != Node::Seq || n.seq.size() != 3) bad(path + ": expected a sequence of 3 numbers");
+        YamlReader{n.seq[0], path}.value(v.x);
+        YamlReader{n.seq[1], path}.value(v.y);
+        YamlReader{n.seq[2], path}.value(v.z);
+    }
+    void value(Color &c) {  // color.rs:8-16: a sequence here, a map on the wire
+        Vec3 v;
+        value(v);
+        c = Color{v.x, v.y, v.z};
+    }
+    template <class T> void value(std::vector<T> &items) {
+        if (n.kind != Node::Seq && n.kind != Node::Null) bad(path + ": expected a sequence");
+        items.resize(n.seq.size());
+        for (size_t i = 0; i < n.seq.size(); i++) YamlReader{n.seq[i], below() + "[" + std::to_string(i) + "]"}.value(items[i]);
+    }
+    void value(MaterialData &m) { enumeration(m); }
+    void value(ShapeData &s) { enumeration(s); }
+    // the variant called as the map's one key, if the enum has one, becomes current and reads the key's value
+    struct Variant {
+        const YamlReader &r;
+        bool found = false;
+        template <class Select> void variant(const char *name, bool, Select select) {
+            if (r.n.map[0].first != name) return;
+            found = true;
+            YamlReader{r.n.map[0].second, r.path + "." + name}.value(select());
+        }
+    };
+    template <class E> void enumeration(E &e) {  // externally tagged: a one-key map
+        if (n.kind != Node::Map || n.map.size() != 1) bad(path + ": expected an externally tagged enum (one-key map)");
+        Variant chosen{*this};
+        variants(chosen, e);
+        if (!chosen.found) bad(path + ": unknown variant `" + n.map[0].first + "`, expected one of " + variant_names(e));
+    }
+    template <class S> void value(S &s) {
+        if (n.kind != Node::Map) bad(below() + ": expected a map");
+        fields(*this, s);
+        check(s);
+    }
+
+    // what only the loader refuses, once the struct is read (the ABI checks the same values again, flux_abi.h)
+    template <class S> void check(const S &) {}
+    void check(DiskData &k) {
+        if (!(std::isfinite(k.radius) && k.radius >= 0.0)) bad(below() + "." + field_name(k, k.radius) + ": expected a finite number >= 0");
+    }
+    void check(DielectricData &m) {
+        if (!(std::isfinite(m.refraction_index) && m.refraction_index > 0.0))
+            bad(below() + "." + field_name(m, m.refraction_index) + ": expected a finite number > 0");
+    }
+};
 
 SceneData scene_from_node(const Node &d) {
     SceneData sd;
-    const Node &name = req(d, "scene_name", "scene");
-    if (name.kind != Node::Scalar) bad("scene.scene_name: expected a string");
-    sd.scene_name = name.scalar;
-    const Node &o = req(d, "output_settings", "scene");
-    sd.output_settings.image_width = usize(req(o, "image_width", "output_settings"), "output_settings.image_width");
-    sd.output_settings.image_height = usize(req(o, "image_height", "output_settings"), "output_settings.image_height");
-    sd.output_settings.pixel_size = num(req(o, "pixel_size", "output_settings"), "output_settings.pixel_size");
-    sd.background = color(req(d, "background", "scene"), "scene.background");
-    const Node &shapes = req(d, "shapes", "scene");
-    if (shapes.kind != Node::Seq && shapes.kind != Node::Null) bad("scene.shapes: expected a sequence");
-    for (size_t i = 0; i < shapes.seq.size(); i++) sd.shapes.push_back(shape(shapes.seq[i], "shapes[" + std::to_string(i) + "]"));
-    const Node &cs = req(d, "camera_settings", "scene");
-    sd.camera_settings.eye = vec3(req(cs, "eye", "camera_settings"), "camera_settings.eye");
-    sd.camera_settings.look_at = vec3(req(cs, "look_at", "camera_settings"), "camera_settings.look_at");
-    sd.camera_settings.up = vec3(req(cs, "up", "camera_settings"), "camera_settings.up");
-    const Node &cd = req(d, "camera_data", "scene");
-    sd.camera_data.zoom_factor = num(req(cd, "zoom_factor", "camera_data"), "camera_data.zoom_factor");
-    sd.camera_data.view_plane_distance = num(req(cd, "view_plane_distance", "camera_data"), "camera_data.view_plane_distance");
-    sd.camera_data.focal_distance = num(req(cd, "focal_distance", "camera_data"), "camera_data.focal_distance");
-    sd.camera_data.lens_radius = num(req(cd, "lens_radius", "camera_data"), "camera_data.lens_radius");
+    YamlReader{d, "scene"}.value(sd);
     return sd;
 }
 
@@ -131,9 +112,11 @@ double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+void set3(double *d, const Vec3 &v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }
+void set3(double *d, const Color &c) { d[0] = c.r; d[1] = c.g; d[2] = c.b; }
+
 flux_material to_abi(const MaterialData &m) {
     flux_material o{};
-    auto set3 = [](double *d, const Color &c) { d[0] = c.r; d[1] = c.g; d[2] = c.b; };
     if (auto p = std::get_if<MatteData>(&m)) {
         o.kind = FLUX_MAT_MATTE;
         set3(o.color, p->diffuse_color);
@@ -185,19 +168,19 @@ AbiScene::AbiScene(const SceneData &sd) : name(sd.scene_name) {
         fs = flux_shape{};
         if (auto s = std::get_if<SphereData>(&sd.shapes[i])) {
             fs.kind = FLUX_SHAPE_SPHERE;
-            fs.p[0] = s->center.x; fs.p[1] = s->center.y; fs.p[2] = s->center.z;
+            set3(fs.p, s->center);
             fs.radius = s->radius;
             fs.invert = s->invert ? 1 : 0;
             fs.material = to_abi(s->material);
         } else if (auto p = std::get_if<PlaneData>(&sd.shapes[i])) {
             fs.kind = FLUX_SHAPE_PLANE;
-            fs.p[0] = p->point.x; fs.p[1] = p->point.y; fs.p[2] = p->point.z;
-            fs.n[0] = p->normal.x; fs.n[1] = p->normal.y; fs.n[2] = p->normal.z;
+            set3(fs.p, p->point);
+            set3(fs.n, p->normal);
             fs.material = to_abi(p->material);
         } else if (auto k = std::get_if<DiskData>(&sd.shapes[i])) {
             fs.kind = FLUX_SHAPE_DISK;
-            fs.p[0] = k->center.x; fs.p[1] = k->center.y; fs.p[2] = k->center.z;
-            fs.n[0] = k->normal.x; fs.n[1] = k->normal.y; fs.n[2] = k->normal.z;
+            set3(fs.p, k->center);
+            set3(fs.n, k->normal);
             fs.radius = k->radius;
             fs.material = to_abi(k->material);
         }
@@ -206,11 +189,11 @@ AbiScene::AbiScene(const SceneData &sd) : name(sd.scene_name) {
     desc.image_width = sd.output_settings.image_width;
     desc.image_height = sd.output_settings.image_height;
     desc.pixel_size = sd.output_settings.pixel_size;
-    desc.background[0] = sd.background.r; desc.background[1] = sd.background.g; desc.background[2] = sd.background.b;
+    set3(desc.background, sd.background);
     const CameraSettings &c = sd.camera_settings;
-    desc.eye[0] = c.eye.x; desc.eye[1] = c.eye.y; desc.eye[2] = c.eye.z;
-    desc.look_at[0] = c.look_at.x; desc.look_at[1] = c.look_at.y; desc.look_at[2] = c.look_at.z;
-    desc.up[0] = c.up.x; desc.up[1] = c.up.y; desc.up[2] = c.up.z;
+    set3(desc.eye, c.eye);
+    set3(desc.look_at, c.look_at);
+    set3(desc.up, c.up);
     desc.zoom_factor = sd.camera_data.zoom_factor;
     desc.view_plane_distance = sd.camera_data.view_plane_distance;
     desc.focal_distance = sd.camera_data.focal_distance;

@@ -33,7 +33,7 @@ struct FluxError : std::runtime_error {
     FluxError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
 };
 
-// ---- scene description (serde schema of the reference) ---------------------------------------
+// ---- scene description (the reference's plain data; field and variant names: scene_schema.hpp) ----
 struct Color { double r = 0, g = 0, b = 0; };
 struct Vec3 { double x = 0, y = 0, z = 0; };
 

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <set>
 #include <string>
+#include <vector>
 
 #include "flux_host.hpp"
 #include "flux_net.hpp"
@@ -34,6 +35,97 @@ static bool throws(const std::string &yaml, const char *needle) {
         return std::string(e.what()).find(needle) != std::string::npos;
     }
     return false;
+}
+
+static std::string hex(const std::string &b) {
+    static const char *d = "0123456789abcdef";
+    std::string h;
+    for (unsigned char c : b) { h.push_back(d[c >> 4]); h.push_back(d[c & 15]); }
+    return h;
+}
+
+// SHA-256 (FIPS 180-4) of a byte string, as lowercase hex: pins wire messages too long to write out
+static std::string sha256_hex(const std::string &msg) {
+    static const uint32_t K[64] = {
+        0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
+        0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
+        0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
+        0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3,
+        0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f,
+        0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    std::string m = msg;
+    m.push_back((char)0x80);
+    while (m.size() % 64 != 56) m.push_back('\0');
+    for (int k = 7; k >= 0; k--) m.push_back((char)(((uint64_t)msg.size() * 8) >> (8 * k)));
+    auto rotr = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
+    for (size_t off = 0; off < m.size(); off += 64) {
+        uint32_t w[64];
+        for (int t = 0; t < 16; t++)
+            w[t] = (uint32_t)(unsigned char)m[off + 4 * t] << 24 | (uint32_t)(unsigned char)m[off + 4 * t + 1] << 16 |
+                   (uint32_t)(unsigned char)m[off + 4 * t + 2] << 8 | (uint32_t)(unsigned char)m[off + 4 * t + 3];
+        for (int t = 16; t < 64; t++)
+            w[t] = (rotr(w[t - 2], 17) ^ rotr(w[t - 2], 19) ^ (w[t - 2] >> 10)) + w[t - 7] +
+                   (rotr(w[t - 15], 7) ^ rotr(w[t - 15], 18) ^ (w[t - 15] >> 3)) + w[t - 16];
+        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+        for (int t = 0; t < 64; t++) {
+            const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K[t] + w[t];
+            const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+            hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+        }
+        h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+    }
+    std::string out;
+    for (uint32_t v : h)
+        for (int k = 3; k >= 0; k--) out.push_back((char)(v >> (8 * k)));
+    return hex(out);
+}
+
+// One CBOR item re-written the way another serde_cbor peer may send it: every map with its pairs in reversed order and one
+// unknown key added, every enum ["Name", payload] as {"Name": payload}.  Returns "" on an item the node protocol never writes.
+static std::string scramble(cbor::Decoder &d) {
+    cbor::Encoder e;
+    uint64_t n = 0;
+    std::string s;
+    switch (d.peek()) {
+        case cbor::Type::Map: {
+            if (!d.read_map(n) || n == cbor::Decoder::kIndefinite) return "";
+            std::vector<std::string> pairs;
+            for (uint64_t k = 0; k < n; k++) {
+                if (!d.read_text(s)) return "";
+                cbor::Encoder key;
+                key.text(s);
+                const std::string value = scramble(d);
+                if (value.empty()) return "";
+                pairs.push_back(key.out + value);
+            }
+            e.map(n + 1);
+            for (size_t k = pairs.size(); k-- > 0;) {
+                e.out += pairs[k];
+                if (k == pairs.size() / 2) {  // the unknown key sits among the known ones; its value nests
+                    e.key("not_a_field");
+                    e.array(2); e.text("x"); e.map(1); e.key("y"); e.null();
+                }
+            }
+            return e.out;
+        }
+        case cbor::Type::Array: {
+            if (!d.read_array(n) || n == cbor::Decoder::kIndefinite) return "";
+            const bool is_enum = n == 2 && d.peek() == cbor::Type::Text;
+            if (is_enum) e.map(1); else e.array(n);
+            for (uint64_t k = 0; k < n; k++) {
+                const std::string item = scramble(d);
+                if (item.empty()) return "";
+                e.out += item;
+            }
+            return e.out;
+        }
+        case cbor::Type::Text: if (!d.read_text(s)) return ""; e.text(s); return e.out;
+        case cbor::Type::UInt: if (!d.read_uint(n)) return ""; e.uint(n); return e.out;
+        case cbor::Type::Float: { double f; if (!d.read_number(f)) return ""; e.real(f); return e.out; }
+        case cbor::Type::Bool: { bool b; if (!d.read_bool(b)) return ""; e.boolean(b); return e.out; }
+        default: return "";
+    }
 }
 
 // A Worker that renders nothing: per work unit it sleeps `ms_per_unit` and reports rows filled with its id
@@ -336,12 +428,6 @@ int main(int argc, char **argv) {
     }
     {
         // CBOR codec against the RFC 8949 Appendix A examples (published test vectors of the format)
-        auto hex = [](const std::string &b) {
-            static const char *d = "0123456789abcdef";
-            std::string h;
-            for (unsigned char c : b) { h.push_back(d[c >> 4]); h.push_back(d[c & 15]); }
-            return h;
-        };
         auto unhex = [](const std::string &h) {
             std::string b;
             for (size_t k = 0; k + 1 < h.size(); k += 2) b.push_back((char)std::stoi(h.substr(k, 2), nullptr, 16));
@@ -460,12 +546,6 @@ int main(int argc, char **argv) {
     }
     {
         // node-protocol messages: serde_cbor 0.9 layout on the way out, both enum layouts on the way in
-        auto hex = [](const std::string &b) {
-            static const char *d = "0123456789abcdef";
-            std::string h;
-            for (unsigned char c : b) { h.push_back(d[c >> 4]); h.push_back(d[c & 15]); }
-            return h;
-        };
         cbor::Encoder e0;
         encode_worker_info(e0, WorkerInfo{16});
         CHECK(hex(e0.out) == "a1" "6b6e756d5f74687265616473" "10");  // {"num_threads": 16}
@@ -507,6 +587,37 @@ int main(int argc, char **argv) {
             CHECK(pl && pl->normal.y == 1.0 && std::get<MatteData>(pl->material).diffuse_coefficient == 1.0);
             CHECK(std::get<SphereData>(b.shapes[0]).invert);
         }
+        // the SetJob bytes of every shipped scene, pinned: field order, map sizes, enum layout and float widths on the wire.
+        // Then the same message as another peer may write it (scramble): it decodes to a value that encodes to the pinned bytes.
+        CHECK(sha256_hex("abc") == "ba7816bf8f01cfea414140de5dae2223b00361a396177a9cb410ff61f20015ad");  // FIPS 180-4 example
+        struct Pin { const char *scene, *sha256; } pins[] = {
+            {"demo1.yml", "a844a820abf21c9c62adbeff94d958b4f0f2fb5501f2b60ddb11a0e13d4b279b"},
+            {"demo2.yml", "c3af76be414e7001304320bd90e1d5af68b96d63bcb223a1bc663bbb97b212ba"},
+            {"disk_light.yml", "1e8b1da3bf432adf3e3dd4a5a3f8294bb45d161be5a12a8a1ecd119936bcb8c6"},
+            {"glass.yml", "41e4784d0eea4aaf47b0ff4f57d97cc0cbe6547f56471393f74168a5827213e3"}};
+        for (const Pin &p : pins) {
+            NetworkWorkerRequest req;
+            req.kind = NetworkWorkerRequest::SetJob;
+            req.job.id = JobID{123456789012345ull, 2};
+            req.job.scene_data = scene_from_yaml_file(scenes + "/" + p.scene);
+            req.job.config = JobConfiguration{128, 5, 50};
+            cbor::Encoder e;
+            encode_request(e, req);
+            std::printf("SetJob %s: %zu bytes, sha256 %s\n", p.scene, e.out.size(), sha256_hex(e.out).c_str());
+            CHECK(sha256_hex(e.out) == p.sha256);
+            cbor::StringReader canonical(e.out);
+            cbor::Decoder dc(canonical);
+            const std::string other = scramble(dc);
+            CHECK(!other.empty() && canonical.at_end() && other != e.out && other.size() > e.out.size());
+            CHECK((unsigned char)other[0] == 0xa1);  // {"SetJob": ...}
+            cbor::StringReader r(other);
+            cbor::Decoder d(r);
+            NetworkWorkerRequest back;
+            CHECK(decode_request(d, back) && r.at_end() && back.kind == NetworkWorkerRequest::SetJob);
+            cbor::Encoder again;
+            encode_request(again, back);
+            CHECK(again.out == e.out);
+        }
         // the same request in the serde_cbor >= 0.10 layout ({"WorkUnit": {...}}) and with an unknown field
         {
             cbor::Encoder e;
@@ -543,6 +654,8 @@ int main(int argc, char **argv) {
         fin.kind = RenderEvent::RenderingFinished;
         fin.time_s = 1538352010.5;
         encode_event(e4, fin);
+        std::printf("event stream: %zu bytes, sha256 %s\n", e4.out.size(), sha256_hex(e4.out).c_str());
+        CHECK(sha256_hex(e4.out) == "d50cd4a59adecf30b41a1f4f9208e4e8d375de86489498013f73666a898a8e05");
         {
             cbor::StringReader r(e4.out);  // a stream of concatenated values, as StreamDeserializer reads it
             cbor::Decoder d(r);

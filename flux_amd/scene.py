@@ -205,9 +205,18 @@ def material_from_yaml(m, what="material") -> MaterialData:
                      "`Matte`, `Emissive`, `Reflective`, `GlossyReflective`, `Dielectric`")
 
 
-def shape_from_yaml(m, what="shape") -> ShapeData:
+def shape_from_yaml(m, what="shape"):
+    """A ShapeData, or a MeshData for the Mesh / Triangle extensions (mesh_from_yaml below)."""
     tag, b = _single_variant(m, what)
     w = f"{what}.{tag}"
+    if tag in ("Mesh", "Triangle"):
+        return mesh_from_yaml(tag, b, what)
+    if tag == "Disk":  # extension
+        radius = _num(b, "radius", w)
+        if not (math.isfinite(radius) and radius >= 0.0):
+            raise SceneError(f"{w}.radius: expected a finite number >= 0, got {radius!r}")
+        return DiskData(_vec3(_req(b, "center", w), w + ".center"), _vec3(_req(b, "normal", w), w + ".normal"), radius,
+                        material_from_yaml(_req(b, "material", w), w + ".material"))
     if tag == "Sphere":
         inv = _req(b, "invert", w)
         if not isinstance(inv, bool):
@@ -217,7 +226,7 @@ def shape_from_yaml(m, what="shape") -> ShapeData:
     if tag == "Plane":
         return PlaneData(_vec3(_req(b, "point", w), w + ".point"), _vec3(_req(b, "normal", w), w + ".normal"),
                          material_from_yaml(_req(b, "material", w), w + ".material"))
-    raise SceneError(f"{what}: unknown variant `{tag}`, expected one of `Sphere`, `Plane`")
+    raise SceneError(f"{what}: unknown variant `{tag}`, expected one of `Sphere`, `Plane`, `Disk`, `Mesh`, `Triangle`")
 
 
 def _usize(m, key, what) -> int:
@@ -387,29 +396,6 @@ def mesh_from_yaml(tag, b, what):
     if t.size and (t.min() < 0 or t.max() >= len(v)):
         raise SceneError(f"{w}: triangle index out of range (have {len(v)} vertices)")
     return MeshData(v, t.astype(np.uint32), mat)
-
-
-_shape_from_yaml_reference = shape_from_yaml
-
-
-def disk_from_yaml(b, what):
-    w = f"{what}.Disk"
-    radius = _num(b, "radius", w)
-    if not (math.isfinite(radius) and radius >= 0.0):
-        raise SceneError(f"{w}.radius: expected a finite number >= 0, got {radius!r}")
-    return DiskData(_vec3(_req(b, "center", w), w + ".center"), _vec3(_req(b, "normal", w), w + ".normal"), radius,
-                    material_from_yaml(_req(b, "material", w), w + ".material"))
-
-
-def shape_from_yaml(m, what="shape"):  # noqa: F811  (extends the reference enum with Disk / Mesh / Triangle)
-    tag, b = _single_variant(m, what)
-    if tag in ("Mesh", "Triangle"):
-        return mesh_from_yaml(tag, b, what)
-    if tag == "Disk":
-        return disk_from_yaml(b, what)
-    if tag not in ("Sphere", "Plane"):
-        raise SceneError(f"{what}: unknown variant `{tag}`, expected one of `Sphere`, `Plane`, `Disk`, `Mesh`, `Triangle`")
-    return _shape_from_yaml_reference(m, what)
 
 
 def split_shapes(sd: SceneData):
