@@ -95,6 +95,8 @@ static void free_ctx(flux_ctx *c) {
     (void)hipFree(c->d_disc);
     (void)hipFree(c->d_hemi);
     (void)hipFree(c->d_gloss);
+    (void)hipFree(c->d_glossx);
+    (void)hipFree(c->d_gxoff);
     (void)hipFree(c->d_setrows);
     (void)hipFree(c->d_rowperm);
     (void)hipFree(c->d_invperm);
@@ -240,6 +242,14 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     alloc(&c->d_disc, pix_bytes);
     alloc(&c->d_hemi, hemi_bytes);
     alloc(&c->d_gloss, pix_bytes * 2);
+    // the glossy lobe's angle table (RenderParams::glossx) where the host scene assigned its exponents slots; FLUX_SAMPLE_TABLES=0
+    // builds the context without it (tests and A/B runs: every glossy bounce then keeps the arithmetic in the loop)
+    const char *tables_env = std::getenv("FLUX_SAMPLE_TABLES");
+    const int gx_stride = (tables_env && std::atoi(tables_env) == 0) ? 0 : h.rp.gx_stride;
+    if (gx_stride) {
+        alloc(&c->d_glossx, own * c->N * (size_t)gx_stride);
+        alloc_copy(&c->d_gxoff, h.gx_off);
+    }
     alloc(&c->d_setrows, own * sizeof(DevSetRows));
     alloc(&c->d_rowperm, perm_bytes);
     alloc(&c->d_invperm, perm_bytes);
@@ -261,6 +271,9 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         e = generate_tables(seed, c->S, c->sets, c->D, c->n, c->H, c->d_pix, c->d_disc, c->d_hemi, c->d_rowperm, c->d_invperm, nullptr, tab_ms);
     if (e == hipSuccess) {
         e = generate_gloss_table(c->d_pix, (size_t)c->sets.count * c->N, c->d_gloss, nullptr);
+        if (e == hipSuccess && gx_stride)
+            e = generate_glossx_table(c->d_gloss, (size_t)c->sets.count * c->N, h.gx_inv_e1.data(), h.rp.n_gloss_exp, gx_stride / 16,
+                                      c->d_glossx, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     laps.lap(FLUX_CREATE_MS_TABLES);
@@ -268,15 +281,16 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     laps.ms[FLUX_CREATE_MS_TABLES] -= tab_ms[0] + tab_ms[2];
     laps.ms[FLUX_CREATE_MS_ALLOC] += tab_ms[0];
     laps.ms[FLUX_CREATE_MS_FREE] += tab_ms[2];
-    // where each held set's rows of the sample tables start: one 32-B record per slot, so that a kernel forms a table address with one
+    // where each held set's rows of the sample tables start: one 64-B record per slot, so that a kernel forms a table address with one
     // scalar load instead of a 64-bit multiply-add chain per table and pass (render_body.inc FLUX_SET_ROWS)
     if (e == hipSuccess) {
-        std::vector<DevSetRows> rows(own);
+        std::vector<DevSetRows> rows(own, DevSetRows{});
         for (size_t m = 0; m < own; m++) {
             rows[m].pix = c->d_pix + m * c->N;
             rows[m].disc = c->d_disc + m * c->N;
             rows[m].hemi = c->d_hemi + m * c->D * c->N * kHemiDoubles;
             rows[m].gloss = c->d_gloss + m * c->N * 4;
+            rows[m].glossx = gx_stride ? c->d_glossx + m * c->N * (size_t)(gx_stride / 16) : nullptr;
         }
         copy(c->d_setrows, rows);
     }
@@ -295,6 +309,9 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.disc = c->d_disc;
     rp.hemi = c->d_hemi;
     rp.gloss = c->d_gloss;
+    rp.glossx = c->d_glossx;
+    rp.gx_off = c->d_gxoff;
+    rp.gx_stride = gx_stride;
     rp.set_rows = c->d_setrows;
     rp.rowperm = c->d_rowperm;
     rp.invperm = c->d_invperm;

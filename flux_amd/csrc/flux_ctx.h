@@ -85,7 +85,9 @@ struct flux_ctx {
     double2 *d_pix = nullptr, *d_disc = nullptr;
     double *d_hemi = nullptr;
     double *d_gloss = nullptr;  // FAST glossy-lobe factors of pixel_sets
-    flux::DevSetRows *d_setrows = nullptr;  // per table slot: where the set's rows of the four tables start
+    double2 *d_glossx = nullptr;  // the glossy lobe's angles per held sample and exponent slot (RenderParams::glossx), or nullptr
+    int32_t *d_gxoff = nullptr;   // RenderParams::gx_off, with d_glossx
+    flux::DevSetRows *d_setrows = nullptr;  // per table slot: where the set's rows of the sample tables start
     int32_t *d_rowperm = nullptr, *d_invperm = nullptr;
     unsigned long long *d_stats = nullptr;
     bool stats_on = false;

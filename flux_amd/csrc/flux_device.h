@@ -141,12 +141,15 @@ struct SetRange {
     uint32_t first, stride, count;
 };
 
-// Where one held sample set's rows of the four sample tables start (abi.hip fills one record per table slot).
+// Where one held sample set's rows of the sample tables start (abi.hip fills one record per table slot).  64 B: a power of two, so
+// that a set's record is a shift away from the base (render_body.inc set_rows_of).
 struct DevSetRows {
     const double2 *pix, *disc;
     const double *hemi, *gloss;
+    const double2 *glossx;  // the set's rows of RenderParams::glossx, or nullptr
+    const void *pad[3];
 };
-static_assert(sizeof(DevSetRows) == 32, "DevSetRows layout");
+static_assert(sizeof(DevSetRows) == 64, "DevSetRows layout");
 
 // Kernel argument block (by value -> kernarg segment -> scalar loads).
 struct RenderParams {
@@ -247,6 +250,15 @@ struct RenderParams {
     // extension: 1 = some shape or mesh is a Dielectric (kMatDielectric).  The kernels' dielectric branch sits behind this uniform
     // flag, and the launch keeps such a scene out of the TYP instantiations and the split kernel's hit queue (launch_plan.cpp plan_render)
     int32_t has_diel;
+    // FAST, analytic kernels: the glossy lobe's angles per (set, sample, exponent), glossx[slot][i][k] = (cos theta, sin theta) of
+    // to_unit_hemi for the k-th distinct 1 / (exponent + 1) among the scene's GlossyReflective hit records (render.hip
+    // generate_glossx_table: bit for bit what fast_bounce computes from gloss[..].z).  gx_stride: bytes per sample (16 per
+    // exponent held), 0 = no table (no glossy record, more than kGlossExpSlots exponents, a glossy_long scene, or
+    // FLUX_SAMPLE_TABLES=0).  gx_off[hit]: 16 k for a glossy hit record, in scan order as frec.  n_gloss_exp: the distinct exponents
+    // (counted up to kGlossExpSlots + 1).  The rows of a set: DevSetRows::glossx.
+    const double2 *glossx;
+    const int32_t *gx_off;
+    int32_t gx_stride, n_gloss_exp;
 };
 
 }  // namespace flux

@@ -26,6 +26,10 @@
 
 namespace flux {
 
+// Most distinct glossy exponents a context tabulates the lobe's angles for (RenderParams::glossx): a scene with more keeps the
+// arithmetic in the loop
+constexpr int kGlossExpSlots = 4;
+
 // The split kernel's ray queue: 64 queued paths per wave, structure of arrays [field][slot]: ox oy oz dx dy dz tr tg tb, then the
 // sample index and Path::self (int)
 constexpr int kQueueDoubles = 9;

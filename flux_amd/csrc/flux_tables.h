@@ -20,6 +20,10 @@ hipError_t generate_sampler_grid(int kind, uint64_t seed, uint32_t n, double *d_
 // FAST glossy lobe factors of the pixel samples: gloss[s][i] = (cos 2 pi x, sin 2 pi x, log2(1 - y), 0) with
 // flux_math.h's functions (render.hip, FAST arithmetic).  Asynchronous on `stream`.
 hipError_t generate_gloss_table(const double2 *pix, size_t count, double *gloss, hipStream_t stream);
+// The glossy lobe's angles for the scene's n <= kGlossExpSlots exponents: out[t][k] = (cos theta, sin theta) of sample t (of `count`
+// held samples, `gloss` as generate_gloss_table wrote it) for inv_e1[k], `pad` >= n entries per sample (render.hip: bit for bit the
+// values fast_bounce computes in the loop).  Asynchronous on `stream`.
+hipError_t generate_glossx_table(const double *gloss, size_t count, const double *inv_e1, int n, int pad, double2 *out, hipStream_t stream);
 hipError_t hemi_to_aos(size_t SD, size_t N, const double *in, double *out, hipStream_t stream);
 
 // Camera::render (trace.rs:53-97).  variant: FLUX_KERNEL_*; math: FLUX_MATH_FAST / FLUX_MATH_STRICT (render_body.inc).  Runs

@@ -23,10 +23,11 @@ size_t shade_rays_lds(const RenderParams &p, int math) {
 }
 
 // The TYP instantiations: scan_shapes_fast's TYP turns these values into constants of the instantiation, and it leaves the disks'
-// loop and the dielectric lobe out.  The split kernel's usual scene ...
+// loop and the dielectric lobe out.  The split kernel's usual scene -- whose glossy bounces, if it has any, read the lobe's angles
+// from the table (RenderParams::glossx: in TYP the arithmetic they replace is not compiled) ...
 static bool split_typ(const RenderParams &p) {
     return p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 &&
-           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0;
+           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0 && (p.n_gloss_exp == 0 || p.gx_stride != 0);
 }
 // ... and the usual analytic set beside a mesh in render_bvh4_kernel, whose records it keeps in LDS (no environment shortcut there)
 static bool bvh4_typ(const RenderParams &p, bool lds_scene) {

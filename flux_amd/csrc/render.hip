@@ -156,6 +156,37 @@ hipError_t generate_gloss_table(const double2 *pix, size_t count, double *gloss,
 
 namespace flux {
 
+// The glossy lobe's angles of every held sample for the scene's exponents (RenderParams::glossx): entry (t, k) of `pad` >= n per sample =
+// (cos theta, sin theta) of to_unit_hemi for inv_e1[k], from the tabulated log2(1 - y) (gloss[t].z).  The operations are the ones
+// fast_bounce performs per bounce where the table is absent, in its order and with its roundings -- the product rounded on its own,
+// 2^x by fexp2_tab over kExp2Poly (RenderParams::exp2c holds the same values), 1 - c c as ONE fused multiply-add, fsqrt --, written
+// out and compiled without contraction, so that a stored value is bit for bit the one the loop would compute.  Entries k >= n are zero.
+struct GlossExps {
+    double inv_e1[kGlossExpSlots];
+};
+__global__ void glossx_fill_kernel(const double *__restrict__ gloss, size_t count, GlossExps e, int n, int pad, double2 *__restrict__ out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count * (size_t)pad) return;
+    const size_t t = j / (size_t)pad;
+    const int k = (int)(j - t * (size_t)pad);
+    double2 v = make_double2(0.0, 0.0);
+    if (k < n) {
+        const double m_inv_e1 = k == 0 ? e.inv_e1[0] : k == 1 ? e.inv_e1[1] : k == 2 ? e.inv_e1[2] : e.inv_e1[3];
+        const double cos_theta = fastmath::fexp2_tab(m_inv_e1 * gloss[t * 4 + 2], fastmath::kExp2Poly);
+        const double sin_theta = fastmath::fsqrt(fastmath::ffma(-cos_theta, cos_theta, 1.0));
+        v = make_double2(cos_theta, sin_theta);
+    }
+    out[j] = v;
+}
+hipError_t generate_glossx_table(const double *gloss, size_t count, const double *inv_e1, int n, int pad, double2 *out, hipStream_t stream) {
+    if (count == 0 || n < 1 || n > kGlossExpSlots || pad < n) return count == 0 ? hipSuccess : hipErrorInvalidValue;
+    GlossExps e{};
+    for (int k = 0; k < n; k++) e.inv_e1[k] = inv_e1[k];
+    const size_t threads = count * (size_t)pad;
+    glossx_fill_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream>>>(gloss, count, e, n, pad, out);
+    return hipGetLastError();
+}
+
 // the kernel the launch planner names (launch_plan.cpp), in the copy of render_body.inc it names
 hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream) {
     const LaunchPlan L = plan_render(p, variant, math);

@@ -75,7 +75,7 @@ __device__ __forceinline__ double2 gather_global_d2(const void *base, uint32_t b
 // A sample set's table rows (DevSetRows) by a 32-bit BYTE offset from the wave-uniform base: the scalar load takes it as its offset
 // operand.  (As an index the compiler widened it: a 64-bit shift and a 64-bit add -- four scalar instructions -- at every use.)
 __device__ __forceinline__ const DevSetRows &set_rows_of(const RenderParams &P, uint32_t set) {
-    return *reinterpret_cast<const DevSetRows *>(reinterpret_cast<const char *>(P.set_rows) + (set << 5));
+    return *reinterpret_cast<const DevSetRows *>(reinterpret_cast<const char *>(P.set_rows) + (set << 6));
 }
 
 // -DFLUX_DEBUG_TRIPS (experiment builds, scripts/): wave-level trip counts of the loop sections, added by the first
@@ -1080,8 +1080,19 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
                 const char *gbase = !TRIS ? reinterpret_cast<const char *>(set_rows_of(P, set).gloss)
                                                              : reinterpret_cast<const char *>(P.gloss + (size_t)set * P.nsamp * 4);
                 const double2 cs = gather_global_d2(gbase, i * 32u);
-                const double cos_theta = fastmath::fexp2_tab(m_inv_e1 * gather_global<double>(gbase, i * 32u + 16u), P.exp2c);   // 1 - y > 0 for every sample (y < 1)
-                const double sin_theta = fastmath::fsqrt(1.0 - cos_theta * cos_theta);
+                double cos_theta, sin_theta;
+                // ... and, in the analytic kernels, (cos theta, sin theta) themselves where the context tabulated them for the scene's
+                // exponents (RenderParams::glossx: the fill applies the operations below, bit for bit): one 16-B gather at the sample's
+                // entry for the record's exponent.  TYP: the launch plan picks it only with the table.  Elsewhere: the launch's flag.
+                if (!TRIS && (TYP || P.gx_stride != 0)) {
+                    const uint32_t xoff = __umul24(i, (uint32_t)P.gx_stride) + (uint32_t)gather_global<int32_t>(P.gx_off, (uint32_t)hit << 2);
+                    const double2 csx = gather_global_d2(set_rows_of(P, set).glossx, xoff);
+                    cos_theta = csx.x;
+                    sin_theta = csx.y;
+                } else {
+                    cos_theta = fastmath::fexp2_tab(m_inv_e1 * gather_global<double>(gbase, i * 32u + 16u), P.exp2c);   // 1 - y > 0 for every sample (y < 1)
+                    sin_theta = fastmath::fsqrt(1.0 - cos_theta * cos_theta);  // (contracted to ONE fused multiply-add: the fill spells it out)
+                }
                 hx = sin_theta * cs.x;
                 hy = sin_theta * cs.y;
                 hz = cos_theta;

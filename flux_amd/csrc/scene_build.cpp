@@ -198,12 +198,39 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     rp.n_sph = (int32_t)fsph.size();
     rp.n_pln = (int32_t)fpln.size();
     rp.n_dsk = (int32_t)fdsk.size();
+    // The glossy lobe's angle table (RenderParams::glossx): a slot for every distinct 1 / (exponent + 1) among the glossy records --
+    // compared as bit patterns, collected in YAML order -- while at most kGlossExpSlots of them occur; each glossy record's byte offset
+    // into a sample's entries (16 B a slot), in scan order as the records.  A scene with more exponents gets no table.
+    std::vector<const DevHitRec *> frec_all;
+    for (const auto *v : {&frec_s, &frec_p, &frec_d})
+        for (const DevHitRec &hr : *v) frec_all.push_back(&hr);
+    auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; };
+    auto slot_of = [&](double v) {
+        size_t k = 0;
+        while (k < h.gx_inv_e1.size() && !same_bits(h.gx_inv_e1[k], v)) k++;
+        return k;
+    };
+    {
+        std::vector<const DevHitRec *> yaml(frec_all);
+        std::sort(yaml.begin(), yaml.end(), [](const DevHitRec *a, const DevHitRec *b) { return a->orig_id < b->orig_id; });
+        for (const DevHitRec *hr : yaml)
+            if (hr->mat_kind == kMatGlossy && h.gx_inv_e1.size() <= (size_t)kGlossExpSlots && slot_of(hr->inv_e1) == h.gx_inv_e1.size())
+                h.gx_inv_e1.push_back(hr->inv_e1);
+    }
+    rp.n_gloss_exp = (int32_t)h.gx_inv_e1.size();
+    h.gx_off.assign(frec_all.size() + 1, 0);  // (+1 as the records themselves, FsceneLayout::rec: never empty, so the upload has bytes to copy)
     for (const DevHitRec &hr : frec_p)
         if (!hr.unit_normal) rp.glossy_long = 1;
     for (const DevHitRec &hr : frec_d)  // a disk's normal is a plane's: the same rule
         if (!hr.unit_normal) rp.glossy_long = 1;
     rp.unit_dirs = rp.glossy_long ? 0 : 1;
     rp.self_skip = rp.glossy_long ? 0 : 1;
+    // (a glossy_long scene takes the long-form weights, outside the kernels the table serves)
+    if (rp.n_gloss_exp >= 1 && rp.n_gloss_exp <= kGlossExpSlots && !rp.glossy_long) {
+        rp.gx_stride = 16 * rp.n_gloss_exp;
+        for (size_t k = 0; k < frec_all.size(); k++)
+            if (frec_all[k]->mat_kind == kMatGlossy) h.gx_off[k] = 16 * (int32_t)slot_of(frec_all[k]->inv_e1);
+    }
     for (const DevScanSphere &sp : fsph)
         if (!(std::fabs(sp.px) < 1e3 && std::fabs(sp.py) < 1e3 && std::fabs(sp.pz) < 1e3 && sp.rr < 1e6)) rp.self_skip = 0;
     // the environment shortcut (flux_device.h env_short): exactly one `invert` sphere, Emissive, of ordinary size

@@ -8,6 +8,7 @@
 
 #include "../../include/flux_abi.h"
 #include "flux_device.h"
+#include "flux_plan.h"
 
 namespace flux {
 
@@ -44,6 +45,12 @@ struct HostScene {
     bool filter32 = false;  // fsph32 is usable (else RenderParams::fsph32 and f32_top are null)
     int f32_half = -1;      // RenderParams::f32_half = fsph32 + f32_half, null when -1
     int f32_top = 0;        // RenderParams::f32_top = fsph32 + f32_top
+    // The glossy lobe's angle table (RenderParams::glossx).  gx_inv_e1: the distinct 1 / (exponent + 1) bit patterns of the
+    // GlossyReflective hit records, in YAML order, at most kGlossExpSlots + 1 of them (rp.n_gloss_exp = its size; one more than the
+    // cap means "too many": no table).  gx_off: per hit record, in scan order as the records, 16 * its value's index there -- all
+    // zeros, and rp.gx_stride 0, for a scene that gets no table.
+    std::vector<double> gx_inv_e1;
+    std::vector<int32_t> gx_off;
 };
 
 // `scene` as validate_job (abi.hip) passed it.  Returns FLUX_OK, or FLUX_E_INVALID with the message in `error` (too many triangles
