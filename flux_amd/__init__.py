@@ -8,13 +8,13 @@ from . import _lib
 from ._lib import (FluxError, KERNEL_DEFAULT, KERNEL_REFILL, KERNEL_SPLIT, KERNEL_STATIC, MATH_FAST, MATH_STRICT, SHARD_AUTO, SHARD_ROWS,
                    SHARD_SETS)
 from .render import MultiRenderer, Renderer, debug_fastmath, release_comms, render_frame_multi, sampler_grid, work_units, write_ppm
-from .scene import (CameraData, CameraSettings, DielectricData, DiskData, EmissiveData, GlossyReflectiveData, JobConfiguration, MatteData,
+from .scene import (CameraData, CameraSettings, BoxData, DielectricData, DiskData, EmissiveData, GlossyReflectiveData, JobConfiguration, MatteData,
                     OutputSettings, PlaneData, ReflectiveData, SceneData, SceneError, SphereData, WorkUnit,
                     WorkUnitResult, load_scene, scene_from_dict)
 
 __all__ = [
     "FluxError", "Renderer", "work_units", "write_ppm", "load_scene", "scene_from_dict", "SceneData", "SceneError",
-    "CameraSettings", "CameraData", "OutputSettings", "SphereData", "PlaneData", "DiskData", "MatteData", "EmissiveData",
+    "CameraSettings", "CameraData", "OutputSettings", "SphereData", "PlaneData", "DiskData", "BoxData", "MatteData", "EmissiveData",
     "ReflectiveData", "GlossyReflectiveData", "DielectricData", "JobConfiguration", "WorkUnit", "WorkUnitResult", "KERNEL_DEFAULT",
     "KERNEL_STATIC", "KERNEL_REFILL", "KERNEL_SPLIT", "MATH_FAST", "MATH_STRICT", "debug_fastmath", "sampler_grid",
     "MultiRenderer", "render_frame_multi", "release_comms", "SHARD_AUTO", "SHARD_SETS", "SHARD_ROWS",

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("FLUX_HIP_LIB") or os.path.join(_HERE, "libflux_hip.so
 
 FLUX_OK = 0
 E_INVALID, E_DEVICE, E_NOMEM, E_IO = -1, -2, -3, -4
-SHAPE_SPHERE, SHAPE_PLANE, SHAPE_DISK = 0, 1, 2  # SHAPE_DISK: extension (include/flux_abi.h FLUX_SHAPE_DISK)
+SHAPE_SPHERE, SHAPE_PLANE, SHAPE_DISK, SHAPE_BOX = 0, 1, 2, 3  # SHAPE_DISK, SHAPE_BOX: extensions (include/flux_abi.h)
 MAT_MATTE, MAT_EMISSIVE, MAT_REFLECTIVE, MAT_GLOSSY = 0, 1, 2, 3
 MAT_DIELECTRIC = 4  # extension (include/flux_abi.h FLUX_MAT_DIELECTRIC)
 KERNEL_DEFAULT, KERNEL_STATIC, KERNEL_REFILL, KERNEL_SPLIT = 0, 1, 2, 3

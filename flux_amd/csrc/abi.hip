@@ -148,8 +148,13 @@ int validate_job(const flux_scene_desc &scene, const flux_job_cfg &cfg, uint64_t
         return fail(FLUX_E_INVALID, "flat shape list limited to 4096 shapes, got %llu", (unsigned long long)scene.num_shapes);
     for (uint64_t i = 0; i < scene.num_shapes; i++) {
         const flux_shape &s = scene.shapes[i];
-        if (s.kind != FLUX_SHAPE_SPHERE && s.kind != FLUX_SHAPE_PLANE && s.kind != FLUX_SHAPE_DISK)
+        if (s.kind != FLUX_SHAPE_SPHERE && s.kind != FLUX_SHAPE_PLANE && s.kind != FLUX_SHAPE_DISK && s.kind != FLUX_SHAPE_BOX)
             return fail(FLUX_E_INVALID, "shape %llu: unknown kind %d", (unsigned long long)i, s.kind);
+        if (s.kind == FLUX_SHAPE_BOX)
+            for (int a = 0; a < 3; a++)
+                if (!(std::isfinite(s.p[a]) && std::isfinite(s.n[a]) && s.p[a] < s.n[a]))
+                    return fail(FLUX_E_INVALID, "shape %llu: box corners must be finite with corner0 < corner1 on axis %c, got %g and %g",
+                                (unsigned long long)i, "xyz"[a], s.p[a], s.n[a]);
         if (s.kind == FLUX_SHAPE_DISK && !(std::isfinite(s.radius) && s.radius >= 0.0))
             return fail(FLUX_E_INVALID, "shape %llu: disk radius must be finite and >= 0, got %g", (unsigned long long)i, s.radius);
         if (int rc = validate_material(s.material, "shape", i)) return rc;
@@ -330,6 +335,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.sshapes = reinterpret_cast<const DevShape *>(fs + h.fs.ss);
     rp.pxc = reinterpret_cast<const double *>(fs + h.fs.pxc);
     rp.fdsk = reinterpret_cast<const DevScanDisk *>(fs + h.fs.dsk);
+    rp.fbox = reinterpret_cast<const DevScanBox *>(fs + h.fs.box);
     laps.lap(FLUX_CREATE_MS_UPLOAD);
     laps.ms[FLUX_CREATE_MS_TOTAL] = 0.0;
     for (int k = 1; k < FLUX_CREATE_TIMING_WORDS; k++) laps.ms[FLUX_CREATE_MS_TOTAL] += laps.ms[k];  // (the parts sum to the total by construction)

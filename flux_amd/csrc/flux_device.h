@@ -43,6 +43,7 @@ constexpr double kInvPi = 1.0 / kPi;                   // constants.rs:5
 constexpr int kShapeSphere = 0;
 constexpr int kShapePlane = 1;
 constexpr int kShapeDisk = 2;  // extension: Plane::hit bounded to |q - centre|^2 <= rr (include/flux_abi.h FLUX_SHAPE_DISK)
+constexpr int kShapeBox = 3;   // extension: axis-aligned box, BoundingBox::hit's slabs as a shape (include/flux_abi.h FLUX_SHAPE_BOX)
 constexpr int kMatMatte = 0;
 constexpr int kMatEmissive = 1;
 constexpr int kMatReflective = 2;
@@ -52,12 +53,12 @@ constexpr int kMatDielectric = 4;  // extension: Fresnel-sampled glass (include/
 // One shape, 128 B.  The shape loop index is wave-uniform, so these are
 // fetched with scalar loads (s_load_dwordx8/x16) and live in SGPRs.
 struct DevShape {
-    double px, py, pz;     // sphere centre | plane point | disk centre
+    double px, py, pz;     // sphere centre | plane point | disk centre (a box keeps its corners in c0 / c1, as a sphere's AABB)
     double rr;             // radius*radius (shapes.rs:179 recomputes it per ray); first 32 B = sphere quadratic.  Disk: its r^2
     double c0x, c0y, c0z;  // sphere AABB corner0 (Sphere::new, shapes.rs:154-169) | plane / disk normal
     double radius;         // sphere radius
-    double c1x, c1y, c1z;  // sphere AABB corner1
-    double inv;            // invert_val: -1 if `invert` else +1 (shapes.rs:181)
+    double c1x, c1y, c1z;  // sphere AABB corner1 | box corner1 (c0: its corner0)
+    double inv;            // invert_val: -1 if `invert` else +1 (shapes.rs:181); a box's too
     int32_t kind;
     int32_t pad0;
     double inv_rad;        // inv / radius (FAST path: the sphere normal's scale in one rounding)
@@ -115,10 +116,20 @@ struct DevScanDisk {    // 64 B: a DevScanPlane with r^2 in its pad (extension, 
     double rr;          // radius^2: a hit needs |q - centre|^2 <= rr, q the hit point
 };
 static_assert(sizeof(DevScanDisk) == 64, "DevScanDisk layout");
+struct DevScanBox {        // 64 B (extension, kShapeBox)
+    double c0x, c0y, c0z;  // corner0
+    double c1x, c1y, c1z;  // corner1 (> corner0 on every axis: abi.hip)
+    int32_t id;            // index in YAML order (tie-break)
+    int32_t pad0;
+    double inv;            // -1 if `invert` else +1: the sign its six hit records' normals carry
+};
+static_assert(sizeof(DevScanBox) == 64, "DevScanBox layout");
 // Everything Scene::shade needs about the winning shape, fetched in ONE per-lane batch (6 x 16 B) after
-// the scan instead of a chain of dependent loads.  Indexed in scan order: spheres, then planes, then disks.
+// the scan instead of a chain of dependent loads.  Indexed in scan order: spheres, then planes, then disks, then SIX per box --
+// one per face, record 6 j + 2 axis + (1 if the face's outward normal is +e_axis), each a plane's record with that face's normal --
+// so everything behind the scan treats a box face as a plane.
 struct DevHitRec {      // 96 B
-    double cx, cy, cz;  // sphere centre | plane / disk normal
+    double cx, cy, cz;  // sphere centre | plane / disk / box-face normal
     double inv_rad;     // sphere: invert_val / radius
     // Emissive: the emitted radiance color * power (materials.rs:45).  Every other material: the FAST bounce weight f (n.wi)/pdf in
     // its closed form -- f / INV_PI for Matte (f = diffuse_color kd INV_PI, brdf.rs:30: the same two IEEE multiplications the kernels
@@ -194,7 +205,7 @@ struct RenderParams {
     // FAST path scene (same shapes as `shapes`/`mats`)
     const DevScanSphere *fsph;
     const DevScanPlane *fpln;
-    const DevHitRec *frec;  // [n_sph + n_pln + n_dsk]
+    const DevHitRec *frec;  // [n_sph + n_pln + n_dsk + 6 n_box]
     const DevScanSphere32 *fsph32;  // [n_sph] f32 candidate-filter records, or nullptr (a coordinate beyond f32's safe range)
     const DevShape *sshapes;        // [n_sph] the spheres' STRICT records in scan order (pad0 = YAML index): STRICT's candidates
     int32_t n_sph, n_pln;
@@ -259,6 +270,12 @@ struct RenderParams {
     const double2 *glossx;
     const int32_t *gx_off;
     int32_t gx_stride, n_gloss_exp;
+    // extension: boxes (kShapeBox), scanned after the disks with a wave-uniform loop; hit records n_sph + n_pln + n_dsk + 6 j + face
+    const DevScanBox *fbox;
+    int32_t n_box;
 };
+
+// hit records of a scene (DevHitRec): one per sphere, plane and disk, six per box
+__host__ __device__ inline int hit_records(const RenderParams &p) { return p.n_sph + p.n_pln + p.n_dsk + 6 * p.n_box; }
 
 }  // namespace flux

@@ -23,16 +23,16 @@ size_t shade_rays_lds(const RenderParams &p, int math) {
 }
 
 // The TYP instantiations: scan_shapes_fast's TYP turns these values into constants of the instantiation, and it leaves the disks'
-// loop and the dielectric lobe out.  The split kernel's usual scene -- whose glossy bounces, if it has any, read the lobe's angles
+// and the boxes' loops and the dielectric lobe out.  The split kernel's usual scene -- whose glossy bounces, if it has any, read the lobe's angles
 // from the table (RenderParams::glossx: in TYP the arithmetic they replace is not compiled) ...
 static bool split_typ(const RenderParams &p) {
     return p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.env_short == 1 && p.n_uni == 1 &&
-           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0 && (p.n_gloss_exp == 0 || p.gx_stride != 0);
+           p.fsph32 != nullptr && p.n_dsk == 0 && p.n_box == 0 && p.has_diel == 0 && (p.n_gloss_exp == 0 || p.gx_stride != 0);
 }
 // ... and the usual analytic set beside a mesh in render_bvh4_kernel, whose records it keeps in LDS (no environment shortcut there)
 static bool bvh4_typ(const RenderParams &p, bool lds_scene) {
     return lds_scene && p.n_sph <= 32 && p.glossy_long == 0 && p.unit_dirs == 1 && p.self_skip == 1 && p.n_uni == 1 &&
-           p.fsph32 != nullptr && p.n_dsk == 0 && p.has_diel == 0;
+           p.fsph32 != nullptr && p.n_dsk == 0 && p.n_box == 0 && p.has_diel == 0;
 }
 
 LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
@@ -72,7 +72,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
         size_t lds4 = (size_t)(p.bvh4_stack > 0 ? p.bvh4_stack : 1) * 64 * sizeof(int);
         // the analytic set's records + the materials in LDS behind the stack (round 5) while they are small: a one-wave block must stay
         // within the 6 LDS granules (7 680 B) that 5 waves/SIMD leave it, and the copy is made once per pixel
-        const size_t scene4 = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_mats * sizeof(DevMaterial) +
+        const size_t scene4 = (size_t)hit_records(p) * sizeof(DevHitRec) + (size_t)p.n_mats * sizeof(DevMaterial) +
                               (size_t)p.n_sph * sizeof(DevScanSphere);
         const bool lds_scene4 = lds4 + scene4 <= 7680;
         if (lds_scene4) lds4 += scene4;
@@ -92,7 +92,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     // serves scenes whose records fit 16 KiB there (64 spheres -- the pixel mask's width -- leave room for 85 planes, demo2's 12 for 154;
     // until round 6 the rule was "at most 16 planes", and a seventeenth sent the scene to the refill kernel); larger analytic scenes
     // take the refill kernel, which reads the records from global memory (the launch plan says which)
-    const size_t scene_lds = (size_t)(p.n_sph + p.n_pln + p.n_dsk) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
+    const size_t scene_lds = (size_t)hit_records(p) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
     if (fast && variant == FLUX_KERNEL_SPLIT && !tris && p.n_sph <= 64 && scene_lds <= 16384) {
         L.kernel = 2;
         L.block = block;
@@ -116,7 +116,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
             uint32_t th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
             if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
             int bits = 1;
-            while ((1 << bits) < p.n_sph + p.n_pln + p.n_dsk) ++bits;
+            while ((1 << bits) < hit_records(p)) ++bits;
             if (cap >= 64u + th && bits * p.max_depth <= 32) {
                 L.hq_cap = (int)cap;
                 L.hq_th = (int)th;

@@ -349,6 +349,50 @@ __device__ __forceinline__ bool disk_hit(const DevScanDisk &S, const Ray &r, dou
     return t > tmin && ex * ex + ey * ey + ez * ez <= S.rr;
 }
 
+// ---- boxes (extension, include/flux_abi.h FLUX_SHAPE_BOX; DESIGN.md §5d) ----
+// The ray's side of BoundingBox::hit (shapes.rs:107,114,121): a_k = 1 / d_k, once per ray and not per box.  STRICT: IEEE division.
+// FAST: flux_math.h's fdiv, which is defined for a finite normal divisor; a wave with a lane outside that (a zero -- whose +-inf the
+// slabs' NaN rule needs --, a subnormal, a NaN) takes the IEEE quotient for that lane.
+struct BoxRay {
+    double ax, ay, az;
+};
+__device__ __forceinline__ double box_rcp(double d) {
+#if FLUX_FAST
+    double a = fastmath::fdiv(1.0, d);
+    const bool plain = fabs(d) > 1e-290 && fabs(d) < 1e290;
+    if (ballot64(!plain) != 0ull) a = plain ? a : 1.0 / d;
+    return a;
+#else
+    return 1.0 / d;
+#endif
+}
+__device__ __forceinline__ BoxRay box_ray(const Ray &r) { return BoxRay{box_rcp(r.dx), box_rcp(r.dy), box_rcp(r.dz)}; }
+// BoundingBox::hit's slabs (shapes.rs:99-131) as a shape, in the order the spec writes them (include/flux_abi.h flux_shape).  max and
+// min are the reference's own (shapes.rs:90-96: a > b ? a : b, a < b ? a : b): a ray parallel to a slab with its origin ON one of the
+// slab's planes has 0 * inf = NaN there, which those forms drop for the x and y slabs (the slab bounds nothing) and hand through for
+// the z slab (t0 or t1 is NaN, `t0 < t1` fails: a miss) -- box_z_nan_miss is the same arithmetic in front of a sphere.  The hit is the
+// entry t0 if t0 > T_MIN, else the exit t1 if t1 > T_MIN.  `face` = 2 axis + (1: the face's outward normal is +e_axis), the first axis
+// in x, y, z order whose own bound IS t: entry through the low face (normal -e) when a >= 0, exit through the high one.
+__device__ __forceinline__ bool box_shape_hit(double c0x, double c0y, double c0z, double c1x, double c1y, double c1z, const Ray &r,
+                                              const BoxRay &A, double tmin, double &t, int &face) {
+    const bool px = A.ax >= 0.0, py = A.ay >= 0.0, pz = A.az >= 0.0;
+    const double lox = (c0x - r.ox) * A.ax, hix = (c1x - r.ox) * A.ax;
+    const double loy = (c0y - r.oy) * A.ay, hiy = (c1y - r.oy) * A.ay;
+    const double loz = (c0z - r.oz) * A.az, hiz = (c1z - r.oz) * A.az;
+    const double tx0 = px ? lox : hix, tx1 = px ? hix : lox;
+    const double ty0 = py ? loy : hiy, ty1 = py ? hiy : loy;
+    const double tz0 = pz ? loz : hiz, tz1 = pz ? hiz : loz;
+    const double m0 = ty0 > tz0 ? ty0 : tz0, t0 = tx0 > m0 ? tx0 : m0;
+    const double m1 = ty1 < tz1 ? ty1 : tz1, t1 = tx1 < m1 ? tx1 : m1;
+    const bool entry = t0 > tmin;
+    t = entry ? t0 : t1;
+    const double bx = entry ? tx0 : tx1, by = entry ? ty0 : ty1;
+    const int axis = bx == t ? 0 : (by == t ? 1 : 2);
+    const bool pa = axis == 0 ? px : (axis == 1 ? py : pz);
+    face = 2 * axis + (entry != pa ? 1 : 0);
+    return t0 < t1 && t > tmin;
+}
+
 // ---- the conservative f32 sphere filter (flux_device.h DevScanSphere32), shared by FAST's scan and -- round 5 -- STRICT's ----
 // Only a SUPERSET of the spheres a ray can hit comes out of it; the exact f64 test of the arithmetic in use decides every hit
 // afterwards.  The ray's side of the test: u, o.u, 2 o and o.o (1 - 8e-6) in f32, each splatted into a pair.  (The records hold the
@@ -486,14 +530,34 @@ __device__ __forceinline__ void scan_disks(const RenderParams &P, const Ray &r, 
     }
 }
 
-// FAST: nearest analytic shape (spheres, planes, disks) of Scene::hit.  `best` = winning HIT RECORD index
-// (scan order: spheres, then planes, then disks) or -1; `tb` its distance.
+// Boxes after the disks, in the same places and by the same rules: wave-uniform, the corners in scalar registers, one scalar compare
+// when the scene has none; the guarded update, an equal t decided by the YAML index.  The ray's reciprocals are formed once, in front of
+// the loop.  `best` = the hit FACE's record, n_sph + n_pln + n_dsk + 6 j + face: behind the scan a box face is a plane.
+__device__ __forceinline__ void scan_boxes(const RenderParams &P, const Ray &r, double tmin, int &best, int &best_id, double &tb) {
+    if (P.n_box <= 0) return;
+    const BoxRay A = box_ray(r);
+    const int rec0 = P.n_sph + P.n_pln + P.n_dsk;
+    for (int j = 0; j < P.n_box; ++j) {
+        const DevScanBox &S = P.fbox[j];
+        double t;
+        int face;
+        if (box_shape_hit(S.c0x, S.c0y, S.c0z, S.c1x, S.c1y, S.c1z, r, A, tmin, t, face) &&
+            (best < 0 || t < tb || (t == tb && S.id < best_id))) {
+            best = rec0 + 6 * j + face;
+            best_id = S.id;
+            tb = t;
+        }
+    }
+}
+
+// FAST: nearest analytic shape (spheres, planes, disks, boxes) of Scene::hit.  `best` = winning HIT RECORD index
+// (scan order: spheres, then planes, then disks, then six face records per box) or -1; `tb` its distance.
 template <bool ENV_SHORT = false, bool LDS_SCENE = false, bool MAX32 = false, bool TYP = false, int ZF = -1>
 __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ray &r, int self, int &best, double &tb,
                                                  long long *lap = nullptr, const char *fsph_lds = nullptr) {
     (void)fsph_lds;  // LDS_SCENE (the split kernel): the block's LDS copy of the scan spheres for the per-lane gathers
     // FAST scan over the compact records of flux_device.h (DevScanPlane / DevScanSphere): `best` is the
-    // winning shape's HIT RECORD index (scan order: spheres, then planes), `best_id` its YAML index.
+    // winning shape's HIT RECORD index (scan order: spheres, planes, disks, a box's six faces), `best_id` its YAML index.
     // Planes first (Plane::hit, shapes.rs:135-152): IEEE division keeps the reference's +-inf / NaN
     // behaviour for rays parallel to the plane.  Planes come in YAML order, so an equal t never replaces.
     int best_id = -1;
@@ -527,7 +591,11 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
     }
     // (TYP: the launch takes that instantiation only for a scene without disks -- the loop, even never entered, cost the split kernel
     // 1.2 % on demo2 in code it moved around)
-    if (!TYP) scan_disks(P, r, tmin, best, best_id, tb);
+    // (... and only for a scene without boxes)
+    if (!TYP) {
+        scan_disks(P, r, tmin, best, best_id, tb);
+        scan_boxes(P, r, tmin, best, best_id, tb);
+    }
     // Spheres, phase 1: wave-uniform index, operands in SGPRs, all lanes active -- only the half-b
     // discriminant of Sphere::hit (shapes.rs:176-184 with b = 2 hb along the unit direction: disc/4a = hb_u^2 - c)
     // plus the "sphere entirely behind the origin" rejection (c > 0 and hb > 0 => both roots negative).
@@ -788,6 +856,13 @@ __device__ __forceinline__ int scene_hit(const RenderParams &P, const Ray &r, in
             double t;
             if (disk_hit(S, r, kTMin, t)) consider(t, S.id, -1, best, bslot, tb);
         }
+        for (int j = 0; j < P.n_box; ++j) {  // boxes (extension): the hit face travels in the slot, -2 - face (shade_hit)
+            const DevScanBox &S = P.fbox[j];
+            double t;
+            int face;
+            if (box_shape_hit(S.c0x, S.c0y, S.c0z, S.c1x, S.c1y, S.c1z, r, BoxRay{ax, ay, az}, kTMin, t, face))
+                consider(t, S.id, -2 - face, best, bslot, tb);
+        }
         // the filter's ray: unit direction (2-ulp reciprocal square root: it only feeds the conservative test), o.o
         const double rs = fastmath::frsqrt(a);
         const double ux = r.dx * rs, uy = r.dy * rs, uz = r.dz * rs;
@@ -862,11 +937,17 @@ __device__ __forceinline__ int scene_hit(const RenderParams &P, const Ray &r, in
                 double den = r.dx * S.c0x + r.dy * S.c0y + r.dz * S.c0z;
                 double t = num / den;
                 if (t > kTMin) consider(t, base + k, -1, best, bslot, tb);
-            } else {
+            } else if (S.kind == kShapeDisk) {
                 // disk (extension): centre in p, normal in c0, r^2 in rr
                 const DevScanDisk D = {S.px, S.py, S.pz, S.c0x, S.c0y, S.c0z, base + k, 0, S.rr};
                 double t;
                 if (disk_hit(D, r, kTMin, t)) consider(t, base + k, -1, best, bslot, tb);
+            } else {
+                // box (extension): corners in c0 / c1; the hit face travels in the slot, -2 - face (shade_hit)
+                double t;
+                int face;
+                if (box_shape_hit(S.c0x, S.c0y, S.c0z, S.c1x, S.c1y, S.c1z, r, BoxRay{ax, ay, az}, kTMin, t, face))
+                    consider(t, base + k, -2 - face, best, bslot, tb);
             }
         }
         while (cand) {
@@ -1357,6 +1438,11 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
         const double inv = S->inv, rad = S->radius;
         n = mk(((p.r.ox - S->px) + t * d.x) * inv / rad, ((p.r.oy - S->py) + t * d.y) * inv / rad,
                ((p.r.oz - S->pz) + t * d.z) * inv / rad);
+    } else if (S->kind == kShapeBox) {
+        // the face scene_hit found (slot = -2 - face): its outward unit axis, negated for `invert` -- the bits of FAST's face record
+        const int face = -2 - slot;
+        const double v = ((face & 1) ? 1.0 : -1.0) * S->inv;
+        n = mk(face < 2 ? v : 0.0, (face >> 1) == 1 ? v : 0.0, face >= 4 ? v : 0.0);
     } else {
         n = mk(S->c0x, S->c0y, S->c0z);
     }
@@ -1957,7 +2043,10 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
             tb = t;
         }
     }
-    if (!TYP) scan_disks(P, r, tmin, best, best_id, tb);  // (TYP: a scene without disks, as in scan_shapes_fast)
+    if (!TYP) {  // (TYP: a scene without disks or boxes, as in scan_shapes_fast)
+        scan_disks(P, r, tmin, best, best_id, tb);
+        scan_boxes(P, r, tmin, best, best_id, tb);
+    }
     // a primary direction is normalize(...) (trace.rs:44-51): already the unit direction the quadratic is solved along
     const double rs = 1.0, ux = r.dx, uy = r.dy, uz = r.dz, len = 1.0;
     const bool zflat = r.dz == 0.0, any_zflat = any64(zflat);  // box_z_nan_miss, as in scan_shapes_fast
@@ -2022,17 +2111,19 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
     const uint32_t K = blockDim.x >> 6, sub = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t s_lo = (uint32_t)((uint64_t)N * sub / K), s_hi = (uint32_t)((uint64_t)N * (sub + 1) / K);
     // (the scene records FIRST, at an LDS address the compiler knows; the queues behind them)
-    const size_t scene_lds_bytes = (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec) + (size_t)P.n_sph * sizeof(DevScanSphere);
+    // (TYP: a scene without boxes, whose six records each the general count adds)
+    const int n_rec = TYP ? P.n_sph + P.n_pln + P.n_dsk : hit_records(P);
+    const size_t scene_lds_bytes = (size_t)n_rec * sizeof(DevHitRec) + (size_t)P.n_sph * sizeof(DevScanSphere);
     double *q = lds_stack + scene_lds_bytes / 8 + (size_t)sub * (HQ ? (size_t)hq_cap * kHitQBytesPerSlot / 8 : kQueueBytesPerWave / 8);
     int *qi = reinterpret_cast<int *>(q + (HQ ? (size_t)kHitQDoubles * hq_cap : (size_t)kQueueDoubles * 64));  // this wave's queue: [field][slot]
     // The scene's hit records (96 B per shape) and scan spheres (32 B) copied into the block's LDS behind the queues: the per-lane gathers
     // of the shading step and of the candidate loop -- dependent loads in the middle of a pass, ~600 cycles each from the L2 -- become
     // LDS reads (~100).  The launch plan reserves the bytes (plan_render: the split kernel serves scenes whose records fit 16 KiB).
     const char *const frec_lds = reinterpret_cast<const char *>(lds_stack);
-    const char *const fsph_lds = frec_lds + (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec);
+    const char *const fsph_lds = frec_lds + (size_t)n_rec * sizeof(DevHitRec);
     {
         uint32_t *dst = reinterpret_cast<uint32_t *>(const_cast<char *>(frec_lds));
-        const uint32_t nrec_w = (uint32_t)(P.n_sph + P.n_pln + P.n_dsk) * (uint32_t)(sizeof(DevHitRec) / 4), nsph_w = (uint32_t)P.n_sph * 8u;
+        const uint32_t nrec_w = (uint32_t)n_rec * (uint32_t)(sizeof(DevHitRec) / 4), nsph_w = (uint32_t)P.n_sph * 8u;
         const uint32_t *src_r = reinterpret_cast<const uint32_t *>(P.frec), *src_s = reinterpret_cast<const uint32_t *>(P.fsph);
         for (uint32_t w = (uint32_t)tid; w < nrec_w; w += blockDim.x) dst[w] = src_r[w];
         for (uint32_t w = (uint32_t)tid; w < nsph_w; w += blockDim.x) dst[nrec_w + w] = src_s[w];
@@ -2879,11 +2970,12 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_BVH4) void render_bvh4
     // step's dependent gathers -- triangle record -> material record, hit record, a sphere record per candidate -- lose an L2 round trip
     // (LDS_SCENE: the launch plan chose this instantiation and reserved the bytes -- small analytic sets only, plan_render)
     const char *const frec_lds = reinterpret_cast<const char *>(lds_stack) + (size_t)(P.bvh4_stack > 0 ? P.bvh4_stack : 1) * kEntry;
-    const char *const mats_lds = frec_lds + (size_t)(P.n_sph + P.n_pln + P.n_dsk) * sizeof(DevHitRec);
+    const int n_rec = TYP ? P.n_sph + P.n_pln + P.n_dsk : hit_records(P);  // (TYP: a scene without boxes)
+    const char *const mats_lds = frec_lds + (size_t)n_rec * sizeof(DevHitRec);
     const char *const fsph_lds = mats_lds + (size_t)P.n_mats * sizeof(DevMaterial);
     if constexpr (LDS_SCENE) {
         uint32_t *dst = reinterpret_cast<uint32_t *>(const_cast<char *>(frec_lds));
-        const uint32_t n1 = (uint32_t)(P.n_sph + P.n_pln + P.n_dsk) * (uint32_t)(sizeof(DevHitRec) / 4), n2 = (uint32_t)P.n_mats * (uint32_t)(sizeof(DevMaterial) / 4),
+        const uint32_t n1 = (uint32_t)n_rec * (uint32_t)(sizeof(DevHitRec) / 4), n2 = (uint32_t)P.n_mats * (uint32_t)(sizeof(DevMaterial) / 4),
                        n3 = (uint32_t)P.n_sph * 8u;
         const uint32_t *s1 = reinterpret_cast<const uint32_t *>(P.frec), *s2 = reinterpret_cast<const uint32_t *>(P.mats),
                        *s3 = reinterpret_cast<const uint32_t *>(P.fsph);

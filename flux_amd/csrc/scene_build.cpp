@@ -55,7 +55,7 @@ DevMaterial make_material(const flux_material &m) {
     return dm;
 }
 
-// Sphere::new (shapes.rs:154-169); a plane or disk keeps its normal as given in c0
+// Sphere::new (shapes.rs:154-169); a plane or disk keeps its normal as given in c0; a box its corners where a sphere keeps its AABB's
 DevShape make_shape(const flux_shape &s) {
     DevShape d{};
     d.kind = s.kind;
@@ -73,6 +73,15 @@ DevShape make_shape(const flux_shape &s) {
         d.c1x = s.p[0] + s.radius;
         d.c1y = s.p[1] + s.radius;
         d.c1z = s.p[2] + s.radius;
+    } else if (s.kind == FLUX_SHAPE_BOX) {
+        d.px = d.py = d.pz = 0.0;
+        d.c0x = s.p[0];
+        d.c0y = s.p[1];
+        d.c0z = s.p[2];
+        d.c1x = s.n[0];
+        d.c1y = s.n[1];
+        d.c1z = s.n[2];
+        d.inv = s.invert ? -1.0 : 1.0;
     } else {
         d.c0x = s.n[0];
         d.c0y = s.n[1];
@@ -122,7 +131,8 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     std::vector<DevScanSphere> fsph;
     std::vector<DevScanPlane> fpln;
     std::vector<DevScanDisk> fdsk;
-    std::vector<DevHitRec> frec_s, frec_p, frec_d;
+    std::vector<DevScanBox> fbox;
+    std::vector<DevHitRec> frec_s, frec_p, frec_d, frec_b;
     // STRICT's sphere records in SCAN order (its scan takes its candidates from the same f32 filter, whose bit k is scan sphere
     // k): the DevShape as it is, with the YAML index -- the tie rule's key -- in pad0
     std::vector<DevShape> sshapes;
@@ -139,6 +149,19 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
             dk.px = d.px; dk.py = d.py; dk.pz = d.pz; dk.nx = d.c0x; dk.ny = d.c0y; dk.nz = d.c0z; dk.id = (int32_t)i; dk.rr = d.rr;
             fdsk.push_back(dk);
             frec_d.push_back(r);
+        } else if (d.kind == kShapeBox) {
+            DevScanBox bx{};
+            bx.c0x = d.c0x; bx.c0y = d.c0y; bx.c0z = d.c0z; bx.c1x = d.c1x; bx.c1y = d.c1y; bx.c1z = d.c1z; bx.id = (int32_t)i; bx.inv = d.inv;
+            fbox.push_back(bx);
+            // six plane records, one per face: 2 axis + (1: the outward normal is +e_axis), the normal negated for `invert`
+            for (int face = 0; face < 6; face++) {
+                DevHitRec f = r;
+                f.shape_kind = kShapePlane;
+                f.unit_normal = 1;
+                f.cx = f.cy = f.cz = 0.0;
+                (face / 2 == 0 ? f.cx : face / 2 == 1 ? f.cy : f.cz) = ((face & 1) ? 1.0 : -1.0) * d.inv;
+                frec_b.push_back(f);
+            }
         } else {
             DevScanPlane pl{};
             pl.px = d.px; pl.py = d.py; pl.pz = d.pz; pl.nx = d.c0x; pl.ny = d.c0y; pl.nz = d.c0z; pl.id = (int32_t)i;
@@ -177,7 +200,7 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
         }
     }
 
-    h.fs = fscene_layout(fsph.size(), fpln.size(), fdsk.size(), ns, W, H);
+    h.fs = fscene_layout(fsph.size(), fpln.size(), fdsk.size(), fbox.size(), ns, W, H);
     h.fscene.assign(h.fs.bytes, 0);
     put(h.fscene, h.fs.sph, fsph);
     put(h.fscene, h.fs.pln, fpln);
@@ -186,7 +209,9 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     put(h.fscene, h.fs.rec + (frec_s.size() + frec_p.size()) * sizeof(DevHitRec), frec_d);
     put(h.fscene, h.fs.s32, fsph32);
     put(h.fscene, h.fs.ss, sshapes);
+    put(h.fscene, h.fs.rec + (frec_s.size() + frec_p.size() + frec_d.size()) * sizeof(DevHitRec), frec_b);
     put(h.fscene, h.fs.dsk, fdsk);
+    put(h.fscene, h.fs.box, fbox);
     // The split kernel's per-pixel constants of the primary ray (trace.rs:56-57, 93-94) as two tables a wave reads with scalar loads
     // in its ray-generation step: x - half_w for every column, (H - row) - half_h for every row -- the same two IEEE operations the
     // kernels perform, done once here
@@ -198,11 +223,12 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     rp.n_sph = (int32_t)fsph.size();
     rp.n_pln = (int32_t)fpln.size();
     rp.n_dsk = (int32_t)fdsk.size();
+    rp.n_box = (int32_t)fbox.size();
     // The glossy lobe's angle table (RenderParams::glossx): a slot for every distinct 1 / (exponent + 1) among the glossy records --
     // compared as bit patterns, collected in YAML order -- while at most kGlossExpSlots of them occur; each glossy record's byte offset
     // into a sample's entries (16 B a slot), in scan order as the records.  A scene with more exponents gets no table.
     std::vector<const DevHitRec *> frec_all;
-    for (const auto *v : {&frec_s, &frec_p, &frec_d})
+    for (const auto *v : {&frec_s, &frec_p, &frec_d, &frec_b})
         for (const DevHitRec &hr : *v) frec_all.push_back(&hr);
     auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; };
     auto slot_of = [&](double v) {
@@ -382,17 +408,18 @@ void build_camera(const flux_scene_desc &scene, HostScene &h) {
 
 }  // namespace
 
-FsceneLayout fscene_layout(size_t n_sph, size_t n_pln, size_t n_dsk, size_t n_shapes, uint32_t W, uint32_t H) {
+FsceneLayout fscene_layout(size_t n_sph, size_t n_pln, size_t n_dsk, size_t n_box, size_t n_shapes, uint32_t W, uint32_t H) {
     auto align128 = [](size_t x) { return (x + 127) & ~(size_t)127; };
     FsceneLayout f;
     f.sph = 0;
     f.pln = f.sph + (n_sph + 1) * sizeof(DevScanSphere);
     f.rec = f.pln + (n_pln + 1) * sizeof(DevScanPlane);
-    f.s32 = f.rec + (n_shapes + 1) * sizeof(DevHitRec);
+    f.s32 = f.rec + (n_shapes + 5 * n_box + 1) * sizeof(DevHitRec);  // (a box has six records)
     f.ss = align128(f.s32 + ((n_sph + 1) / 2 + 4) * sizeof(DevScanSphere32));
     f.pxc = align128(f.ss + (n_sph + 1) * sizeof(DevShape));
     f.dsk = align128(f.pxc + ((size_t)W + H) * sizeof(double));
-    f.bytes = f.dsk + (n_dsk + 1) * sizeof(DevScanDisk);
+    f.box = f.dsk + (n_dsk + 1) * sizeof(DevScanDisk);  // (no spare record: a scene without boxes keeps the bytes it had)
+    f.bytes = f.box + n_box * sizeof(DevScanBox);
     return f;
 }
 

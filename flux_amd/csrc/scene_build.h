@@ -13,18 +13,19 @@
 namespace flux {
 
 // Where each region of the FAST scene image starts, in bytes from its base.  fscene_layout() computes it once; the host build
-// fills the image by it and the upload points RenderParams::fsph .. fdsk into the device copy by it.
+// fills the image by it and the upload points RenderParams::fsph .. fbox into the device copy by it.
 struct FsceneLayout {
     size_t sph = 0;    // DevScanSphere[n_sph + 1] (+1: the scan reads one record ahead)
     size_t pln = 0;    // DevScanPlane[n_pln + 1]
-    size_t rec = 0;    // DevHitRec[n_shapes + 1]: spheres, planes, disks
+    size_t rec = 0;    // DevHitRec[n_shapes + 5 n_box + 1]: spheres, planes, disks, six per box
     size_t s32 = 0;    // DevScanSphere32[(n_sph + 1) / 2 + 4] (+4 pairs: the filter loads whole groups of 8 spheres)
     size_t ss = 0;     // DevShape[n_sph + 1], 128-B aligned: STRICT's spheres in scan order
     size_t pxc = 0;    // double[W + H], 128-B aligned: the primary ray's per-column and per-row constants
     size_t dsk = 0;    // DevScanDisk[n_dsk + 1], 128-B aligned
+    size_t box = 0;    // DevScanBox[n_box], behind the disks
     size_t bytes = 0;  // the whole image
 };
-FsceneLayout fscene_layout(size_t n_sph, size_t n_pln, size_t n_dsk, size_t n_shapes, uint32_t W, uint32_t H);
+FsceneLayout fscene_layout(size_t n_sph, size_t n_pln, size_t n_dsk, size_t n_box, size_t n_shapes, uint32_t W, uint32_t H);
 
 struct HostScene {
     std::vector<DevShape> shapes;   // one record at least

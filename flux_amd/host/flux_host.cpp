@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "scene_schema.hpp"
 #include "yaml_lite.hpp"
@@ -30,6 +31,10 @@ struct YamlReader {
         const Node *f = n.find(key);
         if (!f) bad(below() + ": missing field `" + key + "`");
         YamlReader{*f, below() + "." + key}.value(member);
+    }
+    // a field the schema marks optional (scene_schema.hpp optional_field): absent, the member keeps its default
+    template <class M> void optional(const char *key, M &member) {
+        if (const Node *f = n.find(key)) YamlReader{*f, below() + "." + key}.value(member);
     }
     void value(double &v) {
         if (n.kind != Node::Scalar) bad(path + ": expected a number");
@@ -95,6 +100,15 @@ struct YamlReader {
     template <class S> void check(const S &) {}
     void check(DiskData &k) {
         if (!(std::isfinite(k.radius) && k.radius >= 0.0)) bad(below() + "." + field_name(k, k.radius) + ": expected a finite number >= 0");
+    }
+    void check(BoxData &k) {
+        const double c0[3] = {k.corner0.x, k.corner0.y, k.corner0.z}, c1[3] = {k.corner1.x, k.corner1.y, k.corner1.z};
+        for (int a = 0; a < 3; a++) {
+            const std::string axis(1, "xyz"[a]);
+            if (!std::isfinite(c0[a])) bad(below() + "." + field_name(k, k.corner0) + ": expected finite numbers (axis " + axis + ")");
+            if (!(std::isfinite(c1[a]) && c0[a] < c1[a]))
+                bad(below() + "." + field_name(k, k.corner1) + ": expected finite numbers above corner0 (axis " + axis + ")");
+        }
     }
     void check(DielectricData &m) {
         if (!(std::isfinite(m.refraction_index) && m.refraction_index > 0.0))
@@ -183,6 +197,12 @@ AbiScene::AbiScene(const SceneData &sd) : name(sd.scene_name) {
             set3(fs.n, k->normal);
             fs.radius = k->radius;
             fs.material = to_abi(k->material);
+        } else if (auto b = std::get_if<BoxData>(&sd.shapes[i])) {
+            fs.kind = FLUX_SHAPE_BOX;
+            set3(fs.p, b->corner0);
+            set3(fs.n, b->corner1);
+            fs.invert = b->invert ? 1 : 0;
+            fs.material = to_abi(b->material);
         }
     }
     desc.scene_name = name.c_str();

@@ -49,7 +49,9 @@ struct SphereData { Vec3 center; double radius = 0; MaterialData material; bool 
 struct PlaneData { Vec3 point, normal; MaterialData material; };
 // extension (include/flux_abi.h FLUX_SHAPE_DISK): a closed disk; a reference node cannot decode it
 struct DiskData { Vec3 center, normal; double radius = 0; MaterialData material; };
-using ShapeData = std::variant<SphereData, PlaneData, DiskData>;
+// extension (include/flux_abi.h FLUX_SHAPE_BOX): an axis-aligned box, corner0 < corner1 on every axis; `invert` is optional in YAML
+struct BoxData { Vec3 corner0, corner1; MaterialData material; bool invert = false; };
+using ShapeData = std::variant<SphereData, PlaneData, DiskData, BoxData>;
 
 struct CameraSettings { Vec3 eye, look_at, up; };
 struct CameraData { double zoom_factor = 1, view_plane_distance = 0, focal_distance = 0, lens_radius = 0; };

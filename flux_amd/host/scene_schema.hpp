@@ -71,6 +71,19 @@ template <class V> void fields(V &v, DiskData &s) {
     v("material", s.material);
 }
 
+// a field a reader may not find: a visitor that has optional(name, member) gets that call, every other one the plain v(name, member)
+template <class V, class M> auto optional_field(V &v, const char *name, M &member, int) -> decltype(v.optional(name, member)) {
+    return v.optional(name, member);
+}
+template <class V, class M> void optional_field(V &v, const char *name, M &member, long) { v(name, member); }
+
+template <class V> void fields(V &v, BoxData &s) {
+    v("corner0", s.corner0);
+    v("corner1", s.corner1);
+    v("material", s.material);
+    optional_field(v, "invert", s.invert, 0);  // may be absent in YAML (it keeps its default, false); always on the wire
+}
+
 template <class V> void fields(V &v, OutputSettings &o) {
     v("image_width", o.image_width);
     v("image_height", o.image_height);
@@ -155,6 +168,7 @@ template <class V> void variants(V &v, ShapeData &s) {  // scene.rs:71-74
     alternative<SphereData>(v, "Sphere", s);
     alternative<PlaneData>(v, "Plane", s);
     alternative<DiskData>(v, "Disk", s);  // extension: a reference node rejects the unknown variant
+    alternative<BoxData>(v, "Box", s);    // extension, likewise
 }
 template <class V> void variants(V &v, RenderEvent &ev) {  // manager.rs:16-22
     RenderingStartedEvent started{ev.job_id, {ev.time_s}};

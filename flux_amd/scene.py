@@ -119,7 +119,21 @@ class DiskData:
     material: MaterialData
 
 
-ShapeData = Union[SphereData, PlaneData, DiskData]  # scene.rs:71-74 + the Disk extension
+@dataclass
+class BoxData:
+    """Extension (absent in the reference): an axis-aligned box.  YAML:
+        - Box: {corner0: [x, y, z], corner1: [x, y, z], invert: bool (optional, default false), material: {...}}
+    corner0 < corner1 on every axis.  BoundingBox::hit's slabs (shapes.rs:99-131) as a shape: the hit is the entry if it lies
+    beyond T_MIN, else the exit; the normal is the hit face's outward unit axis, negated for `invert` (a room lit from its
+    walls), never flipped towards the ray.  Ties: YAML index among the analytic shapes.  include/flux_abi.h flux_shape has the
+    whole rule, DESIGN.md §5d the rest."""
+    corner0: Vec3
+    corner1: Vec3
+    material: MaterialData
+    invert: bool = False
+
+
+ShapeData = Union[SphereData, PlaneData, DiskData, BoxData]  # scene.rs:71-74 + the Disk and Box extensions
 
 
 @dataclass
@@ -217,6 +231,17 @@ def shape_from_yaml(m, what="shape"):
             raise SceneError(f"{w}.radius: expected a finite number >= 0, got {radius!r}")
         return DiskData(_vec3(_req(b, "center", w), w + ".center"), _vec3(_req(b, "normal", w), w + ".normal"), radius,
                         material_from_yaml(_req(b, "material", w), w + ".material"))
+    if tag == "Box":  # extension
+        c0, c1 = _vec3(_req(b, "corner0", w), w + ".corner0"), _vec3(_req(b, "corner1", w), w + ".corner1")
+        for k in range(3):
+            if not math.isfinite(c0[k]):
+                raise SceneError(f"{w}.corner0: expected finite numbers, got {c0[k]!r} on axis {'xyz'[k]}")
+            if not (math.isfinite(c1[k]) and c0[k] < c1[k]):
+                raise SceneError(f"{w}.corner1: expected finite numbers above corner0, got {c1[k]!r} against {c0[k]!r} on axis {'xyz'[k]}")
+        inv = b.get("invert", False)
+        if not isinstance(inv, bool):
+            raise SceneError(f"{w}.invert: expected a boolean, got {inv!r}")
+        return BoxData(c0, c1, material_from_yaml(_req(b, "material", w), w + ".material"), inv)
     if tag == "Sphere":
         inv = _req(b, "invert", w)
         if not isinstance(inv, bool):
@@ -226,7 +251,7 @@ def shape_from_yaml(m, what="shape"):
     if tag == "Plane":
         return PlaneData(_vec3(_req(b, "point", w), w + ".point"), _vec3(_req(b, "normal", w), w + ".normal"),
                          material_from_yaml(_req(b, "material", w), w + ".material"))
-    raise SceneError(f"{what}: unknown variant `{tag}`, expected one of `Sphere`, `Plane`, `Disk`, `Mesh`, `Triangle`")
+    raise SceneError(f"{what}: unknown variant `{tag}`, expected one of `Sphere`, `Plane`, `Disk`, `Box`, `Mesh`, `Triangle`")
 
 
 def _usize(m, key, what) -> int:
@@ -342,6 +367,11 @@ class SceneDesc:
                 fs.p[:] = s.center
                 fs.n[:] = s.normal
                 fs.radius = s.radius
+            elif isinstance(s, BoxData):
+                fs.kind = _lib.SHAPE_BOX
+                fs.p[:] = s.corner0
+                fs.n[:] = s.corner1
+                fs.invert = 1 if s.invert else 0
             else:
                 raise TypeError(f"not a ShapeData: {s!r}")
             fs.material = material_to_abi(s.material)

@@ -48,6 +48,9 @@ extern "C" {
  * Added without an ABI version bump: a library that predates it rejects kind 2 in flux_ctx_create with
  * FLUX_E_INVALID ("unknown kind"), which is how a client detects support. */
 #define FLUX_SHAPE_DISK 2
+/* EXTENSION (absent in the reference): an axis-aligned box, see flux_shape.  Added without an ABI version bump, as the
+ * disk: a library that predates it rejects kind 3 in flux_ctx_create with FLUX_E_INVALID ("unknown kind"). */
+#define FLUX_SHAPE_BOX 3
 
 /* MaterialData variants: fluxcore/src/shapes.rs:42-47 */
 #define FLUX_MAT_MATTE 0       /* MatteData            shapes.rs:52-56 */
@@ -91,7 +94,22 @@ typedef struct flux_material {
  * (the next segment's origin) has |q - p|^2 <= radius^2; a non-finite t is a miss.
  * Two-sided, normal as given (as the plane's); it emits towards -n only
  * (materials.rs:44).  radius must be finite and >= 0 (0: a degenerate disk),
- * else flux_ctx_create returns FLUX_E_INVALID.  Ties: YAML index, as every shape. */
+ * else flux_ctx_create returns FLUX_E_INVALID.  Ties: YAML index, as every shape.
+ * box (extension, FLUX_SHAPE_BOX): p = corner0, n = corner1, `invert` honoured, radius ignored.
+ * Every corner component must be finite and corner0[k] < corner1[k] on each axis, else
+ * flux_ctx_create returns FLUX_E_INVALID (before any device work).  BoundingBox::hit's slabs
+ * (shapes.rs:99-131) as a shape: per axis k = x, y, z: a_k = 1/d_k and (tmin_k, tmax_k) =
+ * ((c0_k - o_k) a_k, (c1_k - o_k) a_k) if a_k >= 0, else swapped; t0 = max(tmin_x, max(tmin_y,
+ * tmin_z)), t1 = min(tmax_x, min(tmax_y, tmax_z)) with the reference's max(a,b) = a > b ? a : b
+ * and min(a,b) = a < b ? a : b.  A ray parallel to a slab that starts ON one of its planes has
+ * 0 * inf = NaN there: those forms drop a NaN of the x or y slab (the slab then bounds nothing)
+ * and hand a NaN of the z slab through, which is a miss.  No hit unless t0 < t1; then t = t0 (the
+ * entry) if t0 > T_MIN, else t = t1 (the exit) if t1 > T_MIN, else no hit.  The face is on the
+ * first axis k (x, y, z) with tmin_k == t (entry) resp. tmax_k == t (exit); the normal is that
+ * face's outward unit axis (entry: -e_k if a_k >= 0 else +e_k; exit: the opposite), negated
+ * for `invert`, never flipped towards the ray.  So an Emissive box emits outwards, an inverted
+ * one inwards (a room), and a Dielectric box is entered at c > 0.  Ties: YAML index.
+ * DESIGN.md section 5d. */
 typedef struct flux_shape {
     int32_t kind;
     int32_t invert;
