@@ -34,11 +34,18 @@ constexpr int kGlossExpSlots = 4;
 // sample index and Path::self (int)
 constexpr int kQueueDoubles = 9;
 constexpr int kQueueBytesPerWave = (kQueueDoubles * 64) * 8 + 2 * 64 * 4;
-// The hit queue (plan_render chooses C per scene): C slots per wave, [field][slot] as above -- o d t, then hit | depth << 16, the
+// The hit queue (plan_render chooses C per scene): C slots per wave -- o d t, hit | depth << 16, the
 // sample index and the bounce list (render_body.inc render_split_kernel): 68 B a slot
 constexpr int kHitQDoubles = 7;
 constexpr int kHitQInts = 3;
 constexpr int kHitQBytesPerSlot = kHitQDoubles * 8 + kHitQInts * 4;
+// A wave's pool is an array of C such slots, 17 dwords each (an odd stride: a wave's accesses do not collide on LDS banks): the three
+// ints first, then the doubles as dword pairs at 4-byte alignment.  Entries are allocated downwards from the pool's top: entry k
+// (0 the oldest) is slot C - 1 - k.
+constexpr uint32_t kHitQDwordsPerSlot = kHitQBytesPerSlot / 4;
+constexpr uint32_t hitq_entry_dword(uint32_t C, uint32_t k) { return (C - 1u - k) * kHitQDwordsPerSlot; }
+// The room phase A needs before it runs: the scan behind it may park a hit from each of its 64 lanes.
+constexpr bool hitq_admits_phase_a(uint32_t C, uint32_t nhit) { return nhit + 64u <= C; }
 
 // The copy of render_body.inc a launch runs (render.hip): the STRICT arithmetic, the FAST one, or the FAST one with the dielectric
 // lobe (RenderParams::has_diel)

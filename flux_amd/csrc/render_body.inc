@@ -1948,7 +1948,10 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, TRIS ? FLUX_WPE_WIDE
 // The two queues' layouts, kQueueBytesPerWave and kHitQBytesPerSlot, are in flux_plan.h: the launch plan reserves their LDS.
 // A queued path: ox oy oz dx dy dz tr tg tb, the sample index and Path::self (GlossySpecular's re-mapped sample is read from the
 // glossy-lobe table by the sample index, so the pixel sample itself is dead after the primary ray).
-// The hit queue (plan_render chooses C per scene): C slots per wave, structure of arrays [field][slot] as above.
+// The hit queue (plan_render chooses C per scene): C slots per wave, an array of structures (flux_plan.h): a slot is 17 dwords -- the
+// three ints, then the seven doubles as dword pairs --, so one multiply-add gives a lane its slot's address and every field is a
+// constant offset from it (field-major arrays of C entries, C known only at the launch, cost an address addition per field), and the
+// odd stride keeps a wave's accesses off each other's LDS banks.
 // Phase B only CLASSIFIES its hits; a continuing hit is parked here -- the segment o d and its hit distance t (8 B each), the hit-record
 // index and the depth (one int), the sample index (int) and the path's throughput -- and its bounce runs later, in a pass whose free
 // lanes take a full batch of parked hits at once (bounce_parked_hit), instead of under the sparse mask of the scan's survivors.
@@ -2091,6 +2094,13 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
     }
 }
 
+// A double of a hit-queue entry: entries are arrays of dwords at 4-byte alignment (flux_plan.h), read and written as dword pairs.
+__device__ __forceinline__ double lds_dword_pair(const uint32_t *p) { return __hiloint2double((int)p[1], (int)p[0]); }
+__device__ __forceinline__ void lds_dword_pair_store(uint32_t *p, double v) {
+    p[0] = (uint32_t)__double2loint(v);
+    p[1] = (uint32_t)__double2hiint(v);
+}
+
 // HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
 // bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see launch_plan.cpp plan_render): the 64-entry ray queue and phase B's
 // bounce at once, in the lanes that continue.
@@ -2115,7 +2125,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
     const int n_rec = TYP ? P.n_sph + P.n_pln + P.n_dsk : hit_records(P);
     const size_t scene_lds_bytes = (size_t)n_rec * sizeof(DevHitRec) + (size_t)P.n_sph * sizeof(DevScanSphere);
     double *q = lds_stack + scene_lds_bytes / 8 + (size_t)sub * (HQ ? (size_t)hq_cap * kHitQBytesPerSlot / 8 : kQueueBytesPerWave / 8);
-    int *qi = reinterpret_cast<int *>(q + (HQ ? (size_t)kHitQDoubles * hq_cap : (size_t)kQueueDoubles * 64));  // this wave's queue: [field][slot]
+    int *qi = reinterpret_cast<int *>(q + (size_t)kQueueDoubles * 64);  // the ray queue: [field][slot]; the hit queue's pool starts at q
     // The scene's hit records (96 B per shape) and scan spheres (32 B) copied into the block's LDS behind the queues: the per-lane gathers
     // of the shading step and of the candidate loop -- dependent loads in the middle of a pass, ~600 cycles each from the L2 -- become
     // LDS reads (~100).  The launch plan reserves the bytes (plan_render: the split kernel serves scenes whose records fit 16 KiB).
@@ -2147,8 +2157,9 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
         const uint32_t C = (uint32_t)hq_cap, H = (uint32_t)hq_th;
         const uint32_t bmask = (1u << hq_bits) - 1u;
         const DevHitRec *const recs = reinterpret_cast<const DevHitRec *>(frec_lds);
+        uint32_t *const pool = reinterpret_cast<uint32_t *>(q);  // this wave's C entries (flux_plan.h hitq_entry_dword)
         uint32_t next = s_lo;  // wave-uniform cursor: first unstarted sample of this wave's slice
-        uint32_t nhit = 0;     // wave-uniform: parked hits, in slots C-1, C-2, ... (the newest at C - nhit)
+        uint32_t nhit = 0;     // wave-uniform: parked hits, entries 0 .. nhit-1 (entry k in slot C-1-k: the newest at C - nhit)
         constexpr int kDeadDepth = 0x7fffffff;  // (as in the loop below: "no path" kept in the depth)
         // Every lane is free at the top of a pass: the scan of the pass before ended or parked each of its paths.  So no path state is
         // carried from pass to pass -- only the sums, the statistics and the two counts.
@@ -2166,7 +2177,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             uint32_t ml = 0;  // the records of the path's bounces so far, entry k at bit k * hq_bits
             // ---- phase A, while fewer than H hits are parked and the queue has room for all 64 continuations: samples next .. next+63,
             //      their continuing paths stay in their lanes
-            const bool run_a = next < s_hi && nhit < H && nhit + 64u <= C;
+            const bool run_a = next < s_hi && nhit < H && hitq_admits_phase_a(C, nhit);
             if (run_a) {
                 FLUX_TRIP(P, 12);
                 FLUX_CENSUS(P, 0);
@@ -2220,25 +2231,25 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 const unsigned long long freemask = ballot64(p.depth == kDeadDepth);
                 const uint32_t nfree = (uint32_t)__popcll(freemask);
                 const uint32_t take = nfree < nhit ? nfree : nhit;
-                if (!run_a || take >= H || !(next < s_hi && nhit + 64u <= C)) {
+                if (!run_a || take >= H || !(next < s_hi && hitq_admits_phase_a(C, nhit))) {
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(freemask >> 32),
                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)freemask, 0u));
                     if (p.depth == kDeadDepth && rank < take) {
                         FLUX_CENSUS(P, 15);
-                        const uint32_t slot = C - nhit + rank;
-                        p.r.ox = q[0 * C + slot];
-                        p.r.oy = q[1 * C + slot];
-                        p.r.oz = q[2 * C + slot];
-                        p.r.dx = q[3 * C + slot];
-                        p.r.dy = q[4 * C + slot];
-                        p.r.dz = q[5 * C + slot];
-                        const double t = q[6 * C + slot];
-                        const int hd = qi[slot];
-                        i = (uint32_t)qi[C + slot];
+                        const uint32_t *e = pool + hitq_entry_dword(C, nhit - 1u - rank);
+                        p.r.ox = lds_dword_pair(e + 3);
+                        p.r.oy = lds_dword_pair(e + 5);
+                        p.r.oz = lds_dword_pair(e + 7);
+                        p.r.dx = lds_dword_pair(e + 9);
+                        p.r.dy = lds_dword_pair(e + 11);
+                        p.r.dz = lds_dword_pair(e + 13);
+                        const double t = lds_dword_pair(e + 15);
+                        const int hd = (int)e[0];
+                        i = e[1];
                         const int hit = hd & 0xffff;
                         p.depth = hd >> 16;
                         // the throughput, front to back as fast_bounce formed it (the first bounce's weight, then one product per bounce)
-                        ml = (uint32_t)qi[2 * C + slot];
+                        ml = e[2];
                         const DevHitRec &R0 = recs[ml & bmask];
                         p.tr = R0.fr;
                         p.tg = R0.fg;
@@ -2290,18 +2301,18 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             if (cont) {
                 // (room: the queue held at most C - 64 hits when this pass's phase A ran, and a pass without it parks no more paths
                 // than it took from the queue)
-                const uint32_t slot = C - 1u - nhit - __builtin_amdgcn_mbcnt_hi((uint32_t)(pmask >> 32),
-                                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)pmask, 0u));
-                q[0 * C + slot] = p.r.ox;
-                q[1 * C + slot] = p.r.oy;
-                q[2 * C + slot] = p.r.oz;
-                q[3 * C + slot] = p.r.dx;
-                q[4 * C + slot] = p.r.dy;
-                q[5 * C + slot] = p.r.dz;
-                q[6 * C + slot] = t;
-                qi[slot] = hit | (p.depth << 16);
-                qi[C + slot] = (int)i;
-                qi[2 * C + slot] = (int)ml;
+                uint32_t *e = pool + hitq_entry_dword(C, nhit + __builtin_amdgcn_mbcnt_hi((uint32_t)(pmask >> 32),
+                                                                                           __builtin_amdgcn_mbcnt_lo((uint32_t)pmask, 0u)));
+                e[0] = (uint32_t)(hit | (p.depth << 16));
+                e[1] = i;
+                e[2] = ml;
+                lds_dword_pair_store(e + 3, p.r.ox);
+                lds_dword_pair_store(e + 5, p.r.oy);
+                lds_dword_pair_store(e + 7, p.r.oz);
+                lds_dword_pair_store(e + 9, p.r.dx);
+                lds_dword_pair_store(e + 11, p.r.dy);
+                lds_dword_pair_store(e + 13, p.r.dz);
+                lds_dword_pair_store(e + 15, t);
             }
             nhit += (uint32_t)__popcll(pmask);
         }
