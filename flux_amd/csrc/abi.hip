@@ -97,6 +97,7 @@ static void free_ctx(flux_ctx *c) {
     (void)hipFree(c->d_gloss);
     (void)hipFree(c->d_glossx);
     (void)hipFree(c->d_gxoff);
+    (void)hipFree(c->d_tput);
     (void)hipFree(c->d_setrows);
     (void)hipFree(c->d_rowperm);
     (void)hipFree(c->d_invperm);
@@ -255,6 +256,21 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         alloc(&c->d_glossx, own * c->N * (size_t)gx_stride);
         alloc_copy(&c->d_gxoff, h.gx_off);
     }
+    // the throughput product table (RenderParams::tput) where the job's renders would take parked hits from the hit queue and the
+    // table stays within its cap (flux_plan.h); FLUX_THROUGHPUT_TABLE=0 builds the context without it (tests and A/B runs: the take then
+    // multiplies the list up).  A switch of its own: what FLUX_SAMPLE_TABLES=0 removes from a context is the sample tables' bytes.
+    int tput_bits = 0;
+    {
+        RenderParams job = h.rp;
+        job.nsamp = c->N;
+        job.max_depth = (int32_t)c->D;
+        const char *tput_env = std::getenv("FLUX_THROUGHPUT_TABLE");
+        if (!(tput_env && std::atoi(tput_env) == 0) && tput_table_bytes(job, &tput_bits)) {
+            std::vector<double> tput;
+            build_tput_table(h, tput_bits, (int)c->D, tput);
+            alloc_copy(&c->d_tput, tput);
+        }
+    }
     alloc(&c->d_setrows, own * sizeof(DevSetRows));
     alloc(&c->d_rowperm, perm_bytes);
     alloc(&c->d_invperm, perm_bytes);
@@ -317,6 +333,8 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.glossx = c->d_glossx;
     rp.gx_off = c->d_gxoff;
     rp.gx_stride = gx_stride;
+    rp.tput = c->d_tput;
+    rp.tput_bits = c->d_tput ? tput_bits : 0;
     rp.set_rows = c->d_setrows;
     rp.rowperm = c->d_rowperm;
     rp.invperm = c->d_invperm;

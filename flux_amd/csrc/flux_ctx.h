@@ -87,6 +87,7 @@ struct flux_ctx {
     double *d_gloss = nullptr;  // FAST glossy-lobe factors of pixel_sets
     double2 *d_glossx = nullptr;  // the glossy lobe's angles per held sample and exponent slot (RenderParams::glossx), or nullptr
     int32_t *d_gxoff = nullptr;   // RenderParams::gx_off, with d_glossx
+    double *d_tput = nullptr;     // RenderParams::tput, or nullptr
     flux::DevSetRows *d_setrows = nullptr;  // per table slot: where the set's rows of the sample tables start
     int32_t *d_rowperm = nullptr, *d_invperm = nullptr;
     unsigned long long *d_stats = nullptr;

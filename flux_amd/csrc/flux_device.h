@@ -273,6 +273,11 @@ struct RenderParams {
     // extension: boxes (kShapeBox), scanned after the disks with a wave-uniform loop; hit records n_sph + n_pln + n_dsk + 6 j + face
     const DevScanBox *fbox;
     int32_t n_box;
+    // split kernel with the hit queue: the throughput product table (flux_plan.h tput_index) -- per bounce list a
+    // parked hit can carry, the product of its bounces' weights (r, g, b), front to back as the take's loop forms it -- or nullptr
+    // (the loop).  tput_bits: the bits per list entry it is laid out for; a launch whose plan has another hq_bits passes nullptr.
+    int32_t tput_bits;
+    const double *tput;
 };
 
 // hit records of a scene (DevHitRec): one per sphere, plane and disk, six per box

@@ -39,13 +39,36 @@ constexpr int kQueueBytesPerWave = (kQueueDoubles * 64) * 8 + 2 * 64 * 4;
 constexpr int kHitQDoubles = 7;
 constexpr int kHitQInts = 3;
 constexpr int kHitQBytesPerSlot = kHitQDoubles * 8 + kHitQInts * 4;
-// A wave's pool is an array of C such slots, 17 dwords each (an odd stride: a wave's accesses do not collide on LDS banks): the three
-// ints first, then the doubles as dword pairs at 4-byte alignment.  Entries are allocated downwards from the pool's top: entry k
-// (0 the oldest) is slot C - 1 - k.
+// A wave's pool is an array of C such slots, 17 dwords each (an odd stride: a wave's accesses do not collide on LDS banks): the seven
+// doubles first, each a dword pair at an even dword of the slot (4-byte alignment: one ds_read2_b32 / ds_write2_b32 is one double),
+// then the three ints.  Entries are allocated downwards from the pool's top: entry k (0 the oldest) is slot C - 1 - k.
+enum HitQField : uint32_t {  // a field's first dword in its slot
+    kHitQOx = 0, kHitQOy = 2, kHitQOz = 4, kHitQDx = 6, kHitQDy = 8, kHitQDz = 10, kHitQT = 12,
+    kHitQHitDepth = 14,  // hit | depth << 16
+    kHitQSample = 15,
+    kHitQList = 16,      // the bounce list
+};
 constexpr uint32_t kHitQDwordsPerSlot = kHitQBytesPerSlot / 4;
 constexpr uint32_t hitq_entry_dword(uint32_t C, uint32_t k) { return (C - 1u - k) * kHitQDwordsPerSlot; }
 // The room phase A needs before it runs: the scan behind it may park a hit from each of its 64 lanes.
 constexpr bool hitq_admits_phase_a(uint32_t C, uint32_t nhit) { return nhit + 64u <= C; }
+
+// The throughput product table (RenderParams::tput): for a scene whose parked hits the hit queue takes, the
+// product of the bounce weights of every bounce list a parked hit can carry, so that the take reads it instead of multiplying it up.
+// A list of n entries (n = depth - 1 = 1 .. max_depth - 1, hq_bits each, entry 0 the first bounce) is entry
+//     tput_index(n * hq_bits, ml) = (1 << n * hq_bits) | ml
+// -- the lists of length n fill [2^(n bits), 2^(n bits + 1)), so the table has 2 << (max_depth - 1) * hq_bits entries of
+// kTputEntryBytes (r, g, b).  The index relies on ml's bits above n * hq_bits being zero; they are by construction (the kernel
+// sets ml = hit, then ml |= hit << n * hq_bits per bounce, hit < 2^hq_bits).
+// A context holds the table only while it stays within kTputTableMaxBytes (demo2, 12 records, 4 bits, depth 5: 2^17 entries, 3 MiB;
+// 17 records or more at depth 5, 5 bits: 48 MiB -- no table, the take multiplies the list up as before).
+constexpr size_t kTputEntryBytes = 24;
+constexpr size_t kTputTableMaxBytes = (size_t)4 << 20;
+constexpr uint32_t tput_index(uint32_t list_bits, uint32_t ml) { return (1u << list_bits) | ml; }
+// Bytes of the table a context for this job builds -- rp as the upload fills it: the scene's fields, nsamp and max_depth --, 0 for
+// none: the hit queue is not planned for the job (launch_plan.cpp plan_render), a parked hit cannot exist (max_depth < 2), or the table
+// would exceed the cap.  `bits`: the hit queue's bits per list entry the table is laid out for.
+size_t tput_table_bytes(const RenderParams &p, int *bits = nullptr);
 
 // The copy of render_body.inc a launch runs (render.hip): the STRICT arithmetic, the FAST one, or the FAST one with the dielectric
 // lobe (RenderParams::has_diel)

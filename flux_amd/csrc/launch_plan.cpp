@@ -35,6 +35,50 @@ static bool bvh4_typ(const RenderParams &p, bool lds_scene) {
            p.fsph32 != nullptr && p.n_dsk == 0 && p.n_box == 0 && p.has_diel == 0;
 }
 
+// K, the waves that share a pixel's samples in the refill and split kernels: the largest power of two
+// <= min(N / FLUX_MIN_SAMPLES_PER_WAVE, FLUX_MAX_WAVES_PER_PIXEL), from the sample count only
+static unsigned waves_per_pixel(uint32_t N) {
+    unsigned K = 1;
+    while (K * 2u <= (unsigned)FLUX_MAX_WAVES_PER_PIXEL && (uint64_t)K * 2u * FLUX_MIN_SAMPLES_PER_WAVE <= N) K *= 2u;
+    return K;
+}
+
+// The split kernel's scene copy in LDS, and whether the kernel serves the scene at all (see plan_render)
+static size_t split_scene_lds(const RenderParams &p) {
+    return (size_t)hit_records(p) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
+}
+static bool split_serves(const RenderParams &p) { return p.n_tris == 0 && p.n_sph <= 64 && split_scene_lds(p) <= 16384; }
+
+// Whether the split kernel at K waves per pixel runs this scene with the hit queue, and with what C, H and bits per list entry (the
+// rule: plan_render's comment at its call)
+static bool plan_hitq(const RenderParams &p, unsigned K, size_t scene_lds, uint32_t &cap, uint32_t &th, int &bits) {
+    if (p.glossy_long != 0 || p.has_diel != 0) return false;
+    const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
+    const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
+    cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
+    if (const char *e = std::getenv("FLUX_SPLIT_HITQ_CAP")) cap = std::min(cap, (uint32_t)std::max(0, std::atoi(e)) & ~1u);
+    th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
+    if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
+    bits = 1;
+    while ((1 << bits) < hit_records(p)) ++bits;
+    return cap >= 64u + th && bits * p.max_depth <= 32;
+}
+
+size_t tput_table_bytes(const RenderParams &p, int *bits_out) {
+    uint32_t cap, th;
+    int bits;
+    // (a context cannot know which kernel its renders will ask for: the table is there for every job the split kernel would run with
+    // the hit queue -- FAST arithmetic, 64 samples or more --, and a render that runs another kernel leaves it unread)
+    if (p.nsamp < 64u || p.max_depth < 2 || !split_serves(p) || !plan_hitq(p, waves_per_pixel(p.nsamp), split_scene_lds(p), cap, th, bits))
+        return 0;
+    const int list_bits = bits * (p.max_depth - 1);  // (<= 32 - bits: plan_hitq)
+    if (list_bits + 1 > 24) return 0;                // (the kernel forms the entry's byte offset with a 24-bit multiply)
+    const size_t bytes = ((size_t)2 << list_bits) * kTputEntryBytes;
+    if (bytes > kTputTableMaxBytes) return 0;
+    if (bits_out) *bits_out = bits;
+    return bytes;
+}
+
 LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     LaunchPlan L;
     L.copy = kernel_copy(p, math);
@@ -54,9 +98,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
         waves = 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows +
                         ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
     // refill kernel: K waves per pixel (block = pixel), K from the sample count only
-    unsigned K = 1;  // largest power of two <= min(N / FLUX_MIN_SAMPLES_PER_WAVE, FLUX_MAX_WAVES_PER_PIXEL)
-    if (variant != FLUX_KERNEL_STATIC)
-        while (K * 2u <= (unsigned)FLUX_MAX_WAVES_PER_PIXEL && (uint64_t)K * 2u * FLUX_MIN_SAMPLES_PER_WAVE <= N) K *= 2u;
+    unsigned K = variant != FLUX_KERNEL_STATIC ? waves_per_pixel(N) : 1u;
     const bool tris = p.n_tris > 0;
     // STRICT keeps 32 B of recursion stack per level and lane in LDS: fewer waves per pixel where four would not fit the
     // 64 KiB a block may have (K = 4 holds 7 levels, K = 1 31); still a function of the job alone, never of the sharding
@@ -92,8 +134,8 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     // serves scenes whose records fit 16 KiB there (64 spheres -- the pixel mask's width -- leave room for 85 planes, demo2's 12 for 154;
     // until round 6 the rule was "at most 16 planes", and a seventeenth sent the scene to the refill kernel); larger analytic scenes
     // take the refill kernel, which reads the records from global memory (the launch plan says which)
-    const size_t scene_lds = (size_t)hit_records(p) * sizeof(DevHitRec) + (size_t)p.n_sph * sizeof(DevScanSphere);
-    if (fast && variant == FLUX_KERNEL_SPLIT && !tris && p.n_sph <= 64 && scene_lds <= 16384) {
+    const size_t scene_lds = split_scene_lds(p);
+    if (fast && variant == FLUX_KERNEL_SPLIT && split_serves(p)) {
         L.kernel = 2;
         L.block = block;
         L.waves_per_pixel = K;
@@ -108,21 +150,13 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
         // FLUX_SPLIT_HITQ_CAP / FLUX_SPLIT_HITQ_TAKE_AT override C (at most what fits) and H.
         // A scene with a dielectric keeps the ray queue too: a dielectric bounce's weight depends on the branch it took, which its hit
         // record does not tell.
-        if (p.glossy_long == 0 && p.has_diel == 0) {
-            const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
-            const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
-            uint32_t cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
-            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_CAP")) cap = std::min(cap, (uint32_t)std::max(0, std::atoi(e)) & ~1u);
-            uint32_t th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
-            if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
-            int bits = 1;
-            while ((1 << bits) < hit_records(p)) ++bits;
-            if (cap >= 64u + th && bits * p.max_depth <= 32) {
-                L.hq_cap = (int)cap;
-                L.hq_th = (int)th;
-                L.hq_bits = bits;
-                L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
-            }
+        uint32_t cap, th;
+        int bits;
+        if (plan_hitq(p, K, scene_lds, cap, th, bits)) {
+            L.hq_cap = (int)cap;
+            L.hq_th = (int)th;
+            L.hq_bits = bits;
+            L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
         }
         return L;
     }

@@ -1949,7 +1949,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, TRIS ? FLUX_WPE_WIDE
 // A queued path: ox oy oz dx dy dz tr tg tb, the sample index and Path::self (GlossySpecular's re-mapped sample is read from the
 // glossy-lobe table by the sample index, so the pixel sample itself is dead after the primary ray).
 // The hit queue (plan_render chooses C per scene): C slots per wave, an array of structures (flux_plan.h): a slot is 17 dwords -- the
-// three ints, then the seven doubles as dword pairs --, so one multiply-add gives a lane its slot's address and every field is a
+// seven doubles as dword pairs on even dwords, then the three ints --, so one multiply-add gives a lane its slot's address and every field is a
 // constant offset from it (field-major arrays of C entries, C known only at the launch, cost an address addition per field), and the
 // odd stride keeps a wave's accesses off each other's LDS banks.
 // Phase B only CLASSIFIES its hits; a continuing hit is parked here -- the segment o d and its hit distance t (8 B each), the hit-record
@@ -1958,7 +1958,8 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, TRIS ? FLUX_WPE_WIDE
 // The throughput is kept as the list of the path's earlier bounce records, `bits` per bounce in one int (68 B a slot; three doubles,
 // 88 B a slot, was measured slower: DESIGN.md §4, the hit queue): without long-form glossy weights (P.glossy_long) a bounce
 // of an analytic shape multiplies the throughput by its record's (fr, fg, fb) and nothing else, so the product recomputed front to back from the block's LDS copy of the records is bit
-// for bit the running one.  Every decision of the pass loop is a count (wave-uniform), so frames stay bit-reproducible.
+// for bit the running one -- and so is the same product formed once per scene on the host: where the context holds the throughput
+// product table (RenderParams::tput, flux_plan.h tput_index) the take gathers the list's product from it.  Every decision of the pass loop is a count (wave-uniform), so frames stay bit-reproducible.
 
 // The spheres a primary ray of pixel (row, col) can hit: a conservative wave-uniform mask (bit = scan index).
 // Every primary ray starts on the lens, |o - eye| <= R = lens_radius (to_poisson_disc maps into the unit disc,
@@ -2101,6 +2102,12 @@ __device__ __forceinline__ void lds_dword_pair_store(uint32_t *p, double v) {
     p[1] = (uint32_t)__double2hiint(v);
 }
 
+// Entry k of a wave's pool (flux_plan.h hitq_entry_dword: slot C - 1 - k), its byte offset formed with a 24-bit multiply so that it
+// and the pool's address are one v_mad_u32_u24 (C is a few hundred at the most).
+__device__ __forceinline__ uint32_t *hitq_entry(uint32_t *pool, uint32_t C, uint32_t k) {
+    return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(pool) + __umul24(C - 1u - k, (uint32_t)kHitQBytesPerSlot));
+}
+
 // HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
 // bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see launch_plan.cpp plan_render): the 64-entry ray queue and phase B's
 // bounce at once, in the lanes that continue.
@@ -2236,31 +2243,43 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)freemask, 0u));
                     if (p.depth == kDeadDepth && rank < take) {
                         FLUX_CENSUS(P, 15);
-                        const uint32_t *e = pool + hitq_entry_dword(C, nhit - 1u - rank);
-                        p.r.ox = lds_dword_pair(e + 3);
-                        p.r.oy = lds_dword_pair(e + 5);
-                        p.r.oz = lds_dword_pair(e + 7);
-                        p.r.dx = lds_dword_pair(e + 9);
-                        p.r.dy = lds_dword_pair(e + 11);
-                        p.r.dz = lds_dword_pair(e + 13);
-                        const double t = lds_dword_pair(e + 15);
-                        const int hd = (int)e[0];
-                        i = e[1];
+                        const uint32_t *e = hitq_entry(pool, C, nhit - 1u - rank);
+                        p.r.ox = lds_dword_pair(e + kHitQOx);
+                        p.r.oy = lds_dword_pair(e + kHitQOy);
+                        p.r.oz = lds_dword_pair(e + kHitQOz);
+                        p.r.dx = lds_dword_pair(e + kHitQDx);
+                        p.r.dy = lds_dword_pair(e + kHitQDy);
+                        p.r.dz = lds_dword_pair(e + kHitQDz);
+                        const double t = lds_dword_pair(e + kHitQT);
+                        const int hd = (int)e[kHitQHitDepth];
+                        i = e[kHitQSample];
                         const int hit = hd & 0xffff;
                         p.depth = hd >> 16;
-                        // the throughput, front to back as fast_bounce formed it (the first bounce's weight, then one product per bounce)
-                        ml = e[2];
-                        const DevHitRec &R0 = recs[ml & bmask];
-                        p.tr = R0.fr;
-                        p.tg = R0.fg;
-                        p.tb = R0.fb;
-                        for (int k = 1; k < p.depth - 1; ++k) {
-                            const DevHitRec &Rk = recs[(ml >> (k * hq_bits)) & bmask];
-                            p.tr *= Rk.fr;
-                            p.tg *= Rk.fg;
-                            p.tb *= Rk.fb;
+                        ml = e[kHitQList];
+                        // the list's bits: depth - 1 entries.  ml's bits above them are zero -- it was set to the first hit and has had
+                        // one hit (< 2^hq_bits) or-ed in just above the list per bounce, below -- which tput_index relies on
+                        const uint32_t list_bits = __umul24((uint32_t)(p.depth - 1), (uint32_t)hq_bits);
+                        // the throughput, front to back as fast_bounce formed it (the first bounce's weight, then one product per bounce):
+                        // read from the scene's product table where the context holds one (wave-uniform; flux_plan.h tput_index), ...
+                        if (P.tput != nullptr) {
+                            const uint32_t off = __umul24(tput_index(list_bits, ml), (uint32_t)kTputEntryBytes);
+                            p.tr = gather_global<double>(P.tput, off);
+                            p.tg = gather_global<double>(P.tput, off + 8u);
+                            p.tb = gather_global<double>(P.tput, off + 16u);
+                        } else {  // ... or multiplied up from the records
+                            const DevHitRec &R0 = recs[ml & bmask];
+                            p.tr = R0.fr;
+                            p.tg = R0.fg;
+                            p.tb = R0.fb;
+#pragma unroll 1
+                            for (int k = 1; k < p.depth - 1; ++k) {
+                                const DevHitRec &Rk = recs[(ml >> (k * hq_bits)) & bmask];
+                                p.tr *= Rk.fr;
+                                p.tg *= Rk.fg;
+                                p.tb *= Rk.fb;
+                            }
                         }
-                        ml |= (uint32_t)hit << ((p.depth - 1) * hq_bits);
+                        ml |= (uint32_t)hit << list_bits;
                         bounce_parked_hit<STATS, TYP>(P, p, set_p, i, hit, t, st, 6, frec_lds);
                     }
                     nhit -= take;
@@ -2301,18 +2320,18 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             if (cont) {
                 // (room: the queue held at most C - 64 hits when this pass's phase A ran, and a pass without it parks no more paths
                 // than it took from the queue)
-                uint32_t *e = pool + hitq_entry_dword(C, nhit + __builtin_amdgcn_mbcnt_hi((uint32_t)(pmask >> 32),
-                                                                                           __builtin_amdgcn_mbcnt_lo((uint32_t)pmask, 0u)));
-                e[0] = (uint32_t)(hit | (p.depth << 16));
-                e[1] = i;
-                e[2] = ml;
-                lds_dword_pair_store(e + 3, p.r.ox);
-                lds_dword_pair_store(e + 5, p.r.oy);
-                lds_dword_pair_store(e + 7, p.r.oz);
-                lds_dword_pair_store(e + 9, p.r.dx);
-                lds_dword_pair_store(e + 11, p.r.dy);
-                lds_dword_pair_store(e + 13, p.r.dz);
-                lds_dword_pair_store(e + 15, t);
+                uint32_t *e = hitq_entry(pool, C, nhit + __builtin_amdgcn_mbcnt_hi((uint32_t)(pmask >> 32),
+                                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)pmask, 0u)));
+                lds_dword_pair_store(e + kHitQOx, p.r.ox);
+                lds_dword_pair_store(e + kHitQOy, p.r.oy);
+                lds_dword_pair_store(e + kHitQOz, p.r.oz);
+                lds_dword_pair_store(e + kHitQDx, p.r.dx);
+                lds_dword_pair_store(e + kHitQDy, p.r.dy);
+                lds_dword_pair_store(e + kHitQDz, p.r.dz);
+                lds_dword_pair_store(e + kHitQT, t);
+                e[kHitQHitDepth] = (uint32_t)(hit | (p.depth << 16));
+                e[kHitQSample] = i;
+                e[kHitQList] = ml;
             }
             nhit += (uint32_t)__popcll(pmask);
         }
@@ -3371,10 +3390,13 @@ static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p,
     if (L.kernel == 2) {
         const int c = L.hq_cap, h = L.hq_th, bits = L.hq_bits;
         const bool hq = L.hq_cap > 0;
+        // (the throughput product table only where it is laid out for this plan's list entries)
+        RenderParams ps = p;
+        if (!hq || ps.tput_bits != bits) ps.tput = nullptr;
 #define FLUX_LAUNCH_SPLIT(MAX32, TYP, HQ)                                                                      \
     do {                                                                                                       \
-        if (stats) render_split_kernel<true, MAX32, TYP, HQ><<<g, b, lds, stream>>>(p, c, h, bits);            \
-        else render_split_kernel<false, MAX32, TYP, HQ><<<g, b, lds, stream>>>(p, c, h, bits);                 \
+        if (stats) render_split_kernel<true, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits);           \
+        else render_split_kernel<false, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits);                \
     } while (0)
 #if FLUX_DIEL
         if (L.typ || hq) return hipErrorInvalidValue;

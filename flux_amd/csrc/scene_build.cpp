@@ -292,6 +292,38 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     }
 }
 
+}  // namespace
+
+void build_tput_table(const HostScene &h, int bits, int max_depth, std::vector<double> &out) {
+    const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(h.fscene.data() + h.fs.rec);
+    const uint32_t n_rec = (uint32_t)hit_records(h.rp);
+    out.assign(((size_t)2 << (bits * (max_depth - 1))) * 3, 0.0);
+    // lists of one entry: the first bounce's weight as it stands ...
+    for (uint32_t e = 0; e < n_rec; e++) {
+        double *t = &out[(size_t)tput_index((uint32_t)bits, e) * 3];
+        t[0] = rec[e].fr; t[1] = rec[e].fg; t[2] = rec[e].fb;
+    }
+    // ... and a list of n entries: the product of its first n - 1, times its last one's weight (one IEEE multiplication per channel
+    // and bounce, front to back, as the kernel's loop).  Only lists of records the scene has are visited: n_rec^n of the 2^(n bits).
+    std::vector<uint32_t> heads(n_rec), lists;
+    for (uint32_t e = 0; e < n_rec; e++) heads[e] = e;
+    for (int n = 2; n < max_depth; n++) {
+        const uint32_t head_bits = (uint32_t)(bits * (n - 1));
+        lists.clear();
+        lists.reserve(heads.size() * n_rec);
+        for (uint32_t e = 0; e < n_rec; e++)
+            for (const uint32_t head : heads) {
+                const uint32_t ml = head | (e << head_bits);
+                const double *a = &out[(size_t)tput_index(head_bits, head) * 3];
+                double *t = &out[(size_t)tput_index(head_bits + (uint32_t)bits, ml) * 3];
+                t[0] = a[0] * rec[e].fr; t[1] = a[1] * rec[e].fg; t[2] = a[2] * rec[e].fb;
+                lists.push_back(ml);
+            }
+        heads.swap(lists);
+    }
+}
+
+namespace {
 // The extension's meshes: one triangle record per triangle (hit order: after all shapes), the binary BVH, its quantised nodes and the
 // 4-wide arena
 int build_meshes(const flux_scene_desc &scene, HostScene &h, std::string &error) {

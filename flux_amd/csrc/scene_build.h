@@ -58,4 +58,10 @@ struct HostScene {
 // for a context, or a mesh the BVH cannot hold).  Host allocation failures and thread creation throw.
 int build_host_scene(const flux_scene_desc &scene, HostScene &out, std::string &error);
 
+// The throughput product table (flux_plan.h tput_index, RenderParams::tput) of the scene's hit records for lists of `bits` bits per
+// entry and 1 .. max_depth - 1 entries: 2 << bits * (max_depth - 1) entries of (r, g, b).  Entry (n, ml) is
+// ((R[e0].f * R[e1].f) * ...) * R[e(n-1)].f per channel -- plain IEEE products in the order of the split kernel's loop, so bit for
+// bit its result; entries whose list names a record the scene does not have stay zero.
+void build_tput_table(const HostScene &h, int bits, int max_depth, std::vector<double> &out);
+
 }  // namespace flux
