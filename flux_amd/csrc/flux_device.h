@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "flux_bvh.h"
+#include "flux_env_verdict.h"
 
 // Numeric tunables of the data layout / launch mapping (the boolean either/ors of rounds 1-5 are folded into the code: render.hip).
 // The render path as shipped: hemi_sets as [S][D][N][4] (one aligned 32-B sector per sample); waves ordered by sample set, one set
@@ -278,6 +279,9 @@ struct RenderParams {
     // (the loop).  tput_bits: the bits per list entry it is laid out for; a launch whose plan has another hq_bits passes nullptr.
     int32_t tput_bits;
     const double *tput;
+    // split kernel: the environment sphere's side of the f32 verdict that stands in front of the shortcut (flux_env_verdict.h): its
+    // negated centre, p.p - r^2, p.p + r^2 and env_deep in f32, rounded once on the host (meaningful with env_short)
+    EnvSphere32 env32;
 };
 
 // hit records of a scene (DevHitRec): one per sphere, plane and disk, six per box

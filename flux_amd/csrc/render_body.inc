@@ -550,12 +550,38 @@ __device__ __forceinline__ void scan_boxes(const RenderParams &P, const Ray &r, 
     }
 }
 
+// Which side of a sphere a ray met, without the normal.  Emissive::path_shade's facing test is -n.d > 0 with n = (pt - c) inv_rad and
+// pt = o + t d: n.d = (hb + t) inv_rad along a unit d, and Sphere::hit's roots are t = -hb -+ e, e = sqrt(dq): n.d = -+e inv_rad.  So
+// the test's answer is "the near root was taken" XOR "inv_rad < 0" -- unless e is rounding noise.  What the shading step computes for
+// n.d differs from -+e inv_rad by the roundings of t (two operations and the square root's few ulp, of magnitudes below |o - c| + r),
+// of the three components of pt - c and of the dot product: under the self-skip rule's guards (|o|^2 < 0.999e6, centres and radii
+// below 1e3, hence t < 4e3) less than 20 x 1.1e-16 x 1e4 = 2.2e-11 |inv_rad|, plus t (|d|^2 - 1) < 4e3 x 4e-16.  The answer counts
+// as known for dq >= 1e-12, e >= 1e-6: five orders of magnitude above that.  (Compared on the high word, as an integer: dq >= 0 here.)
+constexpr int kFaceDqHi = 0x3d719799;                     // 1e-12 = 0x3d719799'812dea11: a high word above it
+constexpr float kFaceEnvFront = 1.8446744073709552e19f;   // 0x5f800000: known, the far root (an `invert` sphere: front)
+__device__ __forceinline__ float sphere_facing(double dq, bool near_root) {
+    const float hq = __int_as_float(__double2hiint(dq));
+    return near_root ? -hq : hq;
+}
+__device__ __forceinline__ bool facing_known(int facing) { return (facing & 0x7fffffff) > kFaceDqHi; }
+// (inv_rad_hi: the high word of the record's inv_rad)
+__device__ __forceinline__ bool facing_front(int facing, int inv_rad_hi) { return (facing ^ inv_rad_hi) < 0; }
+
 // FAST: nearest analytic shape (spheres, planes, disks, boxes) of Scene::hit.  `best` = winning HIT RECORD index
 // (scan order: spheres, then planes, then disks, then six face records per box) or -1; `tb` its distance.
-template <bool ENV_SHORT = false, bool LDS_SCENE = false, bool MAX32 = false, bool TYP = false, int ZF = -1>
+// FACING (the split kernel's phase B with its hit queue): `*facing` tells the shading step which side of the winner the ray met, so that
+// an Emissive hit's facing test needs no normal (sphere_facing above, shade_hit_fast).
+template <bool ENV_SHORT = false, bool LDS_SCENE = false, bool MAX32 = false, bool TYP = false, int ZF = -1, bool FACING = false>
 __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ray &r, int self, int &best, double &tb,
-                                                 long long *lap = nullptr, const char *fsph_lds = nullptr) {
+                                                 long long *lap = nullptr, const char *fsph_lds = nullptr, int *facing = nullptr) {
     (void)fsph_lds;  // LDS_SCENE (the split kernel): the block's LDS copy of the scan spheres for the per-lane gathers
+    (void)facing;
+    // FACING: the winner's discriminant dq / a as the high word of the double, with the sign bit set when Sphere::hit took the NEAR
+    // root -- kept as a float so that the sign is a source modifier of the select --, or 0 = unknown: a plane, a disk, a box face, a
+    // sphere decided by the exact code behind the candidate loop, and every winner of a pass outside the guards (ZF != 0; a scene
+    // without P.self_skip).  ZF == 0 and P.self_skip are the self-skip rule's guards: |o|^2 < 0.999e6, centres and radii below 1e3.
+    constexpr bool FACE = FACING && ZF == 0;
+    float face = 0.0f;
     // FAST scan over the compact records of flux_device.h (DevScanPlane / DevScanSphere): `best` is the
     // winning shape's HIT RECORD index (scan order: spheres, planes, disks, a box's six faces), `best_id` its YAML index.
     // Planes first (Plane::hit, shapes.rs:135-152): IEEE division keeps the reference's +-inf / NaN
@@ -639,6 +665,12 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
     float oof;
     const FilterRay32 F32 = filter_ray32_f(r.ox, r.oy, r.oz, ux, uy, uz, oof);
     const bool big = ZF == 0 ? false : !(oof < 1e30f);  // beyond f32's safe range (or NaN): every sphere stays a candidate for this lane
+    // The environment shortcut's f32 verdict (flux_env_verdict.h), ray side, from the filter's operands: three values for the code behind
+    // the candidate loop.  ZF == 0 only: no lane's origin is beyond |o|^2 < 0.999e6 and none has direction.z == 0.
+    constexpr bool ENV32 = ENV_SHORT && ZF == 0;
+    EnvRay32 E32 = EnvRay32{0.0f, 0.0f, 0.0f};
+    if (ENV32 && p_env_short && p_unit_dirs)
+        E32 = env_ray32(P.env32, F32.o2x2[0], F32.o2y2[0], F32.o2z2[0], F32.u_x[0], F32.u_y[0], F32.u_z[0], F32.ou2[0], oof);
     // `self` = the sphere this ray leaves outwards (shade_hit), or -1.  Its own quadratic has c = |o - p|^2 - r^2 within
     // rounding of 0 and hb >= 0, so its roots are <= sqrt(|c|): with every magnitude below 1e3 (scene: P.self_skip;
     // previous segment: shade_hit; this origin: here) |c| < 1e-8 and the reference's test fails t > T_MIN = 5e-4 --
@@ -710,6 +742,7 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
                 if (dq >= 0.0) {  // shapes.rs:181-183 (a NaN fails, as the reference's `t > T_MIN` on NaN)
                     const double e = fastmath::fsqrt_nonneg(dq);
                     double t = (-hb - e) * rs;             // shapes.rs:189
+                    const float face_k = sphere_facing(dq, t > tmin);
                     if (!(t > tmin)) t = (-hb + e) * rs;  // shapes.rs:201
                     if (t > tmin) {
                         // min_by + Hit::compare: smaller t wins; equal t keeps the lower YAML index.  Spheres come in
@@ -721,6 +754,7 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
                         if (take) {
                             best = base + k;
                             tb = t;
+                            if (FACE) face = face_k;
                         }
                     }
                 }
@@ -738,6 +772,24 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
         for (int j = 0; j < p_n_uni; ++j) {
             FLUX_CENSUS(P, 5);
             const int k = P.uni_idx[j];
+            if (ENV32 && p_env_short && p_unit_dirs) {
+                // The shortcut below, decided in f32 first: per lane "the environment wins", "loses" or "undecided", each from the sign
+                // of |o + tb u - p|^2 - r^2 with a margin that covers the f32 roundings and the f64 shortcut's own "too close to call"
+                // band (flux_env_verdict.h).  A wave without an undecided lane takes the verdicts -- they are the f64 shortcut's for
+                // every lane, and it would have passed its vote -- for one conversion and four f32 operations in place of 16 f64
+                // operations and 5 f64 compares; any other wave runs the code below as it stands.  (The votes as lane masks of the
+                // compares, as below.  A NaN fails every compare: undecided.)
+                float g_lo, g_hi;
+                env_g32(E32, (float)tb, g_lo, g_hi);
+                if ((ballot64(!(E32.cp < P.env32.deep)) | (ballot64(best >= 0) & ballot64(!(g_lo > 0.0f)) & ballot64(!(g_hi < 0.0f)))) == 0ull) {
+                    if (best < 0 || g_lo > 0.0f) {
+                        best = k;
+                        tb = 2.0 * P.env_radius;
+                        if (FACE) face = kFaceEnvFront;
+                    }
+                    continue;
+                }
+            }
             // (TYP: the one such sphere's record is in the kernel arguments)
             const DevScanSphere S = TYP ? DevScanSphere{P.env_px, P.env_py, P.env_pz, P.env_rr} : P.fsph[k];
             const double tx = r.ox - S.px, ty = r.oy - S.py, tz = r.oz - S.pz;
@@ -765,6 +817,7 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
                     if (best < 0 || (s > 0.0 && dq < s2)) {
                         best = k;
                         tb = 2.0 * P.env_radius;  // >= -hb + e for an origin inside: |hb| <= |o - p| < r and e <= r (a wave-uniform value: no per-lane arithmetic)
+                        if (FACE) face = kFaceEnvFront;  // the far root of an `invert` sphere: the facing test holds (above)
                     }
                     continue;
                 }
@@ -782,10 +835,12 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
                 if (take) {
                     best = k;
                     tb = t;
+                    if (FACE) face = 0.0f;
                 }
             }
         }
     }
+    if (FACING) *facing = (FACE && (TYP || P.self_skip != 0)) ? __float_as_int(face) : 0;
 }
 #endif
 
@@ -1287,10 +1342,13 @@ __device__ __forceinline__ int analytic_hit_fields(const RenderParams &P, const 
 // keeps the compiler from threading `bounce` back into phase 1 (it is 1 on exactly one way into the join).
 // BOUNCE = false (the split kernel's phase B with its hit queue): phase 1 only -- the hit is classified, a continuing path's state is
 // left as it was and its bounce runs later from the parked hit (bounce_parked_hit).
-template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false, bool BOUNCE = true>
+// FACING (with BOUNCE = false): `facing` is the scan's word on which side of the winner the ray met (scan_shapes_fast, sphere_facing).
+template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false, bool BOUNCE = true, bool FACING = false>
 __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, int slot, double t,
-                                               double &Lr, double &Lg, double &Lb, Stats &st, int cz, const char *frec_lds = nullptr) {
+                                               double &Lr, double &Lg, double &Lb, Stats &st, int cz, const char *frec_lds = nullptr,
+                                               int facing = 0) {
     (void)frec_lds;  // LDS_SCENE: the block's LDS copy of the hit records
+    (void)facing;
     (void)cz;  // census builds: section offset of the caller (split kernel: 0 = phase B, 3 = phase A)
     int bounce = 0;
     const bool is_tri = TRIS && slot >= 0;
@@ -1323,7 +1381,17 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
         }
         if (kind == kMatEmissive) {  // materials.rs:41-50
             if (STATS) st.c[5]++;
-            const bool front = ((n.x * -1.0) * d.x + (n.y * -1.0) * d.y + (n.z * -1.0) * d.z) > 0.0;
+            bool front;
+            // FACING: the normal has no other consumer here, so where the scan knows the side of every Emissive hit of the wave the
+            // test is two integer operations on the record's inv_rad -- no record reads for the centre, no point, no normal, no dot
+            // product.  One vote; a wave with an Emissive lane the scan does not vouch for (a plane, a disk, a grazing hit, a pass
+            // outside the guards) computes the test for all of them as ever.
+            if (FACING && ballot64(!facing_known(facing)) == 0ull) {
+                const DevHitRec &R = *reinterpret_cast<const DevHitRec *>(frec_lds + (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
+                front = facing_front(facing, reinterpret_cast<const int *>(&R.inv_rad)[1]);
+            } else {
+                front = ((n.x * -1.0) * d.x + (n.y * -1.0) * d.y + (n.z * -1.0) * d.z) > 0.0;
+            }
             Lr = fr;
             Lg = fg;
             Lb = fb;
@@ -2303,11 +2371,12 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 if (STATS) st.c[1]++;
                 const float ofx = (float)p.r.ox, ofy = (float)p.r.oy, ofz = (float)p.r.oz;
                 const float oo32 = __builtin_fmaf(ofz, ofz, __builtin_fmaf(ofy, ofy, ofx * ofx));
+                int facing;
                 if (__builtin_expect((ballot64(p.r.dz == 0.0) | ballot64(!(oo32 < 0.999e6f))) != 0ull, 0))
-                    scan_shapes_fast<true, true, MAX32, TYP, 1>(P, p.r, p.self, hit, t, nullptr, fsph_lds);
+                    scan_shapes_fast<true, true, MAX32, TYP, 1, true>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
                 else
-                    scan_shapes_fast<true, true, MAX32, TYP, 0>(P, p.r, p.self, hit, t, nullptr, fsph_lds);
-                cont = shade_hit_fast<STATS, false, true, TYP, false, false>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds);
+                    scan_shapes_fast<true, true, MAX32, TYP, 0, true>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
+                cont = shade_hit_fast<STATS, false, true, TYP, false, false, true>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds, facing);
             }
             if (live && !cont) {
                 if (STATS && !trace) st.c[7]++;

@@ -274,6 +274,7 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     if (rp.n_uni == 1) {
         const DevScanSphere &es = fsph[rp.uni_idx[0]];
         rp.env_px = es.px; rp.env_py = es.py; rp.env_pz = es.pz; rp.env_rr = es.rr;
+        rp.env32 = env_sphere32(es.px, es.py, es.pz, es.rr, rp.env_deep);  // ... and in f32, for the verdict in front of the shortcut
     }
     // the filter's group walk for at most 32 spheres (render_body.inc sphere_filter32: the same arithmetic, done once), as pair
     // indices into fsph32 that the upload turns into pointers
