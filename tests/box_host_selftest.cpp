@@ -6,44 +6,12 @@
 // Prints "shape <i> <fields>" for every flux_shape of scenes/box_room.yml (compared with the Python loader by the test), one
 // "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <fstream>
-#include <sstream>
 #include <string>
 
 #include "../flux_amd/csrc/flux_plan.h"
 #include "../flux_amd/csrc/scene_build.h"
-#include "../flux_amd/host/flux_host.hpp"
-#include "../flux_amd/host/flux_net.hpp"
-
-using namespace flux_host;
-
-#define CHECK(c)                                                            \
-    do {                                                                    \
-        if (!(c)) {                                                         \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c);      \
-            return 1;                                                       \
-        }                                                                   \
-    } while (0)
-
-static bool throws(const std::string &text, const std::string &needle) {
-    try {
-        scene_from_yaml_text(text);
-    } catch (const FluxError &e) {
-        if (std::string(e.what()).find(needle) != std::string::npos && e.code == FLUX_E_INVALID) return true;
-        std::printf("message: %s\n", e.what());
-    }
-    return false;
-}
-
-static bool same_vec(const Vec3 &a, const Vec3 &b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
-
-static std::string replaced(std::string text, const std::string &what, const std::string &with) {
-    const size_t at = text.find(what);
-    if (at == std::string::npos) return "";
-    return text.replace(at, what.size(), with);
-}
+#include "host_selftest.hpp"
 
 int main(int argc, char **argv) {
     if (argc < 2) {
@@ -62,20 +30,11 @@ int main(int argc, char **argv) {
     {
         CHECK(abi.desc.num_shapes == 5 && abi.shapes[0].kind == FLUX_SHAPE_BOX && FLUX_SHAPE_BOX == 3 && abi.shapes[0].invert == 1);
         CHECK(abi.shapes[2].kind == FLUX_SHAPE_BOX && abi.shapes[2].invert == 0 && abi.shapes[2].p[0] == -5.0 && abi.shapes[2].n[2] == 4.5);
-        for (size_t i = 0; i < abi.shapes.size(); i++) {
-            const flux_shape &s = abi.shapes[i];
-            std::printf("shape %zu %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", i,
-                        s.kind, s.invert, s.p[0], s.p[1], s.p[2], s.n[0], s.n[1], s.n[2], s.radius, s.material.kind, s.material.color[0],
-                        s.material.color[1], s.material.color[2], s.material.ambient[0], s.material.ambient[1], s.material.ambient[2],
-                        s.material.k, s.material.exponent);
-        }
+        print_flux_shapes(abi);
         std::printf("ok abi scene\n");
     }
     {   // the loader's corner checks: the field's path in every message
-        std::ifstream f(path);
-        std::stringstream ss;
-        ss << f.rdbuf();
-        const std::string good = ss.str();
+        const std::string good = read_file(path);
         const std::string c0 = "      corner0: [-5.0, 0.0, 1.0]\n", c1 = "      corner1: [-1.5, 2.0, 4.5]\n";
         CHECK(good.find(c0) != std::string::npos && good.find(c1) != std::string::npos);
         CHECK(throws(replaced(good, c0, ""), "shapes[2].Box: missing field `corner0`"));
@@ -98,28 +57,15 @@ int main(int argc, char **argv) {
         std::printf("ok yaml corners\n");
     }
     {   // CBOR: SetJob with the box scene, decoded back field for field and re-encoded to the same bytes
-        NetworkWorkerRequest req;
-        req.kind = NetworkWorkerRequest::SetJob;
-        req.job.scene_data = sd;
-        req.job.config = JobConfiguration{3, 5, 50};
-        cbor::Encoder e;
-        encode_request(e, req);
-        const std::string raw = e.out;
-        CHECK(raw.find("Box") != std::string::npos && raw.find("corner1") != std::string::npos);
-        cbor::StringReader r(raw);
-        cbor::Decoder d(r);
+        std::string raw;
         NetworkWorkerRequest back;
-        CHECK(decode_request(d, back));
-        CHECK(back.kind == NetworkWorkerRequest::SetJob);
-        CHECK(back.job.scene_data.shapes.size() == sd.shapes.size());
-        for (size_t i = 0; i < sd.shapes.size(); i++) CHECK(back.job.scene_data.shapes[i].index() == sd.shapes[i].index());
+        if (set_job_round_trip(sd, raw, back)) return 1;
+        CHECK(raw.find("Box") != std::string::npos && raw.find("corner1") != std::string::npos);
         const BoxData *b = std::get_if<BoxData>(&back.job.scene_data.shapes[0]);
         CHECK(b != nullptr && same_vec(b->corner0, room->corner0) && same_vec(b->corner1, room->corner1) && b->invert);
         const BoxData *g = std::get_if<BoxData>(&back.job.scene_data.shapes[3]);
         CHECK(g != nullptr && !g->invert && std::holds_alternative<GlossyReflectiveData>(g->material));
-        cbor::Encoder e2;
-        encode_request(e2, back);
-        CHECK(e2.out == raw);
+        NetworkWorkerRequest req = back;  // the same scene: it re-encoded to the same bytes
         req.job.scene_data.shapes.push_back(BoxData{Vec3{0.1, -2.5, -1e300}, Vec3{1.0 / 3.0, 0, 1e300}, EmissiveData{Color{1, 2, 3}, 0.5}, true});
         cbor::Encoder e3;
         encode_request(e3, req);

@@ -5,34 +5,10 @@
 // Prints "shape <i> <fields>" for every flux_shape of scenes/glass.yml (compared with the Python loader by the test), one
 // "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <fstream>
-#include <sstream>
 #include <string>
 
-#include "../flux_amd/host/flux_host.hpp"
-#include "../flux_amd/host/flux_net.hpp"
-
-using namespace flux_host;
-
-#define CHECK(c)                                                            \
-    do {                                                                    \
-        if (!(c)) {                                                         \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c);      \
-            return 1;                                                       \
-        }                                                                   \
-    } while (0)
-
-static bool throws(const std::string &text, const std::string &needle) {
-    try {
-        scene_from_yaml_text(text);
-    } catch (const FluxError &e) {
-        if (std::string(e.what()).find(needle) != std::string::npos && e.code == FLUX_E_INVALID) return true;
-        std::printf("message: %s\n", e.what());
-    }
-    return false;
-}
+#include "host_selftest.hpp"
 
 static const MaterialData &material_of(const ShapeData &s) {
     if (auto *p = std::get_if<SphereData>(&s)) return p->material;
@@ -58,20 +34,11 @@ int main(int argc, char **argv) {
         const AbiScene abi(sd);
         CHECK(abi.desc.num_shapes == 13 && abi.shapes[3].material.kind == FLUX_MAT_DIELECTRIC && FLUX_MAT_DIELECTRIC == 4);
         CHECK(abi.shapes[5].material.k == 1.33 && abi.shapes[5].material.color[1] == 0.95);
-        for (size_t i = 0; i < abi.shapes.size(); i++) {
-            const flux_shape &s = abi.shapes[i];
-            std::printf("shape %zu %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", i,
-                        s.kind, s.invert, s.p[0], s.p[1], s.p[2], s.n[0], s.n[1], s.n[2], s.radius, s.material.kind, s.material.color[0],
-                        s.material.color[1], s.material.color[2], s.material.ambient[0], s.material.ambient[1], s.material.ambient[2],
-                        s.material.k, s.material.exponent);
-        }
+        print_flux_shapes(abi);
         std::printf("ok abi scene\n");
     }
     {   // the loader's refraction-index checks: the field's path in every message
-        std::ifstream f(path);
-        std::stringstream ss;
-        ss << f.rdbuf();
-        const std::string good = ss.str();
+        const std::string good = read_file(path);
         const std::string line = "    refraction_index: 1.5\n";
         const size_t at = good.find(line);
         CHECK(at != std::string::npos);
@@ -99,29 +66,15 @@ int main(int argc, char **argv) {
         std::printf("ok yaml refraction index\n");
     }
     {   // CBOR: SetJob with the glass scene, decoded back field for field and re-encoded to the same bytes
-        NetworkWorkerRequest req;
-        req.kind = NetworkWorkerRequest::SetJob;
-        req.job.scene_data = sd;
-        req.job.config = JobConfiguration{3, 5, 50};
-        cbor::Encoder e;
-        encode_request(e, req);
-        const std::string raw = e.out;
-        CHECK(raw.find("Dielectric") != std::string::npos);
-        cbor::StringReader r(raw);
-        cbor::Decoder d(r);
+        std::string raw;
         NetworkWorkerRequest back;
-        CHECK(decode_request(d, back));
-        CHECK(back.kind == NetworkWorkerRequest::SetJob);
-        CHECK(back.job.scene_data.shapes.size() == sd.shapes.size());
-        for (size_t i = 0; i < sd.shapes.size(); i++) {
-            CHECK(back.job.scene_data.shapes[i].index() == sd.shapes[i].index());
+        if (set_job_round_trip(sd, raw, back)) return 1;
+        CHECK(raw.find("Dielectric") != std::string::npos);
+        for (size_t i = 0; i < sd.shapes.size(); i++)
             CHECK(material_of(back.job.scene_data.shapes[i]).index() == material_of(sd.shapes[i]).index());
-        }
         const DielectricData *b = std::get_if<DielectricData>(&material_of(back.job.scene_data.shapes[5]));
         CHECK(b && b->refraction_index == 1.33 && b->transmit_color.r == 0.8 && b->transmit_color.g == 0.95 && b->transmit_color.b == 1.0);
-        cbor::Encoder e2;
-        encode_request(e2, back);
-        CHECK(e2.out == raw);
+        NetworkWorkerRequest req = back;  // the same scene: it re-encoded to the same bytes
         // odd values on a plane and a disk survive too (shortest exact float encodings)
         req.job.scene_data.shapes.push_back(PlaneData{Vec3{0, -3, 0}, Vec3{0, 1, 0}, DielectricData{1.0 / 3.0, Color{0.1, 1e-300, 2.5}}});
         req.job.scene_data.shapes.push_back(DiskData{Vec3{1, 2, 3}, Vec3{0, 0, -1}, 0.5, DielectricData{2.4175, Color{1, 1, 1}}});

@@ -5,36 +5,10 @@
 // Prints "shape <i> <fields>" for every flux_shape of scenes/disk_light.yml (compared with the Python loader by the test), one
 // "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <fstream>
-#include <sstream>
 #include <string>
 
-#include "../flux_amd/host/flux_host.hpp"
-#include "../flux_amd/host/flux_net.hpp"
-
-using namespace flux_host;
-
-#define CHECK(c)                                                            \
-    do {                                                                    \
-        if (!(c)) {                                                         \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c);      \
-            return 1;                                                       \
-        }                                                                   \
-    } while (0)
-
-static bool throws(const std::string &text, const std::string &needle) {
-    try {
-        scene_from_yaml_text(text);
-    } catch (const FluxError &e) {
-        if (std::string(e.what()).find(needle) != std::string::npos && e.code == FLUX_E_INVALID) return true;
-        std::printf("message: %s\n", e.what());
-    }
-    return false;
-}
-
-static bool same_vec(const Vec3 &a, const Vec3 &b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
+#include "host_selftest.hpp"
 
 int main(int argc, char **argv) {
     if (argc < 2) {
@@ -50,20 +24,11 @@ int main(int argc, char **argv) {
     {
         const AbiScene abi(sd);
         CHECK(abi.desc.num_shapes == 13 && abi.shapes[1].kind == FLUX_SHAPE_DISK && FLUX_SHAPE_DISK == 2);
-        for (size_t i = 0; i < abi.shapes.size(); i++) {
-            const flux_shape &s = abi.shapes[i];
-            std::printf("shape %zu %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", i,
-                        s.kind, s.invert, s.p[0], s.p[1], s.p[2], s.n[0], s.n[1], s.n[2], s.radius, s.material.kind, s.material.color[0],
-                        s.material.color[1], s.material.color[2], s.material.ambient[0], s.material.ambient[1], s.material.ambient[2],
-                        s.material.k, s.material.exponent);
-        }
+        print_flux_shapes(abi);
         std::printf("ok abi scene\n");
     }
     {   // the loader's radius checks: the field's path in every message
-        std::ifstream f(path);
-        std::stringstream ss;
-        ss << f.rdbuf();
-        const std::string good = ss.str();
+        const std::string good = read_file(path);
         CHECK(good.find("      radius: 5.0\n      material:\n        Emissive:\n          color: [1, 0.9686, 0.8588]\n          power: 10.0") !=
               std::string::npos);
         const size_t at = good.find("      radius: 5.0\n      material:\n        Emissive:\n          color: [1, 0.9686, 0.8588]\n          power: 10.0");
@@ -86,29 +51,16 @@ int main(int argc, char **argv) {
         std::printf("ok yaml radius\n");
     }
     {   // CBOR: SetJob with the disk scene, decoded back field for field and re-encoded to the same bytes
-        NetworkWorkerRequest req;
-        req.kind = NetworkWorkerRequest::SetJob;
-        req.job.scene_data = sd;
-        req.job.config = JobConfiguration{3, 5, 50};
-        cbor::Encoder e;
-        encode_request(e, req);
-        const std::string raw = e.out;
-        CHECK(raw.find("Disk") != std::string::npos);
-        cbor::StringReader r(raw);
-        cbor::Decoder d(r);
+        std::string raw;
         NetworkWorkerRequest back;
-        CHECK(decode_request(d, back));
-        CHECK(back.kind == NetworkWorkerRequest::SetJob);
-        CHECK(back.job.scene_data.shapes.size() == sd.shapes.size());
-        for (size_t i = 0; i < sd.shapes.size(); i++) CHECK(back.job.scene_data.shapes[i].index() == sd.shapes[i].index());
+        if (set_job_round_trip(sd, raw, back)) return 1;
+        CHECK(raw.find("Disk") != std::string::npos);
         const DiskData *b = std::get_if<DiskData>(&back.job.scene_data.shapes[1]);
         CHECK(b != nullptr);
         CHECK(same_vec(b->center, disk->center) && same_vec(b->normal, disk->normal) && b->radius == disk->radius);
         const EmissiveData *em = std::get_if<EmissiveData>(&b->material);
         CHECK(em != nullptr && em->power == 10.0 && em->color.g == 0.9686);
-        cbor::Encoder e2;
-        encode_request(e2, back);
-        CHECK(e2.out == raw);
+        NetworkWorkerRequest req = back;  // the same scene: it re-encoded to the same bytes
         // a disk of radius 0 and an odd radius survive too (shortest exact float encodings)
         req.job.scene_data.shapes[1] = DiskData{Vec3{0.1, -2.5, 1e300}, Vec3{0, 0, 0}, 0.0, EmissiveData{Color{1, 2, 3}, 0.5}};
         req.job.scene_data.shapes.push_back(DiskData{Vec3{1, 2, 3}, Vec3{0.3, -0.7, 1.1}, 1.0 / 3.0, MatteData{}});

@@ -15,37 +15,22 @@ import yaml
 
 import box_spec
 from conftest import ROOT, SCENES
+from extension_checks import build_host_selftest, cpp_shapes, run_host_selftest, shape_fields
 
 BOX_SCENE = os.path.join(SCENES, "box_room.yml")
-
-
-def _fields(s):
-    m = s.material
-    return [s.kind, s.invert, *s.p, *s.n, s.radius, m.kind, *m.color, *m.ambient, m.k, m.exponent]
 
 
 def _build_selftest(exe, extra=()):
     """tests/box_host_selftest.cpp against the C++ host layer and the host scene build (CPU only: no compute call).  Host-only
     clang, as for tests/scene_build_selftest.cpp: plain g++ cannot compile flux_device.h's ext_vector_type records."""
-    from flux_amd import build
-    build.build_hip()
-    host = os.path.join(ROOT, "flux_amd", "host")
-    csrc = os.path.join(ROOT, "flux_amd", "csrc")
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                    "-pthread", "-Wall", *extra, "-o", exe, os.path.join(ROOT, "tests", "box_host_selftest.cpp"),
-                    os.path.join(csrc, "scene_build.cpp"), os.path.join(csrc, "bvh.cpp"), os.path.join(csrc, "launch_plan.cpp")] +
-                   [os.path.join(host, s) for s in build.HOST_SOURCES] +
-                   ["-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"),
-                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
+    csrc = [os.path.join(ROOT, "flux_amd", "csrc", s) for s in ("scene_build.cpp", "bvh.cpp", "launch_plan.cpp")]
+    return build_host_selftest("box", exe, "/opt/rocm/llvm/bin/clang++", csrc,
+                               ("-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", *extra))
 
 
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
-    exe = _build_selftest(str(tmp_path_factory.mktemp("box") / "box_host_selftest"))
-    out = subprocess.run([exe, SCENES], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    return run_host_selftest(_build_selftest(str(tmp_path_factory.mktemp("box") / "box_host_selftest")))
 
 
 def test_cpp_selftest(selftest):
@@ -76,14 +61,10 @@ def test_both_loaders_give_the_same_flux_shapes(flux, selftest):
     assert isinstance(sd.shapes[2].material, flux.MatteData) and isinstance(sd.shapes[3].material, flux.GlossyReflectiveData)
     desc = SceneDesc(sd)
     assert desc.desc.num_shapes == 5 and desc.shapes[0].kind == flux._lib.SHAPE_BOX and desc.shapes[0].invert == 1
-    cpp = {}
-    for line in selftest.splitlines():
-        if line.startswith("shape "):
-            tok = line.split()
-            cpp[int(tok[1])] = [int(tok[2]), int(tok[3])] + [float(x) for x in tok[4:11]] + [int(tok[11])] + [float(x) for x in tok[12:]]
+    cpp = cpp_shapes(selftest)
     assert sorted(cpp) == list(range(5))
     for i in range(5):
-        py = _fields(desc.shapes[i])
+        py = shape_fields(desc.shapes[i])
         assert py == cpp[i], (i, py, cpp[i])  # %.17g round-trips every double exactly
 
 

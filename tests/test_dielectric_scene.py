@@ -6,37 +6,22 @@ import copy
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import yaml
 
 from conftest import ROOT, SCENES
+from extension_checks import build_host_selftest, cpp_shapes, run_host_selftest, shape_fields
 from dielectric_spec import bounce, fresnel, fresnel_cos
 
 GLASS_SCENE = os.path.join(SCENES, "glass.yml")
 
 
-def _fields(s):
-    m = s.material
-    return [s.kind, s.invert, *s.p, *s.n, s.radius, m.kind, *m.color, *m.ambient, m.k, m.exponent]
-
-
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
     """tests/dielectric_host_selftest.cpp built against the C++ host layer (CPU only: no compute call)."""
-    from flux_amd import build
-    build.build_hip()
-    exe = str(tmp_path_factory.mktemp("dielectric") / "dielectric_host_selftest")
-    host = os.path.join(ROOT, "flux_amd", "host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "dielectric_host_selftest.cpp")] +
-                   [os.path.join(host, s) for s in build.HOST_SOURCES] +
-                   ["-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"),
-                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    out = subprocess.run([exe, SCENES], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    return run_host_selftest(build_host_selftest("dielectric", str(tmp_path_factory.mktemp("dielectric") / "dielectric_host_selftest")))
 
 
 def test_cpp_selftest(selftest):
@@ -52,14 +37,10 @@ def test_both_loaders_give_the_same_flux_shapes(flux, selftest):
     assert desc.desc.num_shapes == 13
     assert [i for i in range(13) if desc.shapes[i].material.kind == flux._lib.MAT_DIELECTRIC] == [3, 5, 7]
     assert desc.shapes[5].material.k == 1.33 and tuple(desc.shapes[5].material.color) == (0.8, 0.95, 1.0)
-    cpp = {}
-    for line in selftest.splitlines():
-        if line.startswith("shape "):
-            tok = line.split()
-            cpp[int(tok[1])] = [int(tok[2]), int(tok[3])] + [float(x) for x in tok[4:11]] + [int(tok[11])] + [float(x) for x in tok[12:]]
+    cpp = cpp_shapes(selftest)
     assert sorted(cpp) == list(range(13))
     for i in range(13):
-        py = _fields(desc.shapes[i])
+        py = shape_fields(desc.shapes[i])
         assert py == cpp[i], (i, py, cpp[i])  # %.17g round-trips every double exactly
 
 

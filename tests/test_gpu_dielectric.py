@@ -10,40 +10,22 @@ closed forms and agreement between kernels:
 """
 import copy
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, SCENES, small_scene
+from conftest import SCENES, small_scene
 from dielectric_spec import bounce, fresnel_cos
+from extension_checks import cli_frame, host_bins, loopback_frames, math_mode, render, row_tiles, set_sharded_frame, small_yaml
 
 pytestmark = pytest.mark.gpu
 
 T_MIN = 0.0005
 
 
-def _mode(flux, name):
-    return flux.MATH_FAST if name == "fast" else flux.MATH_STRICT
-
-
 def _glass(small=(64, 48)):
     import flux_amd as flux
     return small_scene(flux.load_scene(os.path.join(SCENES, "glass.yml")), *small)
-
-
-def _render(flux, sd, n, math_mode, kernel=None, traversal=None, seed=1, depth=5):
-    with flux.Renderer(sd, flux.JobConfiguration(n, depth, 50), seed=seed) as r:
-        r.set_math(math_mode)
-        if kernel is not None:
-            r.set_kernel(kernel)
-        if traversal is not None:
-            r.set_traversal(traversal)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan()
 
 
 # ---- 1. rays against the spec --------------------------------------------------------------------------------------
@@ -202,7 +184,7 @@ def test_random_rays_against_the_spec(flux, kind, math_name):
     o, d = _rays(rng, tg, per * batches)
     total = {"rays": 0, "excluded": 0, "reflect": 0, "transmit": 0, "multi": 0}
     with flux.Renderer(sd, flux.JobConfiguration(8, DEPTH, 50), seed=3) as r:
-        r.set_math(_mode(flux, math_name))
+        r.set_math(math_mode(flux, math_name))
         hemi = r.table(flux._lib.TABLE_HEMI)  # [set][depth][sample][xyz]
         u1 = hemi[0, 0, :, 2]
         # the samples whose first u spreads over (0, 0.7): both branches at every angle band
@@ -244,7 +226,7 @@ def test_inside_a_sphere_total_internal_reflection(flux):
     d = np.column_stack([-np.sin(phi), 0.02 * np.cos(phi), np.cos(phi)])
     for m in ("fast", "strict"):
         with flux.Renderer(sd, flux.JobConfiguration(2, DEPTH, 50), seed=3) as r:
-            r.set_math(_mode(flux, m))
+            r.set_math(math_mode(flux, m))
             rgb, hit, _ = r.debug_shade(o, d, 1, 0, 0)
         assert np.all(hit == 0) and np.all(rgb == 0.0), m  # lost to the depth limit: never escaped
         want, nb, _ = _trace(tg, o, d, np.ones(DEPTH), RI)
@@ -278,7 +260,7 @@ def test_fresnel_closed_form(flux, math_name):
     W, ps, root = 32, 2.0, 8
     n = root * root
     with flux.Renderer(_fresnel_scene(flux, 1.0, W, ps), flux.JobConfiguration(root, 3, 50), seed=5) as r:
-        r.set_math(_mode(flux, math_name))
+        r.set_math(math_mode(flux, math_name))
         r.enable_stats(True)
         r.stats(reset=True)
         img = r.render_frame()
@@ -301,7 +283,7 @@ def test_fresnel_closed_form(flux, math_name):
     assert 0.05 < st["dielectric_reflections"] / (W * W * n) < 0.6
     # flipped: the camera is on the glass side; beyond the critical angle every sample reflects totally
     with flux.Renderer(_fresnel_scene(flux, -1.0, W, ps), flux.JobConfiguration(root, 3, 50), seed=5) as r:
-        r.set_math(_mode(flux, math_name))
+        r.set_math(math_mode(flux, math_name))
         r.enable_stats(True)
         img2 = r.render_frame()
         st2 = r.stats()
@@ -348,7 +330,7 @@ def test_white_furnace(flux, math_name):
     W, root = 48, 8
     n = root * root
     depth = 32 if math_name == "fast" else 24
-    img, st, plan = _render(flux, _furnace(flux, W), root, _mode(flux, math_name), depth=depth)
+    img, st, plan = render(flux, _furnace(flux, W), root, math_mode(flux, math_name), depth=depth)
     assert img.max() <= 1.0 + 1e-12
     lit = np.round(img[:, :, 0] * n)
     assert np.all(img[:, :, 0] == img[:, :, 1]) and np.all(img[:, :, 0] == img[:, :, 2])
@@ -369,9 +351,9 @@ def _glass_mesh(flux):
 @pytest.mark.parametrize("math_name", ["fast", "strict"])
 def test_static_refill_split_agree(flux, demo2, monkeypatch, math_name):
     sd = _glass()
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     n = 16
-    base, sbase, _ = _render(flux, sd, n, m, flux.KERNEL_STATIC)
+    base, sbase, _ = render(flux, sd, n, m, flux.KERNEL_STATIC)
     assert sbase["dielectric_reflections"] > 0 and sbase["dielectric_transmissions"] > 0
     for kernel in (flux.KERNEL_REFILL, flux.KERNEL_SPLIT):
         for cap in (None, "0", "96"):
@@ -379,7 +361,7 @@ def test_static_refill_split_agree(flux, demo2, monkeypatch, math_name):
                 monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
             else:
                 monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", cap)
-            img, st, plan = _render(flux, sd, n, m, kernel)
+            img, st, plan = render(flux, sd, n, m, kernel)
             assert st == sbase, (kernel, cap, st, sbase)
             assert np.abs(img - base).max() <= 1e-12, (kernel, cap)
     monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
@@ -405,13 +387,13 @@ def test_static_refill_split_agree(flux, demo2, monkeypatch, math_name):
 @pytest.mark.parametrize("math_name", ["fast", "strict"])
 def test_bvh_kernels_agree(flux, math_name):
     sd = _glass_mesh(flux)
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     n = 8
-    base, sbase, pbase = _render(flux, sd, n, m, traversal=flux._lib.TRAVERSE_BRUTE)
+    base, sbase, pbase = render(flux, sd, n, m, traversal=flux._lib.TRAVERSE_BRUTE)
     assert sbase["dielectric_transmissions"] > 0
     plans = set()
     for traversal in (flux._lib.TRAVERSE_BVH, flux._lib.TRAVERSE_BVH_BINARY):
-        img, st, plan = _render(flux, sd, n, m, traversal=traversal)
+        img, st, plan = render(flux, sd, n, m, traversal=traversal)
         plans.add(plan["kernel"])
         keys = [k for k in st if k not in ("bvh_nodes", "tris_tested")]
         assert {k: st[k] for k in keys} == {k: sbase[k] for k in keys}, traversal
@@ -423,8 +405,8 @@ def test_bvh_kernels_agree(flux, math_name):
 @pytest.mark.parametrize("mesh", [False, True])
 def test_fast_against_strict(flux, mesh):
     sd = _glass_mesh(flux) if mesh else _glass()
-    a, sa, _ = _render(flux, sd, 8, flux.MATH_FAST)
-    b, sb, _ = _render(flux, sd, 8, flux.MATH_STRICT)
+    a, sa, _ = render(flux, sd, 8, flux.MATH_FAST)
+    b, sb, _ = render(flux, sd, 8, flux.MATH_STRICT)
     assert np.abs(a - b).max() < 1e-4
     for k in ("dielectric_reflections", "dielectric_transmissions", "emissive_hits", "misses"):
         assert abs(sa[k] - sb[k]) <= 1e-5 * sa["samples"], k
@@ -433,34 +415,15 @@ def test_fast_against_strict(flux, mesh):
 # ---- 5. shares and loopback ranks ------------------------------------------------------------------------------------
 
 def test_set_shares_row_tiles_and_loopback_ranks(flux):
-    import torch
-    from flux_amd.dist import SetSharder, hip_render_sets_fn
     sd = _glass((50, 37))
     cfg = flux.JobConfiguration(8, 5, 50)
     with flux.Renderer(sd, cfg, seed=11) as r:
         want = r.render_frame()
-        # row tiles, reassembled
-        tiles = [r.render_rows(a, min(a + 9, r.height) - 1) for a in range(0, r.height, 9)]
-        assert np.array_equal(np.concatenate(tiles, axis=0), want)
-        dev = torch.device("cuda", 0)
-        rowperm = torch.from_numpy(r.row_perm_table())
-        fn = hip_render_sets_fn(r)
+        assert np.array_equal(row_tiles(r, 9), want)
         for world in (1, 2, 3):
-            shards = []
-            for rank in range(world):
-                sh = SetSharder(r.height, r.width, rank, world, dev, rowperm)
-                sh.render(fn)
-                torch.cuda.synchronize()
-                if sh.local is not sh.render_buf:
-                    sh.local[:, : sh.count] = sh.render_buf
-                shards.append(sh)
-            s0 = shards[0]
-            got = s0.assemble().cpu() if world == 1 else torch.stack([s.local for s in shards])[s0._g, s0._r, s0._m].cpu()
-            assert np.array_equal(got.numpy(), want), world
-    for G in (2,):
-        mode = flux.SHARD_SETS | flux._lib.SHARD_LOOPBACK
-        with flux.MultiRenderer(sd, cfg, seed=11, devices=[0] * G, shard=mode) as m:
-            assert np.array_equal(m.render_frame(), want), G
+            assert np.array_equal(set_sharded_frame(flux, r, world).numpy(), want), world
+    for G, _, frame in loopback_frames(flux, sd, cfg, 11, (2,), (flux.SHARD_SETS,)):
+        assert np.array_equal(frame, want), G
 
 
 # ---- 6. refractive index 1 -----------------------------------------------------------------------------------------
@@ -473,9 +436,9 @@ def test_index_one_changes_nothing(flux, demo2, math_name):
     base.shapes = base.shapes[:2]
     glass = copy.deepcopy(base)
     glass.shapes.append(flux.SphereData((-1.5, 3.0, 0.0), 1.5, flux.DielectricData(1.0, (1.0, 1.0, 1.0)), False))
-    m = _mode(flux, math_name)
-    a, sa, _ = _render(flux, base, 8, m)
-    b, sb, _ = _render(flux, glass, 8, m)
+    m = math_mode(flux, math_name)
+    a, sa, _ = render(flux, base, 8, m)
+    b, sb, _ = render(flux, glass, 8, m)
     assert sb["dielectric_reflections"] == 0 and sb["dielectric_transmissions"] > 1000
     assert sb["depth_exhausted"] == 0
     assert np.abs(a - b).max() <= 1e-12
@@ -483,30 +446,13 @@ def test_index_one_changes_nothing(flux, demo2, math_name):
 
 # ---- 7. the CLI ----------------------------------------------------------------------------------------------------
 
-def _small_glass_yml(tmp_path, w=64, h=48):
-    text = open(os.path.join(SCENES, "glass.yml")).read()
-    text = re.sub(r"image_width: 800", f"image_width: {w}", text)
-    text = re.sub(r"image_height: 600", f"image_height: {h}", text)
-    text = re.sub(r"pixel_size: 0.5", f"pixel_size: {0.5 * 800 / w!r}", text)
-    p = tmp_path / "glass.yml"
-    p.write_text(text)
-    return str(p)
-
-
 def test_cli_writes_the_python_frame(flux, tmp_path):
-    from flux_amd import build
-    build.build_host()
-    flux_bin = os.path.join(ROOT, "flux_amd", "host", "flux")
-    scene = _small_glass_yml(tmp_path)
+    flux_bin, _ = host_bins()
+    scene = small_yaml(os.path.join(SCENES, "glass.yml"), tmp_path, 64, 48)
     sd = flux.load_scene(scene)
     assert sd.output_settings.image_width == 64 and isinstance(sd.shapes[3].material, flux.DielectricData)
     with flux.Renderer(sd, flux.JobConfiguration(3, 5, 16), seed=5) as r:
         want_img = r.render_frame()
-    want = tmp_path / "want.ppm"
-    flux.write_ppm(str(want), want_img)
-    out = tmp_path / "out"
-    out.mkdir()
-    r = subprocess.run([flux_bin, scene, "-r", "3", "-d", "5", "-R", "16", "--seed", "5", "--gpus", "1", "--outdir", str(out)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    assert open(out / "glass.ppm", "rb").read() == open(want, "rb").read()
+    flux.write_ppm(str(tmp_path / "want.ppm"), want_img)
+    got = cli_frame(flux_bin, scene, ["-r", "3", "-d", "5", "-R", "16", "--seed", "5"], tmp_path / "out")
+    assert got == open(tmp_path / "want.ppm", "rb").read()

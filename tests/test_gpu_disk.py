@@ -9,22 +9,16 @@ The CPU checker is frozen and knows no disk, so the evidence comes three ways:
 import copy
 import math
 import os
-import re
-import subprocess
-import time
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, SCENES, small_scene
+from conftest import SCENES, small_scene
+from extension_checks import cli_frame, host_bins, loopback_frames, math_mode, node_frame, render, set_sharded_frame, small_yaml
 
 pytestmark = pytest.mark.gpu
 
 T_MIN = 0.0005
-
-
-def _mode(flux, name):
-    return flux.MATH_FAST if name == "fast" else flux.MATH_STRICT
 
 
 def _plane_to_disk(flux, sd, radius=1e3):
@@ -43,32 +37,19 @@ def _small_mesh(flux):
     return MeshData(v, t, flux.MatteData((0.6, 0.8, 0.5), (0, 0, 0), 0.9))
 
 
-def _render(flux, sd, n, math_mode, kernel=None, traversal=None, seed=1):
-    with flux.Renderer(sd, flux.JobConfiguration(n, 5, 50), seed=seed) as r:
-        r.set_math(math_mode)
-        if kernel is not None:
-            r.set_kernel(kernel)
-        if traversal is not None:
-            r.set_traversal(traversal)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan()["kernel"]
-
-
 @pytest.mark.parametrize("scene", ["demo1", "demo2"])
 @pytest.mark.parametrize("math_name", ["fast", "strict"])
 def test_plane_equivalence(flux, oracle_mod, demo1, demo2, scene, math_name):
     plane = small_scene(demo1 if scene == "demo1" else demo2, 64, 48)
     disk = _plane_to_disk(flux, plane)
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     for n in (4, 16):
         want_o = oracle_mod.Oracle(plane, flux.JobConfiguration(n, 5, 50), seed=1)
         o_img = want_o.render_frame(threads=8) if n == 4 or scene == "demo2" else None
         o_stats = want_o.stats() if o_img is not None else None
         for kernel in (flux.KERNEL_STATIC, flux.KERNEL_REFILL, flux.KERNEL_SPLIT):
-            a, sa, _ = _render(flux, plane, n, m, kernel)
-            b, sb, _ = _render(flux, disk, n, m, kernel)
+            a, sa, _ = render(flux, plane, n, m, kernel)
+            b, sb, _ = render(flux, disk, n, m, kernel)
             assert sa == sb, (n, kernel, sa, sb)
             assert np.abs(a - b).max() <= 1e-12, (n, kernel)
             assert np.array_equal(a, b), (n, kernel)  # bit-equal: the same operations decide every hit
@@ -82,17 +63,17 @@ def test_plane_equivalence_with_a_mesh(flux, oracle_mod, demo2, math_name):
     plane = small_scene(demo2, 64, 48)
     plane.shapes.append(_small_mesh(flux))
     disk = _plane_to_disk(flux, plane)
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     n = 8
     o = oracle_mod.Oracle(plane, flux.JobConfiguration(n, 5, 50), seed=1)
     o_img = o.render_frame(threads=8)
     o_stats = o.stats()
     plans = set()
     for traversal in (flux._lib.TRAVERSE_BVH, flux._lib.TRAVERSE_BVH_BINARY, flux._lib.TRAVERSE_BRUTE):
-        a, sa, pa = _render(flux, plane, n, m, traversal=traversal)
-        b, sb, pb = _render(flux, disk, n, m, traversal=traversal)
-        plans.add(pb)
-        assert pa == pb
+        a, sa, pa = render(flux, plane, n, m, traversal=traversal)
+        b, sb, pb = render(flux, disk, n, m, traversal=traversal)
+        plans.add(pb["kernel"])
+        assert pa["kernel"] == pb["kernel"]
         assert sa == sb, (traversal, sa, sb)
         assert np.array_equal(a, b), traversal
         assert np.abs(b - o_img).max() < 1e-4, traversal
@@ -109,10 +90,10 @@ def test_out_of_reach_disk_changes_nothing(flux, demo2, math_name):
     base = small_scene(demo2, 64, 48)
     far = copy.deepcopy(base)
     far.shapes.insert(1, flux.DiskData((0.0, -50.0, 3.0), (0.0, 1.0, 0.0), 10.0, flux.EmissiveData((1.0, 0.0, 0.0), 50.0)))
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     for n, kernel in ((4, flux.KERNEL_STATIC), (8, flux.KERNEL_REFILL), (16, flux.KERNEL_SPLIT)):
-        a, sa, _ = _render(flux, base, n, m, kernel)
-        b, sb, _ = _render(flux, far, n, m, kernel)
+        a, sa, _ = render(flux, base, n, m, kernel)
+        b, sb, _ = render(flux, far, n, m, kernel)
         assert sa == sb and np.abs(a - b).max() <= 1e-12 and np.array_equal(a, b), (n, kernel)
 
 
@@ -178,7 +159,7 @@ def test_random_rays_against_the_spec(flux, math_name):
     sd = _ray_scene(flux, [flux.DiskData(c, n, radius, flux.EmissiveData(EMIT, POWER))])
     o, d = _random_rays(rng, c, n, radius, 100000)
     with flux.Renderer(sd, flux.JobConfiguration(2, 3, 50), seed=2) as r:
-        r.set_math(_mode(flux, math_name))
+        r.set_math(math_mode(flux, math_name))
         rgb, hit, t = r.debug_shade(o, d, 1, 0, 0)
     tw, hw, rim = _spec(o, d, c, n, radius * radius)
     keep = ~rim
@@ -196,7 +177,7 @@ def test_random_rays_against_the_spec(flux, math_name):
 
 @pytest.mark.parametrize("math_name", ["fast", "strict"])
 def test_ray_corner_cases(flux, math_name):
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     cfg = flux.JobConfiguration(2, 3, 50)
     emis = flux.EmissiveData(EMIT, POWER)
     c = (0.0, 2.0, 0.0)
@@ -234,7 +215,7 @@ def test_ray_corner_cases(flux, math_name):
 @pytest.mark.parametrize("math_name", ["fast", "strict"])
 def test_tie_with_a_coplanar_plane(flux, math_name):
     """Equal t: the lower YAML index wins, whichever of the two is scanned first (planes are scanned before disks)."""
-    m = _mode(flux, math_name)
+    m = math_mode(flux, math_name)
     c, up = (0.2, 0.5, -0.1), (0.0, 1.0, 0.0)
     emis = flux.EmissiveData(EMIT, POWER)
     matte = flux.MatteData((0.5, 0.5, 0.5), (0, 0, 0), 1.0)
@@ -296,7 +277,7 @@ def test_closed_form_floor_under_a_disk(flux, math_name):
     assert abs(_solid_angle(np.zeros(1), np.zeros(1), a, h)[0] / (2 * np.pi) - (1 - h / math.hypot(h, a))) < 1e-12
     sd, eye_h, vpd, ps = _floor_scene(flux, a, h, -1.0, W)
     with flux.Renderer(sd, flux.JobConfiguration(n, 2, 50), seed=5) as r:
-        r.set_math(_mode(flux, math_name))
+        r.set_math(math_mode(flux, math_name))
         img = r.render_frame()
     # pixel (row, col) sees the floor at (e/d) (u U + v V), u = aps (col - W/2 + sx), v = aps ((H - row) - H/2 + sy), U = -x, V = +z:
     # Omega averaged over the footprint (4 x 4 points per pixel)
@@ -315,7 +296,7 @@ def test_closed_form_floor_under_a_disk(flux, math_name):
     # flipped: the disk faces away from the floor, which then receives nothing at all
     sd2, *_ = _floor_scene(flux, a, h, 1.0, W)
     with flux.Renderer(sd2, flux.JobConfiguration(8, 2, 50), seed=5) as r:
-        r.set_math(_mode(flux, math_name))
+        r.set_math(math_mode(flux, math_name))
         assert np.all(r.render_frame() == 0.0)
 
 
@@ -326,88 +307,28 @@ def _disk_light(flux, w=64, h=48):
 
 
 def test_set_shares_and_loopback_ranks(flux):
-    import torch
-    from flux_amd.dist import SetSharder, hip_render_sets_fn
     sd = _disk_light(flux, 50, 37)
     cfg = flux.JobConfiguration(8, 5, 50)
     with flux.Renderer(sd, cfg, seed=11) as r:
         want = r.render_frame()
-        dev = torch.device("cuda", 0)
-        rowperm = torch.from_numpy(r.row_perm_table())
-        fn = hip_render_sets_fn(r)
         for world in (1, 2, 3):
-            shards = []
-            for rank in range(world):
-                sh = SetSharder(r.height, r.width, rank, world, dev, rowperm)
-                sh.render(fn)
-                torch.cuda.synchronize()
-                if sh.local is not sh.render_buf:
-                    sh.local[:, : sh.count] = sh.render_buf
-                shards.append(sh)
-            s0 = shards[0]
-            got = s0.assemble().cpu() if world == 1 else torch.stack([s.local for s in shards])[s0._g, s0._r, s0._m].cpu()
-            assert np.array_equal(got.numpy(), want), world
-    for G in (2, 3):
-        mode = flux.SHARD_SETS | flux._lib.SHARD_LOOPBACK
-        with flux.MultiRenderer(sd, cfg, seed=11, devices=[0] * G, shard=mode) as m:
-            assert np.array_equal(m.render_frame(), want), G
-
-
-def _host_bins():
-    from flux_amd import build
-    build.build_host()
-    host = os.path.join(ROOT, "flux_amd", "host")
-    return os.path.join(host, "flux"), os.path.join(host, "flux_node")
-
-
-def _small_disk_yml(tmp_path, w=64, h=48):
-    text = open(os.path.join(SCENES, "disk_light.yml")).read()
-    text = re.sub(r"image_width: 800", f"image_width: {w}", text)
-    text = re.sub(r"image_height: 600", f"image_height: {h}", text)
-    text = re.sub(r"pixel_size: 0.5", f"pixel_size: {0.5 * 800 / w!r}", text)
-    p = tmp_path / "disk_light.yml"
-    p.write_text(text)
-    return str(p)
+            assert np.array_equal(set_sharded_frame(flux, r, world).numpy(), want), world
+    for G, _, frame in loopback_frames(flux, sd, cfg, 11, (2, 3), (flux.SHARD_SETS,)):
+        assert np.array_equal(frame, want), G
 
 
 def test_cli_and_node_write_the_python_frame(flux, tmp_path):
-    flux_bin, node_bin = _host_bins()
-    scene = _small_disk_yml(tmp_path)
+    flux_bin, node_bin = host_bins()
+    scene = small_yaml(os.path.join(SCENES, "disk_light.yml"), tmp_path, 64, 48)
     sd = flux.load_scene(scene)
     assert sd.output_settings.image_width == 64 and isinstance(sd.shapes[1], flux.DiskData)
     with flux.Renderer(sd, flux.JobConfiguration(3, 5, 16), seed=5) as r:
         want_img = r.render_frame()
-    want = tmp_path / "want.ppm"
-    flux.write_ppm(str(want), want_img)
-    direct, remote = tmp_path / "direct", tmp_path / "remote"
-    direct.mkdir()
-    remote.mkdir()
+    flux.write_ppm(str(tmp_path / "want.ppm"), want_img)
+    want = open(tmp_path / "want.ppm", "rb").read()
     common = ["-r", "3", "-d", "5", "-R", "16", "--seed", "5"]
-    r = subprocess.run([flux_bin, scene] + common + ["--gpus", "1", "--outdir", str(direct)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    assert open(direct / "disk_light.ppm", "rb").read() == open(want, "rb").read()
-    log = open(tmp_path / "node.log", "w")
-    node = subprocess.Popen([node_bin, "-h", "127.0.0.1", "-p", "0", "-t", "4", "--seed", "5", "--once"],
-                            stdout=log, stderr=subprocess.STDOUT, text=True)
-    try:
-        port = None
-        for _ in range(600):
-            mm = re.search(r"Listening on port (\d+)", open(tmp_path / "node.log").read())
-            if mm:
-                port = mm.group(1)
-                break
-            assert node.poll() is None, open(tmp_path / "node.log").read()
-            time.sleep(0.05)
-        assert port, "flux_node did not come up"
-        r = subprocess.run([flux_bin, scene] + common + ["-L", "-n", f"127.0.0.1:{port}", "--outdir", str(remote)],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr + r.stdout
-        assert node.wait(timeout=30) == 0
-    finally:
-        if node.poll() is None:
-            node.kill()
-        log.close()
-    assert open(remote / "disk_light.ppm", "rb").read() == open(want, "rb").read()
+    assert cli_frame(flux_bin, scene, common, tmp_path / "direct") == want
+    assert node_frame(flux_bin, node_bin, scene, common, tmp_path / "remote", tmp_path) == want
 
 
 def test_launch_plans(flux):

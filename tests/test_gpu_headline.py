@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import max_abs_diff
+from extension_checks import set_sharded_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -151,29 +152,6 @@ def test_kernels_agree_at_four_waves_per_pixel(flux, headline):
     assert np.array_equal(_render_blocks(r, ROW_BLOCKS), out[(flux.MATH_FAST, flux.KERNEL_SPLIT)])
 
 
-def _set_sharded_frame(flux, r, world):
-    """The frame assembled from the `world` per-rank set shares, rendered one after the other on this GPU."""
-    import torch
-    from flux_amd.dist import SetSharder, hip_render_sets_fn
-    dev = torch.device("cuda", 0)
-    rowperm = torch.from_numpy(r.row_perm_table())
-    fn = hip_render_sets_fn(r)
-    shards = []
-    for rank in range(world):
-        sh = SetSharder(r.height, r.width, rank, world, dev, rowperm)
-        assert r.launch_plan(num_sets=sh.count)["waves_per_pixel"] == r.launch_plan()["waves_per_pixel"]
-        sh.render(fn)
-        torch.cuda.synchronize()
-        if sh.local is not sh.render_buf:
-            sh.local[:, : sh.count] = sh.render_buf
-        shards.append(sh)
-    s0 = shards[0]
-    if world == 1:
-        return s0.assemble().cpu()
-    gathered = torch.stack([s.local for s in shards])  # what all_gather_into_tensor produces
-    return gathered[s0._g, s0._r, s0._m].cpu()
-
-
 @pytest.mark.parametrize("n", [32, 128])
 def test_the_call_bench_times_equals_render_frame(flux, demo2, headline, n):
     """(c) 800x600 at 1024 and 16384 spp: SetSharder over flux_render_sets_device -- world 1 is bench.py's timed call,
@@ -185,8 +163,8 @@ def test_the_call_bench_times_equals_render_frame(flux, demo2, headline, n):
         r.set_kernel(flux.KERNEL_DEFAULT)
         full = torch.from_numpy(r.render_frame())
         assert torch.isfinite(full).all()
-        assert torch.equal(_set_sharded_frame(flux, r, 1), full)
-        assert torch.equal(_set_sharded_frame(flux, r, 8), full)
+        assert torch.equal(set_sharded_frame(flux, r, 1, check_plan=True), full)
+        assert torch.equal(set_sharded_frame(flux, r, 8, check_plan=True), full)
         # ... and the row tiles of `bench.py --shard rows` (FrameSharder: rows g, g + 8, ...)
         from flux_amd.dist import FrameSharder, hip_render_fn
         dev = torch.device("cuda", 0)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import max_abs_diff, small_scene
+from extension_checks import math_mode, set_sharded_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +22,10 @@ TOL_TIGHT = 1e-9   # what FP64 + same operation order actually delivers
 MATH_MODES = ["fast", "strict"]
 
 
-def _mode(flux, name):
-    return {"fast": flux.MATH_FAST, "strict": flux.MATH_STRICT}[name]
-
-
 def _pair(flux, oracle_mod, sd, n, D=5, seed=1, math="fast"):
     cfg = flux.JobConfiguration(n, D, 50)
     r = flux.Renderer(sd, cfg, seed=seed)
-    r.set_math(_mode(flux, math))
+    r.set_math(math_mode(flux, math))
     return r, oracle_mod.Oracle(sd, cfg, seed=seed)
 
 
@@ -200,7 +197,7 @@ def test_gpu_matches_committed_golden(flux, demo1, demo2, name, math):
     sd = small_scene(demo1 if name == "demo1" else demo2, 64, 48)
     want = np.load(os.path.join(GOLDEN, f"{name}_64x48_n4_seed1.npy"))
     with flux.Renderer(sd, flux.JobConfiguration(4, 5, 50), seed=1) as r:
-        r.set_math(_mode(flux, math))
+        r.set_math(math_mode(flux, math))
         assert max_abs_diff(r.render_frame(), want) < TOL_IMAGE
 
 
@@ -211,7 +208,7 @@ def test_full_size_properties(flux, demo2, math):
     bitwise run-to-run determinism, static == refill up to summation order, strided == contiguous rows,
     all values finite and in [0,1] after max_to_one."""
     with flux.Renderer(demo2, flux.JobConfiguration(32, 5, 50), seed=1) as r:
-        r.set_math(_mode(flux, math))
+        r.set_math(math_mode(flux, math))
         a = r.render_rows(296, 303)
         b = r.render_rows(296, 303)
         assert np.array_equal(a, b)
@@ -236,7 +233,7 @@ def test_fast_equals_strict_full_size(flux, demo2):
     with flux.Renderer(demo2, flux.JobConfiguration(32, 5, 50), seed=1) as r:
         out, stats = {}, {}
         for name in MATH_MODES:
-            r.set_math(_mode(flux, name))
+            r.set_math(math_mode(flux, name))
             r.enable_stats(True)
             r.stats(reset=True)
             out[name] = r.render_rows(280, 311)
@@ -256,7 +253,7 @@ def test_gpu_matches_reference_published_render(flux, demo2, math):
     from conftest import GOLDEN
     ref = np.load(os.path.join(GOLDEN, "demo2_ref_100x75.npy")).astype(np.float64)
     with flux.Renderer(demo2, flux.JobConfiguration(128, 5, 50), seed=1) as r:
-        r.set_math(_mode(flux, math))
+        r.set_math(math_mode(flux, math))
         img = r.render_frame()
     assert np.isfinite(img).all() and img.min() >= 0.0 and img.max() <= 1.0
     small = img.reshape(75, 8, 100, 8, 3).mean(axis=(1, 3))
@@ -313,25 +310,13 @@ def test_set_sharded_render_equals_full_frame(flux, demo2, math, world):
     """flux_render_sets_device: the G per-rank shares (sets s % G == g), rendered one after the other on this one
     GPU and reassembled by SetSharder's indexing, give the bit-identical frame of the row-based render."""
     import torch
-    from flux_amd.dist import SetSharder, hip_render_sets_fn
+    from flux_amd.dist import SetSharder
     sd = small_scene(demo2, 40, 24)
-    dev = torch.device("cuda", 0)
     with flux.Renderer(sd, flux.JobConfiguration(8, 5, 50), seed=3) as r:
-        r.set_math(_mode(flux, math))
+        r.set_math(math_mode(flux, math))
         full = torch.from_numpy(r.render_frame())
-        rowperm = torch.from_numpy(r.row_perm_table())
-        fn = hip_render_sets_fn(r)
-        shards = []
-        for rank in range(world):
-            sh = SetSharder(24, 40, rank, world, dev, rowperm)
-            sh.render(fn)
-            torch.cuda.synchronize()
-            sh.local[:, : sh.count] = sh.render_buf
-            shards.append(sh)
-        gathered = torch.stack([s.local for s in shards])  # what all_gather_into_tensor produces
-        s0 = shards[0]
-        frame = gathered[s0._g, s0._r, s0._m].cpu()
-        assert torch.equal(frame, full)
+        assert torch.equal(set_sharded_frame(flux, r, world), full)
+        s0 = SetSharder(24, 40, 0, world, torch.device("cuda", 0), torch.from_numpy(r.row_perm_table()))
         with pytest.raises(flux.FluxError):
             r.render_sets_device(0, 1, 41, s0.render_buf.data_ptr())   # more sets than exist
         r.set_kernel(flux.KERNEL_STATIC)
@@ -462,7 +447,7 @@ def test_fast_means_strict_where_a_plane_normal_is_not_unit(flux, oracle_mod, de
         plane.normal = normal
         with flux.Renderer(sd, cfg, seed=5) as r:
             for math in MATH_MODES:
-                r.set_math(_mode(flux, math))
+                r.set_math(math_mode(flux, math))
                 plan = r.launch_plan()
                 want_math = flux.MATH_STRICT if (label == "scaled" or math == "strict") else flux.MATH_FAST
                 assert plan["math"] == want_math, (label, math, plan)

@@ -8,14 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import small_scene
+from extension_checks import math_mode
 
 pytestmark = pytest.mark.gpu
 
 MODES = ["fast", "strict"]
-
-
-def _mode(flux, name):
-    return flux.MATH_FAST if name == "fast" else flux.MATH_STRICT
 
 
 def _oracle_rays(o, origins, dirs, depth, set_index, sample_index):
@@ -33,7 +30,7 @@ def _check(flux, oracle_mod, sd, origins, dirs, math, depth=1, D=5, n=4, set_ind
     o = oracle_mod.Oracle(sd, cfg, seed=4)
     want_hit, want_t, want_rgb = _oracle_rays(o, origins, dirs, depth, set_index, sample_index)
     with flux.Renderer(sd, cfg, seed=4) as r:
-        r.set_math(_mode(flux, math))
+        r.set_math(math_mode(flux, math))
         rgb, hit, t = r.debug_shade(origins, dirs, depth, set_index, sample_index)
     assert np.array_equal(hit, want_hit), np.nonzero(hit != want_hit)[0][:10]
     fin = np.isfinite(want_t)
@@ -190,7 +187,7 @@ def test_grazing_rays_through_the_f32_filter(flux, oracle_mod, demo2, math):
     want_hit = np.array([w[0] for w in want])
     want_t = np.array([w[1] if w[0] >= 0 else 0.0 for w in want])
     with flux.Renderer(sd, cfg, seed=4) as r:
-        r.set_math(_mode(flux, math))
+        r.set_math(math_mode(flux, math))
         _, hit, t = r.debug_shade(origins, dirs, 5, 1, 3)
     assert np.array_equal(hit, want_hit), np.nonzero(hit != want_hit)[0][:10]
     # a grazing hit's distance -hb -/+ sqrt(dq) is ill-conditioned in dq (d t / d dq = 1 / (2 sqrt(dq))): STRICT shares the

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SCENES
+from extension_checks import cli_frame, host_bins, node_frame
 
 HOST = os.path.join(ROOT, "flux_amd", "host")
 
@@ -88,43 +89,16 @@ def test_cli_renders_demo1_like_the_oracle(binaries, flux, oracle_mod, demo1, tm
 
 
 @pytest.mark.gpu
-def test_node_protocol_end_to_end(binaries, tmp_path):
+def test_node_protocol_end_to_end(tmp_path):
     """`flux_node` (GPU worker behind the reference's CBOR/TCP node protocol) serving `flux -n host:port -L`:
     the frame assembled from the node's RowsReady events equals the frame of a direct local render, bit for
     bit (same seed; colours cross the wire as exact shortest-float CBOR)."""
-    import re
-    import time
-    flux_bin = binaries[0]
-    node_bin = os.path.join(HOST, "flux_node")
+    flux_bin, node_bin = host_bins()
     direct, remote = tmp_path / "direct", tmp_path / "remote"
-    direct.mkdir()
-    remote.mkdir()
     scene = os.path.join(SCENES, "demo2.yml")
     common = ["-r", "3", "-d", "5", "-R", "64", "--seed", "5"]
-    r = subprocess.run([flux_bin, scene] + common + ["--gpus", "1", "--outdir", str(direct)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    log = open(tmp_path / "node.log", "w")
-    node = subprocess.Popen([node_bin, "-h", "127.0.0.1", "-p", "0", "-t", "4", "--seed", "5", "--once"],
-                            stdout=log, stderr=subprocess.STDOUT, text=True)
-    try:
-        port = None
-        for _ in range(600):
-            m = re.search(r"Listening on port (\d+)", open(tmp_path / "node.log").read())
-            if m:
-                port = m.group(1)
-                break
-            assert node.poll() is None, open(tmp_path / "node.log").read()
-            time.sleep(0.05)
-        assert port, "flux_node did not come up"
-        r = subprocess.run([flux_bin, scene] + common + ["-L", "-n", f"127.0.0.1:{port}", "--outdir", str(remote)],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr + r.stdout
-        assert "Connecting to worker" in r.stdout and "rendering finished, total time" in r.stdout
-        assert node.wait(timeout=30) == 0
-    finally:
-        if node.poll() is None:
-            node.kill()
-        log.close()
+    cli_frame(flux_bin, scene, common, direct)
+    node_frame(flux_bin, node_bin, scene, common, remote, tmp_path, stdout_has=("Connecting to worker", "rendering finished, total time"))
     a, b = _read_ppm(str(direct / "demo2.ppm")), _read_ppm(str(remote / "demo2.ppm"))
     assert a.shape == (600, 800, 3) and np.array_equal(a, b)
     out = open(tmp_path / "node.log").read()

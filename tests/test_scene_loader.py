@@ -5,7 +5,8 @@ import os
 import pytest
 import yaml
 
-from conftest import SCENES
+from conftest import SCENES, small_scene
+from extension_checks import small_yaml
 
 
 def test_demo_scenes_load(flux, demo1, demo2):
@@ -94,3 +95,18 @@ def test_flatten_to_abi(flux, demo2):
     assert pl.kind == flux._lib.SHAPE_PLANE and list(pl.n) == [0.0, 1.0, 0.0]
     assert pl.material.kind == flux._lib.MAT_MATTE and list(pl.material.ambient) == [1.0, 1.0, 1.0]
     assert sdesc.shapes[0].invert == 1
+
+
+@pytest.mark.parametrize("w,h", [(16, 12), (64, 48)])
+@pytest.mark.parametrize("name", ["disk_light.yml", "glass.yml", "box_room.yml"])
+def test_small_yaml_is_small_scene(flux, tmp_path, name, w, h):
+    """tests/extension_checks.py shrinks a shipped scene as text for the command-line tools; the GPU tests shrink the loaded scene
+    (conftest.small_scene).  Both must give the same scene, field for field."""
+    path = os.path.join(SCENES, name)
+    got, want = flux.load_scene(small_yaml(path, tmp_path, w, h)), small_scene(flux.load_scene(path), w, h)
+    assert got.output_settings == want.output_settings and (w, h) == (got.output_settings.image_width, got.output_settings.image_height)
+    assert got.scene_name == want.scene_name and got.background == want.background
+    assert got.camera_settings == want.camera_settings and got.camera_data == want.camera_data
+    assert len(got.shapes) == len(want.shapes)
+    for i, (a, b) in enumerate(zip(got.shapes, want.shapes)):
+        assert a == b, i
