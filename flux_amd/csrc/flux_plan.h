@@ -91,6 +91,8 @@ struct LaunchPlan {
     int tris = 0;                  // kernels 0 and 1: the instantiation with the mesh (TRIS)
     int typ = 0;                   // kernels 2 and 4: the instantiation for the usual analytic scene (TYP)
     int max32 = 0;                 // kernel 2: at most 32 spheres, one group of the sphere filter (MAX32)
+    int uniform_a = 1;             // kernel 2: phase A shades a wave whose primaries all hit one shape from that shape's record as a scalar
+                                   // (render_body.inc shade_primary_hits); FLUX_SPLIT_UNIFORM_A=0: the general step everywhere
 };
 LaunchPlan plan_render(const RenderParams &p, int variant, int math);
 

@@ -142,6 +142,8 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
         L.lds = (size_t)kQueueBytesPerWave * K + scene_lds;
         L.typ = split_typ(p) ? 1 : 0;
         L.max32 = p.n_sph <= 32 ? 1 : 0;
+        // FLUX_SPLIT_UNIFORM_A=0 (tests, A/B runs): phase A's general shading step for every wave (render_body.inc shade_primary_hits)
+        if (const char *e = std::getenv("FLUX_SPLIT_UNIFORM_A")) L.uniform_a = std::atoi(e) != 0 ? 1 : 0;
         // The hit queue: as many slots as the LDS leaves a wave at FLUX_WPE_SPLIT waves/SIMD -- the CU's 128 granules of
         // 1280 B shared by 4 * FLUX_WPE_SPLIT / K blocks, less the scene copy and the 96 B of `part` (demo2, K = 4: 25 granules, 7 568 B
         // a wave, 110 slots of 68 B; H = 46).  A scene that leaves fewer than 64 + H slots (H at least FLUX_HITQ_MIN_TAKE), or whose bounce list does not fit 32 bits or does

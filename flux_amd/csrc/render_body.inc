@@ -1142,7 +1142,11 @@ __device__ __forceinline__ void path_begin(Path &p) {
 // triangle's DevMaterial (is_tri: the Matte factor 1 / INV_PI is then applied here).  ax / az: the lobe frame's helper vector (DevHitRec).
 // FIRST: the path's first bounce (phase A of the split kernel): its throughput is still exactly 1, so it BECOMES the weight (1.0 * w = w
 // bit for bit) instead of being multiplied by it.
-template <bool STATS, bool TRIS, bool TYP = false, bool FIRST = false>
+// UNI: `hit` and everything read from its record (kind, n of a stored-normal shape, fr / fg / fb, ax / az, unit_n, convex) are
+// wave-uniform (shade_primary_hits): the tests on them are scalar branches, and what a branch makes an identity -- the (c1, c2) selects,
+// a Matte bounce's x 1.0, the normalisation's select, dot(n, wi) of a shape that is not a convex sphere -- is not executed.  Every
+// operation that IS executed has the operands and the order of the general form.
+template <bool STATS, bool TRIS, bool TYP = false, bool FIRST = false, bool UNI = false>
 __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, int slot, double t, V3 n,
                                             V3 d, V3 pt, int kind, double fr, double fg, double fb, double m_inv_e1, double ax, double az,
                                             bool unit_n, bool convex, bool is_tri, Stats &st, int cz) {
@@ -1192,6 +1196,7 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
             wi = w;
         } else {
             double hx, hy, hz;
+            double c1u = 0.0, c2u = 0.0;  // UNI: (c1, c2) named where the branch knows the material
             if (matte) {
                 FLUX_CENSUS(P, 7 + cz);
                 if (STATS) st.c[2]++;
@@ -1207,6 +1212,8 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
                 hx = hxy.x;
                 hy = hxy.y;
                 hz = gather_global<double>(hbase, hoff + 16u);
+                c1u = hy;
+                c2u = hx;
                 if (TRIS && is_tri) scale = 1.0 / kInvPi;  // (n.wi) / ((n.wi) INV_PI); an analytic shape's record holds the product already
             } else {
                 FLUX_CENSUS(P, 8 + cz);
@@ -1232,10 +1239,12 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
                 hx = sin_theta * cs.x;
                 hy = sin_theta * cs.y;
                 hz = cos_theta;
+                c1u = hx;
+                c2u = hy;
             }
             const V3 b1 = normalize(cross(mk(ax, 1.0, az), w));
             const V3 b2 = cross(b1, w);
-            const double c1 = matte ? hy : hx, c2 = matte ? hx : hy;
+            const double c1 = UNI ? c1u : (matte ? hy : hx), c2 = UNI ? c2u : (matte ? hx : hy);
             const V3 q = mk(c1 * b1.x + c2 * b2.x, c1 * b1.y + c2 * b2.y, c1 * b1.z + c2 * b2.z);
             const V3 hw = mk(hz * w.x, hz * w.y, hz * w.z);
             const V3 wi0 = mk(q.x + hw.x, q.y + hw.y, q.z + hw.z);
@@ -1244,7 +1253,9 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
                 // |wi0| = 1 to a few ulp already and the division changes nothing above rounding (as in to_unit_hemi): it is
                 // kept for the hits whose normal is NOT unit (a plane stored with a non-unit normal)
                 wi = wi0;
-                if (p_glossy_long) {  // the scene's flag (abi.hip): a scalar compare instead of a vote of the wave on `!unit_n`
+                if (UNI) {
+                    if (p_glossy_long && !unit_n) wi = normalize(wi0);
+                } else if (p_glossy_long) {  // the scene's flag (abi.hip): a scalar compare instead of a vote of the wave on `!unit_n`
                     const V3 wn = normalize(wi0);
                     wi = unit_n ? wi0 : wn;
                 }
@@ -1282,14 +1293,26 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
     // wi (3/2 - |wi|^2 / 2), exact to the square of the deviation, keeps every such direction within an ulp of unit length.
     // (A Matte bounce builds its direction afresh around the unit normal: nothing accumulates there.)
     // (the factor is selected per lane -- exactly 1 for a Matte bounce --, not the three products: two selects instead of six)
-    if (p_unit_dirs) {
+    if (UNI) {
+        if (p_unit_dirs && !matte) {  // (Matte: x 1.0 is x)
+            double ww = dot(wi, wi);
+            asm("" : "+v"(ww));  // (keeps the branch: the optimiser would run the step for every wave and select its result)
+            const double ss = __builtin_fma(-0.5, ww, 1.5);
+            wi = mk(wi.x * ss, wi.y * ss, wi.z * ss);
+        }
+    } else if (p_unit_dirs) {
         const double ss = matte ? 1.0 : __builtin_fma(-0.5, dot(wi, wi), 1.5);
         wi = mk(wi.x * ss, wi.y * ss, wi.z * ss);
     }
     // the child leaves a convex sphere outwards from a hit at most 1e3 away: it cannot hit that sphere again (scan_shapes_fast)
     // (t < 1e3 on the high word: 1000.0 is 0x408f4000'00000000, so for every double -- negative, infinite, NaN -- the signed compare of
     // the high words decides as the f64 compare does, and its 32-bit literal sits in the instruction where the f64 one took two scalar moves)
-    p.self = (p_self_skip && convex && __double2hiint(t) < 0x408f4000 && dot(n, wi) >= 0.0) ? hit : -1;
+    if (UNI) {
+        p.self = -1;
+        if (p_self_skip && convex) p.self = (__double2hiint(t) < 0x408f4000 && dot(n, wi) >= 0.0) ? hit : -1;
+    } else {
+        p.self = (p_self_skip && convex && __double2hiint(t) < 0x408f4000 && dot(n, wi) >= 0.0) ? hit : -1;
+    }
     if (FIRST) {
         p.tr = fr * scale;
         p.tg = fg * scale;
@@ -1313,11 +1336,31 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
 // loads (DevHitRec) instead of shape -> kind -> fields -> material chains.  Returns the shape's material index.  One copy, shared by
 // the shading step (shade_hit_fast) and the split kernel's bounce of a parked hit (bounce_parked_hit), so that both form the normal
 // from the same operands with the same operations.
-template <bool LDS_SCENE>
+// UNI: `hit` is wave-uniform, so the record is too: ONE read of P.frec[hit] through the scalar cache (the records are constant for
+// the kernel's lifetime: the constant address space says so) instead of a 96-byte gather per lane, and a scalar branch on the shape's
+// kind instead of the select -- the sphere's normal is formed only for a sphere.
+typedef const __attribute__((address_space(4))) DevHitRec *HitRecScalar;
+template <bool LDS_SCENE, bool UNI = false>
 __device__ __forceinline__ int analytic_hit_fields(const RenderParams &P, const Ray &r, int hit, double t, const char *frec_lds, V3 &n,
                                                    int &kind, bool &unit_n, bool &convex, double &fr, double &fg, double &fb,
                                                    double &m_inv_e1, double &ax, double &az) {
     (void)frec_lds;
+    if (UNI) {
+        const HitRecScalar Ru = (HitRecScalar)(reinterpret_cast<uintptr_t>(P.frec) + (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
+        kind = Ru->mat_kind;
+        unit_n = Ru->unit_normal != 0;
+        fr = Ru->fr; fg = Ru->fg; fb = Ru->fb; m_inv_e1 = Ru->inv_e1;
+        ax = Ru->ax; az = Ru->az;
+        const double cx = Ru->cx, cy = Ru->cy, cz = Ru->cz, inv_rad = Ru->inv_rad;
+        if (Ru->shape_kind == kShapeSphere) {
+            n = mk(((r.ox - cx) + t * r.dx) * inv_rad, ((r.oy - cy) + t * r.dy) * inv_rad, ((r.oz - cz) + t * r.dz) * inv_rad);
+            convex = inv_rad > 0.0;
+        } else {
+            n = mk(cx, cy, cz);
+            convex = false;
+        }
+        return Ru->orig_id;
+    }
     const DevHitRec R = *reinterpret_cast<const DevHitRec *>((LDS_SCENE ? frec_lds : reinterpret_cast<const char *>(P.frec)) +
                                                               (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
     kind = R.mat_kind;
@@ -1343,7 +1386,10 @@ __device__ __forceinline__ int analytic_hit_fields(const RenderParams &P, const 
 // BOUNCE = false (the split kernel's phase B with its hit queue): phase 1 only -- the hit is classified, a continuing path's state is
 // left as it was and its bounce runs later from the parked hit (bounce_parked_hit).
 // FACING (with BOUNCE = false): `facing` is the scan's word on which side of the winner the ray met (scan_shapes_fast, sphere_facing).
-template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false, bool BOUNCE = true, bool FACING = false>
+// UNI (analytic shapes): `hit` is wave-uniform (shade_primary_hits).  The three ways out are then scalar branches, so the bounce runs where the
+// hit is classified: no join, and none of the defaults the join defines for the ways that do not bounce.
+template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false, bool BOUNCE = true, bool FACING = false,
+          bool UNI = false>
 __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, int slot, double t,
                                                double &Lr, double &Lg, double &Lb, Stats &st, int cz, const char *frec_lds = nullptr,
                                                int facing = 0) {
@@ -1377,7 +1423,7 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
             ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
             az = kind == kMatMatte ? 0.0071 : 0.00764;
         } else {
-            p.mat = analytic_hit_fields<LDS_SCENE>(P, p.r, hit, t, frec_lds, n, kind, unit_n, convex, fr, fg, fb, m_inv_e1, ax, az);
+            p.mat = analytic_hit_fields<LDS_SCENE, UNI>(P, p.r, hit, t, frec_lds, n, kind, unit_n, convex, fr, fg, fb, m_inv_e1, ax, az);
         }
         if (kind == kMatEmissive) {  // materials.rs:41-50
             if (STATS) st.c[5]++;
@@ -1404,9 +1450,15 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
                 Lb = front ? fb : 0.0;
             }
         } else {
+            if (UNI) {
+                if (BOUNCE) fast_bounce<STATS, TRIS, TYP, FIRST, true>(P, p, set, i, hit, slot, t, n, d, pt, kind, fr, fg, fb, m_inv_e1, ax, az,
+                                                                       unit_n, convex, is_tri, st, cz);
+                return true;
+            }
             bounce = 1;
         }
     }
+    if (UNI) return false;
     asm("" : "+v"(bounce));
     if (BOUNCE && bounce) {
         fast_bounce<STATS, TRIS, TYP, FIRST>(P, p, set, i, hit, slot, t, n, d, pt, kind, fr, fg, fb, m_inv_e1, ax, az, unit_n, convex, is_tri, st,
@@ -2176,12 +2228,36 @@ __device__ __forceinline__ uint32_t *hitq_entry(uint32_t *pool, uint32_t C, uint
     return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(pool) + __umul24(C - 1u - k, (uint32_t)kHitQBytesPerSlot));
 }
 
+// Phase A's shading step (both loops of the split kernel), entered by the lanes of `valid`.  A wave's 64 primaries sample one pixel, so
+// mostly they all hit the same shape (demo2: 68 % of the pixels see nothing but the floor).  One vote -- every active lane holds the
+// hit of the first active one, -1 for a miss included; the lanes past the slice's end are not active here, so their copy of the last
+// sample has no say -- and the step runs with that hit as a scalar (shade_hit_fast's UNI).  A wave that fails the vote, and every wave
+// of a launch with uni_a == 0 (FLUX_SPLIT_UNIFORM_A=0, launch_plan.cpp), runs the general step.  Same values either way.
+// (census sections 16 / 17: the passes that take the uniform step / the general one)
+template <bool STATS, bool TYP, bool UNIFORM_A>
+__device__ __forceinline__ bool shade_primary_hits(const RenderParams &P, Path &p, uint32_t set, uint32_t ia, int hit, double t, double &Lr,
+                                                   double &Lg, double &Lb, Stats &st, const char *frec_lds, int uni_a) {
+    if (UNIFORM_A) {
+        const int hu = __builtin_amdgcn_readfirstlane(hit);
+        if (uni_a != 0 && ballot64(hit != hu) == 0ull) {
+            FLUX_CENSUS(P, 16);
+            return shade_hit_fast<STATS, false, true, TYP, true, true, false, true>(P, p, set, ia, hu, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
+        }
+    }
+    FLUX_CENSUS(P, 17);
+    return shade_hit_fast<STATS, false, true, TYP, true>(P, p, set, ia, hit, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
+}
+// The instantiations of render_split_kernel whose phase A has the uniform step: those that hold it within the kernel's 96 registers
+// without a spill (DESIGN.md section 4, profiles/r12_uniform_phase_a/registers.txt) -- every one with the hit queue, and TYP with the
+// ray queue.  The other two ray-queue instantiations stand at 96 and 95 registers without it and would spill 28 and 22 more.
+constexpr bool split_uniform_a(bool TYP, bool HQ) { return HQ || TYP; }
+
 // HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
 // bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see launch_plan.cpp plan_render): the 64-entry ray queue and phase B's
 // bounce at once, in the lanes that continue.
 template <bool STATS, bool MAX32, bool TYP, bool HQ = false>
 __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void render_split_kernel(const RenderParams P0, int hq_cap, int hq_th,
-                                                                                                  int hq_bits) {
+                                                                                                  int hq_bits, int uni_a) {
     (void)hq_cap;
     (void)hq_th;
     (void)hq_bits;
@@ -2282,7 +2358,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 if (valid) {
                     double Lr, Lg, Lb;
                     FLUX_CENSUS(P, 2);
-                    cont = shade_hit_fast<STATS, false, true, TYP, true>(P, p, set_p, ia, hit, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
+                    cont = shade_primary_hits<STATS, TYP, split_uniform_a(TYP, HQ)>(P, p, set_p, ia, hit, t, Lr, Lg, Lb, st, frec_lds, uni_a);
                     if (cont && p.depth > P.max_depth) {  // scene.rs:164-165 on entry to the next level
                         cont = false;
                         Lr = Lg = Lb = 0.0;
@@ -2509,7 +2585,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 if (valid) {
                     double Lr, Lg, Lb;
                     FLUX_CENSUS(P, 2);
-                    cont = shade_hit_fast<STATS, false, true, TYP, true>(P, pa, set_p, ia, hit, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
+                    cont = shade_primary_hits<STATS, TYP, split_uniform_a(TYP, HQ)>(P, pa, set_p, ia, hit, t, Lr, Lg, Lb, st, frec_lds, uni_a);
                     if (cont && pa.depth > P.max_depth) {  // scene.rs:164-165 on entry to the next level
                         cont = false;
                         Lr = Lg = Lb = 0.0;
@@ -3464,8 +3540,8 @@ static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p,
         if (!hq || ps.tput_bits != bits) ps.tput = nullptr;
 #define FLUX_LAUNCH_SPLIT(MAX32, TYP, HQ)                                                                      \
     do {                                                                                                       \
-        if (stats) render_split_kernel<true, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits);           \
-        else render_split_kernel<false, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits);                \
+        if (stats) render_split_kernel<true, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);  \
+        else render_split_kernel<false, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);   \
     } while (0)
 #if FLUX_DIEL
         if (L.typ || hq) return hipErrorInvalidValue;
