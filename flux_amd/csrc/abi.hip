@@ -98,6 +98,7 @@ static void free_ctx(flux_ctx *c) {
     (void)hipFree(c->d_glossx);
     (void)hipFree(c->d_gxoff);
     (void)hipFree(c->d_tput);
+    (void)hipFree(c->d_lobe);
     (void)hipFree(c->d_setrows);
     (void)hipFree(c->d_rowperm);
     (void)hipFree(c->d_invperm);
@@ -271,6 +272,11 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
             alloc_copy(&c->d_tput, tput);
         }
     }
+    // the lobe-frame table (RenderParams::lobe_frame): 48 B per hit record, filled by the device below; FLUX_LOBE_FRAMES=0 builds the
+    // context without it (scene_build.cpp lobe_frame_table: tests and A/B runs -- every bounce then builds its frame in the loop)
+    std::vector<unsigned char> lobe_entries;
+    const size_t lobe_bytes = lobe_frame_table(h, lobe_entries);
+    if (lobe_bytes) alloc(&c->d_lobe, lobe_bytes);
     alloc(&c->d_setrows, own * sizeof(DevSetRows));
     alloc(&c->d_rowperm, perm_bytes);
     alloc(&c->d_invperm, perm_bytes);
@@ -295,6 +301,8 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         if (e == hipSuccess && gx_stride)
             e = generate_glossx_table(c->d_gloss, (size_t)c->sets.count * c->N, h.gx_inv_e1.data(), h.rp.n_gloss_exp, gx_stride / 16,
                                       c->d_glossx, nullptr);
+        if (e == hipSuccess && c->d_lobe)
+            e = generate_lobe_frame_table(reinterpret_cast<const DevHitRec *>(c->d_fscene + h.fs.rec), (int)lobe_entries.size(), c->d_lobe, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     }
     laps.lap(FLUX_CREATE_MS_TABLES);
@@ -335,6 +343,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.gx_stride = gx_stride;
     rp.tput = c->d_tput;
     rp.tput_bits = c->d_tput ? tput_bits : 0;
+    rp.lobe_frame = c->d_lobe;
     rp.set_rows = c->d_setrows;
     rp.rowperm = c->d_rowperm;
     rp.invperm = c->d_invperm;

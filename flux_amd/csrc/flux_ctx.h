@@ -88,6 +88,7 @@ struct flux_ctx {
     double2 *d_glossx = nullptr;  // the glossy lobe's angles per held sample and exponent slot (RenderParams::glossx), or nullptr
     int32_t *d_gxoff = nullptr;   // RenderParams::gx_off, with d_glossx
     double *d_tput = nullptr;     // RenderParams::tput, or nullptr
+    double *d_lobe = nullptr;     // RenderParams::lobe_frame, or nullptr
     flux::DevSetRows *d_setrows = nullptr;  // per table slot: where the set's rows of the sample tables start
     int32_t *d_rowperm = nullptr, *d_invperm = nullptr;
     unsigned long long *d_stats = nullptr;

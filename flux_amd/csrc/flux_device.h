@@ -282,7 +282,14 @@ struct RenderParams {
     // split kernel: the environment sphere's side of the f32 verdict that stands in front of the shortcut (flux_env_verdict.h): its
     // negated centre, p.p - r^2, p.p + r^2 and env_deep in f32, rounded once on the host (meaningful with env_short)
     EnvSphere32 env32;
+    // split kernel, phase A's uniform step: the lobe frame of every hit record with a stored normal (a plane, a disk, a box face; a
+    // sphere's entry is zero and never read), 48 B a record in frec order: {b1.x, b1.y, b1.z, b2.x, b2.y, b2.z} with b1 =
+    // normalize((ax, 1, az) x n), b2 = b1 x n of the record's own ax, az and normal -- what fast_bounce builds per bounce for a Matte
+    // hit, written by the device itself (render.hip generate_lobe_frame_table).  nullptr: no table (FLUX_LOBE_FRAMES=0), the arithmetic.
+    const double *lobe_frame;
 };
+// bytes per hit record of RenderParams::lobe_frame
+constexpr size_t kLobeFrameBytes = 6 * sizeof(double);
 
 // hit records of a scene (DevHitRec): one per sphere, plane and disk, six per box
 __host__ __device__ inline int hit_records(const RenderParams &p) { return p.n_sph + p.n_pln + p.n_dsk + 6 * p.n_box; }

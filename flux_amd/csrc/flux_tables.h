@@ -24,6 +24,9 @@ hipError_t generate_gloss_table(const double2 *pix, size_t count, double *gloss,
 // held samples, `gloss` as generate_gloss_table wrote it) for inv_e1[k], `pad` >= n entries per sample (render.hip: bit for bit the
 // values fast_bounce computes in the loop).  Asynchronous on `stream`.
 hipError_t generate_glossx_table(const double *gloss, size_t count, const double *inv_e1, int n, int pad, double2 *out, hipStream_t stream);
+// The lobe frames of the scene's n_rec hit records (RenderParams::lobe_frame; `frec` on the device): out[k] = {b1, b2} of record k, zeros
+// for a sphere (render.hip: bit for bit the frame fast_bounce builds in the loop for a Matte hit of the record).  Asynchronous on `stream`.
+hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *out, hipStream_t stream);
 hipError_t hemi_to_aos(size_t SD, size_t N, const double *in, double *out, hipStream_t stream);
 
 // Camera::render (trace.rs:53-97).  variant: FLUX_KERNEL_*; math: FLUX_MATH_FAST / FLUX_MATH_STRICT (render_body.inc).  Runs

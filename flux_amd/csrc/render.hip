@@ -187,6 +187,41 @@ hipError_t generate_glossx_table(const double *gloss, size_t count, const double
     return hipGetLastError();
 }
 
+// The lobe frames of the hit records (RenderParams::lobe_frame): entry k = {b1, b2} of fast_bounce's frame around w = n for record k's
+// stored normal and its own (ax, az); zeros for a sphere, whose normal depends on the hit.  The operations are the ones the FAST loop
+// performs per Matte bounce, in the order and with the fusions its compiled code has (contract(fast) decides them there; here they are
+// written out and compiled without contraction): a x n with one product rounded on its own in y and none in x and z (the 1 of
+// a = (ax, 1, az) needs no product), |.|^2 summed as y y, + x x, + z z, frsqrt from the hardware's seed -- which is why the host cannot
+// build the table --, the three scalings, and b1 x n with each first product rounded and the second fused.
+__global__ void lobe_frame_fill_kernel(const DevHitRec *__restrict__ frec, int n_rec, double *__restrict__ out) {
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= n_rec) return;
+    const DevHitRec R = frec[k];
+    double b1x = 0.0, b1y = 0.0, b1z = 0.0, b2x = 0.0, b2y = 0.0, b2z = 0.0;
+    if (R.shape_kind != kShapeSphere) {
+        const double nx = R.cx, ny = R.cy, nz = R.cz, ax = R.ax, az = R.az;
+        const double x = fastmath::ffma(-az, ny, nz);
+        const double y = fastmath::ffma(az, nx, -(ax * nz));
+        const double z = fastmath::ffma(ax, ny, -nx);
+        const double dd = fastmath::ffma(z, z, fastmath::ffma(x, x, y * y));
+        const double s = fastmath::frsqrt(dd);
+        b1x = x * s;
+        b1y = y * s;
+        b1z = z * s;
+        b2x = fastmath::ffma(nz, b1y, -(ny * b1z));
+        b2y = fastmath::ffma(nx, b1z, -(nz * b1x));
+        b2z = fastmath::ffma(ny, b1x, -(nx * b1y));
+    }
+    double *o = out + (size_t)k * 6;
+    o[0] = b1x; o[1] = b1y; o[2] = b1z;
+    o[3] = b2x; o[4] = b2y; o[5] = b2z;
+}
+hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *out, hipStream_t stream) {
+    if (n_rec <= 0) return hipSuccess;
+    lobe_frame_fill_kernel<<<dim3((unsigned)((n_rec + 63) / 64)), dim3(64), 0, stream>>>(frec, n_rec, out);
+    return hipGetLastError();
+}
+
 // the kernel the launch planner names (launch_plan.cpp), in the copy of render_body.inc it names
 hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream) {
     const LaunchPlan L = plan_render(p, variant, math);

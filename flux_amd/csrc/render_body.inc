@@ -1135,6 +1135,43 @@ __device__ __forceinline__ void path_begin(Path &p) {
 }
 
 #if FLUX_FAST
+// A hit record's entry of the lobe-frame table (RenderParams::lobe_frame) as the uniform step holds it: in scalar registers, read
+// beside the record itself (analytic_hit_fields<UNI>).  on: the context has the table and the record's shape stores its normal, which
+// (nx, ny, nz) then is -- the record's own words, never a copy in vector registers.
+// LF, the table's part in an instantiation's uniform step: kLobeOff -- none, the parent's code; kLobeEarly -- the entry's loads go out
+// with the record's own, so that one wait covers both (TYP); kLobeLate -- they go out in the arm itself: a wait of its own, but twelve
+// scalar registers held for a shorter time, which the instantiations outside TYP do not have to spare (split_lobe_frames).
+constexpr int kLobeOff = 0, kLobeEarly = 1, kLobeLate = 2;
+struct LobeFrameU {
+    double b1x = 0.0, b1y = 0.0, b1z = 0.0, b2x = 0.0, b2y = 0.0, b2z = 0.0;
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    bool on = false;
+};
+typedef const __attribute__((address_space(4))) double *LobeFrameScalar;
+
+// The end of a bounce: the weight into the throughput (FIRST: the throughput is still exactly 1, so it BECOMES the weight) and the
+// child ray from `pt` along `wi`.
+template <bool FIRST>
+__device__ __forceinline__ void advance_path(Path &p, V3 pt, V3 wi, double fr, double fg, double fb, double scale) {
+    if (FIRST) {
+        p.tr = fr * scale;
+        p.tg = fg * scale;
+        p.tb = fb * scale;
+    } else {
+        p.tr *= fr * scale;
+        p.tg *= fg * scale;
+        p.tb *= fb * scale;
+    }
+    p.nb++;
+    p.depth++;
+    p.r.ox = pt.x;
+    p.r.oy = pt.y;
+    p.r.oz = pt.z;
+    p.r.dx = wi.x;
+    p.r.dy = wi.y;
+    p.r.dz = wi.z;
+}
+
 // The bounce of the FAST arithmetic -- the lobe code and the ONLY update of the loop-carried path state --, shared by the two forms of
 // the shading step (shade_hit_fast below: after the join of the miss / emitter exits; shade_hit: after its early returns).  One copy:
 // a fix made here reaches every kernel (ADVICE round 4).
@@ -1146,11 +1183,16 @@ __device__ __forceinline__ void path_begin(Path &p) {
 // wave-uniform (shade_primary_hits): the tests on them are scalar branches, and what a branch makes an identity -- the (c1, c2) selects,
 // a Matte bounce's x 1.0, the normalisation's select, dot(n, wi) of a shape that is not a convex sphere -- is not executed.  Every
 // operation that IS executed has the operands and the order of the general form.
-template <bool STATS, bool TRIS, bool TYP = false, bool FIRST = false, bool UNI = false>
+// UNI with lf.on, a Matte hit: w = n is the record's stored normal, so the frame (b1, b2) is a constant of the record and comes from
+// the table (lf) instead of two cross products and a normalisation of wave-uniform values.  The arm forms wi itself -- the general
+// form's one product and two fused multiply-adds per component, with the frame and the normal as scalar operands -- and leaves: it
+// shares no value with the computing arm, so nothing of the frame is ever copied into vector registers.
+template <bool STATS, bool TRIS, bool TYP = false, bool FIRST = false, bool UNI = false, int LF = kLobeOff>
 __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, int slot, double t, V3 n,
                                             V3 d, V3 pt, int kind, double fr, double fg, double fb, double m_inv_e1, double ax, double az,
-                                            bool unit_n, bool convex, bool is_tri, Stats &st, int cz) {
+                                            bool unit_n, bool convex, bool is_tri, Stats &st, int cz, const LobeFrameU &lf = LobeFrameU()) {
     (void)cz;
+    (void)lf;
     // (TYP: the scene's flags as constants, see scan_shapes_fast)
     const bool p_glossy_long = TYP ? false : P.glossy_long != 0;
     const bool p_unit_dirs = TYP ? true : P.unit_dirs != 0;
@@ -1167,6 +1209,30 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
     double scale = 1.0;
     const bool matte = kind == kMatMatte;
     FLUX_CENSUS(P, 6 + cz);  // the lobe code: every lane whose path continues
+    if (UNI && !TRIS && LF != kLobeOff && matte && lf.on) {
+        LobeFrameU f = lf;
+        if (LF == kLobeLate) {
+            const LobeFrameScalar F = (LobeFrameScalar)(reinterpret_cast<uintptr_t>(P.lobe_frame) + (uint32_t)hit * (uint32_t)kLobeFrameBytes);
+            f.b1x = F[0]; f.b1y = F[1]; f.b1z = F[2];
+            f.b2x = F[3]; f.b2y = F[4]; f.b2z = F[5];
+        }
+        FLUX_CENSUS(P, 7 + cz);
+        FLUX_CENSUS(P, 18);
+        if (STATS) st.c[2]++;
+        const char *hbase = reinterpret_cast<const char *>(set_rows_of(P, set).hemi);
+        const uint32_t hoff = ((uint32_t)(p.depth - 1) * (uint32_t)P.nsamp + i) * 32u;
+        const double2 hxy = gather_global_d2(hbase, hoff);
+        const double hz = gather_global<double>(hbase, hoff + 16u);
+        // q = hy b1 + hx b2, wi = hz n + q
+        const double qx = __builtin_fma(f.b2x, hxy.x, f.b1x * hxy.y);
+        const double qy = __builtin_fma(f.b2y, hxy.x, f.b1y * hxy.y);
+        const double qz = __builtin_fma(f.b2z, hxy.x, f.b1z * hxy.y);
+        V3 wt = mk(__builtin_fma(f.nx, hz, qx), __builtin_fma(f.ny, hz, qy), __builtin_fma(f.nz, hz, qz));
+        if (p_glossy_long && !unit_n) wt = normalize(wt);  // (a stored normal that is not unit: see below)
+        p.self = -1;  // (not a convex sphere)
+        advance_path<FIRST>(p, pt, wt, fr, fg, fb, 1.0);
+        return;
+    }
     // The dielectric branch exists only in the FAST copy that serves scenes with a dielectric (FLUX_DIEL: render.hip's third
     // inclusion of this file, chosen by RenderParams::has_diel) and, there, outside TYP (the launch never picks it for such a scene).
     // The copy every other scene runs is compiled without it, so its code -- and, under contract(fast), every fusion decision of the
@@ -1313,23 +1379,7 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
     } else {
         p.self = (p_self_skip && convex && __double2hiint(t) < 0x408f4000 && dot(n, wi) >= 0.0) ? hit : -1;
     }
-    if (FIRST) {
-        p.tr = fr * scale;
-        p.tg = fg * scale;
-        p.tb = fb * scale;
-    } else {
-        p.tr *= fr * scale;
-        p.tg *= fg * scale;
-        p.tb *= fb * scale;
-    }
-    p.nb++;
-    p.depth++;
-    p.r.ox = pt.x;
-    p.r.oy = pt.y;
-    p.r.oz = pt.z;
-    p.r.dx = wi.x;
-    p.r.dy = wi.y;
-    p.r.dz = wi.z;
+    advance_path<FIRST>(p, pt, wi, fr, fg, fb, scale);
 }
 
 // The fields of an analytic shape's hit (shapes.rs:140-146,191-197) from its record: gathered per lane, one batch of independent
@@ -1338,15 +1388,30 @@ __device__ __forceinline__ void fast_bounce(const RenderParams &P, Path &p, uint
 // from the same operands with the same operations.
 // UNI: `hit` is wave-uniform, so the record is too: ONE read of P.frec[hit] through the scalar cache (the records are constant for
 // the kernel's lifetime: the constant address space says so) instead of a 96-byte gather per lane, and a scalar branch on the shape's
-// kind instead of the select -- the sphere's normal is formed only for a sphere.
+// kind instead of the select -- the sphere's normal is formed only for a sphere.  lf (LF != kLobeOff): whether the uniform step takes
+// the record's lobe frame from the table and, with kLobeEarly, the entry itself.
 typedef const __attribute__((address_space(4))) DevHitRec *HitRecScalar;
-template <bool LDS_SCENE, bool UNI = false>
+template <bool LDS_SCENE, bool UNI = false, int LF = kLobeOff>
 __device__ __forceinline__ int analytic_hit_fields(const RenderParams &P, const Ray &r, int hit, double t, const char *frec_lds, V3 &n,
                                                    int &kind, bool &unit_n, bool &convex, double &fr, double &fg, double &fb,
-                                                   double &m_inv_e1, double &ax, double &az) {
+                                                   double &m_inv_e1, double &ax, double &az, LobeFrameU *lf = nullptr) {
     (void)frec_lds;
     if (UNI) {
         const HitRecScalar Ru = (HitRecScalar)(reinterpret_cast<uintptr_t>(P.frec) + (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
+        if (LF != kLobeOff) {
+            const bool tab = P.lobe_frame != nullptr;
+            if (LF == kLobeEarly) {
+                // (a context without the table: the same six loads from the record's own bytes, which are there to be read, and `on`
+                // says that they mean nothing -- an address selected with two scalar instructions, where a branch around the loads
+                // would put a wait of its own between them and the record's)
+                const LobeFrameScalar F = (LobeFrameScalar)(tab ? reinterpret_cast<uintptr_t>(P.lobe_frame) + (uint32_t)hit * (uint32_t)kLobeFrameBytes
+                                                                : reinterpret_cast<uintptr_t>(Ru));
+                lf->b1x = F[0]; lf->b1y = F[1]; lf->b1z = F[2];
+                lf->b2x = F[3]; lf->b2y = F[4]; lf->b2z = F[5];
+            }
+            lf->nx = Ru->cx; lf->ny = Ru->cy; lf->nz = Ru->cz;
+            lf->on = tab && Ru->shape_kind != kShapeSphere;
+        }
         kind = Ru->mat_kind;
         unit_n = Ru->unit_normal != 0;
         fr = Ru->fr; fg = Ru->fg; fb = Ru->fb; m_inv_e1 = Ru->inv_e1;
@@ -1389,7 +1454,7 @@ __device__ __forceinline__ int analytic_hit_fields(const RenderParams &P, const 
 // UNI (analytic shapes): `hit` is wave-uniform (shade_primary_hits).  The three ways out are then scalar branches, so the bounce runs where the
 // hit is classified: no join, and none of the defaults the join defines for the ways that do not bounce.
 template <bool STATS, bool TRIS, bool LDS_SCENE = false, bool TYP = false, bool FIRST = false, bool BOUNCE = true, bool FACING = false,
-          bool UNI = false>
+          bool UNI = false, int LF = kLobeOff>
 __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, uint32_t set, uint32_t i, int hit, int slot, double t,
                                                double &Lr, double &Lg, double &Lb, Stats &st, int cz, const char *frec_lds = nullptr,
                                                int facing = 0) {
@@ -1405,6 +1470,7 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
     bool unit_n = true;   // triangles store normalize(e1 x e2)
     bool convex = false;  // a sphere hit whose stored normal points outwards (not `invert`)
     double fr = 0.0, fg = 0.0, fb = 0.0, m_inv_e1 = 0.0, ax = 0.0, az = 0.0;
+    LobeFrameU lf;  // UNI: the record's lobe frame, where the context tabulated it
     if (hit < 0) {  // scene.rs:168
         Lr = P.bgr;
         Lg = P.bgg;
@@ -1423,7 +1489,8 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
             ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
             az = kind == kMatMatte ? 0.0071 : 0.00764;
         } else {
-            p.mat = analytic_hit_fields<LDS_SCENE, UNI>(P, p.r, hit, t, frec_lds, n, kind, unit_n, convex, fr, fg, fb, m_inv_e1, ax, az);
+            p.mat = analytic_hit_fields<LDS_SCENE, UNI, UNI ? LF : kLobeOff>(P, p.r, hit, t, frec_lds, n, kind, unit_n, convex, fr, fg, fb, m_inv_e1,
+                                                                             ax, az, &lf);
         }
         if (kind == kMatEmissive) {  // materials.rs:41-50
             if (STATS) st.c[5]++;
@@ -1451,8 +1518,8 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
             }
         } else {
             if (UNI) {
-                if (BOUNCE) fast_bounce<STATS, TRIS, TYP, FIRST, true>(P, p, set, i, hit, slot, t, n, d, pt, kind, fr, fg, fb, m_inv_e1, ax, az,
-                                                                       unit_n, convex, is_tri, st, cz);
+                if (BOUNCE) fast_bounce<STATS, TRIS, TYP, FIRST, true, LF>(P, p, set, i, hit, slot, t, n, d, pt, kind, fr, fg, fb, m_inv_e1, ax,
+                                                                           az, unit_n, convex, is_tri, st, cz, lf);
                 return true;
             }
             bounce = 1;
@@ -2234,14 +2301,14 @@ __device__ __forceinline__ uint32_t *hitq_entry(uint32_t *pool, uint32_t C, uint
 // sample has no say -- and the step runs with that hit as a scalar (shade_hit_fast's UNI).  A wave that fails the vote, and every wave
 // of a launch with uni_a == 0 (FLUX_SPLIT_UNIFORM_A=0, launch_plan.cpp), runs the general step.  Same values either way.
 // (census sections 16 / 17: the passes that take the uniform step / the general one)
-template <bool STATS, bool TYP, bool UNIFORM_A>
+template <bool STATS, bool TYP, bool UNIFORM_A, int LF>
 __device__ __forceinline__ bool shade_primary_hits(const RenderParams &P, Path &p, uint32_t set, uint32_t ia, int hit, double t, double &Lr,
                                                    double &Lg, double &Lb, Stats &st, const char *frec_lds, int uni_a) {
     if (UNIFORM_A) {
         const int hu = __builtin_amdgcn_readfirstlane(hit);
         if (uni_a != 0 && ballot64(hit != hu) == 0ull) {
             FLUX_CENSUS(P, 16);
-            return shade_hit_fast<STATS, false, true, TYP, true, true, false, true>(P, p, set, ia, hu, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
+            return shade_hit_fast<STATS, false, true, TYP, true, true, false, true, LF>(P, p, set, ia, hu, -1, t, Lr, Lg, Lb, st, 3, frec_lds);
         }
     }
     FLUX_CENSUS(P, 17);
@@ -2251,6 +2318,12 @@ __device__ __forceinline__ bool shade_primary_hits(const RenderParams &P, Path &
 // without a spill (DESIGN.md section 4, profiles/r12_uniform_phase_a/registers.txt) -- every one with the hit queue, and TYP with the
 // ray queue.  The other two ray-queue instantiations stand at 96 and 95 registers without it and would spill 28 and 22 more.
 constexpr bool split_uniform_a(bool TYP, bool HQ) { return HQ || TYP; }
+// ... and where that step takes a flat Matte record's lobe frame from the table (RenderParams::lobe_frame), and how (kLobeEarly /
+// kLobeLate above): every such instantiation but <!MAX32, !TYP, HQ>, which spills twelve scalar registers as it stands and would spill
+// four more with the arm (profiles/r13_lobe_frames/registers.txt): it keeps the parent's code.
+constexpr int split_lobe_frames(bool MAX32, bool TYP, bool HQ) {
+    return !split_uniform_a(TYP, HQ) ? kLobeOff : TYP ? kLobeEarly : MAX32 ? kLobeLate : kLobeOff;
+}
 
 // HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
 // bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see launch_plan.cpp plan_render): the 64-entry ray queue and phase B's
@@ -2358,7 +2431,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 if (valid) {
                     double Lr, Lg, Lb;
                     FLUX_CENSUS(P, 2);
-                    cont = shade_primary_hits<STATS, TYP, split_uniform_a(TYP, HQ)>(P, p, set_p, ia, hit, t, Lr, Lg, Lb, st, frec_lds, uni_a);
+                    cont = shade_primary_hits<STATS, TYP, split_uniform_a(TYP, HQ), split_lobe_frames(MAX32, TYP, HQ)>(P, p, set_p, ia, hit, t, Lr, Lg, Lb, st, frec_lds, uni_a);
                     if (cont && p.depth > P.max_depth) {  // scene.rs:164-165 on entry to the next level
                         cont = false;
                         Lr = Lg = Lb = 0.0;
@@ -2585,7 +2658,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 if (valid) {
                     double Lr, Lg, Lb;
                     FLUX_CENSUS(P, 2);
-                    cont = shade_primary_hits<STATS, TYP, split_uniform_a(TYP, HQ)>(P, pa, set_p, ia, hit, t, Lr, Lg, Lb, st, frec_lds, uni_a);
+                    cont = shade_primary_hits<STATS, TYP, split_uniform_a(TYP, HQ), split_lobe_frames(MAX32, TYP, HQ)>(P, pa, set_p, ia, hit, t, Lr, Lg, Lb, st, frec_lds, uni_a);
                     if (cont && pa.depth > P.max_depth) {  // scene.rs:164-165 on entry to the next level
                         cont = false;
                         Lr = Lg = Lb = 0.0;

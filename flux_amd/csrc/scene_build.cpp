@@ -295,6 +295,17 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
 
 }  // namespace
 
+size_t lobe_frame_table(const HostScene &h, std::vector<unsigned char> &has_entry) {
+    has_entry.clear();
+    const char *env = std::getenv("FLUX_LOBE_FRAMES");
+    const size_t n_rec = (size_t)hit_records(h.rp);
+    if ((env && std::atoi(env) == 0) || n_rec == 0) return 0;
+    const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(h.fscene.data() + h.fs.rec);
+    has_entry.resize(n_rec);
+    for (size_t k = 0; k < n_rec; k++) has_entry[k] = rec[k].shape_kind != kShapeSphere;
+    return n_rec * kLobeFrameBytes;
+}
+
 void build_tput_table(const HostScene &h, int bits, int max_depth, std::vector<double> &out) {
     const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(h.fscene.data() + h.fs.rec);
     const uint32_t n_rec = (uint32_t)hit_records(h.rp);

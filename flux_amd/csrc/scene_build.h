@@ -64,4 +64,10 @@ int build_host_scene(const flux_scene_desc &scene, HostScene &out, std::string &
 // bit its result; entries whose list names a record the scene does not have stay zero.
 void build_tput_table(const HostScene &h, int bits, int max_depth, std::vector<double> &out);
 
+// The lobe-frame table (RenderParams::lobe_frame) of the scene: which hit records get an entry -- has_entry[k] = 1 for every record
+// whose shape stores its normal (a plane, a disk, a box face), 0 for a sphere, in scan order as the records -- and the table's size in
+// bytes, kLobeFrameBytes a record, entries or not.  0 and an empty list: no table (a scene without hit records, or FLUX_LOBE_FRAMES=0
+// in the environment: tests and A/B runs).  The entries themselves are the device's work (render.hip generate_lobe_frame_table).
+size_t lobe_frame_table(const HostScene &h, std::vector<unsigned char> &has_entry);
+
 }  // namespace flux

@@ -4,7 +4,8 @@ Sections: 0 phase-A pass, 1 phase-A sphere test, 2 phase-A shading entry, 3 phas
 5 wave-uniform invert-sphere test, 6/7/8 phase-B lobe code / Matte part / Glossy part, 9/10/11 the same three in phase A;
 with the hit queue (phase B parks its continuing hits, sections 6-8 then do not run): 12/13/14 the same three in the bounce of parked
 hits, 15 the lanes that take a parked hit; 16 / 17 the phase-A passes whose shading step runs from one record as a scalar
-(every valid lane holds the same hit) / runs the general step.
+(every valid lane holds the same hit) / runs the general step; 18 the uniform steps that take a flat Matte record's lobe frame
+from the table (RenderParams::lobe_frame).
 usage: python scripts/split_census.py [scene] [root]"""
 import glob, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +13,8 @@ scene = sys.argv[1] if len(sys.argv) > 1 else "demo2"
 n = sys.argv[2] if len(sys.argv) > 2 else "32"
 NAMES = ["A pass", "A sphere test", "A shading entry", "B pass", "B candidate trip", "B invert-sphere test", "B lobe code", "B lobe: Matte part",
          "B lobe: Glossy part", "A lobe code", "A lobe: Matte part", "A lobe: Glossy part", "parked-hit lobe code", "parked lobe: Matte",
-         "parked lobe: Glossy", "lanes taking parked hits", "A shading: uniform step", "A shading: general step"]
+         "parked lobe: Glossy", "lanes taking parked hits", "A shading: uniform step", "A shading: general step",
+         "A shading: uniform step, frame from the table"]
 code = r'''
 import sys, os
 sys.path.insert(0, %r)
