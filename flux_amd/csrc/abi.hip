@@ -63,59 +63,39 @@ int flux_device_count(void) {
 const char *flux_build_id(void) { return FLUX_BUILD_ID; }
 
 int flux_device_warmup(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(FLUX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
+    if (int rc = flux::check_device(device)) return rc;
     DeviceGuard guard(device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", device);
     // the runtime initialises lazily, per subsystem: the device context, the copy engine's staging (first hipMemcpy), the
     // compute queue + this library's code object (first launch), the stream pool (scripts/micro/cold_start.hip times each)
     double xy[2 * 4];
-    double *d = nullptr;
-    hipStream_t s = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, sizeof(xy)));
+    flux::DevBuf<double> d;
+    flux::Stream s;
+    HIP_TRY(d.alloc_bytes(sizeof(xy)));
     hipError_t e = hipMemcpy(d, xy, sizeof(xy), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = flux::generate_sampler_grid(FLUX_SAMPLER_REGULAR, 0, 2, d, nullptr, nullptr);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = s.create();
     if (e != hipSuccess) return fail(FLUX_E_DEVICE, "flux_device_warmup: %s", hipGetErrorString(e));
     return FLUX_OK;
 }
 
-static void free_ctx(flux_ctx *c) {
-    if (!c) return;
-    DeviceGuard g(c->device);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    (void)hipFree(c->d_shapes);
-    (void)hipFree(c->d_mats);
-    (void)hipFree(c->d_fscene);
-    (void)hipFree(c->d_pix);
-    (void)hipFree(c->d_disc);
-    (void)hipFree(c->d_hemi);
-    (void)hipFree(c->d_gloss);
-    (void)hipFree(c->d_glossx);
-    (void)hipFree(c->d_gxoff);
-    (void)hipFree(c->d_tput);
-    (void)hipFree(c->d_lobe);
-    (void)hipFree(c->d_setrows);
-    (void)hipFree(c->d_rowperm);
-    (void)hipFree(c->d_invperm);
-    (void)hipFree(c->d_stats);
-    (void)hipFree(c->d_tris);
-    (void)hipFree(c->d_nodes);
-    (void)hipFree(c->d_nodesq);
-    (void)hipFree(c->d_arena);
-    (void)hipFree(c->d_out);
-    delete c;
-}
-
-void flux_ctx_destroy(flux_ctx *ctx) { free_ctx(ctx); }
+void flux_ctx_destroy(flux_ctx *ctx) { delete ctx; }
 
 }  // extern "C"
 
 namespace flux {
+
+int check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(FLUX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
+    return FLUX_OK;
+}
+int require_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) == hipSuccess && device >= 0 && device < count) return FLUX_OK;
+    return fail(FLUX_E_DEVICE, "no HIP device %d (this library has no CPU fallback)", device);
+}
 
 // a material's kind and, for a Dielectric, its refraction index; `what` and `i` name its owner ("shape 3", "mesh 0")
 static int validate_material(const flux_material &m, const char *what, uint64_t i) {
@@ -185,12 +165,6 @@ int build_host(const flux_scene_desc &scene, HostScene &host) {
     return rc == FLUX_OK ? rc : fail(rc, "%s", error.c_str());
 }
 
-namespace {
-struct FreeCtx {
-    void operator()(flux_ctx *c) const { free_ctx(c); }
-};
-}  // namespace
-
 int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int device, uint64_t first_set, uint64_t set_stride,
            CreateLaps &laps, flux_ctx **out) {
     *out = nullptr;
@@ -199,7 +173,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     (void)hipFree(nullptr);  // the runtime's lazy per-device initialisation, booked under its own word (zero once the process has used the device)
     laps.lap(FLUX_CREATE_MS_RUNTIME);
 
-    std::unique_ptr<flux_ctx, FreeCtx> c(new flux_ctx());
+    std::unique_ptr<flux_ctx> c(new flux_ctx());
     c->device = device;
     c->seed = seed;
     c->n = (uint32_t)cfg.sample_root;
@@ -225,37 +199,37 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     const size_t hemi_bytes = own * c->D * c->N * kHemiDoubles * sizeof(double);
     const size_t perm_bytes = (size_t)c->H * c->S * sizeof(int32_t);
     hipError_t e = hipSuccess;
-    auto alloc = [&](auto **p, size_t bytes) {
+    auto alloc = [&](auto &buf, size_t bytes) {
         if (e != hipSuccess) return;
         laps.lap(FLUX_CREATE_MS_UPLOAD);
-        e = hipMalloc((void **)p, bytes);
+        e = buf.alloc_bytes(bytes);
         if (e == hipSuccess) c->device_bytes += bytes;
         laps.lap(FLUX_CREATE_MS_ALLOC);
     };
     auto copy = [&](void *dst, const auto &v) {
         if (e == hipSuccess) e = hipMemcpy(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
     };
-    auto alloc_copy = [&](auto **p, const auto &v) {
-        alloc(p, v.size() * sizeof(v[0]));
-        copy(*p, v);
+    auto alloc_copy = [&](auto &buf, const auto &v) {
+        alloc(buf, v.size() * sizeof(v[0]));
+        copy(buf, v);
     };
-    alloc_copy(&c->d_shapes, h.shapes);
+    alloc_copy(c->d_shapes, h.shapes);
     // the materials, followed by their bounce weights (render_bvh4_kernel)
-    alloc(&c->d_mats, h.mats.size() * sizeof(DevMaterial) + h.wtab.size() * sizeof(double));
+    alloc(c->d_mats, h.mats.size() * sizeof(DevMaterial) + h.wtab.size() * sizeof(double));
     copy(c->d_mats, h.mats);
     copy(c->d_mats + h.mats.size(), h.wtab);
-    alloc_copy(&c->d_fscene, h.fscene);
-    alloc(&c->d_pix, pix_bytes);
-    alloc(&c->d_disc, pix_bytes);
-    alloc(&c->d_hemi, hemi_bytes);
-    alloc(&c->d_gloss, pix_bytes * 2);
+    alloc_copy(c->d_fscene, h.fscene);
+    alloc(c->d_pix, pix_bytes);
+    alloc(c->d_disc, pix_bytes);
+    alloc(c->d_hemi, hemi_bytes);
+    alloc(c->d_gloss, pix_bytes * 2);
     // the glossy lobe's angle table (RenderParams::glossx) where the host scene assigned its exponents slots; FLUX_SAMPLE_TABLES=0
     // builds the context without it (tests and A/B runs: every glossy bounce then keeps the arithmetic in the loop)
     const char *tables_env = std::getenv("FLUX_SAMPLE_TABLES");
     const int gx_stride = (tables_env && std::atoi(tables_env) == 0) ? 0 : h.rp.gx_stride;
     if (gx_stride) {
-        alloc(&c->d_glossx, own * c->N * (size_t)gx_stride);
-        alloc_copy(&c->d_gxoff, h.gx_off);
+        alloc(c->d_glossx, own * c->N * (size_t)gx_stride);
+        alloc_copy(c->d_gxoff, h.gx_off);
     }
     // the throughput product table (RenderParams::tput) where the job's renders would take parked hits from the hit queue and the
     // table stays within its cap (flux_plan.h); FLUX_THROUGHPUT_TABLE=0 builds the context without it (tests and A/B runs: the take then
@@ -269,28 +243,28 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         if (!(tput_env && std::atoi(tput_env) == 0) && tput_table_bytes(job, &tput_bits)) {
             std::vector<double> tput;
             build_tput_table(h, tput_bits, (int)c->D, tput);
-            alloc_copy(&c->d_tput, tput);
+            alloc_copy(c->d_tput, tput);
         }
     }
     // the lobe-frame table (RenderParams::lobe_frame): 48 B per hit record, filled by the device below; FLUX_LOBE_FRAMES=0 builds the
     // context without it (scene_build.cpp lobe_frame_table: tests and A/B runs -- every bounce then builds its frame in the loop)
     std::vector<unsigned char> lobe_entries;
     const size_t lobe_bytes = lobe_frame_table(h, lobe_entries);
-    if (lobe_bytes) alloc(&c->d_lobe, lobe_bytes);
-    alloc(&c->d_setrows, own * sizeof(DevSetRows));
-    alloc(&c->d_rowperm, perm_bytes);
-    alloc(&c->d_invperm, perm_bytes);
-    alloc(&c->d_stats, FLUX_NUM_STATS * sizeof(unsigned long long));
+    if (lobe_bytes) alloc(c->d_lobe, lobe_bytes);
+    alloc(c->d_setrows, own * sizeof(DevSetRows));
+    alloc(c->d_rowperm, perm_bytes);
+    alloc(c->d_invperm, perm_bytes);
+    alloc(c->d_stats, FLUX_NUM_STATS * sizeof(unsigned long long));
     if (!h.tris.empty()) {
-        alloc_copy(&c->d_tris, h.tris);
-        alloc_copy(&c->d_nodes, h.nodes);
-        alloc_copy(&c->d_nodesq, h.nodesq);
-        if (!h.arena.empty()) alloc_copy(&c->d_arena, h.arena);
+        alloc_copy(c->d_tris, h.tris);
+        alloc_copy(c->d_nodes, h.nodes);
+        alloc_copy(c->d_nodesq, h.nodesq);
+        if (!h.arena.empty()) alloc_copy(c->d_arena, h.arena);
     }
     if (e == hipSuccess) e = hipMemset(c->d_stats, 0, FLUX_NUM_STATS * sizeof(unsigned long long));
     laps.lap(FLUX_CREATE_MS_UPLOAD);
-    if (e == hipSuccess) e = hipEventCreate(&c->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&c->ev1);
+    if (e == hipSuccess) e = c->ev0.create();
+    if (e == hipSuccess) e = c->ev1.create();
     laps.lap(FLUX_CREATE_MS_OTHER);
     // ---- MasterSampleSets::new on the device (sampling.rs:13-33) --------------
     double tab_ms[3] = {0, 0, 0};
@@ -351,7 +325,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.tris = c->d_tris;
     rp.nodes = c->d_nodes;
     rp.nodesq = c->d_nodesq;
-    rp.nodes4 = reinterpret_cast<const DevNode4Q *>(c->d_arena);  // (the arena's kernel reads it as DevNode4A)
+    rp.nodes4 = reinterpret_cast<const DevNode4Q *>(static_cast<DevNode4A *>(c->d_arena));  // (the arena's kernel reads it as DevNode4A)
     const unsigned char *fs = c->d_fscene;
     rp.fsph = reinterpret_cast<const DevScanSphere *>(fs + h.fs.sph);
     rp.fpln = reinterpret_cast<const DevScanPlane *>(fs + h.fs.pln);
@@ -388,10 +362,7 @@ int flux_ctx_create_sets(const flux_scene_desc *scene, const flux_job_cfg *cfg, 
     flux::CreateLaps laps;
     if (int rc = flux::validate_job(*scene, *cfg, first_set, set_stride)) return rc;
     laps.lap(FLUX_CREATE_MS_HOST);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(FLUX_E_INVALID, "device %d out of range [0,%d)", device, ndev);
+    if (int rc = flux::check_device(device)) return rc;
     laps.lap(FLUX_CREATE_MS_RUNTIME);
     return flux::no_throw([&] {
         flux::HostScene host;
@@ -462,6 +433,12 @@ int flux_ctx_set_math(flux_ctx *ctx, int mode) {
     return FLUX_OK;
 }
 
+static flux::RenderParams apply_traversal(const flux_ctx *ctx, flux::RenderParams p) {  // flux_ctx_set_traversal, for renders and flux_debug_shade alike
+    if (ctx->traversal == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
+    if (ctx->traversal == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
+    return p;
+}
+
 int flux_debug_shade(flux_ctx *ctx, uint64_t n, const double *rays, uint64_t depth, uint64_t set_index,
                      uint64_t sample_index, double *out_rgb, int32_t *out_hit, double *out_t) {
     if (!ctx || !rays || !out_rgb) return fail(FLUX_E_INVALID, "null argument");
@@ -472,37 +449,25 @@ int flux_debug_shade(flux_ctx *ctx, uint64_t n, const double *rays, uint64_t dep
         return fail(FLUX_E_INVALID, "depth >= 1, set_index < %u and sample_index < %u required", ctx->S, ctx->N);
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    double *d_rays = nullptr, *d_rgb = nullptr, *d_t = nullptr;
-    int *d_hit = nullptr;
-    hipError_t e = hipMalloc((void **)&d_rays, (size_t)n * 6 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_rgb, (size_t)n * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_t, (size_t)n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_hit, (size_t)n * sizeof(int));
+    flux::DevBuf<double> d_rays, d_rgb, d_t;
+    flux::DevBuf<int> d_hit;
+    hipError_t e = d_rays.alloc((size_t)n * 6);
+    if (e == hipSuccess) e = d_rgb.alloc((size_t)n * 3);
+    if (e == hipSuccess) e = d_t.alloc((size_t)n);
+    if (e == hipSuccess) e = d_hit.alloc((size_t)n);
     if (e == hipSuccess) e = hipMemcpy(d_rays, rays, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice);
-    flux::RenderParams p = ctx->rp;
-    if (ctx->traversal == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
-    if (ctx->traversal == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
+    flux::RenderParams p = apply_traversal(ctx, ctx->rp);
     p.glossy_long = 1;  // caller-supplied directions need not be unit vectors
     p.unit_dirs = 0;
     p.self_skip = 0;
     p.env_short = 0;
-    if (int rc = check_lds_budget_rays(ctx, p)) {
-        (void)hipFree(d_rays);
-        (void)hipFree(d_rgb);
-        (void)hipFree(d_t);
-        (void)hipFree(d_hit);
-        return rc;
-    }
+    if (int rc = check_lds_budget_rays(ctx, p)) return rc;
     if (e == hipSuccess)
         e = flux::launch_shade_rays(p, effective_math(ctx), d_rays, (int)n, (int)depth, (uint32_t)set_index, (uint32_t)sample_index,
                                     d_rgb, d_hit, d_t, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out_rgb, d_rgb, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_hit) e = hipMemcpy(out_hit, d_hit, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_t) e = hipMemcpy(out_t, d_t, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_rays);
-    (void)hipFree(d_rgb);
-    (void)hipFree(d_t);
-    (void)hipFree(d_hit);
     if (e != hipSuccess) return fail(FLUX_E_DEVICE, "debug shade: %s", hipGetErrorString(e));
     return FLUX_OK;
 }
@@ -512,19 +477,15 @@ int flux_sampler_grid(int device, int kind, uint64_t sample_root, uint64_t seed,
     if (kind < FLUX_SAMPLER_REGULAR || kind > FLUX_SAMPLER_CORRELATED_MULTI_JITTERED)
         return fail(FLUX_E_INVALID, "unknown sampler kind %d", kind);
     if (sample_root < 1 || sample_root > 4096) return fail(FLUX_E_INVALID, "sample_root must be in [1, 4096]");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return fail(FLUX_E_DEVICE, "no HIP device %d (this library has no CPU fallback)", device);
+    if (int rc = flux::require_device(device)) return rc;
     DeviceGuard guard(device);
     const size_t N = (size_t)sample_root * sample_root;
-    double *dxy = nullptr, *dh = nullptr;
-    hipError_t e = hipMalloc((void **)&dxy, N * 2 * sizeof(double));
-    if (e == hipSuccess && out_hemi) e = hipMalloc((void **)&dh, N * 3 * sizeof(double));
+    flux::DevBuf<double> dxy, dh;
+    hipError_t e = dxy.alloc(N * 2);
+    if (e == hipSuccess && out_hemi) e = dh.alloc(N * 3);
     if (e == hipSuccess) e = flux::generate_sampler_grid(kind, seed, (uint32_t)sample_root, dxy, dh, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out_xy, dxy, N * 2 * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_hemi) e = hipMemcpy(out_hemi, dh, N * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(dxy);
-    (void)hipFree(dh);
     if (e != hipSuccess) return fail(FLUX_E_DEVICE, "sampler grid: %s", hipGetErrorString(e));
     return FLUX_OK;
 }
@@ -532,33 +493,26 @@ int flux_sampler_grid(int device, int kind, uint64_t sample_root, uint64_t seed,
 int flux_debug_fastmath(int device, int fn, const double *a, const double *b, double *out, uint64_t n) {
     if (!a || !out) return fail(FLUX_E_INVALID, "null argument");
     if (fn < 0 || fn > 9) return fail(FLUX_E_INVALID, "unknown function %d", fn);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return fail(FLUX_E_DEVICE, "no HIP device %d (this library has no CPU fallback)", device);
+    if (int rc = flux::require_device(device)) return rc;
     DeviceGuard guard(device);
     if (n == 0) return FLUX_OK;
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
+    flux::DevBuf<double> da, db, dout;
     const size_t bytes = (size_t)n * sizeof(double);
-    hipError_t e = hipMalloc((void **)&da, bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, bytes);
-    if (e == hipSuccess && b) e = hipMalloc((void **)&db, bytes);
+    hipError_t e = da.alloc((size_t)n);
+    if (e == hipSuccess) e = dout.alloc((size_t)n);
+    if (e == hipSuccess && b) e = db.alloc((size_t)n);
     if (e == hipSuccess) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && b) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = flux::launch_fastmath_probe(fn, da, db, dout, (size_t)n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(da);
-    (void)hipFree(db);
-    (void)hipFree(dout);
     if (e != hipSuccess) return fail(FLUX_E_DEVICE, "fastmath probe: %s", hipGetErrorString(e));
     return FLUX_OK;
 }
 
 // The work fields of a launch: ONE place per entry point, shared by the render call and flux_ctx_launch_plan.
-static flux::RenderParams apply_traversal(const flux_ctx *ctx, flux::RenderParams p) {
+static flux::RenderParams apply_context(const flux_ctx *ctx, flux::RenderParams p) {
     p.stats = ctx->stats_on ? ctx->d_stats : nullptr;
-    if (ctx->traversal == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
-    if (ctx->traversal == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
-    return p;
+    return apply_traversal(ctx, p);
 }
 static flux::RenderParams rows_params(const flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, double *out) {
     flux::RenderParams p = ctx->rp;
@@ -566,7 +520,7 @@ static flux::RenderParams rows_params(const flux_ctx *ctx, uint64_t first_row, u
     p.first_row = (int32_t)first_row;
     p.row_stride = (int32_t)row_stride;
     p.num_rows = (int32_t)num_rows;
-    return apply_traversal(ctx, p);
+    return apply_context(ctx, p);
 }
 static flux::RenderParams sets_params(const flux_ctx *ctx, uint64_t first_set, uint64_t set_stride, uint64_t num_sets, double *out) {
     flux::RenderParams p = ctx->rp;
@@ -580,7 +534,7 @@ static flux::RenderParams sets_params(const flux_ctx *ctx, uint64_t first_set, u
     p.out_by_set = 1;
     p.slot_first = (int32_t)((first_set - ctx->sets.first) / ctx->sets.stride);
     p.slot_stride = (int32_t)(set_stride / ctx->sets.stride);
-    return apply_traversal(ctx, p);
+    return apply_context(ctx, p);
 }
 
 int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, int64_t out[FLUX_PLAN_WORDS]) {
@@ -609,6 +563,18 @@ int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, in
     return FLUX_OK;
 }
 
+// the launch of both render calls, between the context's two events (flux_ctx_last_kernel_ms); `what` names the caller in the LDS refusal
+static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream) {
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+    if (int rc = check_lds_budget(ctx, p, what)) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    HIP_TRY(flux::launch_render(p, ctx->variant, effective_math(ctx), stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    ctx->timed = true;
+    return FLUX_OK;
+}
+
 int flux_render_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
                             void *d_out_rgb, void *hip_stream) {
     if (!ctx) return fail(FLUX_E_INVALID, "null context");
@@ -622,16 +588,7 @@ int flux_render_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stri
         return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
                     (unsigned long long)first_row, (unsigned long long)row_stride,
                     (unsigned long long)num_rows, ctx->H);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out_rgb);
-    if (int rc = check_lds_budget(ctx, p, "flux_render_rows")) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(flux::launch_render(p, ctx->variant, effective_math(ctx), stream));
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    ctx->timed = true;
-    return FLUX_OK;
+    return launch_timed(ctx, rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out_rgb), "flux_render_rows", (hipStream_t)hip_stream);
 }
 
 int flux_render_sets_device(flux_ctx *ctx, uint64_t first_set, uint64_t set_stride, uint64_t num_sets, void *d_out_rgb,
@@ -650,16 +607,7 @@ int flux_render_sets_device(flux_ctx *ctx, uint64_t first_set, uint64_t set_stri
         (num_sets > 1 && set_stride % ctx->sets.stride != 0))
         return fail(FLUX_E_INVALID, "sets %llu + k*%llu are not all among this context's share %u + k*%u (flux_ctx_create_sets)",
                     (unsigned long long)first_set, (unsigned long long)set_stride, ctx->sets.first, ctx->sets.stride);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const flux::RenderParams p = sets_params(ctx, first_set, set_stride, num_sets, (double *)d_out_rgb);
-    if (int rc = check_lds_budget(ctx, p, "flux_render_sets_device")) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(flux::launch_render(p, ctx->variant, effective_math(ctx), stream));
-    HIP_TRY(hipEventRecord(ctx->ev1, stream));
-    ctx->timed = true;
-    return FLUX_OK;
+    return launch_timed(ctx, sets_params(ctx, first_set, set_stride, num_sets, (double *)d_out_rgb), "flux_render_sets_device", (hipStream_t)hip_stream);
 }
 
 int flux_render_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out_rgb) {
@@ -673,10 +621,8 @@ int flux_render_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double
     const uint64_t rows = row_end - row_start + 1;
     const size_t doubles = (size_t)rows * ctx->W * 3;
     if (doubles > ctx->d_out_doubles) {
-        (void)hipFree(ctx->d_out);
-        ctx->d_out = nullptr;
-        ctx->d_out_doubles = 0;
-        HIP_TRY(hipMalloc((void **)&ctx->d_out, doubles * sizeof(double)));
+        ctx->d_out_doubles = 0;  // (stays 0 if the new allocation fails: the old one is released first)
+        HIP_TRY(ctx->d_out.alloc(doubles));
         ctx->d_out_doubles = doubles;
     }
     int rc = flux_render_rows_device(ctx, row_start, 1, rows, ctx->d_out, nullptr);
@@ -754,11 +700,10 @@ int flux_ctx_copy_table(flux_ctx *ctx, int which, double *out, uint64_t out_doub
     if (which == FLUX_TABLE_HEMI) {
         const size_t total = SN * ctx->D * 3;
         if (out_doubles < total) return fail(FLUX_E_INVALID, "output too small: need %zu doubles", total);
-        double *tmp = nullptr;
-        HIP_TRY(hipMalloc((void **)&tmp, total * sizeof(double)));
+        flux::DevBuf<double> tmp;
+        HIP_TRY(tmp.alloc(total));
         hipError_t e = flux::hemi_to_aos((size_t)ctx->sets.count * ctx->D, ctx->N, ctx->d_hemi, tmp, nullptr);
         if (e == hipSuccess) e = hipMemcpy(out, tmp, total * sizeof(double), hipMemcpyDeviceToHost);
-        (void)hipFree(tmp);
         if (e != hipSuccess) return fail(FLUX_E_DEVICE, "hemi copy: %s", hipGetErrorString(e));
         return FLUX_OK;
     }

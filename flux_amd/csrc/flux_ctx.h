@@ -5,8 +5,10 @@
 
 #include <chrono>
 #include <new>
+#include <optional>
 #include <string>
 #include <system_error>
+#include <utility>
 
 #include "../../include/flux_abi.h"
 #include "flux_device.h"
@@ -55,6 +57,44 @@ struct DeviceGuard {
     }
 };
 
+// The entry points' two device checks (abi.hip): FLUX_E_DEVICE unless a HIP device is visible, then FLUX_E_INVALID for one out of range ...
+int check_device(int device);
+int require_device(int device);  // ... or FLUX_E_DEVICE for either
+
+// What DevBuf<T>, Stream and Event share: each owns one handle, is move-only and empty by default, releases in its destructor or reset(), and
+// converts to the handle.  A release runs on the CURRENT device: the structs that hold owners (flux_ctx, flux_multi) make theirs current.
+template <class H, hipError_t (*Release)(H)> class Owner {
+  protected:
+    H h_ = nullptr;
+
+  public:
+    Owner() = default;
+    Owner(Owner &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    ~Owner() { reset(); }
+    void reset() {
+        if (H h = std::exchange(h_, nullptr)) (void)Release(h);
+    }
+    operator H() const { return h_; }
+};
+template <class T> hipError_t free_device(T *p) { return hipFree(p); }
+inline hipError_t drain_and_destroy(hipStream_t s) {  // (what the stream still runs may use what is released after it)
+    (void)hipStreamSynchronize(s);
+    return hipStreamDestroy(s);
+}
+template <class T> struct DevBuf : Owner<T *, free_device<T>> {  // a hipMalloc allocation of T
+    hipError_t alloc_bytes(size_t bytes) {  // releases what it held; hipMalloc's result
+        this->reset();
+        return hipMalloc((void **)&this->h_, bytes);
+    }
+    hipError_t alloc(size_t count) { return alloc_bytes(count * sizeof(T)); }
+};
+struct Stream : Owner<hipStream_t, drain_and_destroy> {
+    hipError_t create() { return hipStreamCreateWithFlags(&h_, hipStreamNonBlocking); }
+};
+struct Event : Owner<hipEvent_t, hipEventDestroy> {
+    hipError_t create() { return hipEventCreate(&h_); }
+};
+
 // The three phases of context creation (abi.hip): the job's checks, which need no device; the host scene build (scene_build.h),
 // its failures reported through fail(); the device half, which makes the context on `device` for the sample sets first_set +
 // k * set_stride and books its time from RUNTIME on.
@@ -74,38 +114,41 @@ int upload(const HostScene &host, const flux_job_cfg &cfg, uint64_t seed, int de
     } while (0)
 
 struct flux_ctx {
+    // Engaged by the destructor.  As the FIRST member it outlives every owner below, so their releases run with `device` current.
+    std::optional<flux::DeviceGuard> dying;
+    ~flux_ctx() { dying.emplace(device); }
     int device = 0;
     flux::RenderParams rp{};  // camera + table pointers; work fields set per launch
     uint64_t seed = 0;
     uint32_t n = 0, N = 0, D = 0, S = 0, W = 0, H = 0;
     flux::SetRange sets{0, 1, 0};  // sets with tables in this context (all S unless created by flux_ctx_create_sets)
-    flux::DevShape *d_shapes = nullptr;
-    flux::DevMaterial *d_mats = nullptr;
-    unsigned char *d_fscene = nullptr;  // the FAST scene image, regions as HostScene::fs lays them out (scene_build.h)
-    double2 *d_pix = nullptr, *d_disc = nullptr;
-    double *d_hemi = nullptr;
-    double *d_gloss = nullptr;  // FAST glossy-lobe factors of pixel_sets
-    double2 *d_glossx = nullptr;  // the glossy lobe's angles per held sample and exponent slot (RenderParams::glossx), or nullptr
-    int32_t *d_gxoff = nullptr;   // RenderParams::gx_off, with d_glossx
-    double *d_tput = nullptr;     // RenderParams::tput, or nullptr
-    double *d_lobe = nullptr;     // RenderParams::lobe_frame, or nullptr
-    flux::DevSetRows *d_setrows = nullptr;  // per table slot: where the set's rows of the sample tables start
-    int32_t *d_rowperm = nullptr, *d_invperm = nullptr;
-    unsigned long long *d_stats = nullptr;
+    flux::DevBuf<flux::DevShape> d_shapes;
+    flux::DevBuf<flux::DevMaterial> d_mats;  // the materials, followed by their bounce weights
+    flux::DevBuf<unsigned char> d_fscene;    // the FAST scene image, regions as HostScene::fs lays them out (scene_build.h)
+    flux::DevBuf<double2> d_pix, d_disc;
+    flux::DevBuf<double> d_hemi;
+    flux::DevBuf<double> d_gloss;     // FAST glossy-lobe factors of pixel_sets
+    flux::DevBuf<double2> d_glossx;   // the glossy lobe's angles per held sample and exponent slot (RenderParams::glossx), or empty
+    flux::DevBuf<int32_t> d_gxoff;    // RenderParams::gx_off, with d_glossx
+    flux::DevBuf<double> d_tput;      // RenderParams::tput, or empty
+    flux::DevBuf<double> d_lobe;      // RenderParams::lobe_frame, or empty
+    flux::DevBuf<flux::DevSetRows> d_setrows;  // per table slot: where the set's rows of the sample tables start
+    flux::DevBuf<int32_t> d_rowperm, d_invperm;
+    flux::DevBuf<unsigned long long> d_stats;
     bool stats_on = false;
     // extension: triangle meshes
-    flux::DevTri *d_tris = nullptr;
-    flux::DevNode *d_nodes = nullptr;
-    flux::DevNode4A *d_arena = nullptr;  // the 4-wide tree of the FAST traversal kernel (RenderParams::nodes4), or nullptr
-    flux::DevNodeQ *d_nodesq = nullptr;
+    flux::DevBuf<flux::DevTri> d_tris;
+    flux::DevBuf<flux::DevNode> d_nodes;
+    flux::DevBuf<flux::DevNode4A> d_arena;  // the 4-wide tree of the FAST traversal kernel (RenderParams::nodes4), or empty
+    flux::DevBuf<flux::DevNodeQ> d_nodesq;
     flux::BvhInfo bvh{};
     int traversal = FLUX_TRAVERSE_BVH;
     int variant = FLUX_KERNEL_DEFAULT;
     int math = FLUX_MATH_FAST;
     // scratch framebuffer for the host-output path
-    double *d_out = nullptr;
+    flux::DevBuf<double> d_out;
     size_t d_out_doubles = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    flux::Event ev0, ev1;
     bool timed = false;
     uint64_t device_bytes = 0;
     double U[3], V[3], Wv[3];

@@ -136,11 +136,11 @@ __global__ void assemble_rows_kernel(const double *__restrict__ gathered, double
 struct Rank {
     int device = 0;
     flux_ctx *ctx = nullptr;
-    hipStream_t stream = nullptr;
-    uint64_t count = 0;           // sets (or rows) this rank renders
-    double *d_render = nullptr;   // sets with count < cmax: the kernel's dense [H][count][3] output, copied into the padded share
-    double *d_share = nullptr;    // what this rank contributes to the gather: [H][cmax][3] or [rmax][W][3], padding zero
-    double *d_gathered = nullptr; // [G] x share
+    flux::Stream stream;
+    uint64_t count = 0;               // sets (or rows) this rank renders
+    flux::DevBuf<double> d_render;    // sets with count < cmax: the kernel's dense [H][count][3] output, copied into the padded share
+    flux::DevBuf<double> d_share;     // what this rank contributes to the gather: [H][cmax][3] or [rmax][W][3], padding zero
+    flux::DevBuf<double> d_gathered;  // [G] x share
     ncclComm_t comm = nullptr;
     std::string error;            // of its creation thread
     int rc = FLUX_OK;
@@ -156,38 +156,33 @@ struct flux_multi {
     uint32_t W = 0, H = 0, S = 0;
     uint64_t per_rank = 0;       // cmax (sets) or rmax (rows)
     size_t share_doubles = 0;    // doubles of one rank's share
-    double *d_frame = nullptr;   // devices[0]: [H][W][3]
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // devices[0]'s stream: kernel end, gather end, reassembly end, copy end
+    flux::DevBuf<double> d_frame;  // devices[0]: [H][W][3]
+    flux::Event ev[4];           // devices[0]'s stream: kernel end, gather end, reassembly end, copy end
     double timing[FLUX_MULTI_TIMING_WORDS] = {};
     bool comms_cached = false;
     int rccl_version = 0;
     uint64_t buffer_bytes = 0;
+
+    // The owners are released HERE, under a guard that outlives the release; a rank's in this order: stream drained, context, buffers, stream.
+    ~flux_multi() {  // (the communicators stay in the process-wide cache)
+        for (Rank &rk : ranks) {
+            DeviceGuard g(rk.device);
+            if (rk.stream) (void)hipStreamSynchronize(rk.stream);
+            flux_ctx_destroy(rk.ctx);
+            rk.d_render.reset();
+            rk.d_share.reset();
+            rk.d_gathered.reset();
+            rk.stream.reset();
+        }
+        if (!ranks.empty()) {
+            DeviceGuard g(ranks[0].device);
+            d_frame.reset();
+            for (flux::Event &e : ev) e.reset();
+        }
+    }
 };
 
 namespace {
-
-void free_multi(flux_multi *m) {
-    if (!m) return;
-    for (Rank &rk : m->ranks) {
-        DeviceGuard g(rk.device);
-        if (rk.stream) (void)hipStreamSynchronize(rk.stream);
-        flux_ctx_destroy(rk.ctx);
-        (void)hipFree(rk.d_render);
-        (void)hipFree(rk.d_share);
-        (void)hipFree(rk.d_gathered);
-        if (rk.stream) (void)hipStreamDestroy(rk.stream);
-    }
-    if (!m->ranks.empty()) {
-        DeviceGuard g(m->ranks[0].device);
-        (void)hipFree(m->d_frame);
-        for (hipEvent_t e : m->ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    delete m;  // (the communicators stay in the process-wide cache)
-}
-struct FreeMulti {
-    void operator()(flux_multi *m) const { free_multi(m); }
-};
 
 // the frame on devices[0]; when out_rgb != nullptr also copied to the host
 int render_frame(flux_multi *m, double *out_rgb) {
@@ -290,6 +285,119 @@ int render_frame(flux_multi *m, double *out_rgb) {
     return FLUX_OK;
 }
 
+// ---- the phases of flux_multi_create, after its argument checks ----------------------------------------------------------
+struct CommInit {  // the communicators of the device list `key` (none in loopback): the cache's, or made by ncclCommInitAll on `thread`
+    std::vector<int> key;
+    std::vector<ncclComm_t> comms;
+    std::string err;
+    bool nomem = false;
+    double ms = 0;
+    flux::JoiningThread thread;  // (the last member: joined before what it writes goes away)
+};
+
+// the cache lookup (flux_multi::comms_cached says what it found); on a miss the thread starts, and finish_comms must follow
+void start_comms(CommInit &ci, flux_multi &m) {
+    ci.comms.assign(ci.key.size(), nullptr);
+    if (m.loopback) return;
+    {
+        std::lock_guard<std::mutex> lk(g_rccl_mu);
+        auto it = g_comms.find(ci.key);
+        if (it != g_comms.end()) {
+            ci.comms = it->second;
+            m.comms_cached = true;
+        }
+        (void)g_rccl.GetVersion(&m.rccl_version);
+    }
+    if (!m.comms_cached)
+        ci.thread = flux::JoiningThread([&ci] {
+            const auto tc = std::chrono::steady_clock::now();
+            try {
+                std::vector<ncclComm_t> cs(ci.key.size(), nullptr);
+                const ncclResult_t r = g_rccl.CommInitAll(cs.data(), (int)cs.size(), ci.key.data());
+                if (r != ncclSuccess)
+                    ci.err = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r);
+                else
+                    ci.comms.swap(cs);
+            } catch (const std::bad_alloc &) {
+                ci.nomem = true;
+            }
+            ci.ms = ms_since(tc);
+        });
+}
+
+void finish_comms(CommInit &ci, const flux_multi &m) {  // joins the thread and hands what it made to the cache
+    ci.thread.join();
+    if (m.comms_cached || m.loopback || !ci.err.empty() || ci.nomem) return;
+    std::lock_guard<std::mutex> lk(g_rccl_mu);
+    auto ins = g_comms.emplace(ci.key, ci.comms);
+    if (!ins.second) {  // another thread created the same list meanwhile: keep the cached ones, drop ours
+        for (ncclComm_t c : ci.comms) (void)g_rccl.CommDestroy(c);
+        ci.comms = ins.first->second;
+    }
+}
+
+// Scene::from_data + Camera::new once, on this thread (the job is the same for every device: manager.rs:156-162); then every device uploads
+// the same host scene, concurrently.  Each rank's HOST word is this build: its context waited for it.  Returns the build's code; an upload's is in its Rank.
+int create_contexts(const flux_scene_desc &scene, const flux_job_cfg &cfg, uint64_t seed, flux_multi &m) {
+    const uint32_t G = (uint32_t)m.ranks.size();
+    const bool sets = m.shard == FLUX_SHARD_SETS;
+    const auto th0 = std::chrono::steady_clock::now();
+    flux::HostScene host;
+    if (int rc = flux::validate_job(scene, cfg, 0, sets ? G : 1)) return rc;
+    if (int rc = flux::build_host(scene, host)) return rc;
+    const double host_ms = ms_since(th0);
+    std::vector<flux::JoiningThread> th;
+    for (uint32_t g = 0; g < G; g++)
+        th.emplace_back([&, g] {
+            Rank &rk = m.ranks[g];
+            const auto tc = std::chrono::steady_clock::now();
+            flux::CreateLaps laps;
+            laps.ms[FLUX_CREATE_MS_HOST] = host_ms;
+            rk.rc = flux::no_throw([&] { return flux::upload(host, cfg, seed, rk.device, sets ? g : 0, sets ? G : 1, laps, &rk.ctx); });
+            if (rk.rc != FLUX_OK) rk.error = flux_last_error();
+            rk.create_ms = host_ms + ms_since(tc);
+        });
+    for (flux::JoiningThread &t : th) t.join();
+    return FLUX_OK;
+}
+
+int alloc_buffers(flux_multi &m, const std::vector<ncclComm_t> &comms) {  // per rank: stream, share, gather; then devices[0]'s frame and events
+    const uint32_t G = (uint32_t)m.ranks.size();
+    const bool sets = m.shard == FLUX_SHARD_SETS;
+    m.W = m.ranks[0].ctx->W;
+    m.H = m.ranks[0].ctx->H;
+    m.S = m.ranks[0].ctx->S;
+    const uint64_t total = sets ? m.S : m.H;  // dealt to the ranks in turn
+    m.per_rank = (total + G - 1) / G;
+    m.share_doubles = sets ? (size_t)m.H * m.per_rank * 3 : (size_t)m.per_rank * m.W * 3;
+    const size_t share_bytes = m.share_doubles * sizeof(double);
+    hipError_t e = hipSuccess;
+    for (uint32_t g = 0; g < G && e == hipSuccess; g++) {
+        Rank &rk = m.ranks[g];
+        rk.comm = comms[g];
+        rk.count = g < total ? (total - g + G - 1) / G : 0;
+        DeviceGuard dg(rk.device);
+        e = rk.stream.create();
+        if (e == hipSuccess) e = rk.d_share.alloc_bytes(share_bytes);
+        if (e == hipSuccess) e = hipMemset(rk.d_share, 0, share_bytes);  // padding stays zero (image.rs:55-59 writes never-received rows as zeros)
+        if (e == hipSuccess) e = rk.d_gathered.alloc_bytes(share_bytes * G);
+        m.buffer_bytes += share_bytes * (G + 1);
+        if (e == hipSuccess && sets && rk.count && rk.count != m.per_rank) {
+            e = rk.d_render.alloc_bytes((size_t)m.H * rk.count * 24);
+            m.buffer_bytes += (size_t)m.H * rk.count * 24;
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e == hipSuccess) {
+        DeviceGuard dg(m.ranks[0].device);
+        e = m.d_frame.alloc_bytes((size_t)m.H * m.W * 24);
+        m.buffer_bytes += (size_t)m.H * m.W * 24;
+        for (int k = 0; k < 4 && e == hipSuccess; k++) e = m.ev[k].create();
+    }
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FLUX_E_NOMEM : FLUX_E_DEVICE, "flux_multi_create: %s", hipGetErrorString(e));
+    return FLUX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -302,10 +410,8 @@ int flux_multi_create(const flux_scene_desc *scene, const flux_job_cfg *cfg, uin
     const bool loopback = (shard & FLUX_SHARD_LOOPBACK) != 0;
     shard &= ~FLUX_SHARD_LOOPBACK;
     if (shard != FLUX_SHARD_AUTO && shard != FLUX_SHARD_SETS && shard != FLUX_SHARD_ROWS) return fail(FLUX_E_INVALID, "unknown shard mode %d", shard);
-    const int ndev = flux_device_count();
-    if (ndev < 1) return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     for (uint64_t a = 0; a < num_devices; a++) {
-        if (devices[a] < 0 || devices[a] >= ndev) return fail(FLUX_E_INVALID, "device %d out of range [0,%d)", devices[a], ndev);
+        if (int rc = flux::check_device(devices[a])) return rc;
         for (uint64_t b = 0; b < a && !loopback; b++)
             if (devices[a] == devices[b]) return fail(FLUX_E_INVALID, "device %d is listed twice", devices[a]);
     }
@@ -315,132 +421,37 @@ int flux_multi_create(const flux_scene_desc *scene, const flux_job_cfg *cfg, uin
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t G = (uint32_t)num_devices;
 
-    std::string err;
     if (!loopback) {
+        std::string err;
         std::lock_guard<std::mutex> lk(g_rccl_mu);
         if (!rccl_load(err)) return fail(FLUX_E_DEVICE, "%s", err.c_str());
     }
     return flux::no_throw([&] {
-        std::unique_ptr<flux_multi, FreeMulti> m(new flux_multi());
+        std::unique_ptr<flux_multi> m(new flux_multi());
         m->shard = shard;
         m->loopback = loopback;
         m->ranks.resize(G);
         for (uint32_t g = 0; g < G; g++) m->ranks[g].device = devices[g];
-
-        // communicators: from the cache, or created on a thread of their own while the contexts come up
-        const std::vector<int> key(devices, devices + G);
-        std::vector<ncclComm_t> comms;
-        std::string comm_err;
-        bool comm_nomem = false;
-        double comm_ms = 0;
-        if (loopback) {
-            comms.assign(G, nullptr);
-        } else {
-            std::lock_guard<std::mutex> lk(g_rccl_mu);
-            auto it = g_comms.find(key);
-            if (it != g_comms.end()) {
-                comms = it->second;
-                m->comms_cached = true;
-            }
-            (void)g_rccl.GetVersion(&m->rccl_version);
-        }
-        flux::JoiningThread comm_thread;
-        if (!m->comms_cached && !loopback)
-            comm_thread = flux::JoiningThread([&] {
-                const auto tc = std::chrono::steady_clock::now();
-                try {
-                    std::vector<ncclComm_t> cs(G, nullptr);
-                    const ncclResult_t r = g_rccl.CommInitAll(cs.data(), (int)G, key.data());
-                    if (r != ncclSuccess)
-                        comm_err = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r);
-                    else
-                        comms.swap(cs);
-                } catch (const std::bad_alloc &) {
-                    comm_nomem = true;
-                }
-                comm_ms = ms_since(tc);
-            });
-        // Scene::from_data + Camera::new once, on this thread (the job is the same for every device: manager.rs:156-162); then
-        // every device uploads the same host scene, concurrently.  Each rank's HOST word is this build: its context waited for it.
-        const auto th0 = std::chrono::steady_clock::now();
-        flux::HostScene host;
-        int host_rc = flux::validate_job(*scene, *cfg, 0, shard == FLUX_SHARD_SETS ? G : 1);
-        if (host_rc == FLUX_OK) host_rc = flux::build_host(*scene, host);
-        const double host_ms = ms_since(th0);
-        std::vector<flux::JoiningThread> th;
-        for (uint32_t g = 0; g < G && host_rc == FLUX_OK; g++)
-            th.emplace_back([&, g] {
-                Rank &rk = m->ranks[g];
-                const auto tc = std::chrono::steady_clock::now();
-                flux::CreateLaps laps;
-                laps.ms[FLUX_CREATE_MS_HOST] = host_ms;
-                const bool sets = shard == FLUX_SHARD_SETS;
-                rk.rc = flux::no_throw([&] { return flux::upload(host, *cfg, seed, rk.device, sets ? g : 0, sets ? G : 1, laps, &rk.ctx); });
-                if (rk.rc != FLUX_OK) rk.error = flux_last_error();
-                rk.create_ms = host_ms + ms_since(tc);
-            });
-        for (flux::JoiningThread &t : th) t.join();
-        comm_thread.join();
-        if (!m->comms_cached && !loopback && comm_err.empty() && !comm_nomem) {
-            std::lock_guard<std::mutex> lk(g_rccl_mu);
-            auto ins = g_comms.emplace(key, comms);
-            if (!ins.second) {  // another thread created the same list meanwhile: keep the cached ones, drop ours
-                for (ncclComm_t c : comms) (void)g_rccl.CommDestroy(c);
-                comms = ins.first->second;
-            }
-        }
+        CommInit ci{std::vector<int>(devices, devices + G)};
+        start_comms(ci, *m);  // the communicators come up while the contexts do; their thread is joined before any result is examined
+        const int host_rc = create_contexts(*scene, *cfg, seed, *m);
+        finish_comms(ci, *m);
         if (host_rc != FLUX_OK) return host_rc;  // (its message is this thread's flux_last_error already)
-        for (uint32_t g = 0; g < G; g++)
-            if (m->ranks[g].rc != FLUX_OK) return fail(m->ranks[g].rc, "device %d: %s", m->ranks[g].device, m->ranks[g].error.c_str());
-        if (comm_nomem) return fail(FLUX_E_NOMEM, "ncclCommInitAll: host allocation failed");
-        if (!comm_err.empty()) return fail(FLUX_E_DEVICE, "%s", comm_err.c_str());
-        m->W = m->ranks[0].ctx->W;
-        m->H = m->ranks[0].ctx->H;
-        m->S = m->ranks[0].ctx->S;
-        if (shard == FLUX_SHARD_SETS) {
-            m->per_rank = (m->S + G - 1) / G;
-            m->share_doubles = (size_t)m->H * m->per_rank * 3;
-        } else {
-            m->per_rank = (m->H + G - 1) / G;
-            m->share_doubles = (size_t)m->per_rank * m->W * 3;
-        }
-        hipError_t e = hipSuccess;
-        for (uint32_t g = 0; g < G && e == hipSuccess; g++) {
-            Rank &rk = m->ranks[g];
-            rk.comm = comms[g];
-            const uint64_t total = shard == FLUX_SHARD_SETS ? m->S : m->H;
-            rk.count = g < total ? (total - g + G - 1) / G : 0;
-            DeviceGuard dg(rk.device);
-            e = hipStreamCreateWithFlags(&rk.stream, hipStreamNonBlocking);
-            const size_t share_bytes = m->share_doubles * sizeof(double);
-            if (e == hipSuccess) e = hipMalloc((void **)&rk.d_share, share_bytes);
-            if (e == hipSuccess) e = hipMemset(rk.d_share, 0, share_bytes);  // padding stays zero (image.rs:55-59 writes never-received rows as zeros)
-            if (e == hipSuccess) e = hipMalloc((void **)&rk.d_gathered, share_bytes * G);
-            m->buffer_bytes += share_bytes * (G + 1);
-            if (e == hipSuccess && shard == FLUX_SHARD_SETS && rk.count && rk.count != m->per_rank) {
-                e = hipMalloc((void **)&rk.d_render, (size_t)m->H * rk.count * 24);
-                m->buffer_bytes += (size_t)m->H * rk.count * 24;
-            }
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
-        if (e == hipSuccess) {
-            DeviceGuard dg(m->ranks[0].device);
-            e = hipMalloc((void **)&m->d_frame, (size_t)m->H * m->W * 24);
-            m->buffer_bytes += (size_t)m->H * m->W * 24;
-            for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventCreate(&m->ev[k]);
-        }
-        if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? FLUX_E_NOMEM : FLUX_E_DEVICE, "flux_multi_create: %s", hipGetErrorString(e));
+        for (const Rank &rk : m->ranks)
+            if (rk.rc != FLUX_OK) return fail(rk.rc, "device %d: %s", rk.device, rk.error.c_str());
+        if (ci.nomem) return fail(FLUX_E_NOMEM, "ncclCommInitAll: host allocation failed");
+        if (!ci.err.empty()) return fail(FLUX_E_DEVICE, "%s", ci.err.c_str());
+        if (int rc = alloc_buffers(*m, ci.comms)) return rc;
         m->timing[0] = ms_since(t0);
         for (const Rank &rk : m->ranks)
             if (rk.create_ms > m->timing[1]) m->timing[1] = rk.create_ms;
-        m->timing[2] = comm_ms;
+        m->timing[2] = ci.ms;
         *out = m.release();
         return FLUX_OK;
     });
 }
 
-void flux_multi_destroy(flux_multi *m) { free_multi(m); }
+void flux_multi_destroy(flux_multi *m) { delete m; }
 
 int flux_multi_render_frame(flux_multi *m, double *out_rgb) {
     if (!m) return fail(FLUX_E_INVALID, "null flux_multi");
@@ -515,8 +526,8 @@ int flux_render_frame_multi(const flux_scene_desc *scene, const flux_job_cfg *cf
     if (!out_rgb) return fail(FLUX_E_INVALID, "null output pointer");
     std::vector<int> all;
     if (!devices) {
+        if (int rc = flux::check_device(0)) return rc;  // (device 0 is there unless none is)
         const int ndev = flux_device_count();
-        if (ndev < 1) return fail(FLUX_E_DEVICE, "no HIP device visible (this library has no CPU fallback)");
         if (num_devices == 0) num_devices = (uint64_t)ndev;
         if (num_devices > (uint64_t)ndev) return fail(FLUX_E_INVALID, "%llu devices requested, %d visible", (unsigned long long)num_devices, ndev);
         for (uint64_t d = 0; d < num_devices; d++) all.push_back((int)d);
