@@ -33,6 +33,10 @@ SHARD_LOOPBACK = 0x100
 MULTI_INFO_WORDS = 8
 MULTI_TIMING_WORDS = 8
 ABI_VERSION = 3
+# first-hit feature buffers (include/flux_abi.h FLUX_AOV_*): doubles per pixel and each channel's first
+AOV_CHANNELS = 8
+AOV_ALBEDO_OFFSET, AOV_NORMAL_OFFSET, AOV_DEPTH, AOV_COVERAGE = 0, 3, 6, 7
+AOV_ALBEDO, AOV_NORMAL = slice(AOV_ALBEDO_OFFSET, AOV_ALBEDO_OFFSET + 3), slice(AOV_NORMAL_OFFSET, AOV_NORMAL_OFFSET + 3)
 
 
 class FluxMaterial(C.Structure):
@@ -90,6 +94,8 @@ SYMBOLS = {
     "flux_render_rows": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]),
     "flux_render_rows_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
     "flux_render_sets_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
+    "flux_render_aov_rows": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]),
+    "flux_render_aov_rows_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
     "flux_ctx_set_kernel": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_traversal": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_math": (C.c_int, [_P, C.c_int]),

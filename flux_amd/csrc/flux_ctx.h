@@ -148,6 +148,9 @@ struct flux_ctx {
     // scratch framebuffer for the host-output path
     flux::DevBuf<double> d_out;
     size_t d_out_doubles = 0;
+    // ... and the feature buffers' own (flux_render_aov_rows)
+    flux::DevBuf<double> d_aov;
+    size_t d_aov_doubles = 0;
     flux::Event ev0, ev1;
     bool timed = false;
     uint64_t device_bytes = 0;

@@ -95,6 +95,10 @@ struct LaunchPlan {
                                    // (render_body.inc shade_primary_hits); FLUX_SPLIT_UNIFORM_A=0: the general step everywhere
 };
 LaunchPlan plan_render(const RenderParams &p, int variant, int math);
+// The same for the feature-buffer kernel (aov_body.inc aov_kernel): `kernel` is 0 (or -1: nothing to do), `copy` never kCopyFastDiel --
+// a first hit runs no lobe --, `lds` the per-lane BVH stack of a mesh scene and nothing else, `blocks` one wave per pixel in
+// map_wave's order from 64 samples on and 64 / N pixels per wave below.
+LaunchPlan plan_aov(const RenderParams &p, int math);
 
 // LDS of the per-lane stacks of `lanes` lanes: the STRICT (f, s) recursion stack, 4 doubles per level, and the BVH traversal stack,
 // one int per level

@@ -33,6 +33,10 @@ hipError_t hemi_to_aos(size_t SD, size_t N, const double *in, double *out, hipSt
 // what plan_render (flux_plan.h) answers for the same arguments.
 hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream);
 
+// The first-hit feature buffers of the rows p names (aov_body.inc): p.out = [num_rows][W][FLUX_AOV_CHANNELS].  Runs what plan_aov
+// (flux_plan.h) answers for the same arguments.
+hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream);
+
 // Scene::shade for caller-supplied rays (device pointers; rays = n x (origin, direction)).
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream);

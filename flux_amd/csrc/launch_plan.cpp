@@ -170,4 +170,27 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     return L;
 }
 
+// The feature-buffer kernel: render_static_kernel's two layouts with the refill kernels' pixel order from 64 samples on.  No
+// recursion stack whatever the arithmetic, so the BVH stack starts at the LDS base (aov_body.inc).
+LaunchPlan plan_aov(const RenderParams &p, int math) {
+    LaunchPlan L;
+    L.copy = math == FLUX_MATH_STRICT ? kCopyStrict : kCopyFast;
+    const uint32_t N = p.nsamp;
+    const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
+    if (npix == 0 || p.set_count <= 0 || N == 0) return L;
+    const uint32_t ppw = N >= 64u ? 1u : 64u / N;
+    uint64_t waves = (npix + ppw - 1) / ppw;
+    // grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
+    if (N >= 64u && p.num_sets == (uint32_t)p.img_w)
+        waves = 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows +
+                        ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
+    const unsigned wpb = FLUX_BLOCK_THREADS / 64;
+    L.kernel = 0;
+    L.block = FLUX_BLOCK_THREADS;
+    L.blocks = (waves + wpb - 1) / wpb;
+    L.tris = p.n_tris > 0 ? 1 : 0;
+    L.lds = lane_stacks_lds(FLUX_MATH_FAST, 0, L.tris != 0, (size_t)p.bvh_stack, L.block);
+    return L;
+}
+
 }  // namespace flux

@@ -41,7 +41,9 @@
 //    dielectric lobe neither TYP nor HQ (the hit queue), which the plan never picks for a scene with a dielectric;
 //  * render_bvh_kernel<STATS>, render_bvh4_kernel<STATS, LDS_SCENE, TYP>: FAST -- TYP only with LDS_SCENE, and not in the copy
 //    with the dielectric lobe;
-//  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy.
+//  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy;
+//  * aov_kernel<TRIS> (aov_body.inc, the first-hit feature buffers: launch_plan.cpp plan_aov): STRICT and FAST, not the copy with the
+//    dielectric lobe -- a first hit runs no lobe.
 #include "flux_device.h"
 #include "flux_plan.h"
 #include "flux_tables.h"
@@ -100,6 +102,7 @@ static_assert(FLUX_BVH4_EARLY_AT >= FLUX_BVH_REFILL_AT,
 namespace flux {
 namespace strict {
 #include "render_body.inc"
+#include "aov_body.inc"
 }  // namespace strict
 }  // namespace flux
 #undef FLUX_FAST
@@ -115,6 +118,7 @@ namespace strict {
 namespace flux {
 namespace fast {
 #include "render_body.inc"
+#include "aov_body.inc"
 }  // namespace fast
 }  // namespace flux
 #undef FLUX_DIEL
@@ -232,6 +236,13 @@ hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream
         case kCopyFastDiel: return fast_diel::launch_render_impl(L, p, stream);
     }
     return hipErrorInvalidValue;
+}
+
+// the feature-buffer kernel as plan_aov lays it out; a scene with a Dielectric runs the FAST copy (no lobe behind a first hit)
+hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream) {
+    const LaunchPlan L = plan_aov(p, math);
+    if (L.kernel < 0) return hipSuccess;
+    return L.copy == kCopyStrict ? strict::launch_aov_impl(L, p, stream) : fast::launch_aov_impl(L, p, stream);
 }
 
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,

@@ -5,12 +5,16 @@
 // wait (:92-94), ImageBuilder writes "<scene_name>.ppm" into the cwd and prints the total time
 // (manager.rs:326-335).  -n/--node ADDRESS[:PORT] adds NetworkWorkers (flux_node processes, flux_net.hpp) and
 // -L leaves the local GPUs out, as in main.rs:37-66.  Additions: --seed (the reference seeds from OS
-// entropy), --gpus, --outdir, --split.  Not carried over: -g (SDL preview), rejected.
+// entropy), --gpus, --outdir, --split, --aov.  Not carried over: -g (SDL preview), rejected.
 //
 // --split sets|rows|units: how the local GPUs share a frame.  `units` is the reference's scheme -- one worker per device pulling
 // WorkUnits from the shared channel (manager.rs:100) --, `sets` / `rows` hand the node's GPUs to ONE MultiGpuWorker (flux_multi_*:
 // per-device contexts with 1/G of the tables, one launch per device, one RCCL all-gather).  Default: sets (rows below 64 spp) when
 // two or more local GPUs are the whole pool, units otherwise (a pool with network nodes needs the shared channel's balancing).
+// --aov: after the frame is written, the first-hit feature buffers of the same job (include/flux_abi.h flux_render_aov_rows: the
+// job's --seed and -r) are rendered on local device 0 and written beside it as <scene_name>.albedo.ppm, .normal.ppm, .depth.ppm
+// and .coverage.ppm (flux_host.hpp aov_image).  They never travel through the worker / node protocol, so a run without a local
+// GPU (-L, --gpus 0, none visible) refuses the flag before any job starts.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,13 +46,16 @@ struct Config {  // flux/src/main.rs:115-124
     int gpus = -1;
     std::string outdir = ".";
     std::string split = "auto";
+    bool aov = false;
 };
 
 void usage() {
     std::fprintf(stderr,
                  "flux (MI355X render path)\n\nUSAGE:\n    flux [FLAGS] [OPTIONS] <scene_file>\n\nFLAGS:\n"
                  "    -L               Do not use the local host (its GPUs) for rendering\n"
-                 "    -g               Show a live graphical preview window during rendering (not supported)\n\nOPTIONS:\n"
+                 "    -g               Show a live graphical preview window during rendering (not supported)\n"
+                 "        --aov        Also write <scene_name>.albedo.ppm, .normal.ppm, .depth.ppm and .coverage.ppm: the first-hit\n"
+                 "                     feature buffers of the frame, rendered on local GPU 0\n\nOPTIONS:\n"
                  "    -d, --depth <DEPTH>          Tracing depth [default 5]\n"
                  "    -n, --node <ADDRESS[:PORT]>  Render using the flux_node process at this address (repeatable)\n"
                  "    -R, --rows <COUNT>           Image rows per work unit [default 50]\n"
@@ -103,6 +110,8 @@ Config config_from_args(int argc, char **argv) {
             c.seed = (uint64_t)parse_usize("--seed", need("--seed"));
         } else if (a == "--gpus") {
             c.gpus = (int)parse_usize("--gpus", need("--gpus"));
+        } else if (a == "--aov") {
+            c.aov = true;
         } else if (a == "--outdir") {
             c.outdir = need("--outdir");
         } else if (a == "--split") {
@@ -143,6 +152,10 @@ int main(int argc, char **argv) {
     } catch (const FluxError &e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;
+    }
+    if (config.aov && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
+        std::fprintf(stderr, "error: --aov renders the feature buffers on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
+        return 2;
     }
     // main.rs:37-66: the local worker(s) unless -L, then one NetworkWorker per -n
     int ndev = config.use_local_worker ? flux_device_count() : 0;
@@ -227,6 +240,24 @@ int main(int argc, char **argv) {
                                config.sample_root * config.sample_root;
         std::printf("wrote %s (%.1f Msamples/s incl. context creation)\n", image_builder.written_path.c_str(),
                     image_builder.total_time_s > 0 ? samples / image_builder.total_time_s / 1e6 : 0.0);
+    }
+    if (rc == 0 && config.aov && !image_builder.written_path.empty()) {
+        try {
+            const std::vector<double> aov = render_feature_buffers(
+                s, JobConfiguration{config.sample_root, config.max_depth, config.rows_per_work_unit}, config.seed, 0);
+            const size_t w = s.output_settings.image_width, h = s.output_settings.image_height;
+            const struct { AovKind kind; const char *name; } outs[] = {
+                {AovKind::Albedo, "albedo"}, {AovKind::Normal, "normal"}, {AovKind::Depth, "depth"}, {AovKind::Coverage, "coverage"}};
+            for (const auto &o : outs) {
+                const std::string path = config.outdir + "/" + s.scene_name + "." + o.name + ".ppm";
+                const std::vector<double> img = aov_image(aov.data(), w, h, o.kind);
+                if (flux_write_ppm(path.c_str(), img.data(), w, h, nullptr) != FLUX_OK) throw FluxError(FLUX_E_IO, flux_last_error());
+                std::printf("wrote %s\n", path.c_str());
+            }
+        } catch (const FluxError &e) {
+            std::fprintf(stderr, "error: --aov: %s\n", e.what());
+            rc = 1;
+        }
     }
     return rc;
 }

@@ -224,6 +224,55 @@ AbiScene::AbiScene(const SceneData &sd) : name(sd.scene_name) {
     desc.meshes = nullptr;
 }
 
+std::vector<double> render_feature_buffers(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device) {
+    AbiScene abi(scene_data);
+    flux_job_cfg cfg{config.sample_root, config.max_trace_depth, config.rows_per_work_unit};
+    flux_ctx *ctx = nullptr;
+    if (int rc = flux_ctx_create(&abi.desc, &cfg, seed, device, &ctx)) throw FluxError(rc, flux_last_error());
+    const size_t w = scene_data.output_settings.image_width, h = scene_data.output_settings.image_height;
+    std::vector<double> aov(w * h * FLUX_AOV_CHANNELS);
+    const int rc = flux_render_aov_rows(ctx, 0, h - 1, aov.data());
+    const std::string why = rc == FLUX_OK ? "" : flux_last_error();
+    flux_ctx_destroy(ctx);
+    if (rc != FLUX_OK) throw FluxError(rc, why);
+    return aov;
+}
+
+std::vector<double> aov_image(const double *aov, size_t width, size_t height, AovKind kind) {
+    const size_t npix = width * height;
+    std::vector<double> rgb(npix * 3);
+    double t_max = 0.0;
+    for (size_t k = 0; k < npix; k++) {
+        const double t = aov[k * FLUX_AOV_CHANNELS + FLUX_AOV_DEPTH];
+        if (std::isfinite(t) && t > t_max) t_max = t;
+    }
+    if (!(t_max > 0.0)) t_max = 1.0;
+    for (size_t k = 0; k < npix; k++) {
+        const double *p = aov + k * FLUX_AOV_CHANNELS;
+        double *o = rgb.data() + k * 3;
+        switch (kind) {
+            case AovKind::Albedo:
+                for (int c = 0; c < 3; c++) o[c] = p[FLUX_AOV_ALBEDO + c] < 1.0 ? p[FLUX_AOV_ALBEDO + c] : 1.0;
+                break;
+            case AovKind::Normal: {
+                const double *n = p + FLUX_AOV_NORMAL;
+                const double len = std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+                for (int c = 0; c < 3; c++) o[c] = len > 0.0 ? 0.5 + 0.5 * (n[c] / len) : 0.5;
+                break;
+            }
+            case AovKind::Depth: {
+                const double t = p[FLUX_AOV_DEPTH];
+                o[0] = o[1] = o[2] = std::isfinite(t) ? p[FLUX_AOV_COVERAGE] * (1.0 - t / t_max) : 0.0;
+                break;
+            }
+            case AovKind::Coverage:
+                o[0] = o[1] = o[2] = p[FLUX_AOV_COVERAGE];
+                break;
+        }
+    }
+    return rgb;
+}
+
 std::vector<WorkUnit> Job::work_units() const {
     const uint64_t h = scene_data.output_settings.image_height;
     int64_t n = flux_work_units(h, config.rows_per_work_unit, nullptr, 0);

@@ -321,4 +321,18 @@ struct AbiScene {
     explicit AbiScene(const SceneData &sd);
 };
 
+// ---- first-hit feature buffers (include/flux_abi.h flux_render_aov_rows) --------------------------
+// The frame's albedo, normal, depth and coverage, [H][W][FLUX_AOV_CHANNELS]: a context on `device` for the job, one
+// flux_render_aov_rows over the frame, the context dropped.  Throws FluxError with the library's message.
+std::vector<double> render_feature_buffers(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device);
+
+// One channel group of such a frame as an image for flux_write_ppm: [H][W] RGB in [0, 1].
+//   Albedo    min(1, x) per channel
+//   Normal    0.5 + 0.5 n / |n| (the zero vector: 0.5)
+//   Depth     grey coverage * (1 - t / t_max), t_max the largest finite depth of the frame (1 if there is none above 0); a
+//             non-finite depth: 0
+//   Coverage  grey
+enum class AovKind { Albedo, Normal, Depth, Coverage };
+std::vector<double> aov_image(const double *aov, size_t width, size_t height, AovKind kind);
+
 }  // namespace flux_host

@@ -125,6 +125,23 @@ class Renderer:
         _lib.check(_lib.lib.flux_render_sets_device(self._handle(), first_set, set_stride, num_sets,
                                                     C.c_void_p(d_out_ptr), C.c_void_p(stream)))
 
+    # -- first-hit feature buffers ---------------------------------------------
+    def render_aov(self, row_start: int = 0, row_end=None) -> np.ndarray:
+        """Albedo, normal, depth and coverage of rows [row_start, row_end] inclusive (default: the frame), [rows, W, 8]:
+        flux_render_aov_rows.  Channels: flux_amd.AOV_ALBEDO, AOV_NORMAL (slices), AOV_DEPTH, AOV_COVERAGE."""
+        if row_end is None:
+            row_end = self.height - 1
+        if row_start < 0 or row_end < row_start:
+            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        out = np.empty((row_end - row_start + 1, self.width, _lib.AOV_CHANNELS), dtype=np.float64)
+        _lib.check(_lib.lib.flux_render_aov_rows(self._handle(), row_start, row_end, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def render_aov_device(self, first_row: int, row_stride: int, num_rows: int, d_out_ptr: int, stream: int = 0):
+        """Asynchronous device-resident feature buffers (see flux_render_aov_rows_device): num_rows * W * 8 doubles."""
+        _lib.check(_lib.lib.flux_render_aov_rows_device(self._handle(), first_row, row_stride, num_rows,
+                                                        C.c_void_p(d_out_ptr), C.c_void_p(stream)))
+
     def debug_shade(self, origins, directions, depth: int = 1, set_index: int = 0, sample_index: int = 0):
         """Scene::shade on the device for the given rays (flux_debug_shade): (rgb [n,3], first-hit index [n], t [n])."""
         o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)

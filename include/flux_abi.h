@@ -235,6 +235,43 @@ int flux_render_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stri
 int flux_render_sets_device(flux_ctx *ctx, uint64_t first_set, uint64_t set_stride, uint64_t num_sets,
                             void *d_out_rgb, void *hip_stream);
 
+/* First-hit feature buffers (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): what a denoiser,
+ * a compositor or an edge-aware filter takes beside the beauty pass.  For pixel (row, col) of a context that holds every sample
+ * set, with set = row_perm(row)[col] % S and N = sample_root^2, take for every i < N the primary ray the render kernels build for
+ * (row, col, set, i) (trace.rs:71-80: pixel sample pixel_sets[set][i], lens sample disc_sets[set][i]) and its first hit by
+ * Scene::hit under the context's arithmetic (flux_ctx_set_math, the routing to STRICT for non-unit plane normals included) and
+ * traversal (flux_ctx_set_traversal): T_MIN, ties to the lowest YAML index, triangles after all shapes.  Per sample:
+ *               hit                                                                   miss
+ *   albedo (3)  a(material)                                                           background
+ *   normal (3)  the shading normal exactly as the bounce would use it: sphere         0
+ *               ((o - c) + t d) invert / radius; plane / disk as stored (never
+ *               normalised or flipped); box face axis (negated for `invert`);
+ *               triangle's stored unit normal
+ *   t           the hit distance                                                      -
+ *   covered     1                                                                     0
+ * a(m): Matte diffuse_coefficient * diffuse_color; Reflective / Glossy reflect_amount * reflect_color; Dielectric transmit_color;
+ * Emissive power * color if -n.d > 0 (materials.rs:44, the side it emits to), else 0.  Values are not clamped.
+ * The pixel's FLUX_AOV_CHANNELS doubles: [0..2] the mean albedo over the N samples, [3..5] the mean normal over the N samples (a
+ * miss contributes 0), [6] depth = the sum of t over the hitting samples / their number, 0 if none (a plane's +inf hit passes
+ * through as inf), [7] coverage = hitting samples / N.  Per-lane partial sums are combined in a fixed order, so the buffers are
+ * bit-reproducible run to run and independent of how rows are grouped into calls.  DESIGN.md section 5e. */
+#define FLUX_AOV_CHANNELS 8
+#define FLUX_AOV_ALBEDO 0
+#define FLUX_AOV_NORMAL 3
+#define FLUX_AOV_DEPTH 6
+#define FLUX_AOV_COVERAGE 7
+/* Rows [row_start, row_end] inclusive into caller-owned host memory: (row_end-row_start+1) * image_width * FLUX_AOV_CHANNELS
+ * doubles, row-major.  Synchronous, argument checks as flux_render_rows.  The call stages through a device buffer of its own:
+ * the scratch framebuffer of flux_render_rows is neither resized nor reused. */
+int flux_render_aov_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out);
+/* Device-resident: rows first_row + k*row_stride, k < num_rows, to d_out (device pointer, num_rows * image_width *
+ * FLUX_AOV_CHANNELS doubles), asynchronously on `hip_stream`.  Argument checks as flux_render_rows_device: row_stride >= 1,
+ * num_rows == 0 is a no-op, and a context of flux_ctx_create_sets is refused with FLUX_E_INVALID (every row uses every set).
+ * One kernel beside the render kernels, with no atomics and no effect on flux_ctx_stats; its launch is recorded between the
+ * context's two events, so flux_ctx_last_kernel_ms reports it when it is the most recent launch. */
+int flux_render_aov_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
+                                void *d_out, void *hip_stream);
+
 /* Render-kernel variants (all produce the same image within rounding):
  *   0 = default (FLUX_KERNEL_SPLIT where it applies, else FLUX_KERNEL_REFILL; STATIC below 64 spp)
  *   1 = FLUX_KERNEL_STATIC: one lane per sample, lanes idle once their path ends
@@ -283,7 +320,7 @@ int flux_ctx_set_math(flux_ctx *ctx, int mode);
 int flux_ctx_set_traversal(flux_ctx *ctx, int mode);
 
 /* Device time (ms, HIP events on the launch stream) of the most recent render
- * kernel launched through this context; synchronises that launch. <0 on error. */
+ * or feature-buffer kernel launched through this context; synchronises that launch. <0 on error. */
 double flux_ctx_last_kernel_ms(flux_ctx *ctx);
 
 /* Path statistics of the launches since the last reset (requires
