@@ -99,7 +99,7 @@ def build_host(force=False, verbose=False):
     build_hip(force=False, verbose=verbose)
     outs = []
     common = [os.path.join(HOST_DIR, s) for s in HOST_SOURCES]
-    hdrs = [os.path.join(HOST_DIR, h) for h in ("flux_host.hpp", "yaml_lite.hpp", "cbor.hpp", "flux_net.hpp", "scene_schema.hpp")] + [os.path.join(ROOT, "include", "flux_abi.h")]
+    hdrs = [os.path.join(HOST_DIR, h) for h in ("flux_host.hpp", "yaml_lite.hpp", "cbor.hpp", "flux_net.hpp", "scene_schema.hpp")] + [os.path.join(ROOT, "include", "flux_abi.h"), os.path.join(CSRC, "joining_thread.h")]
     for name, main in HOST_BINARIES.items():
         out = os.path.join(HOST_DIR, name)
         src = [os.path.join(HOST_DIR, main)] + common

@@ -208,6 +208,7 @@ int main(int argc, char **argv) {
     if (multi) std::printf("The %d local GPU(s) render whole frames as one worker (--split %s: one launch per device, one RCCL all-gather)\n", ndev, split.c_str());
 
     // flux/src/main.rs:70-111: manager, image builder, schedule one job, wait, shut everything down
+    const JobConfiguration job_config{config.sample_root, config.max_depth, config.rows_per_work_unit};
     ImageBuilder image_builder;
     image_builder.output_dir = config.outdir;
     int rc = 0;
@@ -216,8 +217,7 @@ int main(int argc, char **argv) {
         rc = 1;
     } else {
         RenderManager manager(handles);
-        JobHandle job = manager.schedule_job(
-            s, JobConfiguration{config.sample_root, config.max_depth, config.rows_per_work_unit}, image_builder.sender());
+        JobHandle job = manager.schedule_job(s, job_config, image_builder.sender());
         job.wait();
         manager.stop();
     }
@@ -243,8 +243,7 @@ int main(int argc, char **argv) {
     }
     if (rc == 0 && config.aov && !image_builder.written_path.empty()) {
         try {
-            const std::vector<double> aov = render_feature_buffers(
-                s, JobConfiguration{config.sample_root, config.max_depth, config.rows_per_work_unit}, config.seed, 0);
+            const std::vector<double> aov = render_feature_buffers(s, job_config, config.seed, 0);
             const size_t w = s.output_settings.image_width, h = s.output_settings.image_height;
             const struct { AovKind kind; const char *name; } outs[] = {
                 {AovKind::Albedo, "albedo"}, {AovKind::Normal, "normal"}, {AovKind::Depth, "depth"}, {AovKind::Coverage, "coverage"}};

@@ -157,6 +157,35 @@ flux_material to_abi(const MaterialData &m) {
     return o;
 }
 
+flux_job_cfg to_abi(const JobConfiguration &c) { return flux_job_cfg{c.sample_root, c.max_trace_depth, c.rows_per_work_unit}; }
+
+// the C ABI's handles, destroyed on every path out of their scope
+struct CtxDestroy { void operator()(flux_ctx *c) const { flux_ctx_destroy(c); } };
+struct MultiDestroy { void operator()(flux_multi *m) const { flux_multi_destroy(m); } };
+using CtxPtr = std::unique_ptr<flux_ctx, CtxDestroy>;
+using MultiPtr = std::unique_ptr<flux_multi, MultiDestroy>;
+
+// Scene::from_data + Camera::new (workers.rs:46-54); empty with the library's message in flux_last_error(), its code in *rc
+CtxPtr create_ctx(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device, int *rc = nullptr) {
+    AbiScene abi(scene_data);
+    const flux_job_cfg cfg = to_abi(config);
+    flux_ctx *ctx = nullptr;
+    const int code = flux_ctx_create(&abi.desc, &cfg, seed, device, &ctx);
+    if (rc) *rc = code;
+    return CtxPtr(code == FLUX_OK ? ctx : nullptr);
+}
+
+// [nrows][W][3] doubles -> the rows of a WorkUnitResult
+std::vector<std::vector<Color>> to_rows(const double *p, size_t nrows, size_t w) {
+    std::vector<std::vector<Color>> rows(nrows, std::vector<Color>(w));
+    for (auto &row : rows)
+        for (Color &c : row) {
+            c = Color{p[0], p[1], p[2]};
+            p += 3;
+        }
+    return rows;
+}
+
 }  // namespace
 
 SceneData scene_from_yaml_text(const std::string &text) {
@@ -225,16 +254,13 @@ AbiScene::AbiScene(const SceneData &sd) : name(sd.scene_name) {
 }
 
 std::vector<double> render_feature_buffers(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device) {
-    AbiScene abi(scene_data);
-    flux_job_cfg cfg{config.sample_root, config.max_trace_depth, config.rows_per_work_unit};
-    flux_ctx *ctx = nullptr;
-    if (int rc = flux_ctx_create(&abi.desc, &cfg, seed, device, &ctx)) throw FluxError(rc, flux_last_error());
+    int rc = FLUX_OK;
+    const CtxPtr ctx = create_ctx(scene_data, config, seed, device, &rc);
+    if (!ctx) throw FluxError(rc, flux_last_error());
     const size_t w = scene_data.output_settings.image_width, h = scene_data.output_settings.image_height;
     std::vector<double> aov(w * h * FLUX_AOV_CHANNELS);
-    const int rc = flux_render_aov_rows(ctx, 0, h - 1, aov.data());
-    const std::string why = rc == FLUX_OK ? "" : flux_last_error();
-    flux_ctx_destroy(ctx);
-    if (rc != FLUX_OK) throw FluxError(rc, why);
+    rc = flux_render_aov_rows(ctx.get(), 0, h - 1, aov.data());
+    if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());  // (the message is copied before the context goes)
     return aov;
 }
 
@@ -285,108 +311,107 @@ std::vector<WorkUnit> Job::work_units() const {
     return us;
 }
 
+// ---- the local workers' job loop: workers.rs:43-75 ----------------------------------------------
+namespace {
+std::atomic<int> worker_failures{0};
+}
+int GpuWorker::failures() { return worker_failures.load(); }
+void GpuWorker::note_failure() { worker_failures.fetch_add(1); }
+
+void serve_job(WorkerRequest req, const std::string &who, const std::string &range_who,
+               const std::function<std::unique_ptr<RowSource>(const Job &)> &open) {
+    // a C++ worker thread records a failure so that the front-end exits non-zero instead of reporting a frame with missing rows
+    auto give_up = [&](const char *why) {
+        std::fprintf(stderr, "%s: %s\n", who.c_str(), why);
+        GpuWorker::note_failure();
+    };
+    try {
+        const std::unique_ptr<RowSource> source = open(*req.job);
+        if (!source) return give_up(flux_last_error());
+        const size_t w = req.job->scene_data.output_settings.image_width;
+        const size_t h = req.job->scene_data.output_settings.image_height;
+        // while let Ok(unit) = recv_unit.recv()   (workers.rs:56)
+        while (auto unit = req.recv_unit->recv()) {
+            // A unit may come straight off a socket (flux_node): validate before sizing anything.  Rows past the image would make
+            // the reference's ImageBuilder index out of bounds (manager.rs:322-324) -- here the unit is refused.
+            RenderEvent ev;
+            ev.kind = RenderEvent::RowsReady;
+            ev.result.work_unit = *unit;
+            if (unit->row_start <= unit->row_end) {
+                if (unit->row_end >= h) {
+                    std::fprintf(stderr, "%s: work unit rows [%zu,%zu] outside image height %zu\n", range_who.c_str(),
+                                 (size_t)unit->row_start, (size_t)unit->row_end, h);
+                    GpuWorker::note_failure();
+                    return;
+                }
+                const double *p = source->rows(unit->row_start, unit->row_end);  // camera.render(&scene, unit)   (workers.rs:60)
+                if (!p) return give_up(flux_last_error());
+                ev.result.rows = to_rows(p, unit->row_end - unit->row_start + 1, w);
+            }
+            req.send_result->send(std::move(ev));
+        }
+    } catch (const std::exception &e) {
+        give_up(e.what());
+    }
+}
+
 // ---- GpuWorker: workers.rs:26-103 ---------------------------------------------------------------
-GpuWorker::GpuWorker(int device, uint64_t seed)
-    : device_(device), seed_(seed), sender_(std::make_shared<Channel<std::optional<WorkerRequest>>>()) {
-    thread_ = std::thread([this] { run(); });
-}
+namespace {
+struct CtxRows : RowSource {  // one flux_render_rows per unit
+    CtxPtr ctx;
+    size_t w;
+    std::vector<double> buf;
+    CtxRows(CtxPtr c, size_t width) : ctx(std::move(c)), w(width) {}
+    const double *rows(size_t row_start, size_t row_end) override {
+        buf.resize((row_end - row_start + 1) * w * 3);
+        return flux_render_rows(ctx.get(), row_start, row_end, buf.data()) == FLUX_OK ? buf.data() : nullptr;
+    }
+};
+}  // namespace
 
-GpuWorker::~GpuWorker() { stop(); }
-
-void GpuWorker::stop() {  // workers.rs:95-98: send(None), join
-    if (stopped_) return;
-    stopped_ = true;
-    sender_->send(std::nullopt);
-    if (thread_.joinable()) thread_.join();
-}
-
-std::atomic<int> GpuWorker::worker_failures_{0};
-int GpuWorker::failures() { return worker_failures_.load(); }
-void GpuWorker::note_failure() { worker_failures_.fetch_add(1); }
+GpuWorker::GpuWorker(int device, uint64_t seed) : device_(device), seed_(seed), service_([this] { run(); }) {}
 
 void GpuWorker::run() {
     // the worker's one-time set-up, before any job (LocalWorker::new builds its rayon pool here, workers.rs:27-38): the HIP runtime's
     // lazy initialisation on this device, so that a job's timer (manager.rs:145) sees the context's work and not the process's
     (void)flux_device_warmup(device_);
+    const std::string who = "GpuWorker(device " + std::to_string(device_) + ")";
     // 'main: while let Ok(Some((job, recv_unit, send_result, wg))) = r.recv()   (workers.rs:43)
-    for (;;) {
-        auto msg = sender_->recv();
-        if (!msg || !*msg) break;
-        WorkerRequest req = std::move(**msg);
-        // Scene::from_data + Camera::new (workers.rs:46-54)
-        AbiScene abi(req.job->scene_data);
-        flux_job_cfg cfg{req.job->config.sample_root, req.job->config.max_trace_depth,
-                         req.job->config.rows_per_work_unit};
-        flux_ctx *ctx = nullptr;
-        if (flux_ctx_create(&abi.desc, &cfg, seed_, device_, &ctx) != FLUX_OK) {
-            // the reference would panic in the worker thread (workers.rs:78); report and give the job up
-            std::fprintf(stderr, "GpuWorker(device %d): %s\n", device_, flux_last_error());
-            worker_failures_.fetch_add(1);
-            req.wg->done();
-            continue;
-        }
-        const size_t w = req.job->scene_data.output_settings.image_width;
-        const size_t h = req.job->scene_data.output_settings.image_height;
-        std::vector<double> buf;
-        // while let Ok(unit) = recv_unit.recv()   (workers.rs:56)
-        while (auto unit = req.recv_unit->recv()) {
-            // A unit may come straight off a socket (flux_node): validate before sizing anything.  An inverted range is
-            // what the reference renders as NO rows (`row_start..=row_end` is empty, trace.rs:62); rows past the image
-            // would make its ImageBuilder index out of bounds (manager.rs:322-324) -- here the unit is refused.
-            if (unit->row_end < unit->row_start) {
-                RenderEvent ev;
-                ev.kind = RenderEvent::RowsReady;
-                ev.result.work_unit = *unit;
-                req.send_result->send(std::move(ev));
-                continue;
-            }
-            if (unit->row_end >= h) {
-                std::fprintf(stderr, "GpuWorker(device %d): work unit rows [%zu,%zu] outside image height %zu\n", device_,
-                             (size_t)unit->row_start, (size_t)unit->row_end, h);
-                worker_failures_.fetch_add(1);
-                break;
-            }
-            const size_t nrows = unit->row_end - unit->row_start + 1;
-            buf.resize(nrows * w * 3);
-            // camera.render(&scene, unit)   (workers.rs:60)
-            if (flux_render_rows(ctx, unit->row_start, unit->row_end, buf.data()) != FLUX_OK) {
-                // the reference would panic here and take the process down (workers.rs:78); a C++ worker thread records
-                // the failure so that the front-end exits non-zero instead of reporting a frame with missing rows
-                std::fprintf(stderr, "GpuWorker(device %d): %s\n", device_, flux_last_error());
-                worker_failures_.fetch_add(1);
-                break;
-            }
-            RenderEvent ev;
-            ev.kind = RenderEvent::RowsReady;
-            ev.result.work_unit = *unit;
-            ev.result.rows.resize(nrows);
-            for (size_t r = 0; r < nrows; r++) {
-                auto &row = ev.result.rows[r];
-                row.resize(w);
-                const double *p = buf.data() + r * w * 3;
-                for (size_t c = 0; c < w; c++) row[c] = Color{p[3 * c], p[3 * c + 1], p[3 * c + 2]};
-            }
-            req.send_result->send(std::move(ev));
-        }
-        flux_ctx_destroy(ctx);
-        req.wg->done();  // drop(wg)   (workers.rs:74)
-    }
+    while (auto req = service_.next())
+        serve_job(std::move(*req), who, who, [this](const Job &job) -> std::unique_ptr<RowSource> {
+            CtxPtr ctx = create_ctx(job.scene_data, job.config, seed_, device_);
+            if (!ctx) return nullptr;
+            return std::make_unique<CtxRows>(std::move(ctx), job.scene_data.output_settings.image_width);
+        });
 }
 
 // ---- MultiGpuWorker: the node's GPUs as one worker (flux_multi_*) ----------------------------------
+namespace {
+struct FrameRows : RowSource {  // the whole frame at the first unit, slices of it afterwards
+    MultiPtr multi;
+    size_t w, h;
+    std::mutex &mu;  // the worker's, over `timing`
+    std::vector<double> &timing;
+    std::vector<double> frame;
+    FrameRows(MultiPtr m, size_t width, size_t height, std::mutex &timing_mu, std::vector<double> &timing_words)
+        : multi(std::move(m)), w(width), h(height), mu(timing_mu), timing(timing_words) {}
+    const double *rows(size_t row_start, size_t) override {
+        if (frame.empty()) {  // camera.render for the whole image, on all devices (workers.rs:60)
+            frame.resize(w * h * 3);
+            if (flux_multi_render_frame(multi.get(), frame.data()) != FLUX_OK) return nullptr;
+            double t[FLUX_MULTI_TIMING_WORDS];
+            if (flux_multi_timing(multi.get(), t) == FLUX_OK) {
+                std::lock_guard<std::mutex> g(mu);
+                timing.assign(t, t + FLUX_MULTI_TIMING_WORDS);
+            }
+        }
+        return frame.data() + row_start * w * 3;
+    }
+};
+}  // namespace
+
 MultiGpuWorker::MultiGpuWorker(std::vector<int> devices, uint64_t seed, int shard)
-    : devices_(std::move(devices)), seed_(seed), shard_(shard), sender_(std::make_shared<Channel<std::optional<WorkerRequest>>>()) {
-    thread_ = std::thread([this] { run(); });
-}
-
-MultiGpuWorker::~MultiGpuWorker() { stop(); }
-
-void MultiGpuWorker::stop() {
-    if (stopped_) return;
-    stopped_ = true;
-    sender_->send(std::nullopt);
-    if (thread_.joinable()) thread_.join();
-}
+    : devices_(std::move(devices)), seed_(seed), shard_(shard), service_([this] { run(); }) {}
 
 std::vector<double> MultiGpuWorker::last_timing() const {
     std::lock_guard<std::mutex> g(mu_);
@@ -395,100 +420,37 @@ std::vector<double> MultiGpuWorker::last_timing() const {
 
 void MultiGpuWorker::run() {
     {   // one-time set-up per device, concurrently (see GpuWorker::run)
-        std::vector<std::thread> th;
+        std::vector<JoiningThread> th;
         for (int d : devices_) th.emplace_back([d] { (void)flux_device_warmup(d); });
-        for (std::thread &t : th) t.join();
     }
-    for (;;) {
-        auto msg = sender_->recv();
-        if (!msg || !*msg) break;
-        WorkerRequest req = std::move(**msg);
-        // Scene::from_data + Camera::new on every device (workers.rs:46-54), concurrently, + the communicators
-        AbiScene abi(req.job->scene_data);
-        flux_job_cfg cfg{req.job->config.sample_root, req.job->config.max_trace_depth, req.job->config.rows_per_work_unit};
-        flux_multi *m = nullptr;
-        if (flux_multi_create(&abi.desc, &cfg, seed_, devices_.data(), devices_.size(), shard_, &m) != FLUX_OK) {
-            std::fprintf(stderr, "MultiGpuWorker(%zu devices): %s\n", devices_.size(), flux_last_error());
-            GpuWorker::note_failure();
-            req.wg->done();
-            continue;
-        }
-        const size_t w = req.job->scene_data.output_settings.image_width;
-        const size_t h = req.job->scene_data.output_settings.image_height;
-        std::vector<double> frame;
-        bool failed = false;
-        while (auto unit = req.recv_unit->recv()) {
-            if (unit->row_end < unit->row_start) {  // renders as no rows in the reference (trace.rs:62)
-                RenderEvent ev;
-                ev.kind = RenderEvent::RowsReady;
-                ev.result.work_unit = *unit;
-                req.send_result->send(std::move(ev));
-                continue;
-            }
-            if (unit->row_end >= h) {
-                std::fprintf(stderr, "MultiGpuWorker: work unit rows [%zu,%zu] outside image height %zu\n", (size_t)unit->row_start,
-                             (size_t)unit->row_end, h);
-                GpuWorker::note_failure();
-                break;
-            }
-            if (frame.empty() && !failed) {  // the first unit: camera.render for the whole image, on all devices (workers.rs:60)
-                frame.resize(w * h * 3);
-                if (flux_multi_render_frame(m, frame.data()) != FLUX_OK) {
-                    std::fprintf(stderr, "MultiGpuWorker(%zu devices): %s\n", devices_.size(), flux_last_error());
-                    GpuWorker::note_failure();
-                    failed = true;
-                }
-                double t[FLUX_MULTI_TIMING_WORDS];
-                if (!failed && flux_multi_timing(m, t) == FLUX_OK) {
-                    std::lock_guard<std::mutex> g(mu_);
-                    timing_.assign(t, t + FLUX_MULTI_TIMING_WORDS);
-                }
-            }
-            if (failed) break;
-            const size_t nrows = unit->row_end - unit->row_start + 1;
-            RenderEvent ev;
-            ev.kind = RenderEvent::RowsReady;
-            ev.result.work_unit = *unit;
-            ev.result.rows.resize(nrows);
-            for (size_t r = 0; r < nrows; r++) {
-                auto &row = ev.result.rows[r];
-                row.resize(w);
-                const double *p = frame.data() + (unit->row_start + r) * w * 3;
-                for (size_t c = 0; c < w; c++) row[c] = Color{p[3 * c], p[3 * c + 1], p[3 * c + 2]};
-            }
-            req.send_result->send(std::move(ev));
-        }
-        flux_multi_destroy(m);
-        req.wg->done();
-    }
+    const std::string who = "MultiGpuWorker(" + std::to_string(devices_.size()) + " devices)";
+    while (auto req = service_.next())
+        serve_job(std::move(*req), who, "MultiGpuWorker", [this](const Job &job) -> std::unique_ptr<RowSource> {
+            // Scene::from_data + Camera::new on every device (workers.rs:46-54), concurrently, + the communicators
+            AbiScene abi(job.scene_data);
+            const flux_job_cfg cfg = to_abi(job.config);
+            flux_multi *m = nullptr;
+            if (flux_multi_create(&abi.desc, &cfg, seed_, devices_.data(), devices_.size(), shard_, &m) != FLUX_OK) return nullptr;
+            return std::make_unique<FrameRows>(MultiPtr(m), job.scene_data.output_settings.image_width,
+                                               job.scene_data.output_settings.image_height, mu_, timing_);
+        });
 }
 
 // ---- ImageBuilder: manager.rs:278-363 -----------------------------------------------------------
-ImageBuilder::ImageBuilder() : sender_(std::make_shared<Channel<std::optional<RenderEvent>>>()) {
-    thread_ = std::thread([this] { run(); });
-}
-ImageBuilder::~ImageBuilder() { stop(); }
-void ImageBuilder::stop() {
-    if (stopped_) return;
-    stopped_ = true;
-    sender_->send(std::nullopt);
-    if (thread_.joinable()) thread_.join();
-}
+ImageBuilder::ImageBuilder() : service_([this] { run(); }) {}
 
 void ImageBuilder::run() {
-    auto first = sender_->recv();
-    if (!first || !*first || (*first)->kind != RenderEvent::ImageInfo) return;  // manager.rs:291-297
-    const std::string scene_name = (*first)->scene_name;
-    const size_t width = (*first)->width, height = (*first)->height;
-    auto second = sender_->recv();
-    if (!second || !*second || (*second)->kind != RenderEvent::RenderingStarted) return;  // manager.rs:301-307
-    const double start_time = (*second)->time_s;
+    const auto first = service_.next();
+    if (!first || first->kind != RenderEvent::ImageInfo) return;  // manager.rs:291-297
+    const std::string scene_name = first->scene_name;
+    const size_t width = first->width, height = first->height;
+    const auto second = service_.next();
+    if (!second || second->kind != RenderEvent::RenderingStarted) return;  // manager.rs:301-307
+    const double start_time = second->time_s;
     std::vector<double> img(width * height * 3, 0.0);
     std::vector<uint8_t> present(height, 0);
-    for (;;) {
-        auto m = sender_->recv();
-        if (!m || !*m) break;
-        RenderEvent &ev = **m;
+    while (const auto m = service_.next()) {
+        const RenderEvent &ev = *m;
         if (ev.kind == RenderEvent::RowsReady) {  // manager.rs:316-324
             for (size_t i = 0; i < ev.result.rows.size(); i++) {
                 const size_t r = i + ev.result.work_unit.row_start;
@@ -512,57 +474,15 @@ void ImageBuilder::run() {
     }
 }
 
-// ---- the slice of RenderManager the CLI needs: manager.rs:83-186 --------------------------------
-void run_job(const Job &job, const std::vector<WorkerHandle> &workers,
-             const std::shared_ptr<Channel<std::optional<RenderEvent>>> &events) {
-    if (workers.empty()) throw FluxError(FLUX_E_INVALID, "RenderManager::new: must provide at least one worker handle");
-    RenderEvent info;
-    info.kind = RenderEvent::ImageInfo;  // manager.rs:86-98
-    info.scene_name = job.scene_data.scene_name;
-    info.width = job.scene_data.output_settings.image_width;
-    info.height = job.scene_data.output_settings.image_height;
-    events->send(info);
-    auto units = std::make_shared<Channel<WorkUnit>>();  // manager.rs:100 (shared by every worker)
-    for (const WorkUnit &u : job.work_units()) units->send(u);
-    units->close();
-    RenderEvent started;
-    started.kind = RenderEvent::RenderingStarted;  // manager.rs:145-154: before the job reaches the workers
-    started.job_id = job.id;
-    started.time_s = now_s();
-    events->send(started);
-    auto wg = std::make_shared<WaitGroup>();
-    auto shared_job = std::make_shared<Job>(job);
-    for (const WorkerHandle &w : workers) {  // manager.rs:156-162
-        wg->add();
-        w.send(shared_job, units, events, wg);
-    }
-    wg->wait();  // manager.rs:166
-    RenderEvent fin;
-    fin.kind = RenderEvent::RenderingFinished;  // manager.rs:170-185
-    fin.time_s = now_s();
-    events->send(fin);
-}
-
 // ---- JobIDAllocator / RenderManager: job.rs:14-34, manager.rs:72-219 ------------------------------
 JobIDAllocator::JobIDAllocator() {
     std::random_device rd;  // rand::thread_rng().gen() (job.rs:21-24)
     allocator_id_ = ((size_t)rd() << 32) ^ (size_t)rd();
 }
 
-RenderManager::RenderManager(std::vector<WorkerHandle> workers)
-    : workers_(std::move(workers)), queue_(std::make_shared<Channel<std::optional<ScheduledJob>>>()) {
-    if (workers_.empty())
-        throw FluxError(FLUX_E_INVALID, "RenderManager::new: must provide at least one worker handle");
-    thread_ = std::thread([this] { run(); });
-}
-
-RenderManager::~RenderManager() { stop(); }
-
-void RenderManager::stop() {  // manager.rs:215-218
-    if (stopped_) return;
-    stopped_ = true;
-    queue_->send(std::nullopt);
-    if (thread_.joinable()) thread_.join();
+RenderManager::RenderManager(std::vector<WorkerHandle> workers) : workers_(std::move(workers)), service_([this] { run(); }) {
+    // (the thread started above takes nothing but its mailbox until a job is scheduled, and is joined as this unwinds)
+    if (workers_.empty()) throw FluxError(FLUX_E_INVALID, "RenderManager::new: must provide at least one worker handle");
 }
 
 JobHandle RenderManager::schedule_job(const SceneData &scene_data, const JobConfiguration &config,
@@ -578,16 +498,14 @@ JobHandle RenderManager::schedule_job(const SceneData &scene_data, const JobConf
     h.job_id = sj.job.id;
     h.waiter_ = sj.notify_done;
     h.canceller_ = sj.notify_cancel;
-    queue_->send(std::move(sj));
+    service_.mailbox()->send(std::move(sj));
     return h;
 }
 
 void RenderManager::run() {
     // while let Ok(Some((job, notify_done, notify_cancel, result_sender))) = r.recv()   (manager.rs:83)
-    for (;;) {
-        auto msg = queue_->recv();
-        if (!msg || !*msg) break;
-        ScheduledJob sj = std::move(**msg);
+    while (auto msg = service_.next()) {
+        const ScheduledJob &sj = *msg;
         const Job &job = sj.job;
         RenderEvent info;
         info.kind = RenderEvent::ImageInfo;  // manager.rs:86-98
@@ -607,41 +525,40 @@ void RenderManager::run() {
             continue;
         }
         auto wu_queue = std::make_shared<CancellableWorkUnits>(std::move(units));
-        // cancel listener (manager.rs:105-116): ends when a cancel arrives or the job's handle side closes
         auto cancel_ch = sj.notify_cancel;
-        std::thread cancel_listener([cancel_ch, wu_queue] {
-            if (cancel_ch->recv()) wu_queue->cancel();
-        });
-        // work-unit producer (manager.rs:118-141): blocks in send() until a worker takes the unit
-        std::thread producer([ws, wu_queue] {
-            while (auto u = wu_queue->next())
-                if (!ws->send(*u)) break;
-            ws->close();  // dropping the Sender: workers' recv() then fails and they finish the job
-        });
+        bool started_ok = false;
+        {
+            // On every path out of this block, first `release` lets both threads end, then they are joined.  A producer still blocked
+            // in send() must fail once every worker has dropped its Receiver (crossbeam: send on a channel with no receivers errors,
+            // manager.rs:131-136); the reference leaves the listener blocked until the JobHandle drops.
+            JoiningThread cancel_listener, producer;
+            ScopeExit release{[&] {
+                wu_queue->cancel();
+                ws->close();
+                cancel_ch->close();
+            }};
+            // cancel listener (manager.rs:105-116): ends when a cancel arrives or the job's handle side closes
+            cancel_listener = JoiningThread([cancel_ch, wu_queue] {
+                if (cancel_ch->recv()) wu_queue->cancel();
+            });
+            // work-unit producer (manager.rs:118-141): blocks in send() until a worker takes the unit
+            producer = JoiningThread([ws, wu_queue] {
+                while (auto u = wu_queue->next())
+                    if (!ws->send(*u)) break;
+                ws->close();  // dropping the Sender: workers' recv() then fails and they finish the job
+            });
 
-        RenderEvent started;
-        started.kind = RenderEvent::RenderingStarted;  // manager.rs:145-154
-        started.job_id = job.id;
-        started.time_s = now_s();
-        const bool started_ok = sj.result_sender->send(started);
-        if (started_ok) {
-            auto shared_job = std::make_shared<Job>(job);
-            for (const WorkerHandle &w : workers_) {  // manager.rs:156-162
-                wg->add();
-                w.send(shared_job, ws, sj.result_sender, wg);
+            RenderEvent started;
+            started.kind = RenderEvent::RenderingStarted;  // manager.rs:145-154
+            started.job_id = job.id;
+            started.time_s = now_s();
+            started_ok = sj.result_sender->send(started);
+            if (started_ok) {
+                auto shared_job = std::make_shared<Job>(job);
+                for (const WorkerHandle &w : workers_) w.send(shared_job, ws, sj.result_sender, wg);  // manager.rs:156-162
+                wg->wait();                                                                           // manager.rs:166
             }
-            wg->wait();  // manager.rs:166
-            // every worker has dropped its Receiver: a producer still blocked in send() must fail
-            // (crossbeam: send on a channel with no receivers errors, manager.rs:131-136)
-            wu_queue->cancel();
-            ws->close();
-        } else {
-            wu_queue->cancel();
-            ws->close();
         }
-        producer.join();
-        cancel_ch->close();  // the reference leaves the listener blocked until the JobHandle drops
-        cancel_listener.join();
         if (!started_ok) continue;
         RenderEvent fin;
         fin.kind = RenderEvent::RenderingFinished;  // manager.rs:170-177

@@ -5,28 +5,38 @@
 //   JobConfiguration, WorkUnit, Job::work_units      fluxcore/src/job.rs:40-88
 //   RenderEvent, WorkUnitResult, WorkerInfo, trait Worker, WorkerHandle
 //                                                    fluxcore/src/manager.rs:16-52,221-236
-//   LocalWorker job loop -> GpuWorker                fluxcore/src/workers.rs:26-103
+//   LocalWorker job loop -> serve_job (GpuWorker, MultiGpuWorker)   fluxcore/src/workers.rs:26-103
 //   ImageBuilder, Image::write                       fluxcore/src/manager.rs:278-363, image.rs:43-61
 //
-// The reference is Rust; this image has no Rust toolchain, so the mirror is C++ (std::thread and a
+// The reference is Rust; this image has no Rust toolchain, so the mirror is C++ (joining threads and a
 // small channel instead of crossbeam).  All rendering goes through include/flux_abi.h.
 #pragma once
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <optional>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <variant>
 #include <vector>
 
 #include "../../include/flux_abi.h"
+#include "../csrc/joining_thread.h"
 
 namespace flux_host {
+
+using flux::JoiningThread;
+
+// runs `f` on every path out of the scope, unwinding included
+template <class F> struct ScopeExit {
+    F f;
+    ~ScopeExit() { f(); }
+};
+template <class F> ScopeExit(F) -> ScopeExit<F>;
 
 struct FluxError : std::runtime_error {
     int code;
@@ -140,27 +150,78 @@ private:
     bool closed_ = false;
 };
 
-struct WaitGroup {  // crossbeam::sync::WaitGroup: done() once per clone, wait() for all
+// crossbeam::sync::WaitGroup: a clone is a move-only Ticket, taking one counts up and dropping it counts down; wait() for all
+struct WaitGroup {
+    class Ticket {
+    public:
+        Ticket() = default;
+        explicit Ticket(std::shared_ptr<WaitGroup> wg) : wg_(std::move(wg)) { wg_->add(); }
+        Ticket(Ticket &&) noexcept = default;  // (a moved-from shared_ptr is empty: the source releases nothing)
+        Ticket &operator=(Ticket &&o) noexcept {
+            if (this != &o) {
+                if (wg_) wg_->done();
+                wg_ = std::move(o.wg_);
+            }
+            return *this;
+        }
+        ~Ticket() { if (wg_) wg_->done(); }
+    private:
+        std::shared_ptr<WaitGroup> wg_;
+    };
     void add() { std::lock_guard<std::mutex> g(mu); n++; }
     void done() { { std::lock_guard<std::mutex> g(mu); n--; } cv.notify_all(); }
     void wait() { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return n == 0; }); }
     std::mutex mu; std::condition_variable cv; int n = 0;
 };
 
-// WorkerRequest = Option<(Box<Job>, Receiver<WorkUnit>, Sender<Option<RenderEvent>>, WaitGroup)> (manager.rs:36)
+// WorkerRequest = Option<(Box<Job>, Receiver<WorkUnit>, Sender<Option<RenderEvent>>, WaitGroup)> (manager.rs:36).  A worker finishes
+// a job by letting the request go out of scope: that drops the ticket, on every path (drop(wg), workers.rs:74).
 struct WorkerRequest {
     std::shared_ptr<Job> job;
     std::shared_ptr<Channel<WorkUnit>> recv_unit;
     std::shared_ptr<Channel<std::optional<RenderEvent>>> send_result;
-    std::shared_ptr<WaitGroup> wg;
+    WaitGroup::Ticket ticket;
+};
+
+// A mailbox of optional<Msg>, the thread that serves it and the stop-once logic (workers.rs:95-98: send(None), join).  `body` is the
+// thread's function and takes its messages with next().  The thread starts in the constructor and is joined by stop() or by the
+// destructor, so whatever holds a Service holds it as its LAST data member: every member the body reads is then built before the
+// thread starts and destroyed after it is gone, and no owner needs a destructor of its own for that (a base class could not do
+// it: its destructor runs after the derived members').
+template <class Msg> class Service {
+public:
+    using Mailbox = Channel<std::optional<Msg>>;
+    template <class F> explicit Service(F body) : mailbox_(std::make_shared<Mailbox>()), thread_(std::move(body)) {}
+    Service(const Service &) = delete;
+    Service &operator=(const Service &) = delete;
+    ~Service() { stop(); }
+    const std::shared_ptr<Mailbox> &mailbox() const { return mailbox_; }
+    // the next message; nothing once stop() was called or the mailbox is closed
+    std::optional<Msg> next() {
+        auto m = mailbox_->recv();
+        if (!m) return std::nullopt;
+        return std::move(*m);
+    }
+    // idempotent, and fine after the body has returned by itself
+    void stop() {
+        if (stopped_) return;
+        stopped_ = true;
+        mailbox_->send(std::nullopt);
+        thread_.join();
+    }
+private:
+    std::shared_ptr<Mailbox> mailbox_;
+    JoiningThread thread_;
+    bool stopped_ = false;
 };
 
 class WorkerHandle {  // manager.rs:38-52
 public:
     explicit WorkerHandle(std::shared_ptr<Channel<std::optional<WorkerRequest>>> s) : sender_(std::move(s)) {}
-    void send(std::shared_ptr<Job> j, std::shared_ptr<Channel<WorkUnit>> r,
-              std::shared_ptr<Channel<std::optional<RenderEvent>>> s, std::shared_ptr<WaitGroup> wg) const {
-        sender_->send(WorkerRequest{std::move(j), std::move(r), std::move(s), std::move(wg)});
+    // takes the worker's ticket of `wg` (wg.clone(), manager.rs:156-162); a request nobody serves releases it when it is destroyed
+    void send(std::shared_ptr<Job> j, std::shared_ptr<Channel<WorkUnit>> r, std::shared_ptr<Channel<std::optional<RenderEvent>>> s,
+              const std::shared_ptr<WaitGroup> &wg) const {
+        sender_->send(WorkerRequest{std::move(j), std::move(r), std::move(s), WaitGroup::Ticket(wg)});
     }
 private:
     std::shared_ptr<Channel<std::optional<WorkerRequest>>> sender_;
@@ -174,28 +235,39 @@ public:
     virtual WorkerInfo info() const = 0;
 };
 
+// Where a local worker's rows come from, for one job: the image rows [row_start, row_end] as [nrows][W][3] doubles, valid until the
+// next call, or nullptr with the library's message left in flux_last_error().
+class RowSource {
+public:
+    virtual ~RowSource() = default;
+    virtual const double *rows(size_t row_start, size_t row_end) = 0;
+};
+
+// One job of a local worker (the body of LocalWorker's 'main loop, workers.rs:43-75): `open` makes the job's source (nullptr: as
+// above), then every unit pulled from the request's channel is answered with a RowsReady.  An inverted range gets one without rows
+// (what `row_start..=row_end` renders, trace.rs:62).  A unit past the image, a null from `open` or the source, and a std::exception
+// anywhere in the job are reported on stderr after `who` (`range_who` for the unit), counted in GpuWorker::failures() and end the
+// job: the reference panics there (workers.rs:78).  The request's ticket is released on return, on every path.
+void serve_job(WorkerRequest req, const std::string &who, const std::string &range_who,
+               const std::function<std::unique_ptr<RowSource>(const Job &)> &open);
+
 // The GPU sibling of LocalWorker (workers.rs:26-103): one thread; per job it builds the context
 // (Scene::from_data + Camera::new) once, then renders the work units it pulls from the shared channel
 // and emits RenderEvent::RowsReady.
 class GpuWorker : public Worker {
 public:
     GpuWorker(int device, uint64_t seed);
-    ~GpuWorker() override;
-    WorkerHandle handle() const override { return WorkerHandle(sender_); }
-    void stop() override;
+    WorkerHandle handle() const override { return WorkerHandle(service_.mailbox()); }
+    void stop() override { service_.stop(); }
     WorkerInfo info() const override { return WorkerInfo{1}; }
-    // jobs / work units any GpuWorker of this process had to give up (context creation or a render call failed, or a
-    // unit was out of range): the reference panics there (workers.rs:78); the front-ends exit non-zero when this is > 0
+    // jobs / work units any local worker of this process had to give up (see serve_job); the front-ends exit non-zero when this is > 0
     static int failures();
-    static void note_failure();  // (MultiGpuWorker books its failures in the same counter)
+    static void note_failure();
 private:
     void run();
-    static std::atomic<int> worker_failures_;
     int device_;
     uint64_t seed_;
-    std::shared_ptr<Channel<std::optional<WorkerRequest>>> sender_;
-    std::thread thread_;
-    bool stopped_ = false;
+    Service<WorkerRequest> service_;  // last: see Service
 };
 
 // The GPUs of this node as ONE worker behind the same trait: per job it creates a flux_multi (include/flux_abi.h: one context per
@@ -208,9 +280,8 @@ private:
 class MultiGpuWorker : public Worker {
 public:
     MultiGpuWorker(std::vector<int> devices, uint64_t seed, int shard = FLUX_SHARD_AUTO);
-    ~MultiGpuWorker() override;
-    WorkerHandle handle() const override { return WorkerHandle(sender_); }
-    void stop() override;
+    WorkerHandle handle() const override { return WorkerHandle(service_.mailbox()); }
+    void stop() override { service_.stop(); }
     WorkerInfo info() const override { return WorkerInfo{devices_.size()}; }
     // ms of the most recent job: flux_multi_timing's words (create, slowest context, communicators, frame, kernel, gather, reassembly, copy)
     std::vector<double> last_timing() const;
@@ -219,11 +290,9 @@ private:
     std::vector<int> devices_;
     uint64_t seed_;
     int shard_;
-    std::shared_ptr<Channel<std::optional<WorkerRequest>>> sender_;
-    std::thread thread_;
-    bool stopped_ = false;
     mutable std::mutex mu_;
     std::vector<double> timing_;
+    Service<WorkerRequest> service_;  // last: see Service
 };
 
 // ImageBuilder (manager.rs:278-363): assembles RowsReady rows, prints the total time and writes
@@ -231,23 +300,15 @@ private:
 class ImageBuilder {
 public:
     ImageBuilder();
-    ~ImageBuilder();
-    std::shared_ptr<Channel<std::optional<RenderEvent>>> sender() const { return sender_; }
-    void stop();
+    std::shared_ptr<Channel<std::optional<RenderEvent>>> sender() const { return service_.mailbox(); }
+    void stop() { service_.stop(); }
     std::string output_dir = ".";
     double total_time_s = 0;
     std::string written_path;
 private:
     void run();
-    std::shared_ptr<Channel<std::optional<RenderEvent>>> sender_;
-    std::thread thread_;
-    bool stopped_ = false;
+    Service<RenderEvent> service_;  // last: see Service
 };
-
-// One job on the calling thread, no queue and no cancellation (what the CLI's single render needs):
-// ImageInfo, RenderingStarted, all work units through one shared channel, wait, RenderingFinished.
-void run_job(const Job &job, const std::vector<WorkerHandle> &workers,
-             const std::shared_ptr<Channel<std::optional<RenderEvent>>> &events);
 
 // JobIDAllocator (job.rs:14-34): allocator_id is random per allocator, ids count from 0.
 class JobIDAllocator {
@@ -295,10 +356,9 @@ private:
 class RenderManager {
 public:
     explicit RenderManager(std::vector<WorkerHandle> workers);  // throws on an empty vector (manager.rs:74-76)
-    ~RenderManager();
     JobHandle schedule_job(const SceneData &scene_data, const JobConfiguration &config,
                            std::shared_ptr<Channel<std::optional<RenderEvent>>> result_sender);
-    void stop();
+    void stop() { service_.stop(); }
 private:
     struct ScheduledJob {
         Job job;
@@ -308,9 +368,7 @@ private:
     void run();
     std::vector<WorkerHandle> workers_;
     JobIDAllocator ids_;
-    std::shared_ptr<Channel<std::optional<ScheduledJob>>> queue_;
-    std::thread thread_;
-    bool stopped_ = false;
+    Service<ScheduledJob> service_;  // last: see Service
 };
 
 // SceneData -> flux_scene_desc (+ the shape storage it points to)

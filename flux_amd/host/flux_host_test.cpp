@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <future>
+#include <new>
 #include <set>
 #include <string>
 #include <vector>
@@ -132,45 +134,110 @@ static std::string scramble(cbor::Decoder &d) {
 // (the scheduler under test never looks inside the rows).  Same job loop shape as workers.rs:43-75.
 class FakeWorker : public Worker {
 public:
-    FakeWorker(int id, int ms_per_unit)
-        : id_(id), ms_(ms_per_unit), sender_(std::make_shared<Channel<std::optional<WorkerRequest>>>()) {
-        thread_ = std::thread([this] {
-            for (;;) {
-                auto msg = sender_->recv();
-                if (!msg || !*msg) break;
-                WorkerRequest req = std::move(**msg);
-                jobs_seen++;
-                while (auto unit = req.recv_unit->recv()) {
-                    std::this_thread::sleep_for(std::chrono::milliseconds(ms_));
-                    RenderEvent ev;
-                    ev.kind = RenderEvent::RowsReady;
-                    ev.result.work_unit = *unit;
-                    ev.result.rows.assign(unit->row_end - unit->row_start + 1,
-                                          std::vector<Color>(req.job->scene_data.output_settings.image_width,
-                                                             Color{(double)id_, 0, 0}));
-                    units_done++;
-                    req.send_result->send(std::move(ev));
-                }
-                req.wg->done();
-            }
-        });
-    }
-    ~FakeWorker() override { stop(); }
-    WorkerHandle handle() const override { return WorkerHandle(sender_); }
-    void stop() override {
-        if (stopped_) return;
-        stopped_ = true;
-        sender_->send(std::nullopt);
-        thread_.join();
-    }
+    FakeWorker(int id, int ms_per_unit) : id_(id), ms_(ms_per_unit), service_([this] { run(); }) {}
+    WorkerHandle handle() const override { return WorkerHandle(service_.mailbox()); }
+    void stop() override { service_.stop(); }
     WorkerInfo info() const override { return WorkerInfo{1}; }
     std::atomic<int> units_done{0}, jobs_seen{0};
 private:
+    void run() {
+        while (auto req = service_.next()) {  // (the request's ticket is released at the end of each pass)
+            jobs_seen++;
+            while (auto unit = req->recv_unit->recv()) {
+                std::this_thread::sleep_for(std::chrono::milliseconds(ms_));
+                RenderEvent ev;
+                ev.kind = RenderEvent::RowsReady;
+                ev.result.work_unit = *unit;
+                ev.result.rows.assign(unit->row_end - unit->row_start + 1,
+                                      std::vector<Color>(req->job->scene_data.output_settings.image_width, Color{(double)id_, 0, 0}));
+                units_done++;
+                req->send_result->send(std::move(ev));
+            }
+        }
+    }
     int id_, ms_;
-    std::shared_ptr<Channel<std::optional<WorkerRequest>>> sender_;
-    std::thread thread_;
-    bool stopped_ = false;
+    Service<WorkerRequest> service_;  // last: see Service
 };
+
+// The job loop of the local workers (serve_job) over a source the test controls: a 2 x 5 image whose
+// value(row, col, ch) = 100 * row + 10 * col + ch.  The call numbered `null_at` (from 1) of a job returns null, the one
+// numbered `throw_at` throws std::bad_alloc; every call is booked in `calls` first.
+struct SourceWorker : Worker {
+    static constexpr size_t W = 2, H = 5;
+    struct Rows : RowSource {
+        SourceWorker &o;
+        size_t n = 0;
+        std::vector<double> buf;
+        explicit Rows(SourceWorker &owner) : o(owner) {}
+        const double *rows(size_t row_start, size_t row_end) override {
+            {
+                std::lock_guard<std::mutex> g(o.mu);
+                o.calls.push_back({row_start, row_end});
+            }
+            n++;
+            if (n == o.throw_at) throw std::bad_alloc();
+            if (n == o.null_at) return nullptr;
+            buf.clear();
+            for (size_t r = row_start; r <= row_end; r++)
+                for (size_t c = 0; c < W; c++)
+                    for (size_t ch = 0; ch < 3; ch++) buf.push_back(100.0 * r + 10.0 * c + ch);
+            return buf.data();
+        }
+    };
+    WorkerHandle handle() const override { return WorkerHandle(service.mailbox()); }
+    void stop() override { service.stop(); }
+    WorkerInfo info() const override { return WorkerInfo{1}; }
+    std::atomic<size_t> null_at{0}, throw_at{0};
+    std::mutex mu;
+    std::vector<std::pair<size_t, size_t>> calls;
+    Service<WorkerRequest> service{[this] {
+        while (auto req = service.next())
+            serve_job(std::move(*req), "SourceWorker", "SourceWorker", [this](const Job &) { return std::make_unique<Rows>(*this); });
+    }};  // last: see Service
+};
+
+// true once every ticket of `wg` is released; false if that takes more than 5 s (a cap, not a measurement), so that a lost release
+// fails the test where it would otherwise hang
+static bool released(const std::shared_ptr<WaitGroup> &wg) {
+    auto done = std::make_shared<std::promise<void>>();
+    std::future<void> f = done->get_future();
+    std::thread([wg, done] {
+        wg->wait();
+        done->set_value();
+    }).detach();
+    return f.wait_for(std::chrono::seconds(5)) == std::future_status::ready;
+}
+
+static int count(const std::shared_ptr<WaitGroup> &wg) {
+    std::lock_guard<std::mutex> g(wg->mu);
+    return wg->n;
+}
+
+// One job of `units` over the SourceWorker's image on `w`
+struct UnitsRun {
+    bool released = false;  // the request's ticket, within released()'s cap
+    int tickets_left = -1;  // of the job's WaitGroup afterwards: 0 when the one ticket was released exactly once
+    std::vector<RenderEvent> events;
+};
+static UnitsRun run_units(Worker &w, const std::vector<WorkUnit> &units) {
+    auto job = std::make_shared<Job>();
+    job->scene_data.output_settings.image_width = SourceWorker::W;
+    job->scene_data.output_settings.image_height = SourceWorker::H;
+    auto ch = std::make_shared<Channel<WorkUnit>>();
+    for (const WorkUnit &u : units) ch->send(u);
+    ch->close();
+    auto ev = std::make_shared<Channel<std::optional<RenderEvent>>>();
+    auto wg = std::make_shared<WaitGroup>();
+    w.handle().send(job, ch, ev, wg);
+    UnitsRun run;
+    run.released = released(wg);
+    if (!run.released) return run;  // (the worker may still be sending)
+    run.tickets_left = count(wg);
+    ev->close();
+    while (auto m = ev->recv())
+        if (*m) run.events.push_back(**m);
+    return run;
+}
 
 static std::vector<RenderEvent> drain(const std::shared_ptr<Channel<std::optional<RenderEvent>>> &ch) {
     ch->close();
@@ -405,16 +472,12 @@ int main(int argc, char **argv) {
         // a worker that gives the job up without pulling a unit (e.g. context creation failed): the producer
         // blocked on the bounded channel must be released, the job still finishes
         struct QuitterWorker : Worker {
-            std::shared_ptr<Channel<std::optional<WorkerRequest>>> sender = std::make_shared<Channel<std::optional<WorkerRequest>>>();
-            std::thread th{[this] {
-                while (auto m = sender->recv()) {
-                    if (!*m) break;
-                    (**m).wg->done();
-                }
-            }};
-            WorkerHandle handle() const override { return WorkerHandle(sender); }
-            void stop() override { sender->send(std::nullopt); if (th.joinable()) th.join(); }
+            WorkerHandle handle() const override { return WorkerHandle(service.mailbox()); }
+            void stop() override { service.stop(); }
             WorkerInfo info() const override { return WorkerInfo{0}; }
+            Service<WorkerRequest> service{[this] {
+                while (service.next()) {}  // each request is dropped unserved, its ticket with it
+            }};
         } q;
         RenderManager mgr2({q.handle()});
         auto ev3 = std::make_shared<Channel<std::optional<RenderEvent>>>();
@@ -425,6 +488,110 @@ int main(int argc, char **argv) {
         mgr2.stop();
         q.stop();
         std::puts("ok cancel");
+    }
+    {
+        // WaitGroup tickets (crossbeam's WaitGroup clones): taking one counts up, dropping the one that holds it counts down
+        auto wg = std::make_shared<WaitGroup>();
+        {
+            WaitGroup::Ticket a(wg), other(wg);
+            CHECK(count(wg) == 2);
+            WaitGroup::Ticket b(std::move(a));
+            WaitGroup::Ticket c;
+            c = std::move(b);
+            CHECK(count(wg) == 2);  // moved twice: nothing released yet
+            {
+                WaitGroup::Ticket last(std::move(c));
+            }
+            CHECK(count(wg) == 1);  // dropped: released once, and the moved-from a, b, c release nothing below
+        }
+        CHECK(count(wg) == 0 && released(wg));
+        {   // a WorkerRequest destroyed unserved releases: one that was never sent, and one left in a mailbox nobody reads
+            WorkerRequest req{nullptr, nullptr, nullptr, WaitGroup::Ticket(wg)};
+            CHECK(count(wg) == 1);
+        }
+        CHECK(count(wg) == 0);
+        {
+            auto mailbox = std::make_shared<Channel<std::optional<WorkerRequest>>>();
+            WorkerHandle(mailbox).send(nullptr, nullptr, nullptr, wg);
+            CHECK(count(wg) == 1);
+        }
+        CHECK(count(wg) == 0 && released(wg));
+        {   // wait() returns only after the last of three tickets
+            std::vector<WaitGroup::Ticket> t;
+            for (int k = 0; k < 3; k++) t.emplace_back(wg);
+            auto done = std::make_shared<std::promise<void>>();
+            std::future<void> waited = done->get_future();
+            std::thread waiter([wg, done] {
+                wg->wait();
+                done->set_value();
+            });
+            t.pop_back();
+            t.pop_back();
+            const bool early = waited.wait_for(std::chrono::milliseconds(20)) == std::future_status::ready;
+            t.pop_back();
+            const bool late = waited.wait_for(std::chrono::seconds(5)) == std::future_status::ready;
+            if (late) waiter.join(); else waiter.detach();
+            CHECK(!early && late && count(wg) == 0);
+        }
+        std::puts("ok ticket");
+    }
+    {
+        // the local workers' job loop over a fake source: rows converted and placed, an inverted range answered without rows
+        SourceWorker w;
+        const int failures = GpuWorker::failures();
+        const UnitsRun run = run_units(w, {WorkUnit{0, 1, JobID{3, 4}}, WorkUnit{3, 2, JobID{3, 4}}, WorkUnit{4, 4, JobID{3, 4}}});
+        CHECK(run.released && run.tickets_left == 0);
+        const std::vector<RenderEvent> &e = run.events;
+        CHECK(e.size() == 3);
+        for (const RenderEvent &ev : e) CHECK(ev.kind == RenderEvent::RowsReady && ev.result.work_unit.job_id.allocator_id == 3 && ev.result.work_unit.job_id.id == 4);
+        CHECK(e[0].result.work_unit.row_start == 0 && e[0].result.work_unit.row_end == 1 && e[0].result.rows.size() == 2);
+        for (size_t r = 0; r < 2; r++) {
+            CHECK(e[0].result.rows[r].size() == 2);
+            for (size_t c = 0; c < 2; c++) {
+                const Color &px = e[0].result.rows[r][c];
+                CHECK(px.r == 100.0 * r + 10.0 * c && px.g == 100.0 * r + 10.0 * c + 1 && px.b == 100.0 * r + 10.0 * c + 2);
+            }
+        }
+        CHECK(e[1].result.rows.empty() && e[1].result.work_unit.row_start == 3 && e[1].result.work_unit.row_end == 2);
+        CHECK(e[2].result.work_unit.row_start == 4 && e[2].result.work_unit.row_end == 4 && e[2].result.rows.size() == 1);
+        CHECK(e[2].result.rows[0].size() == 2 && e[2].result.rows[0][0].r == 400.0 && e[2].result.rows[0][1].b == 412.0);
+        CHECK(GpuWorker::failures() == failures);
+        w.stop();
+        CHECK((w.calls == std::vector<std::pair<size_t, size_t>>{{0, 1}, {4, 4}}));
+        std::puts("ok worker loop");
+    }
+    {
+        // a job a local worker has to give up: one failure counted, the ticket released, the worker alive for its next job
+        const std::vector<WorkUnit> three = {WorkUnit{0, 0, {}}, WorkUnit{1, 2, {}}, WorkUnit{3, 4, {}}};
+        {   // (a) a unit past the image: refused before the source sees it, and the job ends there
+            SourceWorker w;
+            const int failures = GpuWorker::failures();
+            const UnitsRun run = run_units(w, {WorkUnit{0, 0, {}}, WorkUnit{4, 7, {}}, WorkUnit{1, 1, {}}});
+            CHECK(run.released && run.tickets_left == 0);
+            CHECK(run.events.size() == 1 && run.events[0].result.work_unit.row_end == 0 && run.events[0].result.rows.size() == 1);
+            CHECK(GpuWorker::failures() == failures + 1);
+            w.stop();
+            CHECK((w.calls == std::vector<std::pair<size_t, size_t>>{{0, 0}}));
+        }
+        // (b) the source's second call returns null, (c) it throws std::bad_alloc: the same outcome, and the process lives
+        for (const bool throwing : {false, true}) {
+            SourceWorker w;
+            (throwing ? w.throw_at : w.null_at) = 2;
+            const int failures = GpuWorker::failures();
+            const UnitsRun run = run_units(w, three);
+            CHECK(run.released && run.tickets_left == 0);
+            CHECK(run.events.size() == 1 && run.events[0].result.work_unit.row_end == 0 && run.events[0].result.rows.size() == 1);
+            CHECK(GpuWorker::failures() == failures + 1);
+            w.null_at = w.throw_at = 0;
+            const UnitsRun again = run_units(w, three);  // a second request to the same worker is served in full
+            CHECK(again.released && again.tickets_left == 0 && again.events.size() == 3);
+            CHECK(again.events[0].result.rows.size() == 1 && again.events[1].result.rows.size() == 2 && again.events[2].result.rows.size() == 2);
+            CHECK(again.events[2].result.rows[1][1].b == 412.0);
+            CHECK(GpuWorker::failures() == failures + 1);
+            w.stop();
+            CHECK((w.calls == std::vector<std::pair<size_t, size_t>>{{0, 0}, {1, 2}, {0, 0}, {1, 2}, {3, 4}}));
+        }
+        std::puts("ok worker failure");
     }
     {
         // CBOR codec against the RFC 8949 Appendix A examples (published test vectors of the format)

@@ -323,36 +323,36 @@ NodeServer::NodeServer(const std::string &host, const std::string &port, WorkerH
     hints.ai_flags = AI_PASSIVE;
     const int rc = ::getaddrinfo(host.c_str(), port.c_str(), &hints, &res);
     if (rc != 0) throw FluxError(FLUX_E_IO, "cannot resolve bind address " + host + ":" + port + ": " + gai_strerror(rc));
-    listen_fd_ = ::socket(res->ai_family, res->ai_socktype, res->ai_protocol);
+    const int fd = ::socket(res->ai_family, res->ai_socktype, res->ai_protocol);
     int one = 1;
-    if (listen_fd_ >= 0) ::setsockopt(listen_fd_, SOL_SOCKET, SO_REUSEADDR, &one, sizeof one);
-    if (listen_fd_ < 0 || ::bind(listen_fd_, res->ai_addr, res->ai_addrlen) != 0 || ::listen(listen_fd_, 4) != 0) {
+    if (fd >= 0) ::setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof one);
+    if (fd < 0 || ::bind(fd, res->ai_addr, res->ai_addrlen) != 0 || ::listen(fd, 4) != 0) {
         const std::string why = std::strerror(errno);
         ::freeaddrinfo(res);
-        if (listen_fd_ >= 0) ::close(listen_fd_);
-        listen_fd_ = -1;
+        if (fd >= 0) ::close(fd);
         throw FluxError(FLUX_E_IO, "cannot listen on " + host + ":" + port + ": " + why);
     }
     ::freeaddrinfo(res);
     sockaddr_in sa{};
     socklen_t len = sizeof sa;
-    if (::getsockname(listen_fd_, (sockaddr *)&sa, &len) == 0) port_ = ntohs(sa.sin_port);
+    if (::getsockname(fd, (sockaddr *)&sa, &len) == 0) port_ = ntohs(sa.sin_port);
+    listen_fd_ = fd;
 }
 
 NodeServer::~NodeServer() { stop(); }
 
 void NodeServer::stop() {
     stopping_ = true;
-    if (listen_fd_ >= 0) {
-        ::shutdown(listen_fd_, SHUT_RDWR);
-        ::close(listen_fd_);
-        listen_fd_ = -1;
+    const int fd = listen_fd_.exchange(-1);
+    if (fd >= 0) {
+        ::shutdown(fd, SHUT_RDWR);
+        ::close(fd);
     }
 }
 
 void NodeServer::serve_forever() {  // run_server: one client at a time (main.rs:100-108)
     while (!stopping_) {
-        const int lfd = listen_fd_;
+        const int lfd = listen_fd_.load();
         if (lfd < 0) break;
         const int fd = ::accept(lfd, nullptr, nullptr);
         if (fd < 0) {
@@ -379,8 +379,17 @@ bool NodeServer::handle_client(std::unique_ptr<TcpStream> stream) {
     auto re = std::make_shared<Channel<std::optional<RenderEvent>>>();
     auto wg = std::make_shared<WaitGroup>();
     TcpStream *raw = stream.get();
+    JoiningThread writer;
+    // The reference returns right away and lets the channel drops end the worker's job; here, on every path out of this function,
+    // the unit channel is closed, the worker finishes the units it already holds, its last events are flushed and the writer is
+    // woken; then the writer is joined.
+    ScopeExit release{[&] {
+        wu->close();
+        wg->wait();
+        re->send(std::nullopt);
+    }};
     // result writer (main.rs:41-55): every RenderEvent of the local worker goes back to the manager
-    std::thread writer([raw, re] {
+    writer = JoiningThread([raw, re] {
         while (auto m = re->recv()) {
             if (!*m) break;
             Encoder e;
@@ -391,21 +400,16 @@ bool NodeServer::handle_client(std::unique_ptr<TcpStream> stream) {
             }
         }
     });
-    bool ok = true;
-    size_t jobs = 0;
     Decoder dec(*stream);
     for (;;) {  // for result in stream_de (main.rs:57-87)
         if (dec.peek() == Type::End) break;  // the client closed the stream
         NetworkWorkerRequest req;
         if (!decode_request(dec, req)) {
             std::printf("handle_client: bad request: %s\n", dec.error().empty() ? "unexpected message" : dec.error().c_str());
-            ok = false;
-            break;
+            return false;
         }
         if (req.kind == NetworkWorkerRequest::SetJob) {
             std::printf("Got job\n");
-            wg->add();
-            jobs++;
             worker_.send(std::make_shared<Job>(std::move(req.job)), wu, re, wg);
         } else if (req.kind == NetworkWorkerRequest::WorkUnitMsg) {
             wu->send(req.unit);
@@ -414,36 +418,23 @@ bool NodeServer::handle_client(std::unique_ptr<TcpStream> stream) {
             break;
         }
     }
-    // The reference returns right away and lets the channel drops end the worker's job; here the unit channel is
-    // closed explicitly, the worker finishes the units it already holds, and its last events are flushed.
-    wu->close();
-    if (jobs) wg->wait();
-    re->send(std::nullopt);
-    writer.join();
-    return ok;
+    return true;
 }
 
 // =================================================================================================
 // NetworkWorker: workers.rs:112-258
 // =================================================================================================
-NetworkWorker::NetworkWorker(const std::string &raw_endpoint)
-    : sender_(std::make_shared<Channel<std::optional<WorkerRequest>>>()) {
-    stream_ = TcpStream::connect(raw_endpoint);
+static WorkerInfo node_info(TcpStream &stream, const std::string &raw_endpoint) {
     std::printf("Getting info\n");
-    Decoder d(*stream_);  // the first message is the node's WorkerInfo (workers.rs:134-141)
-    if (!decode_worker_info(d, info_)) throw FluxError(FLUX_E_IO, "Could not get info from network node " + raw_endpoint);
+    Decoder d(stream);  // the first message is the node's WorkerInfo (workers.rs:134-141)
+    WorkerInfo info;
+    if (!decode_worker_info(d, info)) throw FluxError(FLUX_E_IO, "Could not get info from network node " + raw_endpoint);
     std::printf("Got info\n");
-    thread_ = std::thread([this] { run(); });
+    return info;
 }
 
-NetworkWorker::~NetworkWorker() { stop(); }
-
-void NetworkWorker::stop() {  // workers.rs:250-253
-    if (stopped_) return;
-    stopped_ = true;
-    sender_->send(std::nullopt);
-    if (thread_.joinable()) thread_.join();
-}
+NetworkWorker::NetworkWorker(const std::string &raw_endpoint)
+    : stream_(TcpStream::connect(raw_endpoint)), info_(node_info(*stream_, raw_endpoint)), service_([this] { run(); }) {}
 
 void NetworkWorker::run() {
     Decoder events(*stream_);
@@ -460,9 +451,9 @@ void NetworkWorker::run() {
         return true;
     };
     for (;;) {  // while let Ok(Some((job, recv_unit, send_result, wg))) = r.recv()   (workers.rs:152)
-        auto msg = sender_->recv();
-        if (!msg || !*msg) break;
-        WorkerRequest req = std::move(**msg);
+        auto msg = service_.next();
+        if (!msg) break;
+        const WorkerRequest req = std::move(*msg);  // dropped at the end of the pass: drop(wg)
         bool alive = true;
         NetworkWorkerRequest set;
         set.kind = NetworkWorkerRequest::SetJob;
@@ -492,7 +483,6 @@ void NetworkWorker::run() {
             done.kind = NetworkWorkerRequest::Done;  // workers.rs:226
             alive = send_request(done);
         }
-        req.wg->done();  // drop(wg)
         if (!alive) {
             std::fprintf(stderr, "NetworkWorker: connection to the node lost\n");
             break;  // the reference's thread returns on a deserializer error (workers.rs:194-197)

@@ -65,7 +65,7 @@ public:
     size_t clients_served() const { return clients_; }
 private:
     bool handle_client(std::unique_ptr<TcpStream> stream);  // handle_client, main.rs:21-94
-    int listen_fd_ = -1;
+    std::atomic<int> listen_fd_{-1};  // stop() takes it from another thread than serve_forever's
     uint16_t port_ = 0;
     WorkerHandle worker_;
     size_t num_threads_;
@@ -77,17 +77,14 @@ private:
 class NetworkWorker : public Worker {
 public:
     explicit NetworkWorker(const std::string &raw_endpoint);  // connects and reads WorkerInfo; throws on failure
-    ~NetworkWorker() override;
-    WorkerHandle handle() const override { return WorkerHandle(sender_); }
-    void stop() override;
+    WorkerHandle handle() const override { return WorkerHandle(service_.mailbox()); }
+    void stop() override { service_.stop(); }  // workers.rs:250-253
     WorkerInfo info() const override { return info_; }
 private:
     void run();
     std::unique_ptr<TcpStream> stream_;
     WorkerInfo info_;
-    std::shared_ptr<Channel<std::optional<WorkerRequest>>> sender_;
-    std::thread thread_;
-    bool stopped_ = false;
+    Service<WorkerRequest> service_;  // last: see Service
 };
 
 }  // namespace flux_host

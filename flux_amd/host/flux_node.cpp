@@ -4,6 +4,7 @@
 // Flags (main.rs:119-152): -h/--host ADDRESS [0.0.0.0], -p/--port PORT [2000], -t/--threads N (reported in
 // WorkerInfo; default: 1 -- one GPU worker).  Additions: --device I [0], --seed S [1], --once (exit after the
 // first client; used by the tests).  `--help` prints usage (-h is the host flag, as in the reference).
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -58,13 +59,15 @@ int main(int argc, char **argv) {
         std::printf("Listening on port %u\n", (unsigned)server.port());
         std::fflush(stdout);
         if (once) {
-            // serve exactly one client: stop the listener from a helper once a client has come and gone
-            std::thread t([&] {
-                while (server.clients_served() == 0) std::this_thread::sleep_for(std::chrono::milliseconds(20));
+            // serve exactly one client: stop the listener from a helper once a client has come and gone.  The helper also ends,
+            // and is joined, when serve_forever is left some other way.
+            std::atomic<bool> left{false};
+            JoiningThread t([&] {
+                while (server.clients_served() == 0 && !left) std::this_thread::sleep_for(std::chrono::milliseconds(20));
                 server.stop();
             });
+            ScopeExit release{[&] { left = true; }};
             server.serve_forever();
-            t.join();
         } else {
             server.serve_forever();
         }

@@ -24,7 +24,7 @@ def test_host_self_test(binaries, tmp_path):
     assert out.returncode == 0, out.stderr
     assert "all ok" in out.stdout
     for name in ("demo1", "demo2", "yaml errors", "work_units", "channel", "image_builder", "bounded channel",
-                 "render_manager", "cancel", "cbor", "node messages", "node loopback"):
+                 "render_manager", "cancel", "ticket", "worker loop", "worker failure", "cbor", "node messages", "node loopback"):
         assert f"ok {name}" in out.stdout
 
 
