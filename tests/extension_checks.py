@@ -32,6 +32,22 @@ def render(flux, sd, n, math_mode, kernel=None, traversal=None, seed=1, depth=5)
         return img, r.stats(), r.launch_plan()
 
 
+# ---- a box as triangles -------------------------------------------------------------------------------------------------
+
+def box_as_mesh(flux, b):
+    """The box `b` as a 12-triangle mesh of the same material, wound outwards (inwards for an inverted box)."""
+    from flux_amd.scene import MeshData
+    c0, c1 = np.array(b.corner0), np.array(b.corner1)
+    v = np.array([[x, y, z] for x in (c0[0], c1[0]) for y in (c0[1], c1[1]) for z in (c0[2], c1[2])])
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    tris = np.array([t for a, bb, c, dd in quads for t in ((a, bb, c), (a, c, dd))], dtype=np.uint32)
+    ctr = v[tris].mean(axis=1) - 0.5 * (c0 + c1)
+    nrm = np.cross(v[tris[:, 1]] - v[tris[:, 0]], v[tris[:, 2]] - v[tris[:, 0]])
+    flip = (np.einsum("ij,ij->i", nrm, ctr) < 0) != bool(b.invert)  # outward winding; inwards for an inverted box
+    tris[flip] = tris[flip][:, [0, 2, 1]]
+    return MeshData(v, tris, b.material)
+
+
 # ---- a frame from shares ------------------------------------------------------------------------------------------------
 
 def set_sharded_frame(flux, r, world, check_plan=False):

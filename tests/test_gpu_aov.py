@@ -101,7 +101,8 @@ EXTENSION_CASES = [("box_room", "BoxData", None), ("disk_light", None, None), ("
 @pytest.mark.parametrize("name,wanted,camera", EXTENSION_CASES, ids=["box_room", "disk_light", "disk_light_seen", "glass"])
 def test_extension_shapes(flux, oracle_mod, name, wanted, camera, math):
     """Disk, Box and Dielectric, which the restatement rejects: its rays, the first hit and t of Renderer.debug_shade, the normal
-    by the shape's own rule."""
+    by the shape's own rule -- the first hit is the GPU's own here.  The reference that owes the GPU nothing is
+    tests/path_spec.py's first_hits(): tests/test_gpu_ext_fuzz.py holds render_aov() against it on its random scenes."""
     sd = small_scene(flux.load_scene(os.path.join(SCENES, name + ".yml")), aov_spec.W, aov_spec.H)
     if camera is not None:
         sd.camera_settings = flux.CameraSettings(camera[0], camera[1], (0.0, 1.0, 0.0))

@@ -11,7 +11,7 @@ import pytest
 
 import box_spec
 from conftest import SCENES, small_scene
-from extension_checks import cli_frame, host_bins, loopback_frames, math_mode, node_frame, render, row_tiles, set_sharded_frame, small_yaml
+from extension_checks import box_as_mesh as _as_mesh, cli_frame, host_bins, loopback_frames, math_mode, node_frame, render, row_tiles, set_sharded_frame, small_yaml
 from test_box_scene import C0, C1, spec_rays
 
 pytestmark = pytest.mark.gpu
@@ -258,19 +258,6 @@ def test_white_furnace(flux, math_name):
 
 
 # ---- box against 12-triangle cube -----------------------------------------------------------------------------------------
-
-def _as_mesh(flux, b):
-    from flux_amd.scene import MeshData
-    c0, c1 = np.array(b.corner0), np.array(b.corner1)
-    v = np.array([[x, y, z] for x in (c0[0], c1[0]) for y in (c0[1], c1[1]) for z in (c0[2], c1[2])])
-    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
-    tris = np.array([t for a, bb, c, dd in quads for t in ((a, bb, c), (a, c, dd))], dtype=np.uint32)
-    ctr = v[tris].mean(axis=1) - 0.5 * (c0 + c1)
-    nrm = np.cross(v[tris[:, 1]] - v[tris[:, 0]], v[tris[:, 2]] - v[tris[:, 0]])
-    flip = (np.einsum("ij,ij->i", nrm, ctr) < 0) != bool(b.invert)  # outward winding; inwards for an inverted box
-    tris[flip] = tris[flip][:, [0, 2, 1]]
-    return MeshData(v, tris, b.material)
-
 
 QUEUE_BYTES = 9 * 64 * 8 + 2 * 64 * 4  # a wave's ray queue (flux_plan.h kQueueBytesPerWave)
 HITQ_SLOT_BYTES = 7 * 8 + 3 * 4        # a hit queue slot (kHitQBytesPerSlot)

@@ -3,9 +3,10 @@ of 17-dword slots, and a batch bounces Matte and Glossy hits, on stored normals 
 a 36-byte entry for a Matte hit on a stored normal -- were built on this layout, measured slower and not kept: DESIGN.md section 4; the
 scenes below are the ones that told the classes apart.)  Each sample's arithmetic is the immediate bounce's, so against the static
 kernel the images are equal to the summation order (1e-12, tests/test_gpu_split_hit_queue.py) and the path statistics equal the
-oracle's exactly (the oracle knows no Disk, Box or Dielectric: the three shipped scenes that have one are held against the static
-kernel's statistics, which the scenes it does know tie to the oracle's); decisions are counts, so frames are bit-reproducible and
-independent of how they are sharded.
+oracle's exactly (the oracle knows no Disk, Box or Dielectric: here the three shipped scenes that have one are held against the
+static kernel's statistics only; the independent reference for such scenes is tests/path_spec.py, against which
+tests/test_gpu_ext_fuzz.py holds every kernel, the forced hit queue included, on random scenes); decisions are counts, so frames are
+bit-reproducible and independent of how they are sharded.
 
 Scenes (16 x 12 pixels at 256 spp, the split kernel's floor, and at 1024 spp: one wave a pixel, whose LDS share holds the hit queue
 only under the overrides below; 8 x 6 pixels at 16384 spp: four waves a pixel and the plan's own pool of 110 slots or more):
