@@ -7,7 +7,7 @@ built library raises ImportError: there is no CPU fallback.
 from . import _lib
 from ._lib import (AOV_ALBEDO, AOV_CHANNELS, AOV_COVERAGE, AOV_DEPTH, AOV_NORMAL, FluxError, KERNEL_DEFAULT, KERNEL_REFILL, KERNEL_SPLIT, KERNEL_STATIC, MATH_FAST, MATH_STRICT, SHARD_AUTO, SHARD_ROWS,
                    SHARD_SETS)
-from .render import MultiRenderer, Renderer, debug_fastmath, release_comms, render_frame_multi, sampler_grid, work_units, write_ppm
+from .render import MultiRenderer, Renderer, debug_fastmath, denoise, denoise_device, denoise_work_doubles, release_comms, render_frame_multi, sampler_grid, work_units, write_ppm
 from .scene import (CameraData, CameraSettings, BoxData, DielectricData, DiskData, EmissiveData, GlossyReflectiveData, JobConfiguration, MatteData,
                     OutputSettings, PlaneData, ReflectiveData, SceneData, SceneError, SphereData, WorkUnit,
                     WorkUnitResult, load_scene, scene_from_dict)
@@ -18,5 +18,5 @@ __all__ = [
     "ReflectiveData", "GlossyReflectiveData", "DielectricData", "JobConfiguration", "WorkUnit", "WorkUnitResult", "KERNEL_DEFAULT",
     "KERNEL_STATIC", "KERNEL_REFILL", "KERNEL_SPLIT", "MATH_FAST", "MATH_STRICT", "debug_fastmath", "sampler_grid",
     "MultiRenderer", "render_frame_multi", "release_comms", "SHARD_AUTO", "SHARD_SETS", "SHARD_ROWS",
-    "AOV_ALBEDO", "AOV_NORMAL", "AOV_DEPTH", "AOV_COVERAGE", "AOV_CHANNELS",
+    "AOV_ALBEDO", "AOV_NORMAL", "AOV_DEPTH", "AOV_COVERAGE", "AOV_CHANNELS", "denoise", "denoise_device", "denoise_work_doubles",
 ]

@@ -37,6 +37,7 @@ ABI_VERSION = 3
 AOV_CHANNELS = 8
 AOV_ALBEDO_OFFSET, AOV_NORMAL_OFFSET, AOV_DEPTH, AOV_COVERAGE = 0, 3, 6, 7
 AOV_ALBEDO, AOV_NORMAL = slice(AOV_ALBEDO_OFFSET, AOV_ALBEDO_OFFSET + 3), slice(AOV_NORMAL_OFFSET, AOV_NORMAL_OFFSET + 3)
+DENOISE_PARAM_WORDS = 8  # flux_denoise's params: levels, sigma_l, sigma_n, sigma_z, sigma_a, three reserved zeros
 
 
 class FluxMaterial(C.Structure):
@@ -96,6 +97,10 @@ SYMBOLS = {
     "flux_render_sets_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
     "flux_render_aov_rows": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]),
     "flux_render_aov_rows_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
+    "flux_denoise": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)]),
+    "flux_denoise_work_doubles": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "flux_denoise_device": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(C.c_double), _P, _P, C.c_uint64, _P]),
     "flux_ctx_set_kernel": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_traversal": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_math": (C.c_int, [_P, C.c_int]),

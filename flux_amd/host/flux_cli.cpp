@@ -5,7 +5,7 @@
 // wait (:92-94), ImageBuilder writes "<scene_name>.ppm" into the cwd and prints the total time
 // (manager.rs:326-335).  -n/--node ADDRESS[:PORT] adds NetworkWorkers (flux_node processes, flux_net.hpp) and
 // -L leaves the local GPUs out, as in main.rs:37-66.  Additions: --seed (the reference seeds from OS
-// entropy), --gpus, --outdir, --split, --aov.  Not carried over: -g (SDL preview), rejected.
+// entropy), --gpus, --outdir, --split, --aov, --denoise.  Not carried over: -g (SDL preview), rejected.
 //
 // --split sets|rows|units: how the local GPUs share a frame.  `units` is the reference's scheme -- one worker per device pulling
 // WorkUnits from the shared channel (manager.rs:100) --, `sets` / `rows` hand the node's GPUs to ONE MultiGpuWorker (flux_multi_*:
@@ -15,6 +15,9 @@
 // job's --seed and -r) are rendered on local device 0 and written beside it as <scene_name>.albedo.ppm, .normal.ppm, .depth.ppm
 // and .coverage.ppm (flux_host.hpp aov_image).  They never travel through the worker / node protocol, so a run without a local
 // GPU (-L, --gpus 0, none visible) refuses the flag before any job starts.
+// --denoise: the finished frame and the feature buffers of the same job go through the a-trous filter (flux_abi.h flux_denoise) on
+// local device 0 and the result is written beside the frame as <scene_name>.denoised.ppm; refused like --aov without a local GPU.
+// With --aov as well the feature buffers are rendered once and all five files are written.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +50,7 @@ struct Config {  // flux/src/main.rs:115-124
     std::string outdir = ".";
     std::string split = "auto";
     bool aov = false;
+    bool denoise = false;
 };
 
 void usage() {
@@ -55,7 +59,9 @@ void usage() {
                  "    -L               Do not use the local host (its GPUs) for rendering\n"
                  "    -g               Show a live graphical preview window during rendering (not supported)\n"
                  "        --aov        Also write <scene_name>.albedo.ppm, .normal.ppm, .depth.ppm and .coverage.ppm: the first-hit\n"
-                 "                     feature buffers of the frame, rendered on local GPU 0\n\nOPTIONS:\n"
+                 "                     feature buffers of the frame, rendered on local GPU 0\n"
+                 "        --denoise    Also write <scene_name>.denoised.ppm: the frame after a feature-guided a-trous filter on local\n"
+                 "                     GPU 0 (for noisy previews of 1-16 samples per pixel; a clean frame may lose detail)\n\nOPTIONS:\n"
                  "    -d, --depth <DEPTH>          Tracing depth [default 5]\n"
                  "    -n, --node <ADDRESS[:PORT]>  Render using the flux_node process at this address (repeatable)\n"
                  "    -R, --rows <COUNT>           Image rows per work unit [default 50]\n"
@@ -112,6 +118,8 @@ Config config_from_args(int argc, char **argv) {
             c.gpus = (int)parse_usize("--gpus", need("--gpus"));
         } else if (a == "--aov") {
             c.aov = true;
+        } else if (a == "--denoise") {
+            c.denoise = true;
         } else if (a == "--outdir") {
             c.outdir = need("--outdir");
         } else if (a == "--split") {
@@ -155,6 +163,10 @@ int main(int argc, char **argv) {
     }
     if (config.aov && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
         std::fprintf(stderr, "error: --aov renders the feature buffers on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
+        return 2;
+    }
+    if (config.denoise && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
+        std::fprintf(stderr, "error: --denoise filters the frame on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
         return 2;
     }
     // main.rs:37-66: the local worker(s) unless -L, then one NetworkWorker per -n
@@ -241,20 +253,27 @@ int main(int argc, char **argv) {
         std::printf("wrote %s (%.1f Msamples/s incl. context creation)\n", image_builder.written_path.c_str(),
                     image_builder.total_time_s > 0 ? samples / image_builder.total_time_s / 1e6 : 0.0);
     }
-    if (rc == 0 && config.aov && !image_builder.written_path.empty()) {
+    if (rc == 0 && (config.aov || config.denoise) && !image_builder.written_path.empty()) {
+        const char *flag = config.aov ? "--aov" : "--denoise";
         try {
             const std::vector<double> aov = render_feature_buffers(s, job_config, config.seed, 0);
             const size_t w = s.output_settings.image_width, h = s.output_settings.image_height;
-            const struct { AovKind kind; const char *name; } outs[] = {
-                {AovKind::Albedo, "albedo"}, {AovKind::Normal, "normal"}, {AovKind::Depth, "depth"}, {AovKind::Coverage, "coverage"}};
-            for (const auto &o : outs) {
-                const std::string path = config.outdir + "/" + s.scene_name + "." + o.name + ".ppm";
-                const std::vector<double> img = aov_image(aov.data(), w, h, o.kind);
+            const auto write = [&](const char *name, const std::vector<double> &img) {
+                const std::string path = config.outdir + "/" + s.scene_name + "." + name + ".ppm";
                 if (flux_write_ppm(path.c_str(), img.data(), w, h, nullptr) != FLUX_OK) throw FluxError(FLUX_E_IO, flux_last_error());
                 std::printf("wrote %s\n", path.c_str());
+            };
+            if (config.aov) {
+                const struct { AovKind kind; const char *name; } outs[] = {
+                    {AovKind::Albedo, "albedo"}, {AovKind::Normal, "normal"}, {AovKind::Depth, "depth"}, {AovKind::Coverage, "coverage"}};
+                for (const auto &o : outs) write(o.name, aov_image(aov.data(), w, h, o.kind));
+            }
+            if (config.denoise) {
+                flag = "--denoise";
+                write("denoised", denoise_frame(image_builder.image, aov, w, h, 0));
             }
         } catch (const FluxError &e) {
-            std::fprintf(stderr, "error: --aov: %s\n", e.what());
+            std::fprintf(stderr, "error: %s: %s\n", flag, e.what());
             rc = 1;
         }
     }

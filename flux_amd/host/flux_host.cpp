@@ -299,6 +299,15 @@ std::vector<double> aov_image(const double *aov, size_t width, size_t height, Ao
     return rgb;
 }
 
+std::vector<double> denoise_frame(const std::vector<double> &rgb, const std::vector<double> &aov, size_t width, size_t height, int device) {
+    if (rgb.size() != width * height * 3 || aov.size() != width * height * FLUX_AOV_CHANNELS)
+        throw FluxError(FLUX_E_INVALID, "denoise_frame: the buffers do not hold width * height pixels");
+    std::vector<double> out(rgb.size());
+    const int rc = flux_denoise(device, width, height, rgb.data(), aov.data(), nullptr, out.data());
+    if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());
+    return out;
+}
+
 std::vector<WorkUnit> Job::work_units() const {
     const uint64_t h = scene_data.output_settings.image_height;
     int64_t n = flux_work_units(h, config.rows_per_work_unit, nullptr, 0);
@@ -468,6 +477,7 @@ void ImageBuilder::run() {
             written_path = output_dir + "/" + scene_name + ".ppm";
             if (flux_write_ppm(written_path.c_str(), img.data(), width, height, present.data()) != FLUX_OK)
                 std::fprintf(stderr, "ImageBuilder: %s\n", flux_last_error());
+            image = img;
         } else {
             return;  // unexpected message (manager.rs:336-339)
         }

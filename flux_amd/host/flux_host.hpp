@@ -305,6 +305,7 @@ public:
     std::string output_dir = ".";
     double total_time_s = 0;
     std::string written_path;
+    std::vector<double> image;  // the frame as written, [H][W][3]: filled with written_path (read it after stop())
 private:
     void run();
     Service<RenderEvent> service_;  // last: see Service
@@ -392,5 +393,10 @@ std::vector<double> render_feature_buffers(const SceneData &scene_data, const Jo
 //   Coverage  grey
 enum class AovKind { Albedo, Normal, Depth, Coverage };
 std::vector<double> aov_image(const double *aov, size_t width, size_t height, AovKind kind);
+
+// ---- the a-trous denoiser (include/flux_abi.h flux_denoise) ---------------------------------------
+// A frame `rgb` [H][W][3] and its feature buffers `aov` [H][W][FLUX_AOV_CHANNELS] filtered on `device` with the default
+// parameters: the filtered frame.  Throws FluxError with the library's message.
+std::vector<double> denoise_frame(const std::vector<double> &rgb, const std::vector<double> &aov, size_t width, size_t height, int device);
 
 }  // namespace flux_host

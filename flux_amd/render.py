@@ -142,6 +142,10 @@ class Renderer:
         _lib.check(_lib.lib.flux_render_aov_rows_device(self._handle(), first_row, row_stride, num_rows,
                                                         C.c_void_p(d_out_ptr), C.c_void_p(stream)))
 
+    def render_denoised(self, **params) -> np.ndarray:
+        """render_frame() + render_aov() + the a-trous filter (flux_amd.denoise, which takes `params`) on this renderer's device."""
+        return denoise(self.render_frame(), self.render_aov(), device=self.device, **params)
+
     def debug_shade(self, origins, directions, depth: int = 1, set_index: int = 0, sample_index: int = 0):
         """Scene::shade on the device for the given rays (flux_debug_shade): (rgb [n,3], first-hit index [n], t [n])."""
         o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
@@ -377,6 +381,40 @@ def write_ppm(path: str, rgb: np.ndarray, rows_present=None):
         assert rp_arr.shape == (h,)
         rp = rp_arr.ctypes.data_as(C.POINTER(C.c_uint8))
     _lib.check(_lib.lib.flux_write_ppm(path.encode(), rgb.ctypes.data_as(C.POINTER(C.c_double)), w, h, rp))
+
+
+def _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a):
+    """The FLUX_DENOISE_PARAM_WORDS doubles of flux_denoise (the library checks their ranges)."""
+    return (C.c_double * _lib.DENOISE_PARAM_WORDS)(levels, sigma_l, sigma_n, sigma_z, sigma_a, 0.0, 0.0, 0.0)
+
+
+def denoise(rgb, aov, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1) -> np.ndarray:
+    """The feature-guided a-trous filter of flux_denoise (include/flux_abi.h) over a frame `rgb` [H, W, 3] of
+    render_frame() and its feature buffers `aov` [H, W, 8] of render_aov(): the filtered frame, on `device`.  Meant for noisy
+    previews (1-16 spp); a frame that is already clean can come out worse."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    aov = np.ascontiguousarray(aov, dtype=np.float64)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or aov.shape != rgb.shape[:2] + (_lib.AOV_CHANNELS,):
+        raise _lib.FluxError(_lib.E_INVALID, f"denoise: rgb {rgb.shape} and aov {aov.shape} are not [H, W, 3] and [H, W, {_lib.AOV_CHANNELS}]")
+    out = np.empty_like(rgb)
+    dp = C.POINTER(C.c_double)
+    _lib.check(_lib.lib.flux_denoise(int(device), rgb.shape[1], rgb.shape[0], rgb.ctypes.data_as(dp), aov.ctypes.data_as(dp),
+                                     _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a), out.ctypes.data_as(dp)))
+    return out
+
+
+def denoise_work_doubles(width: int, height: int) -> int:
+    """Doubles of device scratch denoise_device needs (flux_denoise_work_doubles; 0 for a size the filter refuses)."""
+    return int(_lib.lib.flux_denoise_work_doubles(width, height))
+
+
+def denoise_device(width: int, height: int, d_rgb_ptr: int, d_aov_ptr: int, d_out_ptr: int, d_work_ptr: int, work_doubles: int,
+                   stream: int = 0, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1):
+    """Asynchronous device-resident filter (see flux_denoise_device): device addresses of the frame, the feature buffers, the
+    output frame and `work_doubles` >= denoise_work_doubles(width, height) doubles of scratch; `stream` a hipStream_t."""
+    _lib.check(_lib.lib.flux_denoise_device(int(device), width, height, C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr),
+                                            _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a), C.c_void_p(d_out_ptr),
+                                            C.c_void_p(d_work_ptr), work_doubles, C.c_void_p(stream)))
 
 
 def debug_fastmath(fn: int, a, b=None, device: int = 0) -> np.ndarray:

@@ -272,6 +272,41 @@ int flux_render_aov_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, do
 int flux_render_aov_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
                                 void *d_out, void *hip_stream);
 
+/* A feature-guided a-trous denoiser for low-sample frames (extension; FLUX_ABI_VERSION unchanged -- a client detects support by
+ * the symbol).  DESIGN.md section 5f; tests/denoise_spec.py states the same filter in numpy.
+ * Inputs: rgb [H][W][3] as flux_render_rows returns it, aov [H][W][FLUX_AOV_CHANNELS] as flux_render_aov_rows returns it, of
+ * which a = the albedo, n = the normal, z = the depth are used (the coverage is not).
+ * Parameters (FLUX_DENOISE_PARAM_WORDS doubles, or NULL for the defaults): [0] levels L, an integer in 1..8, default 5;
+ * [1] sigma_l 2.0; [2] sigma_n 0.35; [3] sigma_z 0.1; [4] sigma_a 0.1 -- each finite and > 0; [5..7] reserved, 0.
+ * With |v|^2 = (v0^2 + v1^2) + v2^2 and lum(c) = (0.2126 r + 0.7152 g) + 0.0722 b:
+ *   usable      a pixel whose rgb, a and n are finite in every component, whose lum(rgb) is finite and whose z is not NaN (+inf
+ *               is a depth).  An unusable pixel is copied to the output bit for bit and contributes to no other pixel.
+ *   G(p, q)     = ((|n_p - n_q|^2 / sigma_n^2) + e_z) + |a_p - a_q|^2 / sigma_a^2, where, both depths finite,
+ *               d = (z_p - z_q) / ((|z_p| + |z_q|) + 1e-300) and e_z = d^2 / sigma_z^2; otherwise e_z = 0 if z_p == z_q, else +inf.
+ *   taps        of a usable p at step s: q = p + s (i, j), i, j in -2..2, rows (j) outer and columns (i) inner; a tap off the
+ *               image or on an unusable pixel is skipped.
+ *   variance    once, on the input, taps at step 1, l = lum(rgb): w = exp2(-min(G(p, q), 1100)), s0 = sum w, m = sum w l_q / s0,
+ *               then over the same taps var_p = sum w (l_q - m)^2 / s0 (two passes: s2 / s0 - m^2 cancels).
+ *   level k     = 0..L-1, s = 2^k, reading the previous level's c and var of all pixels (never in place):
+ *               sd = sigma_l sqrt(var_p) + 1e-8,  w = (h_j h_i) exp2(-min(G(p, q) + |lum(c_p) - lum(c_q)| / sd, 1100)) with
+ *               h = [1/16, 1/4, 3/8, 1/4, 1/16],  c'_p = sum w c_q / sum w,  var'_p = sum w^2 var_q / (sum w)^2.
+ *   output      max_to_one(c_L) (color.rs:35-44) for a usable pixel.
+ * Division and sqrt are IEEE, nothing is fused, sums run in tap order and there are no atomics: the result is bit-reproducible.
+ * The filter roughly quarters the error of a noisy 1-16 spp frame; it can LOSE on a frame that is already clean (section 5f). */
+#define FLUX_DENOISE_PARAM_WORDS 8
+/* Host pointers: rgb and out_rgb hold width * height * 3 doubles, aov width * height * FLUX_AOV_CHANNELS.  Synchronous, on
+ * `device`, in device memory of its own.  Every argument check runs before any device call: FLUX_E_INVALID for a null pointer,
+ * width or height 0, width * height > 2^26, or a parameter outside the ranges above. */
+int flux_denoise(int device, uint64_t width, uint64_t height, const double *rgb, const double *aov,
+                 const double *params, double *out_rgb);
+/* Doubles of device scratch flux_denoise_device needs for an image of this size (0 for a size it refuses). */
+uint64_t flux_denoise_work_doubles(uint64_t width, uint64_t height);
+/* The same filter on device pointers of `device`, asynchronously on `hip_stream`: 2 + L kernel launches.  d_rgb and d_aov are only
+ * read.  `params` is a host pointer, read before the call returns.  Checked as flux_denoise, and FLUX_E_INVALID as well for
+ * work_doubles < flux_denoise_work_doubles(width, height) and for d_out_rgb equal to d_rgb or d_work. */
+int flux_denoise_device(int device, uint64_t width, uint64_t height, void *d_rgb, void *d_aov, const double *params,
+                        void *d_out_rgb, void *d_work, uint64_t work_doubles, void *hip_stream);
+
 /* Render-kernel variants (all produce the same image within rounding):
  *   0 = default (FLUX_KERNEL_SPLIT where it applies, else FLUX_KERNEL_REFILL; STATIC below 64 spp)
  *   1 = FLUX_KERNEL_STATIC: one lane per sample, lanes idle once their path ends
