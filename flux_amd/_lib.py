@@ -37,6 +37,10 @@ ABI_VERSION = 3
 AOV_CHANNELS = 8
 AOV_ALBEDO_OFFSET, AOV_NORMAL_OFFSET, AOV_DEPTH, AOV_COVERAGE = 0, 3, 6, 7
 AOV_ALBEDO, AOV_NORMAL = slice(AOV_ALBEDO_OFFSET, AOV_ALBEDO_OFFSET + 3), slice(AOV_NORMAL_OFFSET, AOV_NORMAL_OFFSET + 3)
+# per-pixel sample moments (include/flux_abi.h FLUX_MOMENT_*): doubles per pixel and each channel's first
+MOMENT_CHANNELS = 8
+MOMENT_RGB_OFFSET, MOMENT_VAR, MOMENT_MEAN_OFFSET, MOMENT_S2 = 0, 3, 4, 7
+MOMENT_RGB, MOMENT_MEAN = slice(MOMENT_RGB_OFFSET, MOMENT_RGB_OFFSET + 3), slice(MOMENT_MEAN_OFFSET, MOMENT_MEAN_OFFSET + 3)
 DENOISE_PARAM_WORDS = 8  # flux_denoise's params: levels, sigma_l, sigma_n, sigma_z, sigma_a, three reserved zeros
 
 
@@ -101,6 +105,11 @@ SYMBOLS = {
                                C.POINTER(C.c_double)]),
     "flux_denoise_work_doubles": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "flux_denoise_device": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(C.c_double), _P, _P, C.c_uint64, _P]),
+    "flux_render_moments_rows": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]),
+    "flux_render_moments_rows_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P]),
+    "flux_denoise_moments": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "flux_denoise_moments_device": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(C.c_double), _P, _P, C.c_uint64, _P]),
     "flux_ctx_set_kernel": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_traversal": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_math": (C.c_int, [_P, C.c_int]),

@@ -399,8 +399,11 @@ static int effective_math(const flux_ctx *ctx) {
 // STRICT keeps the (f,s) recursion stack, 4 doubles per level per lane; mesh scenes the BVH traversal stack, one int per
 // level per lane -- 64 lanes in the FAST state-machine kernel, the block's in the others --; the split kernel its path
 // queues), plus the few static words of the refill / split kernels.  64 KiB per block is the launch limit.
-static int check_lds_budget(const flux_ctx *ctx, const flux::RenderParams &p, const char *what, bool aov = false) {
-    const size_t dyn = aov ? flux::plan_aov(p, effective_math(ctx)).lds : flux::plan_render(p, ctx->variant, effective_math(ctx)).lds;
+enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2 };  // which kernel family a launch runs
+static int check_lds_budget(const flux_ctx *ctx, const flux::RenderParams &p, const char *what, Pass pass = kPassRender) {
+    const size_t dyn = pass == kPassAov       ? flux::plan_aov(p, effective_math(ctx)).lds
+                       : pass == kPassMoments ? flux::plan_moments(p, effective_math(ctx)).lds
+                                              : flux::plan_render(p, ctx->variant, effective_math(ctx)).lds;
     const size_t fixed = 512;
     if (dyn + fixed > 64 * 1024)
         return fail(FLUX_E_INVALID, "%s: %zu B of LDS per block (max_trace_depth %u%s, BVH depth %llu) exceed the 64 KiB limit; use %s", what,
@@ -563,14 +566,16 @@ int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, in
     return FLUX_OK;
 }
 
-// the launch of the render calls and of the feature-buffer calls (`aov`), between the context's two events (flux_ctx_last_kernel_ms);
-// `what` names the caller in the LDS refusal
-static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, bool aov = false) {
+// the launch of the render calls, of the feature-buffer calls and of the moments calls (`pass`), between the context's two events
+// (flux_ctx_last_kernel_ms); `what` names the caller in the LDS refusal
+static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, Pass pass = kPassRender) {
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    if (int rc = check_lds_budget(ctx, p, what, aov)) return rc;
+    if (int rc = check_lds_budget(ctx, p, what, pass)) return rc;
     HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(aov ? flux::launch_aov(p, effective_math(ctx), stream) : flux::launch_render(p, ctx->variant, effective_math(ctx), stream));
+    HIP_TRY(pass == kPassAov       ? flux::launch_aov(p, effective_math(ctx), stream)
+            : pass == kPassMoments ? flux::launch_moments(p, effective_math(ctx), stream)
+                                   : flux::launch_render(p, ctx->variant, effective_math(ctx), stream));
     HIP_TRY(hipEventRecord(ctx->ev1, stream));
     ctx->timed = true;
     return FLUX_OK;
@@ -649,7 +654,7 @@ int flux_render_aov_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_
                     (unsigned long long)num_rows, ctx->H);
     flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out);
     p.stats = nullptr;
-    return launch_timed(ctx, p, "flux_render_aov_rows", (hipStream_t)hip_stream, true);
+    return launch_timed(ctx, p, "flux_render_aov_rows", (hipStream_t)hip_stream, kPassAov);
 }
 
 // (a scratch buffer of its own, d_aov: the framebuffer of flux_render_rows, d_out, is neither resized nor aliased)
@@ -671,6 +676,51 @@ int flux_render_aov_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, do
     int rc = flux_render_aov_rows_device(ctx, row_start, 1, rows, ctx->d_aov, nullptr);
     if (rc != FLUX_OK) return rc;
     HIP_TRY(hipMemcpy(out, ctx->d_aov, doubles * sizeof(double), hipMemcpyDeviceToHost));
+    return FLUX_OK;
+}
+
+// The per-pixel sample moments (moments_body.inc): the argument checks of the feature-buffer calls, and one more -- a single sample
+// has no variance.  Statistics off: the kernel keeps none.
+int flux_render_moments_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *d_out,
+                                    void *hip_stream) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    if (!holds_all_sets(ctx))  // every row uses every sample set (trace.rs:64-69)
+        return fail(FLUX_E_INVALID, "sample moments need all sample sets; this context holds the share %u + k*%u "
+                    "(flux_ctx_create_sets), which no moments call serves", ctx->sets.first, ctx->sets.stride);
+    if (ctx->N < 2)
+        return fail(FLUX_E_INVALID, "sample moments need sample_root >= 2: one sample per pixel has no variance; flux_denoise "
+                    "estimates the variance from the frame itself");
+    if (num_rows == 0) return FLUX_OK;
+    if (!d_out) return fail(FLUX_E_INVALID, "null output pointer");
+    if (row_stride < 1) return fail(FLUX_E_INVALID, "row_stride must be >= 1");
+    if (first_row >= ctx->H || first_row + (num_rows - 1) * row_stride >= ctx->H)
+        return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
+                    (unsigned long long)first_row, (unsigned long long)row_stride,
+                    (unsigned long long)num_rows, ctx->H);
+    flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out);
+    p.stats = nullptr;
+    return launch_timed(ctx, p, "flux_render_moments_rows", (hipStream_t)hip_stream, kPassMoments);
+}
+
+// (a scratch buffer of its own, d_moments: neither the framebuffer of flux_render_rows nor the feature buffers' is resized or aliased)
+int flux_render_moments_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    if (!out) return fail(FLUX_E_INVALID, "null output pointer");
+    if (row_end < row_start || row_end >= ctx->H)
+        return fail(FLUX_E_INVALID, "rows [%llu,%llu] outside image height %u",
+                    (unsigned long long)row_start, (unsigned long long)row_end, ctx->H);
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+    const uint64_t rows = row_end - row_start + 1;
+    const size_t doubles = (size_t)rows * ctx->W * FLUX_MOMENT_CHANNELS;
+    if (doubles > ctx->d_moments_doubles) {
+        ctx->d_moments_doubles = 0;  // (stays 0 if the new allocation fails: the old one is released first)
+        HIP_TRY(ctx->d_moments.alloc(doubles));
+        ctx->d_moments_doubles = doubles;
+    }
+    int rc = flux_render_moments_rows_device(ctx, row_start, 1, rows, ctx->d_moments, nullptr);
+    if (rc != FLUX_OK) return rc;
+    HIP_TRY(hipMemcpy(out, ctx->d_moments, doubles * sizeof(double), hipMemcpyDeviceToHost));
     return FLUX_OK;
 }
 

@@ -4,7 +4,8 @@
 // Its own translation unit under the build's default flags (-ffp-contract=off): every sum and product below keeps the order the
 // header gives it, division and sqrt are IEEE, and the one function that differs from the numpy statement is fexp2 (flux_math.h).
 //
-// Three kernels, all one thread per pixel in blocks of 32 x 8 pixels (four 64-lane waves, each two image rows of 32 pixels):
+// Three kernels, all one thread per pixel in blocks of 32 x 8 pixels (four 64-lane waves, each two image rows of 32 pixels); the
+// measured-variance path of flux_denoise_moments* adds three small ones of the same shape, stated where they stand:
 //   denoise_pack_kernel      AoS rgb + aov -> planes of W*H doubles: albedo (3), normal (3), depth, colour (3).  An unusable pixel
 //                            gets a NaN depth: no usable pixel has one, so the depth plane doubles as the usable flag.
 //   denoise_variance_kernel  the guide-weighted variance of the luminance over 5 x 5, two passes over weights kept in registers.
@@ -144,6 +145,69 @@ __global__ __launch_bounds__(kTileW *kTileH) void denoise_variance_kernel(Frame 
         s2 += w[t] * (d * d);
     }
     f.work[10 * f.npix + idx] = s2 / s0;
+}
+
+// ---- the measured-variance path (flux_denoise_moments*) -----------------------------------------------------
+// The same planes and the same level kernels; what differs is where a pixel's variance comes from:
+//   denoise_pack_moments_kernel  denoise_pack_kernel over the moments buffer ([H][W][8]: rgb = channels 0-2, v = channel 3): a pixel is
+//                                usable only if v is finite and >= 0 as well, and v goes to the SECOND set's variance plane (14),
+//                                which no launch reads before the first level has written it.
+//   denoise_varfilter_kernel     var_p = sum w v_q / sum w over the step-1 taps, w from the guides alone, one pass: plane 14 -> plane 10.
+//   denoise_unusable_kernel      the level kernels copy an unusable pixel from a [H][W][3] frame, which the moments buffer is not: just
+//                                before the last level this kernel writes the unusable pixels' rgb as such a frame into the colour
+//                                planes of the set the last level does not read (and, being the last, does not write).
+__global__ __launch_bounds__(kTileW *kTileH) void denoise_pack_moments_kernel(Frame f, const double *__restrict__ mom,
+                                                                              const double *__restrict__ aov) {
+    int x, y;
+    if (!my_pixel(f, x, y)) return;
+    const size_t idx = (size_t)y * f.W + x;
+    const double *c = mom + idx * FLUX_MOMENT_CHANNELS;
+    const double *g = aov + idx * FLUX_AOV_CHANNELS;
+    const double v = c[FLUX_MOMENT_VAR];
+    bool ok = finite(c[0]) && finite(c[1]) && finite(c[2]) && finite(lum(c[0], c[1], c[2])) && finite(v) && v >= 0.0;
+    for (int k = 0; k < 6; k++) ok = ok && finite(g[k]);
+    const double z = g[FLUX_AOV_DEPTH];
+    ok = ok && z == z;
+    for (int k = 0; k < 6; k++) f.work[k * f.npix + idx] = g[k];
+    f.work[6 * f.npix + idx] = ok ? z : __builtin_nan("");
+    for (int k = 0; k < 3; k++) f.work[(7 + k) * f.npix + idx] = c[k];
+    f.work[14 * f.npix + idx] = v;
+}
+
+__global__ __launch_bounds__(kTileW *kTileH) void denoise_varfilter_kernel(Frame f) {
+    int x, y;
+    if (!my_pixel(f, x, y)) return;
+    const size_t idx = (size_t)y * f.W + x;
+    const double *work = f.work;
+    const double zp = work[6 * f.npix + idx];
+    if (zp != zp) return;  // unusable: no tap ever reads its variance
+    const Guide p = load_guide(work, f.npix, idx, zp);
+    double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int j = -kHalo; j <= kHalo; j++) {
+#pragma unroll
+        for (int i = -kHalo; i <= kHalo; i++) {
+            const int qx = x + i, qy = y + j;
+            if (qx < 0 || qx >= f.W || qy < 0 || qy >= f.H) continue;
+            const size_t q = (size_t)qy * f.W + qx;
+            const double zq = work[6 * f.npix + q];
+            if (zq != zq) continue;
+            const double w = fastmath::fexp2(-__builtin_fmin(guide_exponent(p, load_guide(work, f.npix, q, zq), f), kEMax));
+            s0 += w;
+            s1 += w * work[14 * f.npix + q];
+        }
+    }
+    f.work[10 * f.npix + idx] = s1 / s0;
+}
+
+__global__ __launch_bounds__(kTileW *kTileH) void denoise_unusable_kernel(Frame f, int dst, const double *__restrict__ mom) {
+    int x, y;
+    if (!my_pixel(f, x, y)) return;
+    const size_t idx = (size_t)y * f.W + x;
+    const double zp = f.work[6 * f.npix + idx];
+    if (zp == zp) return;
+    double *frame = f.work + (size_t)dst * f.npix;  // 3 npix doubles, [H][W][3]
+    for (int k = 0; k < 3; k++) frame[idx * 3 + k] = mom[idx * FLUX_MOMENT_CHANNELS + k];
 }
 
 // What a level sums over its taps.
@@ -334,8 +398,9 @@ static int lds_levels() {
     return e ? std::atoi(e) : kDefaultLdsLevels;
 }
 
+// d_rgb: the [H][W][3] frame of flux_denoise, or, `moments`, the [H][W][FLUX_MOMENT_CHANNELS] buffer of flux_denoise_moments
 static hipError_t launch(const Params &p, uint64_t width, uint64_t height, const double *d_rgb, const double *d_aov, double *d_out,
-                         double *d_work, hipStream_t stream) {
+                         double *d_work, hipStream_t stream, bool moments = false) {
     Frame f{};
     f.W = (int32_t)width;
     f.H = (int32_t)height;
@@ -349,12 +414,21 @@ static hipError_t launch(const Params &p, uint64_t width, uint64_t height, const
     f.step = 1;
     // (at most 2^26 / 8 tiles of one column: far inside a 1-D grid)
     const dim3 grid((uint32_t)((uint64_t)f.tiles_x * ((height + kTileH - 1) / kTileH))), block(kTileW * kTileH);
-    hipLaunchKernelGGL(denoise_pack_kernel, grid, block, 0, stream, f, d_rgb, d_aov);
-    hipLaunchKernelGGL(denoise_variance_kernel, grid, block, 0, stream, f);
+    if (moments) {
+        hipLaunchKernelGGL(denoise_pack_moments_kernel, grid, block, 0, stream, f, d_rgb, d_aov);
+        hipLaunchKernelGGL(denoise_varfilter_kernel, grid, block, 0, stream, f);
+    } else {
+        hipLaunchKernelGGL(denoise_pack_kernel, grid, block, 0, stream, f, d_rgb, d_aov);
+        hipLaunchKernelGGL(denoise_variance_kernel, grid, block, 0, stream, f);
+    }
     for (int k = 0; k < p.levels; k++) {
         f.step = 1 << k;
         const int src = (k & 1) ? 11 : 7, dst = (k & 1) ? 7 : 11;
         const bool last = k == p.levels - 1;
+        if (last && moments) {  // the frame the last level copies its unusable pixels from: in the set it neither reads nor writes
+            hipLaunchKernelGGL(denoise_unusable_kernel, grid, block, 0, stream, f, dst, d_rgb);
+            d_rgb = d_work + (size_t)dst * f.npix;
+        }
         if (k < lds_levels()) {
             // the lattice of the largest residue class (alpha = beta = 0), in tiles
             const uint64_t lat_w = (width + f.step - 1) / f.step, lat_h = (height + f.step - 1) / f.step;
@@ -403,6 +477,47 @@ int flux_denoise_device(int device, uint64_t width, uint64_t height, void *d_rgb
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", device);
     HIP_TRY(dn::launch(p, width, height, (const double *)d_rgb, (const double *)d_aov, (double *)d_out_rgb, (double *)d_work,
                        (hipStream_t)hip_stream));
+    return FLUX_OK;
+}
+
+int flux_denoise_moments_device(int device, uint64_t width, uint64_t height, void *d_moments, void *d_aov, const double *params,
+                                void *d_out_rgb, void *d_work, uint64_t work_doubles, void *hip_stream) {
+    if (int rc = dn::check_size(width, height)) return rc;
+    if (!d_moments || !d_aov || !d_out_rgb || !d_work) return fail(FLUX_E_INVALID, "flux_denoise_moments_device: null device pointer");
+    dn::Params p;
+    if (int rc = dn::resolve_params(params, p)) return rc;
+    if (work_doubles < flux_denoise_work_doubles(width, height))
+        return fail(FLUX_E_INVALID, "flux_denoise_moments_device: work_doubles %llu is below flux_denoise_work_doubles = %llu",
+                    (unsigned long long)work_doubles, (unsigned long long)flux_denoise_work_doubles(width, height));
+    if (d_out_rgb == d_moments || d_out_rgb == d_work)
+        return fail(FLUX_E_INVALID, "flux_denoise_moments_device: d_out_rgb must be neither d_moments nor d_work");
+    if (int rc = flux::check_device(device)) return rc;
+    flux::DeviceGuard guard(device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", device);
+    HIP_TRY(dn::launch(p, width, height, (const double *)d_moments, (const double *)d_aov, (double *)d_out_rgb, (double *)d_work,
+                       (hipStream_t)hip_stream, true));
+    return FLUX_OK;
+}
+
+int flux_denoise_moments(int device, uint64_t width, uint64_t height, const double *moments, const double *aov, const double *params,
+                         double *out_rgb) {
+    if (int rc = dn::check_size(width, height)) return rc;
+    if (!moments || !aov || !out_rgb) return fail(FLUX_E_INVALID, "flux_denoise_moments: null pointer");
+    dn::Params p;
+    if (int rc = dn::resolve_params(params, p)) return rc;
+    if (int rc = flux::check_device(device)) return rc;
+    flux::DeviceGuard guard(device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", device);
+    const size_t npix = (size_t)(width * height);
+    flux::DevBuf<double> d_mom, d_aov, d_out, d_work;  // released with `device` still current (guard is older)
+    HIP_TRY(d_mom.alloc(npix * FLUX_MOMENT_CHANNELS));
+    HIP_TRY(d_aov.alloc(npix * FLUX_AOV_CHANNELS));
+    HIP_TRY(d_out.alloc(npix * 3));
+    HIP_TRY(d_work.alloc((size_t)flux_denoise_work_doubles(width, height)));
+    HIP_TRY(hipMemcpy(d_mom, moments, npix * FLUX_MOMENT_CHANNELS * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov, aov, npix * FLUX_AOV_CHANNELS * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(dn::launch(p, width, height, d_mom, d_aov, d_out, d_work, nullptr, true));
+    HIP_TRY(hipMemcpy(out_rgb, d_out, npix * 3 * sizeof(double), hipMemcpyDeviceToHost));  // (synchronises with the null stream)
     return FLUX_OK;
 }
 

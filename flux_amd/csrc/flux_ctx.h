@@ -151,6 +151,9 @@ struct flux_ctx {
     // ... and the feature buffers' own (flux_render_aov_rows)
     flux::DevBuf<double> d_aov;
     size_t d_aov_doubles = 0;
+    // ... and the sample moments' own (flux_render_moments_rows)
+    flux::DevBuf<double> d_moments;
+    size_t d_moments_doubles = 0;
     flux::Event ev0, ev1;
     bool timed = false;
     uint64_t device_bytes = 0;

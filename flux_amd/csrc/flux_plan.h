@@ -99,6 +99,10 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math);
 // a first hit runs no lobe --, `lds` the per-lane BVH stack of a mesh scene and nothing else, `blocks` one wave per pixel in
 // map_wave's order from 64 samples on and 64 / N pixels per wave below.
 LaunchPlan plan_aov(const RenderParams &p, int math);
+// The same for the moments kernel (moments_body.inc moments_kernel): block, grid and LDS as plan_render's STATIC branch computes
+// them -- render_static_kernel's two layouts and its per-lane stacks --, `copy` as kernel_copy answers (the kernel runs the lobes),
+// `kernel` 0 (or -1: nothing to do).
+LaunchPlan plan_moments(const RenderParams &p, int math);
 
 // LDS of the per-lane stacks of `lanes` lanes: the STRICT (f, s) recursion stack, 4 doubles per level, and the BVH traversal stack,
 // one int per level

@@ -37,6 +37,10 @@ hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream
 // (flux_plan.h) answers for the same arguments.
 hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream);
 
+// The per-pixel sample moments of the rows p names (moments_body.inc): p.out = [num_rows][W][FLUX_MOMENT_CHANNELS].  Runs what
+// plan_moments (flux_plan.h) answers for the same arguments.
+hipError_t launch_moments(const RenderParams &p, int math, hipStream_t stream);
+
 // Scene::shade for caller-supplied rays (device pointers; rays = n x (origin, direction)).
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream);

@@ -193,4 +193,23 @@ LaunchPlan plan_aov(const RenderParams &p, int math) {
     return L;
 }
 
+// The moments kernel: plan_render's STATIC branch at every sample count -- pixels in row-major order, FLUX_BLOCK_THREADS lanes a block,
+// the STRICT (f, s) stack and the BVH stack per lane --, in the copy a render of the job runs.
+LaunchPlan plan_moments(const RenderParams &p, int math) {
+    LaunchPlan L;
+    L.copy = kernel_copy(p, math);
+    const uint32_t N = p.nsamp;
+    const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
+    if (npix == 0 || p.set_count <= 0 || N == 0) return L;
+    const uint32_t ppw = N >= 64u ? 1u : 64u / N;
+    const uint64_t waves = (npix + ppw - 1) / ppw;
+    const unsigned wpb = FLUX_BLOCK_THREADS / 64;
+    L.kernel = 0;
+    L.block = FLUX_BLOCK_THREADS;
+    L.blocks = (waves + wpb - 1) / wpb;
+    L.tris = p.n_tris > 0 ? 1 : 0;
+    L.lds = lane_stacks_lds(math, (size_t)p.max_depth, L.tris != 0, (size_t)p.bvh_stack, L.block);
+    return L;
+}
+
 }  // namespace flux

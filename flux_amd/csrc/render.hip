@@ -43,7 +43,8 @@
 //    with the dielectric lobe;
 //  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy;
 //  * aov_kernel<TRIS> (aov_body.inc, the first-hit feature buffers: launch_plan.cpp plan_aov): STRICT and FAST, not the copy with the
-//    dielectric lobe -- a first hit runs no lobe.
+//    dielectric lobe -- a first hit runs no lobe;
+//  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments: launch_plan.cpp plan_moments): every copy -- it runs the lobes.
 #include "flux_device.h"
 #include "flux_plan.h"
 #include "flux_tables.h"
@@ -103,6 +104,7 @@ namespace flux {
 namespace strict {
 #include "render_body.inc"
 #include "aov_body.inc"
+#include "moments_body.inc"
 }  // namespace strict
 }  // namespace flux
 #undef FLUX_FAST
@@ -119,6 +121,7 @@ namespace flux {
 namespace fast {
 #include "render_body.inc"
 #include "aov_body.inc"
+#include "moments_body.inc"
 }  // namespace fast
 }  // namespace flux
 #undef FLUX_DIEL
@@ -129,6 +132,7 @@ namespace fast {
 namespace flux {
 namespace fast_diel {
 #include "render_body.inc"
+#include "moments_body.inc"
 }  // namespace fast_diel
 }  // namespace flux
 #undef FLUX_DIEL
@@ -243,6 +247,18 @@ hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream) {
     const LaunchPlan L = plan_aov(p, math);
     if (L.kernel < 0) return hipSuccess;
     return L.copy == kCopyStrict ? strict::launch_aov_impl(L, p, stream) : fast::launch_aov_impl(L, p, stream);
+}
+
+// the moments kernel as plan_moments lays it out, in the copy a render of the same job runs
+hipError_t launch_moments(const RenderParams &p, int math, hipStream_t stream) {
+    const LaunchPlan L = plan_moments(p, math);
+    if (L.kernel < 0) return hipSuccess;
+    switch (L.copy) {
+        case kCopyStrict: return strict::launch_moments_impl(L, p, stream);
+        case kCopyFast: return fast::launch_moments_impl(L, p, stream);
+        case kCopyFastDiel: return fast_diel::launch_moments_impl(L, p, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,

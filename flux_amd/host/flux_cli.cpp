@@ -5,7 +5,7 @@
 // wait (:92-94), ImageBuilder writes "<scene_name>.ppm" into the cwd and prints the total time
 // (manager.rs:326-335).  -n/--node ADDRESS[:PORT] adds NetworkWorkers (flux_node processes, flux_net.hpp) and
 // -L leaves the local GPUs out, as in main.rs:37-66.  Additions: --seed (the reference seeds from OS
-// entropy), --gpus, --outdir, --split, --aov, --denoise.  Not carried over: -g (SDL preview), rejected.
+// entropy), --gpus, --outdir, --split, --aov, --denoise, --denoise-variance.  Not carried over: -g (SDL preview), rejected.
 //
 // --split sets|rows|units: how the local GPUs share a frame.  `units` is the reference's scheme -- one worker per device pulling
 // WorkUnits from the shared channel (manager.rs:100) --, `sets` / `rows` hand the node's GPUs to ONE MultiGpuWorker (flux_multi_*:
@@ -18,6 +18,10 @@
 // --denoise: the finished frame and the feature buffers of the same job go through the a-trous filter (flux_abi.h flux_denoise) on
 // local device 0 and the result is written beside the frame as <scene_name>.denoised.ppm; refused like --aov without a local GPU.
 // With --aov as well the feature buffers are rendered once and all five files are written.
+// --denoise-variance measured|spatial (with --denoise; default spatial): `measured` renders the job's per-pixel sample moments on local
+// device 0 (flux_render_moments_rows: the frame again, with the variance of its samples) and writes <scene_name>.denoised.ppm from
+// them through flux_denoise_moments, which takes the noise from the samples instead of guessing it from the frame.  Without
+// --denoise, or with another word, the flag is refused with status 2 before any job starts.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +55,7 @@ struct Config {  // flux/src/main.rs:115-124
     std::string split = "auto";
     bool aov = false;
     bool denoise = false;
+    std::string denoise_variance;  // "" (not given), "spatial" or "measured"
 };
 
 void usage() {
@@ -62,6 +67,8 @@ void usage() {
                  "                     feature buffers of the frame, rendered on local GPU 0\n"
                  "        --denoise    Also write <scene_name>.denoised.ppm: the frame after a feature-guided a-trous filter on local\n"
                  "                     GPU 0 (for noisy previews of 1-16 samples per pixel; a clean frame may lose detail)\n\nOPTIONS:\n"
+                 "        --denoise-variance <measured|spatial>  with --denoise: where the filter takes a pixel's noise from [default spatial:\n"
+                 "                     the frame's neighbourhood; measured: the variance of the pixel's samples, from one more render pass]\n"
                  "    -d, --depth <DEPTH>          Tracing depth [default 5]\n"
                  "    -n, --node <ADDRESS[:PORT]>  Render using the flux_node process at this address (repeatable)\n"
                  "    -R, --rows <COUNT>           Image rows per work unit [default 50]\n"
@@ -120,6 +127,12 @@ Config config_from_args(int argc, char **argv) {
             c.aov = true;
         } else if (a == "--denoise") {
             c.denoise = true;
+        } else if (a == "--denoise-variance") {
+            c.denoise_variance = need("--denoise-variance");
+            if (c.denoise_variance != "measured" && c.denoise_variance != "spatial") {
+                std::fprintf(stderr, "error: invalid value '%s' for '--denoise-variance' (measured, spatial)\n", c.denoise_variance.c_str());
+                std::exit(2);
+            }
         } else if (a == "--outdir") {
             c.outdir = need("--outdir");
         } else if (a == "--split") {
@@ -137,6 +150,10 @@ Config config_from_args(int argc, char **argv) {
             std::fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", a.c_str());
             std::exit(2);
         }
+    }
+    if (!c.denoise_variance.empty() && !c.denoise) {
+        std::fprintf(stderr, "error: --denoise-variance says how --denoise measures the noise and needs that flag\n");
+        std::exit(2);
     }
     if (c.input_filename.empty()) {
         std::fprintf(stderr, "error: The following required arguments were not provided:\n    <scene_file>\n");
@@ -270,7 +287,10 @@ int main(int argc, char **argv) {
             }
             if (config.denoise) {
                 flag = "--denoise";
-                write("denoised", denoise_frame(image_builder.image, aov, w, h, 0));
+                if (config.denoise_variance == "measured")
+                    write("denoised", denoise_moments_frame(render_moments(s, job_config, config.seed, 0), aov, w, h, 0));
+                else
+                    write("denoised", denoise_frame(image_builder.image, aov, w, h, 0));
             }
         } catch (const FluxError &e) {
             std::fprintf(stderr, "error: %s: %s\n", flag, e.what());

@@ -264,6 +264,17 @@ std::vector<double> render_feature_buffers(const SceneData &scene_data, const Jo
     return aov;
 }
 
+std::vector<double> render_moments(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device) {
+    int rc = FLUX_OK;
+    const CtxPtr ctx = create_ctx(scene_data, config, seed, device, &rc);
+    if (!ctx) throw FluxError(rc, flux_last_error());
+    const size_t w = scene_data.output_settings.image_width, h = scene_data.output_settings.image_height;
+    std::vector<double> moments(w * h * FLUX_MOMENT_CHANNELS);
+    rc = flux_render_moments_rows(ctx.get(), 0, h - 1, moments.data());
+    if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());  // (the message is copied before the context goes)
+    return moments;
+}
+
 std::vector<double> aov_image(const double *aov, size_t width, size_t height, AovKind kind) {
     const size_t npix = width * height;
     std::vector<double> rgb(npix * 3);
@@ -304,6 +315,16 @@ std::vector<double> denoise_frame(const std::vector<double> &rgb, const std::vec
         throw FluxError(FLUX_E_INVALID, "denoise_frame: the buffers do not hold width * height pixels");
     std::vector<double> out(rgb.size());
     const int rc = flux_denoise(device, width, height, rgb.data(), aov.data(), nullptr, out.data());
+    if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());
+    return out;
+}
+
+std::vector<double> denoise_moments_frame(const std::vector<double> &moments, const std::vector<double> &aov, size_t width, size_t height,
+                                          int device) {
+    if (moments.size() != width * height * FLUX_MOMENT_CHANNELS || aov.size() != width * height * FLUX_AOV_CHANNELS)
+        throw FluxError(FLUX_E_INVALID, "denoise_moments_frame: the buffers do not hold width * height pixels");
+    std::vector<double> out(width * height * 3);
+    const int rc = flux_denoise_moments(device, width, height, moments.data(), aov.data(), nullptr, out.data());
     if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());
     return out;
 }

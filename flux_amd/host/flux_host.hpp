@@ -399,4 +399,14 @@ std::vector<double> aov_image(const double *aov, size_t width, size_t height, Ao
 // parameters: the filtered frame.  Throws FluxError with the library's message.
 std::vector<double> denoise_frame(const std::vector<double> &rgb, const std::vector<double> &aov, size_t width, size_t height, int device);
 
+// ---- per-pixel sample moments and the measured-variance filter (include/flux_abi.h flux_render_moments_rows, flux_denoise_moments) ----
+// The frame with its measured variance, [H][W][FLUX_MOMENT_CHANNELS]: a context on `device` for the job, one
+// flux_render_moments_rows over the frame, the context dropped.  Throws FluxError with the library's message (sample_root 1 is
+// refused: one sample has no variance).
+std::vector<double> render_moments(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device);
+// `moments` [H][W][FLUX_MOMENT_CHANNELS] and `aov` [H][W][FLUX_AOV_CHANNELS] filtered on `device` with the default parameters: the
+// filtered frame [H][W][3].  Buffers of another size are refused before the library is called.
+std::vector<double> denoise_moments_frame(const std::vector<double> &moments, const std::vector<double> &aov, size_t width, size_t height,
+                                          int device);
+
 }  // namespace flux_host

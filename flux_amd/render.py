@@ -142,9 +142,32 @@ class Renderer:
         _lib.check(_lib.lib.flux_render_aov_rows_device(self._handle(), first_row, row_stride, num_rows,
                                                         C.c_void_p(d_out_ptr), C.c_void_p(stream)))
 
-    def render_denoised(self, **params) -> np.ndarray:
-        """render_frame() + render_aov() + the a-trous filter (flux_amd.denoise, which takes `params`) on this renderer's device."""
-        return denoise(self.render_frame(), self.render_aov(), device=self.device, **params)
+    # -- per-pixel sample moments ------------------------------------------------
+    def render_moments(self, row_start: int = 0, row_end=None) -> np.ndarray:
+        """The frame and its measured variance for rows [row_start, row_end] inclusive (default: the frame), [rows, W, 8]:
+        flux_render_moments_rows.  Channels: flux_amd.MOMENT_RGB (the frame), MOMENT_VAR, MOMENT_MEAN (unclamped), MOMENT_S2."""
+        if row_end is None:
+            row_end = self.height - 1
+        if row_start < 0 or row_end < row_start:
+            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        out = np.empty((row_end - row_start + 1, self.width, _lib.MOMENT_CHANNELS), dtype=np.float64)
+        _lib.check(_lib.lib.flux_render_moments_rows(self._handle(), row_start, row_end, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def render_moments_device(self, first_row: int, row_stride: int, num_rows: int, d_out_ptr: int, stream: int = 0):
+        """Asynchronous device-resident sample moments (see flux_render_moments_rows_device): num_rows * W * 8 doubles."""
+        _lib.check(_lib.lib.flux_render_moments_rows_device(self._handle(), first_row, row_stride, num_rows,
+                                                            C.c_void_p(d_out_ptr), C.c_void_p(stream)))
+
+    def render_denoised(self, variance: str = "spatial", **params) -> np.ndarray:
+        """The denoised frame on this renderer's device; `params` are flux_amd.denoise's.  variance="spatial" (the default):
+        render_frame() + render_aov() + flux_amd.denoise, which estimates the noise from the frame.  variance="measured":
+        render_moments() + render_aov() + flux_amd.denoise_moments -- one render, whose per-sample variance guides the filter."""
+        if variance == "spatial":
+            return denoise(self.render_frame(), self.render_aov(), device=self.device, **params)
+        if variance == "measured":
+            return denoise_moments(self.render_moments(), self.render_aov(), device=self.device, **params)
+        raise _lib.FluxError(_lib.E_INVALID, f"render_denoised: variance must be 'spatial' or 'measured', got {variance!r}")
 
     def debug_shade(self, origins, directions, depth: int = 1, set_index: int = 0, sample_index: int = 0):
         """Scene::shade on the device for the given rays (flux_debug_shade): (rgb [n,3], first-hit index [n], t [n])."""
@@ -415,6 +438,33 @@ def denoise_device(width: int, height: int, d_rgb_ptr: int, d_aov_ptr: int, d_ou
     _lib.check(_lib.lib.flux_denoise_device(int(device), width, height, C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr),
                                             _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a), C.c_void_p(d_out_ptr),
                                             C.c_void_p(d_work_ptr), work_doubles, C.c_void_p(stream)))
+
+
+def denoise_moments(moments, aov, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1) -> np.ndarray:
+    """flux_denoise_moments (include/flux_abi.h): the a-trous filter of `denoise` guided by the measured
+    variance -- `moments` [H, W, 8] of render_moments(), whose channels 0..2 are the frame and channel 3 its variance, and `aov`
+    [H, W, 8] of render_aov(): the filtered frame [H, W, 3], on `device`."""
+    moments = np.ascontiguousarray(moments, dtype=np.float64)
+    aov = np.ascontiguousarray(aov, dtype=np.float64)
+    if moments.ndim != 3 or moments.shape[2] != _lib.MOMENT_CHANNELS or aov.shape != moments.shape[:2] + (_lib.AOV_CHANNELS,):
+        raise _lib.FluxError(_lib.E_INVALID, f"denoise_moments: moments {moments.shape} and aov {aov.shape} are not "
+                                             f"[H, W, {_lib.MOMENT_CHANNELS}] and [H, W, {_lib.AOV_CHANNELS}]")
+    out = np.empty(moments.shape[:2] + (3,), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    _lib.check(_lib.lib.flux_denoise_moments(int(device), moments.shape[1], moments.shape[0], moments.ctypes.data_as(dp),
+                                             aov.ctypes.data_as(dp), _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a),
+                                             out.ctypes.data_as(dp)))
+    return out
+
+
+def denoise_moments_device(width: int, height: int, d_moments_ptr: int, d_aov_ptr: int, d_out_ptr: int, d_work_ptr: int,
+                           work_doubles: int, stream: int = 0, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1,
+                           sigma_a=0.1):
+    """Asynchronous device-resident filter (see flux_denoise_moments_device): device addresses of the moments, the feature buffers,
+    the output frame and `work_doubles` >= denoise_work_doubles(width, height) doubles of scratch; `stream` a hipStream_t."""
+    _lib.check(_lib.lib.flux_denoise_moments_device(int(device), width, height, C.c_void_p(d_moments_ptr), C.c_void_p(d_aov_ptr),
+                                                    _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a),
+                                                    C.c_void_p(d_out_ptr), C.c_void_p(d_work_ptr), work_doubles, C.c_void_p(stream)))
 
 
 def debug_fastmath(fn: int, a, b=None, device: int = 0) -> np.ndarray:

@@ -307,6 +307,54 @@ uint64_t flux_denoise_work_doubles(uint64_t width, uint64_t height);
 int flux_denoise_device(int device, uint64_t width, uint64_t height, void *d_rgb, void *d_aov, const double *params,
                         void *d_out_rgb, void *d_work, uint64_t work_doubles, void *hip_stream);
 
+/* Per-pixel sample moments (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): the frame together
+ * with the measured variance of its samples, which a denoiser, an adaptive sampler or a convergence report reads.  DESIGN.md
+ * section 5g; tests/moments_spec.py states the same in numpy.  For pixel (row, col) of a context that holds every sample set,
+ * with N = sample_root^2 >= 4: the N samples the render kernels trace for it, each to its full depth under the context's
+ * arithmetic and traversal, L_i the radiance of sample i and l_i = (0.2126 L_i.r + 0.7152 L_i.g) + 0.0722 L_i.b.  The five sums
+ * of r, g, b, l and l^2 are formed per lane and combined in the fixed order flux_render_rows under FLUX_KERNEL_STATIC combines
+ * its three: no atomics, bit-reproducible, independent of how rows are grouped into calls.  The pixel's FLUX_MOMENT_CHANNELS doubles:
+ *   [0..2] FLUX_MOMENT_RGB   the frame: mean = sum c * (1 / N), then max_to_one (color.rs:35-44) -- bit for bit the pixel
+ *                            flux_render_rows writes under FLUX_KERNEL_STATIC
+ *   [3]    FLUX_MOMENT_VAR   the variance of the estimate lum(channels 0..2): (s2 / N) * k^2, with k = 1 / max(mean.r, mean.g,
+ *                            mean.b) where that maximum exceeds 1 (the factor max_to_one applied), else 1
+ *   [4..6] FLUX_MOMENT_MEAN  the mean radiance before max_to_one
+ *   [7]    FLUX_MOMENT_S2    the sample variance of the luminance, s2 = max(0, sum l^2 - (sum l * sum l) / N) / (N - 1)
+ * The max(0, .) keeps a NaN; nothing else is clamped, so a NaN or inf sample shows in channels 3 and 7.  The one-pass form of s2
+ * carries a relative error of about N 2^-53 (1 + m^2 / s2), m the mean luminance: rounding level at preview sample counts. */
+#define FLUX_MOMENT_CHANNELS 8
+#define FLUX_MOMENT_RGB 0
+#define FLUX_MOMENT_VAR 3
+#define FLUX_MOMENT_MEAN 4
+#define FLUX_MOMENT_S2 7
+/* Rows [row_start, row_end] inclusive into caller-owned host memory: (row_end-row_start+1) * image_width * FLUX_MOMENT_CHANNELS
+ * doubles, row-major.  Synchronous, argument checks as flux_render_aov_rows.  The call stages through a device buffer of its own:
+ * neither the scratch framebuffer of flux_render_rows nor that of flux_render_aov_rows is resized or reused. */
+int flux_render_moments_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out);
+/* Device-resident: rows first_row + k*row_stride, k < num_rows, to d_out (device pointer, num_rows * image_width *
+ * FLUX_MOMENT_CHANNELS doubles), asynchronously on `hip_stream`.  Argument checks as flux_render_aov_rows_device, and
+ * FLUX_E_INVALID as well for sample_root == 1: one sample has no variance (flux_denoise estimates one from the frame itself).  A
+ * job whose per-lane stacks exceed the LDS limit is refused as flux_render_rows_device refuses it under FLUX_KERNEL_STATIC.  One
+ * kernel beside the render kernels, with no effect on flux_ctx_stats; its launch is recorded between the context's two events. */
+int flux_render_moments_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
+                                    void *d_out, void *hip_stream);
+
+/* flux_denoise with the MEASURED variance (tests/denoise_moments_spec.py): moments [H][W][FLUX_MOMENT_CHANNELS]
+ * as flux_render_moments_rows returns it, of which rgb = channels 0..2 and v = channel 3 are used; aov, params (and their
+ * defaults), levels, output, tap skipping and bit-reproducibility as flux_denoise.  It is that filter with exactly two changes:
+ *   usable      a pixel must additionally have v finite and >= 0.
+ *   variance    replaces the spatial estimate: over the same step-1 taps in the same order, with the same
+ *               w = exp2(-min(G(p, q), 1100)):  var_p = sum w v_q / sum w, in one pass.
+ * The prefilter matters: at 4 spp up to half of the pixels have all samples equal, and a variance of exactly 0 would make such
+ * a pixel refuse every neighbour.  Argument checks as flux_denoise. */
+int flux_denoise_moments(int device, uint64_t width, uint64_t height, const double *moments, const double *aov,
+                         const double *params, double *out_rgb);
+/* The same on device pointers of `device`, asynchronously on `hip_stream`: 3 + L kernel launches.  d_moments and d_aov are only
+ * read.  flux_denoise_work_doubles is the scratch size for this call too.  Checked as flux_denoise_device (d_out_rgb may be neither
+ * d_moments nor d_work). */
+int flux_denoise_moments_device(int device, uint64_t width, uint64_t height, void *d_moments, void *d_aov, const double *params,
+                                void *d_out_rgb, void *d_work, uint64_t work_doubles, void *hip_stream);
+
 /* Render-kernel variants (all produce the same image within rounding):
  *   0 = default (FLUX_KERNEL_SPLIT where it applies, else FLUX_KERNEL_REFILL; STATIC below 64 spp)
  *   1 = FLUX_KERNEL_STATIC: one lane per sample, lanes idle once their path ends
