@@ -41,6 +41,9 @@ AOV_ALBEDO, AOV_NORMAL = slice(AOV_ALBEDO_OFFSET, AOV_ALBEDO_OFFSET + 3), slice(
 MOMENT_CHANNELS = 8
 MOMENT_RGB_OFFSET, MOMENT_VAR, MOMENT_MEAN_OFFSET, MOMENT_S2 = 0, 3, 4, 7
 MOMENT_RGB, MOMENT_MEAN = slice(MOMENT_RGB_OFFSET, MOMENT_RGB_OFFSET + 3), slice(MOMENT_MEAN_OFFSET, MOMENT_MEAN_OFFSET + 3)
+# adaptive sampling (include/flux_abi.h FLUX_ADAPTIVE_*): the defaults and the words of `info`
+ADAPTIVE_THRESHOLD, ADAPTIVE_LUM_FLOOR, ADAPTIVE_MIN_PASSES, ADAPTIVE_MAX_PASSES, ADAPTIVE_DILATE = 0.05, 0.01, 1, 8, 1
+ADAPTIVE_INFO_WORDS = 4
 DENOISE_PARAM_WORDS = 8  # flux_denoise's params: levels, sigma_l, sigma_n, sigma_z, sigma_a, three reserved zeros
 
 
@@ -77,6 +80,11 @@ class FluxWorkUnit(C.Structure):
     _fields_ = [("row_start", C.c_uint64), ("row_end", C.c_uint64)]
 
 
+class FluxAdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("lum_floor", C.c_double), ("min_passes", C.c_uint32), ("max_passes", C.c_uint32),
+                ("dilate", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class FluxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"flux error {code}: {msg}")
@@ -110,6 +118,8 @@ SYMBOLS = {
     "flux_denoise_moments": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "flux_denoise_moments_device": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(C.c_double), _P, _P, C.c_uint64, _P]),
+    "flux_render_adaptive_rows": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.POINTER(C.c_double), _P, C.POINTER(C.c_uint64)]),
+    "flux_render_adaptive_rows_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, _P, C.POINTER(C.c_uint64), _P]),
     "flux_ctx_set_kernel": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_traversal": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_math": (C.c_int, [_P, C.c_int]),

@@ -399,7 +399,7 @@ static int effective_math(const flux_ctx *ctx) {
 // STRICT keeps the (f,s) recursion stack, 4 doubles per level per lane; mesh scenes the BVH traversal stack, one int per
 // level per lane -- 64 lanes in the FAST state-machine kernel, the block's in the others --; the split kernel its path
 // queues), plus the few static words of the refill / split kernels.  64 KiB per block is the launch limit.
-enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2 };  // which kernel family a launch runs
+enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2 };  // which kernel family a launch runs (an adaptive pass: plan_moments' LDS)
 static int check_lds_budget(const flux_ctx *ctx, const flux::RenderParams &p, const char *what, Pass pass = kPassRender) {
     const size_t dyn = pass == kPassAov       ? flux::plan_aov(p, effective_math(ctx)).lds
                        : pass == kPassMoments ? flux::plan_moments(p, effective_math(ctx)).lds
@@ -721,6 +721,144 @@ int flux_render_moments_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end
     int rc = flux_render_moments_rows_device(ctx, row_start, 1, rows, ctx->d_moments, nullptr);
     if (rc != FLUX_OK) return rc;
     HIP_TRY(hipMemcpy(out, ctx->d_moments, doubles * sizeof(double), hipMemcpyDeviceToHost));
+    return FLUX_OK;
+}
+
+// ---- adaptive sampling (adaptive_body.inc, adaptive.hip) -------------------------------------------------------
+// The checks that need no context, each with a message of its own; nullptr for a null `params`.
+static int check_adaptive_params(const char *what, const flux_adaptive_params *a) {
+    if (!a) return fail(FLUX_E_INVALID, "%s: null params", what);
+    if (!std::isfinite(a->threshold) || a->threshold < 0.0)
+        return fail(FLUX_E_INVALID, "%s: threshold %g must be finite and >= 0", what, a->threshold);
+    if (!std::isfinite(a->lum_floor) || !(a->lum_floor > 0.0))
+        return fail(FLUX_E_INVALID, "%s: lum_floor %g must be finite and > 0", what, a->lum_floor);
+    if (a->min_passes < 1) return fail(FLUX_E_INVALID, "%s: min_passes must be >= 1", what);
+    if (a->max_passes < a->min_passes)
+        return fail(FLUX_E_INVALID, "%s: max_passes %u is below min_passes %u", what, a->max_passes, a->min_passes);
+    if (a->dilate > 2) return fail(FLUX_E_INVALID, "%s: dilate %u exceeds 2", what, a->dilate);
+    if (a->reserved != 0) return fail(FLUX_E_INVALID, "%s: the reserved word must be 0", what);
+    return FLUX_OK;
+}
+// ... and the ones that need the context but no device
+static int check_adaptive_ctx(const char *what, const flux_ctx *ctx, const flux_adaptive_params *a) {
+    if (!ctx) return fail(FLUX_E_INVALID, "%s: null context", what);
+    if (!holds_all_sets(ctx))  // every row uses every sample set (trace.rs:64-69)
+        return fail(FLUX_E_INVALID, "adaptive sampling needs all sample sets; this context holds the share %u + k*%u "
+                    "(flux_ctx_create_sets), which no adaptive call serves", ctx->sets.first, ctx->sets.stride);
+    if (ctx->N < 2)
+        return fail(FLUX_E_INVALID, "adaptive sampling needs sample_root >= 2: one sample per pass has no variance to decide by");
+    if (a->max_passes > ctx->S)
+        return fail(FLUX_E_INVALID, "%s: max_passes %u exceeds the %u sample sets: a pixel would read a set twice", what, a->max_passes,
+                    ctx->S);
+    return FLUX_OK;
+}
+
+// The rounds.  Rounds r < min_passes run over the identity list and need no selection; every later round
+// first runs the selection and reads its 4-byte count back -- ONE hipStreamSynchronize per such round -- to size the pass and to
+// stop at 0.  `info` costs one more synchronisation behind the finish kernel.  The context's two events span the call's launches.
+int flux_render_adaptive_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *params,
+                                     void *d_out_moments, void *d_out_passes, uint64_t info[FLUX_ADAPTIVE_INFO_WORDS], void *hip_stream) {
+    const char *what = "flux_render_adaptive_rows_device";
+    const flux_adaptive_params *a = (const flux_adaptive_params *)params;
+    if (int rc = check_adaptive_params(what, a)) return rc;
+    if (int rc = check_adaptive_ctx(what, ctx, a)) return rc;
+    if (info) info[0] = info[1] = info[2] = info[3] = 0;
+    if (num_rows == 0) return FLUX_OK;
+    if (!d_out_moments || !d_out_passes) return fail(FLUX_E_INVALID, "%s: null output pointer", what);
+    if (row_stride < 1) return fail(FLUX_E_INVALID, "row_stride must be >= 1");
+    if (first_row >= ctx->H || first_row + (num_rows - 1) * row_stride >= ctx->H)
+        return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
+                    (unsigned long long)first_row, (unsigned long long)row_stride,
+                    (unsigned long long)num_rows, ctx->H);
+    const uint64_t pixels = num_rows * ctx->W;
+    if (pixels > 0x7fffffffull) return fail(FLUX_E_INVALID, "%s: %llu pixels exceed 2^31 - 1", what, (unsigned long long)pixels);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+    flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, nullptr);
+    p.stats = nullptr;
+    if (int rc = check_lds_budget(ctx, p, "flux_render_adaptive_rows", kPassMoments)) return rc;
+    if (pixels > ctx->d_adapt_pixels) {
+        ctx->d_adapt_pixels = 0;  // (stays 0 if a new allocation fails: the old ones are released first)
+        HIP_TRY(ctx->d_adapt_sums.alloc((size_t)pixels * flux::kAdaptiveSums));
+        HIP_TRY(ctx->d_adapt_passes.alloc((size_t)pixels));
+        HIP_TRY(ctx->d_adapt_list.alloc((size_t)pixels));
+        HIP_TRY(ctx->d_adapt_hot.alloc((size_t)pixels));
+        HIP_TRY(ctx->d_adapt_counts.alloc(2));
+        ctx->d_adapt_pixels = (size_t)pixels;
+    }
+    const int math = effective_math(ctx);
+    flux::AdaptiveWork work{};
+    work.sums = ctx->d_adapt_sums;
+    work.passes = ctx->d_adapt_passes;
+    const flux::AdaptiveRule rule{a->threshold * a->threshold, a->lum_floor, ctx->N, a->dilate};
+    uint32_t *d_active = ctx->d_adapt_counts, *d_reached = d_active + 1;
+
+    HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    ctx->timed = false;
+    uint64_t rounds = 0, traced = 0;
+    for (uint32_t r = 0; r < a->max_passes; ++r) {
+        if (r < a->min_passes) {
+            work.list = nullptr;
+            work.count = (uint32_t)pixels;
+        } else {
+            HIP_TRY(flux::launch_adaptive_select(rule, (uint32_t)num_rows, ctx->W, work.sums, work.passes, ctx->d_adapt_hot,
+                                                 ctx->d_adapt_list, d_active, stream));
+            uint32_t active = 0;
+            HIP_TRY(hipMemcpyAsync(&active, d_active, sizeof(active), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (active == 0) break;
+            if (active > pixels) return fail(FLUX_E_DEVICE, "%s: the selection counted %u of %llu pixels", what, active,
+                                             (unsigned long long)pixels);
+            work.list = ctx->d_adapt_list;
+            work.count = active;
+        }
+        work.fresh = r == 0 ? 1u : 0u;  // (the first pass writes the state: nothing is cleared)
+        HIP_TRY(flux::launch_adaptive(p, work, math, stream));
+        rounds += 1;
+        traced += work.count;
+    }
+    HIP_TRY(flux::launch_adaptive_finish(ctx->N, pixels, work.sums, work.passes, (double *)d_out_moments, (uint32_t *)d_out_passes, stream));
+    if (info) HIP_TRY(flux::launch_adaptive_count(a->max_passes, pixels, work.passes, d_reached, stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    ctx->timed = true;
+    if (info) {
+        uint32_t reached = 0;
+        HIP_TRY(hipMemcpyAsync(&reached, d_reached, sizeof(reached), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        info[0] = rounds;
+        info[1] = traced;
+        info[2] = reached;
+        info[3] = 0;
+    }
+    return FLUX_OK;
+}
+
+// (staging buffers of its own, d_adapt_out and d_adapt_map: no other call's scratch is resized or aliased)
+int flux_render_adaptive_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, void *params, double *out_moments, void *out_passes,
+                              uint64_t info[FLUX_ADAPTIVE_INFO_WORDS]) {
+    const char *what = "flux_render_adaptive_rows";
+    const flux_adaptive_params *a = (const flux_adaptive_params *)params;
+    if (int rc = check_adaptive_params(what, a)) return rc;
+    if (int rc = check_adaptive_ctx(what, ctx, a)) return rc;
+    if (!out_moments || !out_passes) return fail(FLUX_E_INVALID, "%s: null output pointer", what);
+    if (row_end < row_start || row_end >= ctx->H)
+        return fail(FLUX_E_INVALID, "rows [%llu,%llu] outside image height %u",
+                    (unsigned long long)row_start, (unsigned long long)row_end, ctx->H);
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+    const uint64_t rows = row_end - row_start + 1;
+    const size_t pixels = (size_t)rows * ctx->W;
+    if (pixels > ctx->d_adapt_out_pixels) {
+        ctx->d_adapt_out_pixels = 0;  // (stays 0 if a new allocation fails: the old ones are released first)
+        HIP_TRY(ctx->d_adapt_out.alloc(pixels * FLUX_MOMENT_CHANNELS));
+        HIP_TRY(ctx->d_adapt_map.alloc(pixels));
+        ctx->d_adapt_out_pixels = pixels;
+    }
+    int rc = flux_render_adaptive_rows_device(ctx, row_start, 1, rows, params, ctx->d_adapt_out, ctx->d_adapt_map, info, nullptr);
+    if (rc != FLUX_OK) return rc;
+    HIP_TRY(hipMemcpy(out_moments, ctx->d_adapt_out, pixels * FLUX_MOMENT_CHANNELS * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_passes, ctx->d_adapt_map, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return FLUX_OK;
 }
 

@@ -154,6 +154,13 @@ struct flux_ctx {
     // ... and the sample moments' own (flux_render_moments_rows)
     flux::DevBuf<double> d_moments;
     size_t d_moments_doubles = 0;
+    // ... and the adaptive sampler's state and work list (flux_render_adaptive_rows*), all sized for d_adapt_pixels pixels: the running
+    // sums [pixels][kAdaptiveSums], the pass counts, the hot flags, the list, and two counters (active pixels, pixels at max_passes);
+    // d_adapt_out / d_adapt_map stage the host entry point's outputs
+    flux::DevBuf<double> d_adapt_sums, d_adapt_out;
+    flux::DevBuf<uint32_t> d_adapt_passes, d_adapt_list, d_adapt_counts, d_adapt_map;
+    flux::DevBuf<unsigned char> d_adapt_hot;
+    size_t d_adapt_pixels = 0, d_adapt_out_pixels = 0;
     flux::Event ev0, ev1;
     bool timed = false;
     uint64_t device_bytes = 0;

@@ -291,6 +291,17 @@ struct RenderParams {
 // bytes per hit record of RenderParams::lobe_frame
 constexpr size_t kLobeFrameBytes = 6 * sizeof(double);
 
+// The adaptive pass's second kernel argument (adaptive_body.inc): the pixels one pass covers and the per-pixel
+// state it adds to.  Pixel indices are local to the call: local row * W + column.
+struct AdaptiveWork {
+    const uint32_t *list;  // [count] pixels of this pass, each at most once; nullptr: the identity list (every pixel of the call)
+    uint32_t count;        // entries of the list
+    uint32_t fresh;        // 1: the call's first pass -- every c counts as 0 and the state is written, not read (it need not be cleared)
+    double *sums;          // [pixels][kAdaptiveSums]: the running sums of r, g, b, l and l l
+    uint32_t *passes;      // [pixels]: c, the passes a pixel has taken
+};
+constexpr int kAdaptiveSums = 5;
+
 // hit records of a scene (DevHitRec): one per sphere, plane and disk, six per box
 __host__ __device__ inline int hit_records(const RenderParams &p) { return p.n_sph + p.n_pln + p.n_dsk + 6 * p.n_box; }
 

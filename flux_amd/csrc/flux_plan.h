@@ -103,6 +103,9 @@ LaunchPlan plan_aov(const RenderParams &p, int math);
 // them -- render_static_kernel's two layouts and its per-lane stacks --, `copy` as kernel_copy answers (the kernel runs the lobes),
 // `kernel` 0 (or -1: nothing to do).
 LaunchPlan plan_moments(const RenderParams &p, int math);
+// The same for one pass of the adaptive sampler (adaptive_body.inc adaptive_pass_kernel): plan_moments' block, LDS and copy, with
+// `blocks` sized by the `entries` of the pass's work list instead of the pixel grid (-1: an empty list).
+LaunchPlan plan_adaptive(const RenderParams &p, int math, uint64_t entries);
 
 // LDS of the per-lane stacks of `lanes` lanes: the STRICT (f, s) recursion stack, 4 doubles per level, and the BVH traversal stack,
 // one int per level

@@ -41,6 +41,25 @@ hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream);
 // plan_moments (flux_plan.h) answers for the same arguments.
 hipError_t launch_moments(const RenderParams &p, int math, hipStream_t stream);
 
+// One pass of the adaptive sampler over the work list `a` names (adaptive_body.inc), for the rows p names: N more samples of every
+// listed pixel added to a.sums, a.passes counted up.  Runs what plan_adaptive (flux_plan.h) answers for (p, math, a.count).
+hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int math, hipStream_t stream);
+
+// What the adaptive sampler runs between and after its passes (adaptive.hip; no lobe code).  `pixels` = rows * width of the call.
+struct AdaptiveRule {
+    double tau2, lum_floor;  // threshold squared, the floor of the mean luminance
+    uint32_t nsamp, dilate;  // N, the Chebyshev radius of the dilation
+};
+// hot[p] per pixel from the state (sums [pixels][kAdaptiveSums], passes [pixels]), then the pixels within `dilate` of a hot one
+// compacted into list, their number in *count (zeroed here first).  Two launches and one 4-byte memset, asynchronous on `stream`.
+hipError_t launch_adaptive_select(const AdaptiveRule &rule, uint32_t rows, uint32_t width, const double *sums, const uint32_t *passes,
+                                  unsigned char *hot, uint32_t *list, uint32_t *count, hipStream_t stream);
+// The state as the moments layout ([pixels][FLUX_MOMENT_CHANNELS], n = N c in place of N) and the pass map.  Asynchronous on `stream`.
+hipError_t launch_adaptive_finish(uint32_t nsamp, uint64_t pixels, const double *sums, const uint32_t *passes, double *out_moments,
+                                  uint32_t *out_passes, hipStream_t stream);
+// *reached (zeroed here first) = the pixels with passes[p] == max_passes.  Asynchronous on `stream`.
+hipError_t launch_adaptive_count(uint32_t max_passes, uint64_t pixels, const uint32_t *passes, uint32_t *reached, hipStream_t stream);
+
 // Scene::shade for caller-supplied rays (device pointers; rays = n x (origin, direction)).
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream);

@@ -212,4 +212,22 @@ LaunchPlan plan_moments(const RenderParams &p, int math) {
     return L;
 }
 
+// One pass of the adaptive sampler: plan_moments with the work list's entries in place of the pixel grid -- 64 / N entries per wave
+// below 64 samples, one from there on --, the same block, LDS and copy.
+LaunchPlan plan_adaptive(const RenderParams &p, int math, uint64_t entries) {
+    LaunchPlan L;
+    L.copy = kernel_copy(p, math);
+    const uint32_t N = p.nsamp;
+    if (entries == 0 || p.set_count <= 0 || N == 0) return L;
+    const uint32_t ppw = N >= 64u ? 1u : 64u / N;
+    const uint64_t waves = (entries + ppw - 1) / ppw;
+    const unsigned wpb = FLUX_BLOCK_THREADS / 64;
+    L.kernel = 0;
+    L.block = FLUX_BLOCK_THREADS;
+    L.blocks = (waves + wpb - 1) / wpb;
+    L.tris = p.n_tris > 0 ? 1 : 0;
+    L.lds = lane_stacks_lds(math, (size_t)p.max_depth, L.tris != 0, (size_t)p.bvh_stack, L.block);
+    return L;
+}
+
 }  // namespace flux

@@ -44,7 +44,9 @@
 //  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy;
 //  * aov_kernel<TRIS> (aov_body.inc, the first-hit feature buffers: launch_plan.cpp plan_aov): STRICT and FAST, not the copy with the
 //    dielectric lobe -- a first hit runs no lobe;
-//  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments: launch_plan.cpp plan_moments): every copy -- it runs the lobes.
+//  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments: launch_plan.cpp plan_moments): every copy -- it runs the lobes;
+//  * adaptive_pass_kernel<TRIS> (adaptive_body.inc, one pass of the adaptive sampler over a work list: launch_plan.cpp plan_adaptive):
+//    every copy, as moments_kernel.
 #include "flux_device.h"
 #include "flux_plan.h"
 #include "flux_tables.h"
@@ -105,6 +107,7 @@ namespace strict {
 #include "render_body.inc"
 #include "aov_body.inc"
 #include "moments_body.inc"
+#include "adaptive_body.inc"
 }  // namespace strict
 }  // namespace flux
 #undef FLUX_FAST
@@ -122,6 +125,7 @@ namespace fast {
 #include "render_body.inc"
 #include "aov_body.inc"
 #include "moments_body.inc"
+#include "adaptive_body.inc"
 }  // namespace fast
 }  // namespace flux
 #undef FLUX_DIEL
@@ -133,6 +137,7 @@ namespace flux {
 namespace fast_diel {
 #include "render_body.inc"
 #include "moments_body.inc"
+#include "adaptive_body.inc"
 }  // namespace fast_diel
 }  // namespace flux
 #undef FLUX_DIEL
@@ -257,6 +262,18 @@ hipError_t launch_moments(const RenderParams &p, int math, hipStream_t stream) {
         case kCopyStrict: return strict::launch_moments_impl(L, p, stream);
         case kCopyFast: return fast::launch_moments_impl(L, p, stream);
         case kCopyFastDiel: return fast_diel::launch_moments_impl(L, p, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// one pass of the adaptive sampler as plan_adaptive lays it out, in the copy a render of the same job runs
+hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int math, hipStream_t stream) {
+    const LaunchPlan L = plan_adaptive(p, math, a.count);
+    if (L.kernel < 0) return hipSuccess;
+    switch (L.copy) {
+        case kCopyStrict: return strict::launch_adaptive_impl(L, p, a, stream);
+        case kCopyFast: return fast::launch_adaptive_impl(L, p, a, stream);
+        case kCopyFastDiel: return fast_diel::launch_adaptive_impl(L, p, a, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -5,7 +5,7 @@
 // wait (:92-94), ImageBuilder writes "<scene_name>.ppm" into the cwd and prints the total time
 // (manager.rs:326-335).  -n/--node ADDRESS[:PORT] adds NetworkWorkers (flux_node processes, flux_net.hpp) and
 // -L leaves the local GPUs out, as in main.rs:37-66.  Additions: --seed (the reference seeds from OS
-// entropy), --gpus, --outdir, --split, --aov, --denoise, --denoise-variance.  Not carried over: -g (SDL preview), rejected.
+// entropy), --gpus, --outdir, --split, --aov, --denoise, --denoise-variance, --adaptive, --adaptive-max-passes.  Not carried over: -g (SDL preview), rejected.
 //
 // --split sets|rows|units: how the local GPUs share a frame.  `units` is the reference's scheme -- one worker per device pulling
 // WorkUnits from the shared channel (manager.rs:100) --, `sets` / `rows` hand the node's GPUs to ONE MultiGpuWorker (flux_multi_*:
@@ -22,6 +22,13 @@
 // device 0 (flux_render_moments_rows: the frame again, with the variance of its samples) and writes <scene_name>.denoised.ppm from
 // them through flux_denoise_moments, which takes the noise from the samples instead of guessing it from the frame.  Without
 // --denoise, or with another word, the flag is refused with status 2 before any job starts.
+// --adaptive <threshold> [--adaptive-max-passes M, default 8]: after the frame is written, the job is rendered once more on local
+// device 0 with adaptive sampling (flux_abi.h flux_render_adaptive_rows: passes of sample_root^2 samples, further ones only where the
+// relative standard error exceeds the threshold; the other parameters at their defaults) and written as <scene_name>.adaptive.ppm,
+// with the passes per pixel as <scene_name>.passes.ppm (grey, c / M); the rounds and the mean samples per pixel are printed.  Refused
+// like --aov without a local GPU.  A threshold that is no finite number >= 0, M = 0, or --adaptive-max-passes without --adaptive,
+// exits with status 2 before any job starts.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +63,9 @@ struct Config {  // flux/src/main.rs:115-124
     bool aov = false;
     bool denoise = false;
     std::string denoise_variance;  // "" (not given), "spatial" or "measured"
+    bool adaptive = false;
+    double adaptive_threshold = 0.0;
+    size_t adaptive_max_passes = 0;  // 0: not given
 };
 
 void usage() {
@@ -69,6 +79,9 @@ void usage() {
                  "                     GPU 0 (for noisy previews of 1-16 samples per pixel; a clean frame may lose detail)\n\nOPTIONS:\n"
                  "        --denoise-variance <measured|spatial>  with --denoise: where the filter takes a pixel's noise from [default spatial:\n"
                  "                     the frame's neighbourhood; measured: the variance of the pixel's samples, from one more render pass]\n"
+                 "        --adaptive <THRESHOLD>   Also write <scene_name>.adaptive.ppm and <scene_name>.passes.ppm: the job with adaptive sampling on\n"
+                 "                     local GPU 0 -- further passes of ROOT^2 samples only where the relative standard error exceeds THRESHOLD\n"
+                 "        --adaptive-max-passes <M>  with --adaptive: most passes a pixel takes [default 8; at most the image width]\n"
                  "    -d, --depth <DEPTH>          Tracing depth [default 5]\n"
                  "    -n, --node <ADDRESS[:PORT]>  Render using the flux_node process at this address (repeatable)\n"
                  "    -R, --rows <COUNT>           Image rows per work unit [default 50]\n"
@@ -133,6 +146,21 @@ Config config_from_args(int argc, char **argv) {
                 std::fprintf(stderr, "error: invalid value '%s' for '--denoise-variance' (measured, spatial)\n", c.denoise_variance.c_str());
                 std::exit(2);
             }
+        } else if (a == "--adaptive") {
+            const char *v = need("--adaptive");
+            char *end = nullptr;
+            c.adaptive_threshold = std::strtod(v, &end);
+            if (end == v || *end != '\0' || !std::isfinite(c.adaptive_threshold) || c.adaptive_threshold < 0.0) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--adaptive' (a finite threshold >= 0)\n", v);
+                std::exit(2);
+            }
+            c.adaptive = true;
+        } else if (a == "--adaptive-max-passes") {
+            c.adaptive_max_passes = parse_usize("--adaptive-max-passes", need("--adaptive-max-passes"));
+            if (c.adaptive_max_passes < 1 || c.adaptive_max_passes > 0xffffffffull) {
+                std::fprintf(stderr, "error: invalid value for '--adaptive-max-passes' (at least 1)\n");
+                std::exit(2);
+            }
         } else if (a == "--outdir") {
             c.outdir = need("--outdir");
         } else if (a == "--split") {
@@ -153,6 +181,10 @@ Config config_from_args(int argc, char **argv) {
     }
     if (!c.denoise_variance.empty() && !c.denoise) {
         std::fprintf(stderr, "error: --denoise-variance says how --denoise measures the noise and needs that flag\n");
+        std::exit(2);
+    }
+    if (c.adaptive_max_passes != 0 && !c.adaptive) {
+        std::fprintf(stderr, "error: --adaptive-max-passes bounds the passes of --adaptive and needs that flag\n");
         std::exit(2);
     }
     if (c.input_filename.empty()) {
@@ -184,6 +216,10 @@ int main(int argc, char **argv) {
     }
     if (config.denoise && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
         std::fprintf(stderr, "error: --denoise filters the frame on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
+        return 2;
+    }
+    if (config.adaptive && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
+        std::fprintf(stderr, "error: --adaptive renders the adaptive frame on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
         return 2;
     }
     // main.rs:37-66: the local worker(s) unless -L, then one NetworkWorker per -n
@@ -294,6 +330,28 @@ int main(int argc, char **argv) {
             }
         } catch (const FluxError &e) {
             std::fprintf(stderr, "error: %s: %s\n", flag, e.what());
+            rc = 1;
+        }
+    }
+    if (rc == 0 && config.adaptive && !image_builder.written_path.empty()) {
+        try {
+            flux_adaptive_params par = adaptive_defaults();
+            par.threshold = config.adaptive_threshold;
+            if (config.adaptive_max_passes != 0) par.max_passes = (uint32_t)config.adaptive_max_passes;
+            const AdaptiveFrame f = render_adaptive(s, job_config, config.seed, 0, par);
+            const size_t w = s.output_settings.image_width, h = s.output_settings.image_height;
+            const auto write = [&](const char *name, const std::vector<double> &img) {
+                const std::string path = config.outdir + "/" + s.scene_name + "." + name + ".ppm";
+                if (flux_write_ppm(path.c_str(), img.data(), w, h, nullptr) != FLUX_OK) throw FluxError(FLUX_E_IO, flux_last_error());
+                std::printf("wrote %s\n", path.c_str());
+            };
+            write("adaptive", moments_frame(f.moments, w, h));
+            write("passes", passes_image(f.passes, w, h, par.max_passes));
+            const double spp = (double)f.pixel_passes * (double)(config.sample_root * config.sample_root) / (double)(w * h);
+            std::printf("adaptive: %llu round(s), %.2f samples per pixel on average, %llu pixel(s) at the %u-pass limit\n",
+                        (unsigned long long)f.rounds, spp, (unsigned long long)f.pixels_at_max_passes, par.max_passes);
+        } catch (const FluxError &e) {
+            std::fprintf(stderr, "error: --adaptive: %s\n", e.what());
             rc = 1;
         }
     }

@@ -329,6 +329,58 @@ std::vector<double> denoise_moments_frame(const std::vector<double> &moments, co
     return out;
 }
 
+flux_adaptive_params adaptive_defaults() {
+    flux_adaptive_params p{};
+    p.threshold = FLUX_ADAPTIVE_THRESHOLD;
+    p.lum_floor = FLUX_ADAPTIVE_LUM_FLOOR;
+    p.min_passes = FLUX_ADAPTIVE_MIN_PASSES;
+    p.max_passes = FLUX_ADAPTIVE_MAX_PASSES;
+    p.dilate = FLUX_ADAPTIVE_DILATE;
+    return p;
+}
+
+AdaptiveFrame render_adaptive(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device,
+                              const flux_adaptive_params &params) {
+    const size_t w = scene_data.output_settings.image_width, h = scene_data.output_settings.image_height;
+    if (params.max_passes > w)
+        throw FluxError(FLUX_E_INVALID, "render_adaptive: max_passes " + std::to_string(params.max_passes) + " exceeds the " +
+                                            std::to_string(w) + " sample sets of an image this wide");
+    int rc = FLUX_OK;
+    const CtxPtr ctx = create_ctx(scene_data, config, seed, device, &rc);
+    if (!ctx) throw FluxError(rc, flux_last_error());
+    AdaptiveFrame f;
+    f.moments.resize(w * h * FLUX_MOMENT_CHANNELS);
+    f.passes.resize(w * h);
+    flux_adaptive_params p = params;
+    uint64_t info[FLUX_ADAPTIVE_INFO_WORDS] = {};
+    rc = flux_render_adaptive_rows(ctx.get(), 0, h - 1, &p, f.moments.data(), f.passes.data(), info);
+    if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());  // (the message is copied before the context goes)
+    f.rounds = info[0];
+    f.pixel_passes = info[1];
+    f.pixels_at_max_passes = info[2];
+    return f;
+}
+
+std::vector<double> moments_frame(const std::vector<double> &moments, size_t width, size_t height) {
+    if (moments.size() != width * height * FLUX_MOMENT_CHANNELS)
+        throw FluxError(FLUX_E_INVALID, "moments_frame: the buffer does not hold width * height pixels");
+    std::vector<double> rgb(width * height * 3);
+    for (size_t k = 0; k < width * height; k++)
+        for (int c = 0; c < 3; c++) rgb[k * 3 + c] = moments[k * FLUX_MOMENT_CHANNELS + FLUX_MOMENT_RGB + c];
+    return rgb;
+}
+
+std::vector<double> passes_image(const std::vector<uint32_t> &passes, size_t width, size_t height, uint32_t max_passes) {
+    if (passes.size() != width * height) throw FluxError(FLUX_E_INVALID, "passes_image: the map does not hold width * height pixels");
+    if (max_passes == 0) throw FluxError(FLUX_E_INVALID, "passes_image: max_passes must be >= 1");
+    std::vector<double> rgb(width * height * 3);
+    for (size_t k = 0; k < width * height; k++) {
+        const double g = passes[k] < max_passes ? (double)passes[k] / (double)max_passes : 1.0;
+        rgb[k * 3] = rgb[k * 3 + 1] = rgb[k * 3 + 2] = g;
+    }
+    return rgb;
+}
+
 std::vector<WorkUnit> Job::work_units() const {
     const uint64_t h = scene_data.output_settings.image_height;
     int64_t n = flux_work_units(h, config.rows_per_work_unit, nullptr, 0);

@@ -409,4 +409,22 @@ std::vector<double> render_moments(const SceneData &scene_data, const JobConfigu
 std::vector<double> denoise_moments_frame(const std::vector<double> &moments, const std::vector<double> &aov, size_t width, size_t height,
                                           int device);
 
+// ---- adaptive sampling (include/flux_abi.h flux_render_adaptive_rows) -----------------------------------------------------------
+// What a call returns: the moments layout with each pixel's own sample count, the passes per pixel, and the call's `info` words.
+struct AdaptiveFrame {
+    std::vector<double> moments;   // [H][W][FLUX_MOMENT_CHANNELS]
+    std::vector<uint32_t> passes;  // [H][W]
+    uint64_t rounds = 0, pixel_passes = 0, pixels_at_max_passes = 0;
+};
+// The defaults of include/flux_abi.h (FLUX_ADAPTIVE_*).
+flux_adaptive_params adaptive_defaults();
+// A context on `device` for the job, one flux_render_adaptive_rows over the frame, the context dropped.  A max_passes beyond the
+// image width is refused before any context exists; everything else throws FluxError with the library's message.
+AdaptiveFrame render_adaptive(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device,
+                              const flux_adaptive_params &params);
+// Channels 0..2 of a moments buffer as a frame [H][W][3], and a pass map as a grey frame c / max_passes.  Buffers that do not hold
+// width * height pixels, and max_passes 0, are refused.
+std::vector<double> moments_frame(const std::vector<double> &moments, size_t width, size_t height);
+std::vector<double> passes_image(const std::vector<uint32_t> &passes, size_t width, size_t height, uint32_t max_passes);
+
 }  // namespace flux_host

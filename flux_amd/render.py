@@ -159,6 +159,54 @@ class Renderer:
         _lib.check(_lib.lib.flux_render_moments_rows_device(self._handle(), first_row, row_stride, num_rows,
                                                             C.c_void_p(d_out_ptr), C.c_void_p(stream)))
 
+    # -- adaptive sampling ---------------------------------------------------------
+    last_adaptive_info = None
+
+    @staticmethod
+    def _adaptive_params(threshold, max_passes, min_passes, lum_floor, dilate):
+        return _lib.FluxAdaptiveParams(float(threshold), float(lum_floor), int(min_passes), int(max_passes), int(dilate), 0)
+
+    def _keep_adaptive_info(self, info):
+        self.last_adaptive_info = {"rounds": int(info[0]), "pixel_passes": int(info[1]), "pixels_at_max_passes": int(info[2]),
+                                   "samples": int(info[1]) * self.config.sample_root ** 2}
+
+    def render_adaptive(self, threshold: float = _lib.ADAPTIVE_THRESHOLD, max_passes: int = _lib.ADAPTIVE_MAX_PASSES,
+                        min_passes: int = _lib.ADAPTIVE_MIN_PASSES, lum_floor: float = _lib.ADAPTIVE_LUM_FLOOR,
+                        dilate: int = _lib.ADAPTIVE_DILATE, row_start: int = 0, row_end=None):
+        """Adaptive sampling of rows [row_start, row_end] inclusive (default: the frame), flux_render_adaptive_rows: passes of one
+        sample set (sample_root² samples) each, every pixel for `min_passes`, then only the pixels whose relative standard error
+        exceeds `threshold` and their neighbours within `dilate`, up to `max_passes` (at most the image width).  Returns
+        (moments [rows, W, 8], passes [rows, W] uint32): the layout of render_moments() with each pixel's own sample count behind
+        its mean and variance, so flux_amd.denoise_moments(moments, r.render_aov()) filters an adaptive frame with its per-pixel
+        variance, and no further denoiser call exists.  With max_passes=1 the moments are render_moments() bit for bit.
+        last_adaptive_info holds the call's rounds, pixel passes, samples and pixels that reached max_passes."""
+        if row_end is None:
+            row_end = self.height - 1
+        if row_start < 0 or row_end < row_start:
+            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        rows = row_end - row_start + 1
+        mom = np.empty((rows, self.width, _lib.MOMENT_CHANNELS), dtype=np.float64)
+        passes = np.empty((rows, self.width), dtype=np.uint32)
+        par = self._adaptive_params(threshold, max_passes, min_passes, lum_floor, dilate)
+        info = (C.c_uint64 * _lib.ADAPTIVE_INFO_WORDS)()
+        _lib.check(_lib.lib.flux_render_adaptive_rows(self._handle(), row_start, row_end, C.byref(par),
+                                                      mom.ctypes.data_as(C.POINTER(C.c_double)), passes.ctypes.data_as(C.c_void_p), info))
+        self._keep_adaptive_info(info)
+        return mom, passes
+
+    def render_adaptive_device(self, first_row: int, row_stride: int, num_rows: int, d_out_moments_ptr: int, d_out_passes_ptr: int,
+                               threshold: float = _lib.ADAPTIVE_THRESHOLD, max_passes: int = _lib.ADAPTIVE_MAX_PASSES,
+                               min_passes: int = _lib.ADAPTIVE_MIN_PASSES, lum_floor: float = _lib.ADAPTIVE_LUM_FLOOR,
+                               dilate: int = _lib.ADAPTIVE_DILATE, stream: int = 0):
+        """Device-resident adaptive sampling (see flux_render_adaptive_rows_device): num_rows * W * 8 doubles and num_rows * W
+        uint32 on `stream`, which the call synchronises once per selective round.  Sets last_adaptive_info."""
+        par = self._adaptive_params(threshold, max_passes, min_passes, lum_floor, dilate)
+        info = (C.c_uint64 * _lib.ADAPTIVE_INFO_WORDS)()
+        _lib.check(_lib.lib.flux_render_adaptive_rows_device(self._handle(), first_row, row_stride, num_rows, C.byref(par),
+                                                             C.c_void_p(d_out_moments_ptr), C.c_void_p(d_out_passes_ptr), info,
+                                                             C.c_void_p(stream)))
+        self._keep_adaptive_info(info)
+
     def render_denoised(self, variance: str = "spatial", **params) -> np.ndarray:
         """The denoised frame on this renderer's device; `params` are flux_amd.denoise's.  variance="spatial" (the default):
         render_frame() + render_aov() + flux_amd.denoise, which estimates the noise from the frame.  variance="measured":

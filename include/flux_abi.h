@@ -355,6 +355,68 @@ int flux_denoise_moments(int device, uint64_t width, uint64_t height, const doub
 int flux_denoise_moments_device(int device, uint64_t width, uint64_t height, void *d_moments, void *d_aov, const double *params,
                                 void *d_out_rgb, void *d_work, uint64_t work_doubles, void *hip_stream);
 
+/* Adaptive sampling (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): further sample sets of
+ * N = sample_root^2 samples for the pixels whose measured variance is still high, and only for those.  DESIGN.md section 5h;
+ * tests/adaptive_spec.py states the same rule in numpy.  A call covers a list of h rows of W columns of a context that holds every
+ * sample set; N >= 4, S = the number of sample sets (the image width).
+ *   state    per pixel the five running sums of r, g, b, l and l^2 (l as for the sample moments) and a pass count c, all 0 at first.
+ *   rounds   r = 0, 1, ... while r < max_passes.  In rounds r < min_passes every pixel is active.  Afterwards, per pixel,
+ *              n = N c,  m = sum l / n,  s2 = max(0, sum l^2 - (sum l * sum l) / n) / (n - 1),
+ *              e2 = (s2 / n) / max(m, lum_floor)^2
+ *            -- the squared relative standard error of the pixel's luminance estimate --, and the pixel is HOT iff
+ *            e2 > threshold^2: a NaN is never hot, an inf stays hot up to max_passes.  A pixel is ACTIVE iff a hot pixel lies within
+ *            Chebyshev distance `dilate` of it, in the call's local row and column index, clipped at the call's edges (a pixel whose
+ *            N samples happened to agree has variance 0 and says nothing about its own error: its neighbours speak for it).  The
+ *            call stops at the first round with no active pixel.
+ *   a pass   of an active pixel draws the N samples of sample set (set0 + c) mod S -- set0 the set the row's permutation gives the
+ *            pixel, c the pixel's OWN count, not the round --, traces each as flux_render_moments_rows traces a sample, combines
+ *            the five per-lane sums into one total as that call does, adds each total to the running sum with one addition, and
+ *            sets c += 1.  max_passes <= S, so no pixel reads a set twice.
+ *   output   [h][W][FLUX_MOMENT_CHANNELS] doubles in the layout of the sample moments with n = N c in place of N (the mean is
+ *            sum * (1.0 / n)), and a [h][W] uint32_t map of c.  With max_passes == 1 the eight channels are bit for bit those of
+ *            flux_render_moments_rows.  flux_denoise_moments filters the buffer as it filters the sample moments, with each pixel's
+ *            own variance.
+ * No atomics on a pixel's state, two runs are bit-equal, and apart from the rows a call covers -- and, for dilate > 0, which rows
+ * are neighbours within it -- the result depends on nothing: with dilate == 0 not on how rows are grouped into calls. */
+typedef struct flux_adaptive_params {
+    double threshold;     /* tau: finite, >= 0 */
+    double lum_floor;     /* finite, > 0 */
+    uint32_t min_passes;  /* >= 1 */
+    uint32_t max_passes;  /* min_passes <= max_passes <= S */
+    uint32_t dilate;      /* 0, 1 or 2 */
+    uint32_t reserved;    /* must be 0 */
+} flux_adaptive_params;
+/* Starting values, not tuned ones.  tests/test_adaptive.py holds a quality run at them (DESIGN.md section 5h has its table and what
+ * it suggests): against a uniform frame of at least as many samples the adaptive frame is level on demo1 and worse on demo2,
+ * where nearly every pixel runs into max_passes; a preview is better served by a threshold of 0.15 to 0.3. */
+#define FLUX_ADAPTIVE_THRESHOLD 0.05
+#define FLUX_ADAPTIVE_LUM_FLOOR 0.01
+#define FLUX_ADAPTIVE_MIN_PASSES 1
+#define FLUX_ADAPTIVE_MAX_PASSES 8
+#define FLUX_ADAPTIVE_DILATE 1
+/* info (optional, may be null): rounds run, pixel-passes traced (samples traced = N times that), pixels that reached max_passes, 0 */
+#define FLUX_ADAPTIVE_INFO_WORDS 4
+/* `params` points to a flux_adaptive_params, which the calls only read, and out_passes / d_out_passes to uint32_t; both are
+ * declared void * because the header keeps to the pointer types its bindings already map.
+ * Rows [row_start, row_end] inclusive into caller-owned host memory: out_moments (rows * image_width * FLUX_MOMENT_CHANNELS
+ * doubles) and out_passes (rows * image_width uint32_t), row-major.  Synchronous.  FLUX_E_INVALID, before any device call and each
+ * with a message of its own, for null params, a threshold that is not finite or negative, a lum_floor that is not finite or not
+ * positive, min_passes < 1, max_passes < min_passes, dilate > 2 and a non-zero reserved word; then for a null context, a context
+ * of flux_ctx_create_sets, sample_root == 1, max_passes > S, null outputs and rows outside the image. */
+int flux_render_adaptive_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, void *params, double *out_moments,
+                              void *out_passes, uint64_t info[FLUX_ADAPTIVE_INFO_WORDS]);
+/* Device-resident: rows first_row + k*row_stride, k < num_rows (the call's local rows 0 .. num_rows - 1), to d_out_moments and
+ * d_out_passes (device pointers) on `hip_stream`; num_rows == 0 is a no-op.  Checked as above, and row_stride >= 1.  NOT
+ * asynchronous: after each selection the host reads the 4-byte count of active pixels back to size the next pass and to stop at 0
+ * -- one synchronisation of `hip_stream` per round beyond min_passes --, and once more behind the last kernel where `info` is
+ * given; without `info`, and with max_passes == min_passes, the call only enqueues.  State and work list live in buffers of the
+ * context, grown on demand.  A job whose per-lane stacks exceed the LDS limit is refused as flux_render_moments_rows_device
+ * refuses it.  No effect on flux_ctx_stats; flux_ctx_last_kernel_ms afterwards is the span from the call's first launch to its
+ * last. */
+int flux_render_adaptive_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *params,
+                                     void *d_out_moments, void *d_out_passes, uint64_t info[FLUX_ADAPTIVE_INFO_WORDS],
+                                     void *hip_stream);
+
 /* Render-kernel variants (all produce the same image within rounding):
  *   0 = default (FLUX_KERNEL_SPLIT where it applies, else FLUX_KERNEL_REFILL; STATIC below 64 spp)
  *   1 = FLUX_KERNEL_STATIC: one lane per sample, lanes idle once their path ends
