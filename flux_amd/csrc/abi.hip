@@ -318,6 +318,12 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.tput = c->d_tput;
     rp.tput_bits = c->d_tput ? tput_bits : 0;
     rp.lobe_frame = c->d_lobe;
+    // the first plane's axis (RenderParams::plane_axis); FLUX_PLANE_AXIS=0 builds the context without it (tests and A/B runs: both scans
+    // then form the first plane's dot products in full)
+    {
+        const char *axis_env = std::getenv("FLUX_PLANE_AXIS");
+        if (axis_env && std::atoi(axis_env) == 0) rp.plane_axis = kPlaneAxisNone;
+    }
     rp.set_rows = c->d_setrows;
     rp.rowperm = c->d_rowperm;
     rp.invperm = c->d_invperm;

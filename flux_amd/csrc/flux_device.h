@@ -6,6 +6,7 @@
 
 #include "flux_bvh.h"
 #include "flux_env_verdict.h"
+#include "flux_plane_axis.h"
 
 // Numeric tunables of the data layout / launch mapping (the boolean either/ors of rounds 1-5 are folded into the code: render.hip).
 // The render path as shipped: hemi_sets as [S][D][N][4] (one aligned 32-B sector per sample); waves ordered by sample set, one set
@@ -287,6 +288,11 @@ struct RenderParams {
     // normalize((ax, 1, az) x n), b2 = b1 x n of the record's own ax, az and normal -- what fast_bounce builds per bounce for a Matte
     // hit, written by the device itself (render.hip generate_lobe_frame_table).  nullptr: no table (FLUX_LOBE_FRAMES=0), the arithmetic.
     const double *lobe_frame;
+    // split kernel, TYP instantiations: the axis of the FIRST scan plane's stored normal (flux_plane_axis.h: kPlaneAxisX/Y/Z), or
+    // kPlaneAxisNone -- no plane, a normal on no axis, a camera outside plane_axis_camera_ok, or FLUX_PLANE_AXIS=0.  The launch takes the
+    // kernel's instantiation for that axis (render_split_kernel<.., AXIS>): the peeled first-plane test of both scans is then
+    // num = p_a - o_a, den = d_a in every wave whose vote admits it (render_body.inc).
+    int32_t plane_axis;
 };
 // bytes per hit record of RenderParams::lobe_frame
 constexpr size_t kLobeFrameBytes = 6 * sizeof(double);

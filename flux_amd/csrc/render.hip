@@ -37,8 +37,9 @@
 // dielectric lobe.  Which copy, kernel and instantiation a call runs, with what block, grid and LDS, is the launch plan's decision
 // (launch_plan.cpp plan_render, host code compiled once); launch_render below only maps the plan to a kernel.  The instantiations:
 //  * render_static_kernel<STATS, TRIS>, render_refill_kernel<STATS, TRIS>: every copy;
-//  * render_split_kernel<STATS, MAX32, TYP, HQ>: FAST -- TYP (the usual analytic scene) only with MAX32, and in the copy with the
-//    dielectric lobe neither TYP nor HQ (the hit queue), which the plan never picks for a scene with a dielectric;
+//  * render_split_kernel<STATS, MAX32, TYP, HQ, AXIS>: FAST -- TYP (the usual analytic scene) only with MAX32, and in the copy with the
+//    dielectric lobe neither TYP nor HQ (the hit queue), which the plan never picks for a scene with a dielectric; AXIS (the first scan
+//    plane's stored normal lies on that axis, RenderParams::plane_axis) other than 0 only with TYP;
 //  * render_bvh_kernel<STATS>, render_bvh4_kernel<STATS, LDS_SCENE, TYP>: FAST -- TYP only with LDS_SCENE, and not in the copy
 //    with the dielectric lobe;
 //  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy;

@@ -571,7 +571,7 @@ __device__ __forceinline__ bool facing_front(int facing, int inv_rad_hi) { retur
 // (scan order: spheres, then planes, then disks, then six face records per box) or -1; `tb` its distance.
 // FACING (the split kernel's phase B with its hit queue): `*facing` tells the shading step which side of the winner the ray met, so that
 // an Emissive hit's facing test needs no normal (sphere_facing above, shade_hit_fast).
-template <bool ENV_SHORT = false, bool LDS_SCENE = false, bool MAX32 = false, bool TYP = false, int ZF = -1, bool FACING = false>
+template <bool ENV_SHORT = false, bool LDS_SCENE = false, bool MAX32 = false, bool TYP = false, int ZF = -1, bool FACING = false, int AXIS = 0>
 __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ray &r, int self, int &best, double &tb,
                                                  long long *lap = nullptr, const char *fsph_lds = nullptr, int *facing = nullptr) {
     (void)fsph_lds;  // LDS_SCENE (the split kernel): the block's LDS copy of the scan spheres for the per-lane gathers
@@ -592,11 +592,24 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
     // The FIRST plane has nothing to compare with (`best` is -1 on entry, every caller): its verdict is one compare and one select, where
     // the loop's general step is three compares and two nested exec-masked regions with their moves.  The split kernel (ENV_SHORT) also
     // takes its distance as it comes: `tb` means something only beside best >= 0, and every later use there is guarded by that.
+    // AXIS (the split kernel's TYP instantiations, one per axis, chosen by the launch from P.plane_axis; ZF = 0 only): the host has found
+    // this plane's stored normal on that axis, so eight of the nine operations of the two dot products only carry exact zeros and
+    // ones, and num = p_a - o_a, den = d_a give the same t bit for bit (flux_plane_axis.h) -- for a ray with d_a != 0, a finite
+    // direction and a finite origin of ordinary size.  The caller's vote in front of ZF = 0 has established that for every lane of the
+    // wave (split_rare_lanes); any other wave runs ZF = 1, this code with the general expressions.  A zero num needs no guard: t
+    // is then a zero of either sign in both forms -- den is not zero -- and fails t > T_MIN whichever it is, and `tb` is read only
+    // beside best >= 0.
+    constexpr bool PLANE_AXIS = AXIS != kPlaneAxisNone && ZF == 0;
     int j0 = 0;
     if (P.n_pln > 0) {
         const DevScanPlane &S = P.fpln[0];
-        const double num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
-        const double den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
+        double num, den;
+        if (PLANE_AXIS) {
+            plane_axis_num_den(AXIS, S.px, S.py, S.pz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, num, den);
+        } else {
+            num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
+            den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
+        }
         const double t = num / den;
         const bool take = t > tmin;
         best = take ? P.n_sph : -1;
@@ -2202,9 +2215,35 @@ __device__ __forceinline__ void pixel_sphere_mask(const RenderParams &P, int row
     }
 }
 
+// Phase B's ONE vote of a pass, in front of scan_shapes_fast's ZF instantiations: the lanes (of those that trace) that keep the wave out
+// of ZF = 0.  As before: a lane with direction.z == 0, and a lane whose origin is beyond the filter's and the self-skip rule's range,
+// |o|^2 >= 0.999e6 in f32 or NaN -- so in a wave that passes, every component of every origin is finite and below 1e3 (an infinite or
+// NaN component, or one beyond f32, makes the sum infinite or NaN).  (|o|^2 and o.u in f32 exactly as filter_ray32_f forms them: the
+// compiler merges the two.)
+// AXIS (the instantiation for a first plane whose normal lies on that axis): the reduced plane test of ZF = 0 also needs, of every lane
+// (flux_plane_axis.h plane_axis_admits, plane_axis_admits_b -- the CPU test holds this vote to that predicate),
+//     d_a != 0                 for a z plane the vote above; else one more compare;
+//     d_x, d_y, d_z finite     |o.u| < 3e38 in f32, one compare of a value the filter forms anyway: an infinite or NaN component of d
+//                              (or one beyond f32) times a finite o_i is infinite or -- o_i = 0 -- NaN, and the fused sum that takes it
+//                              in stays infinite or NaN.  A NaN d_a fails here.
+// Two more vector instructions a pass for demo2's y plane, one for a z plane.
+template <int AXIS>
+__device__ __forceinline__ unsigned long long split_rare_lanes(const Ray &r) {
+    const float ofx = (float)r.ox, ofy = (float)r.oy, ofz = (float)r.oz;
+    const float oo32 = __builtin_fmaf(ofz, ofz, __builtin_fmaf(ofy, ofy, ofx * ofx));
+    unsigned long long rare = ballot64(r.dz == 0.0) | ballot64(!(oo32 < 0.999e6f));
+    if (AXIS != kPlaneAxisNone) {
+        const float ou32 = __builtin_fmaf(ofz, (float)r.dz, __builtin_fmaf(ofy, (float)r.dy, ofx * (float)r.dx));
+        rare |= ballot64(!(__builtin_fabsf(ou32) < 3.0e38f));
+        if (AXIS == kPlaneAxisY) rare |= ballot64(r.dy == 0.0);
+        if (AXIS == kPlaneAxisX) rare |= ballot64(r.dx == 0.0);
+    }
+    return rare;
+}
+
 // Scene::hit for a primary ray against the pixel's candidates: planes and disks as in scan_shapes_fast, then the exact sphere
 // test (shapes.rs:176-214 along the unit direction) with the sphere record in SGPRs and a wave-uniform trip count.
-template <bool TYP>
+template <bool TYP, int AXIS = 0>
 __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const Ray &r, unsigned long long cand_mask,
                                                     unsigned long long in_mask, double in_t0, bool valid, unsigned long long valid_m,
                                                     int &best, double &tb) {
@@ -2215,8 +2254,24 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
     int j0 = 0;
     if (P.n_pln > 0) {  // the first plane: one compare and one select (scan_shapes_fast)
         const DevScanPlane &S = P.fpln[0];
-        const double num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
-        const double den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
+        // AXIS (the instantiation for a plane whose stored normal lies on that axis): num = p_a - o_a, den = d_a, the general t bit for
+        // bit (flux_plane_axis.h) in a wave whose valid lanes all hold |d_a| > 0 -- ONE compare a pass; a NaN fails it.  The rest of
+        // the predicate is the host's: it sets the axis only for a camera of finite scalars below 1e60 (plane_axis_camera_ok), the sample
+        // tables hold points of the unit square and the unit disc, so primary_ray_px's origin is finite and of that size, and its
+        // direction is a finite vector times ONE frsqrt -- finite in all three components or NaN in all three, and a NaN d_a has failed
+        // the compare.  Any other wave forms the dot products in full.  (A zero num needs no guard: scan_shapes_fast.)
+        bool reduced = false;
+        if (AXIS != kPlaneAxisNone) {
+            const double da = AXIS == kPlaneAxisX ? r.dx : AXIS == kPlaneAxisY ? r.dy : r.dz;
+            reduced = (valid_m & ballot64(!(__builtin_fabs(da) > 0.0))) == 0ull;
+        }
+        double num, den;
+        if (AXIS != kPlaneAxisNone && reduced) {
+            plane_axis_num_den(AXIS, S.px, S.py, S.pz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, num, den);
+        } else {
+            num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
+            den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
+        }
         const double t = num / den;
         best = t > tmin ? P.n_sph : -1;
         best_id = S.id;
@@ -2328,7 +2383,11 @@ constexpr int split_lobe_frames(bool MAX32, bool TYP, bool HQ) {
 // HQ: phase B parks its continuing hits in the hit queue of hq_cap slots (see kHitQBytesPerSlot); hq_th = H, hq_bits the
 // bounce list's bits per entry.  Without HQ (scenes the queue does not fit, see launch_plan.cpp plan_render): the 64-entry ray queue and phase B's
 // bounce at once, in the lanes that continue.
-template <bool STATS, bool MAX32, bool TYP, bool HQ = false>
+// AXIS: the axis of the first scan plane's stored normal (flux_plane_axis.h kPlaneAxisX/Y/Z), or 0.  TYP only: the launch takes the
+// instantiation of RenderParams::plane_axis, and both scans take that plane's test in its reduced form (scan_shapes_primary,
+// scan_shapes_fast).  A template argument and not a test of the field: with scalar branches on the field the frame was 3.6 % SLOWER than
+// without the reduced form (146.6 against 141.5 ms), as a constant it is straight-line code (DESIGN.md section 4).
+template <bool STATS, bool MAX32, bool TYP, bool HQ = false, int AXIS = 0>
 __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void render_split_kernel(const RenderParams P0, int hq_cap, int hq_th,
                                                                                                   int hq_bits, int uni_a) {
     (void)hq_cap;
@@ -2426,7 +2485,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 }
                 int hit = -1;
                 double t = 0.0;
-                scan_shapes_primary<TYP>(P, p.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
+                scan_shapes_primary<TYP, AXIS>(P, p.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
                 p.depth = 1;
                 if (valid) {
                     double Lr, Lg, Lb;
@@ -2518,13 +2577,11 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             if (trace) {
                 FLUX_CENSUS(P, 3);
                 if (STATS) st.c[1]++;
-                const float ofx = (float)p.r.ox, ofy = (float)p.r.oy, ofz = (float)p.r.oz;
-                const float oo32 = __builtin_fmaf(ofz, ofz, __builtin_fmaf(ofy, ofy, ofx * ofx));
                 int facing;
-                if (__builtin_expect((ballot64(p.r.dz == 0.0) | ballot64(!(oo32 < 0.999e6f))) != 0ull, 0))
-                    scan_shapes_fast<true, true, MAX32, TYP, 1, true>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
+                if (__builtin_expect(split_rare_lanes<AXIS>(p.r) != 0ull, 0))
+                    scan_shapes_fast<true, true, MAX32, TYP, 1, true, AXIS>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
                 else
-                    scan_shapes_fast<true, true, MAX32, TYP, 0, true>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
+                    scan_shapes_fast<true, true, MAX32, TYP, 0, true, AXIS>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
                 cont = shade_hit_fast<STATS, false, true, TYP, false, false, true>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds, facing);
             }
             if (live && !cont) {
@@ -2654,7 +2711,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 }
                 int hit = -1;
                 double t = 0.0;
-                scan_shapes_primary<TYP>(P, pa.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
+                scan_shapes_primary<TYP, AXIS>(P, pa.r, cand_p, in_p, in_t0, valid, valid_m, hit, t);
                 if (valid) {
                     double Lr, Lg, Lb;
                     FLUX_CENSUS(P, 2);
@@ -2715,13 +2772,10 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 if (STATS) st.c[1]++;
                 int hit = -1;
                 double t = 0.0;
-                // (|o|^2 in f32 exactly as filter_ray32_f forms it: the compiler merges the two)
-                const float ofx = (float)p.r.ox, ofy = (float)p.r.oy, ofz = (float)p.r.oz;
-                const float oo32 = __builtin_fmaf(ofz, ofz, __builtin_fmaf(ofy, ofy, ofx * ofx));
-                if (__builtin_expect((ballot64(p.r.dz == 0.0) | ballot64(!(oo32 < 0.999e6f))) != 0ull, 0))
-                    scan_shapes_fast<true, true, MAX32, TYP, 1>(P, p.r, p.self, hit, t, lap, fsph_lds);
+                if (__builtin_expect(split_rare_lanes<AXIS>(p.r) != 0ull, 0))
+                    scan_shapes_fast<true, true, MAX32, TYP, 1, false, AXIS>(P, p.r, p.self, hit, t, lap, fsph_lds);
                 else
-                    scan_shapes_fast<true, true, MAX32, TYP, 0>(P, p.r, p.self, hit, t, lap, fsph_lds);
+                    scan_shapes_fast<true, true, MAX32, TYP, 0, false, AXIS>(P, p.r, p.self, hit, t, lap, fsph_lds);
                 cont = shade_hit_fast<STATS, false, true, TYP>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds);
             }
             if (live && !cont) {
@@ -3611,17 +3665,26 @@ static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p,
         // (the throughput product table only where it is laid out for this plan's list entries)
         RenderParams ps = p;
         if (!hq || ps.tput_bits != bits) ps.tput = nullptr;
-#define FLUX_LAUNCH_SPLIT(MAX32, TYP, HQ)                                                                      \
-    do {                                                                                                       \
-        if (stats) render_split_kernel<true, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);  \
-        else render_split_kernel<false, MAX32, TYP, HQ><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);   \
+#define FLUX_LAUNCH_SPLIT_AXIS(MAX32, TYP, HQ, AXIS)                                                                  \
+    do {                                                                                                             \
+        if (stats) render_split_kernel<true, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);  \
+        else render_split_kernel<false, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);   \
+    } while (0)
+#define FLUX_LAUNCH_SPLIT(MAX32, TYP, HQ) FLUX_LAUNCH_SPLIT_AXIS(MAX32, TYP, HQ, 0)
+// (TYP: the instantiation of the first plane's axis, RenderParams::plane_axis)
+#define FLUX_LAUNCH_SPLIT_TYP(HQ)                                                         \
+    do {                                                                                  \
+        if (ps.plane_axis == kPlaneAxisY) FLUX_LAUNCH_SPLIT_AXIS(true, true, HQ, kPlaneAxisY);       \
+        else if (ps.plane_axis == kPlaneAxisX) FLUX_LAUNCH_SPLIT_AXIS(true, true, HQ, kPlaneAxisX);  \
+        else if (ps.plane_axis == kPlaneAxisZ) FLUX_LAUNCH_SPLIT_AXIS(true, true, HQ, kPlaneAxisZ);  \
+        else FLUX_LAUNCH_SPLIT(true, true, HQ);                                           \
     } while (0)
 #if FLUX_DIEL
         if (L.typ || hq) return hipErrorInvalidValue;
 #else
         if (L.typ) {
-            if (hq) FLUX_LAUNCH_SPLIT(true, true, true);
-            else FLUX_LAUNCH_SPLIT(true, true, false);
+            if (hq) FLUX_LAUNCH_SPLIT_TYP(true);
+            else FLUX_LAUNCH_SPLIT_TYP(false);
             return hipGetLastError();
         }
         if (hq) {
@@ -3632,7 +3695,9 @@ static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p,
 #endif
         if (L.max32) FLUX_LAUNCH_SPLIT(true, false, false);
         else FLUX_LAUNCH_SPLIT(false, false, false);
+#undef FLUX_LAUNCH_SPLIT_TYP
 #undef FLUX_LAUNCH_SPLIT
+#undef FLUX_LAUNCH_SPLIT_AXIS
         return hipGetLastError();
     }
 #endif

@@ -222,6 +222,8 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
 
     rp.n_sph = (int32_t)fsph.size();
     rp.n_pln = (int32_t)fpln.size();
+    // the first scan plane's axis, from the normal and the point as stored (flux_plane_axis.h); the camera's side: build_host_scene
+    rp.plane_axis = fpln.empty() ? kPlaneAxisNone : plane_axis_of(fpln[0].nx, fpln[0].ny, fpln[0].nz, fpln[0].px, fpln[0].py, fpln[0].pz);
     rp.n_dsk = (int32_t)fdsk.size();
     rp.n_box = (int32_t)fbox.size();
     // The glossy lobe's angle table (RenderParams::glossx): a slot for every distinct 1 / (exponent + 1) among the glossy records --
@@ -503,6 +505,11 @@ int build_host_scene(const flux_scene_desc &scene, HostScene &h, std::string &er
 
     build_fast_scene(scene, h);
     build_camera(scene, h);
+    {   // the reduced first-plane test's word on primary rays rests on these (flux_plane_axis.h plane_axis_camera_ok)
+        const double cam[] = {rp.ex, rp.ey, rp.ez, rp.Ux, rp.Uy, rp.Uz, rp.Vx, rp.Vy, rp.Vz, rp.Wx, rp.Wy, rp.Wz, rp.aps,
+                              rp.half_w, rp.half_h, rp.factor, rp.focal, rp.lens_radius, rp.fwx, rp.fwy, rp.fwz};
+        if (!plane_axis_camera_ok(cam, (int)(sizeof(cam) / sizeof(cam[0])))) rp.plane_axis = kPlaneAxisNone;
+    }
     return build_meshes(scene, h, error);
 }
 

@@ -18,10 +18,12 @@ spec.loader.exec_module(b)
 
 INST = {"bvh4": "render_bvh4_kernel<false, true, true>", "bvh4l": "render_bvh4_kernel<false, true, false>",
         "bvh4g": "render_bvh4_kernel<false, false, false>", "bvh": "render_bvh_kernel<false>",
-        "split": "render_split_kernel<false, true, true, true>", "split_rq": "render_split_kernel<false, true, true, false>",
-        "split32": "render_split_kernel<false, true, false, false>", "split64": "render_split_kernel<false, false, false, false>", "refill": "render_refill_kernel<false, false>",
+        # (the split kernel's fifth argument: the axis of the first plane's normal, flux_plane_axis.h -- 2 = y, demo2's; 0 = none)
+        "split": "render_split_kernel<false, true, true, true, 2>", "split_rq": "render_split_kernel<false, true, true, false, 2>",
+        "split_noaxis": "render_split_kernel<false, true, true, true, 0>", "split_rq_noaxis": "render_split_kernel<false, true, true, false, 0>",
+        "split32": "render_split_kernel<false, true, false, false, 0>", "split64": "render_split_kernel<false, false, false, false, 0>", "refill": "render_refill_kernel<false, false>",
         "static": "render_static_kernel<false, false>", "bvh4s": "render_bvh4_kernel<true, true, true>",
-        "splits": "render_split_kernel<true, true, true, true>", "splits_rq": "render_split_kernel<true, true, true, false>",
+        "splits": "render_split_kernel<true, true, true, true, 2>", "splits_rq": "render_split_kernel<true, true, true, false, 2>",
         "refill_tris": "render_refill_kernel<false, true>", "static_tris": "render_static_kernel<false, true>"}
 args = sys.argv[1:]
 asm_out = None

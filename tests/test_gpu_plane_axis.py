@@ -1,0 +1,138 @@
+"""The split kernel's TYP instantiations take the first scan plane's test as num = p_a - o_a, den = d_a where the host has found the
+plane's stored normal on an axis (RenderParams::plane_axis, flux_amd/csrc/flux_plane_axis.h), in every wave whose vote admits it.
+FLUX_PLANE_AXIS=0 builds the context without the axis: both scans then form the dot products in full.  The two may not differ in a
+single bit: every scene here is rendered both ways with the hit-queue kernel (the plan's own choice at this sample count), with the
+ray-queue kernel (FLUX_SPLIT_HITQ_CAP=0) and with phase A's general shading step (FLUX_SPLIT_UNIFORM_A=0) -- np.array_equal, equal path
+statistics -- and the frame with the axis has the oracle's path statistics and its image to 1e-4 (the tolerance of
+tests/test_gpu_lobe_frames.py).
+
+8 x 6 pixels at sample root 128 (16384 spp: four waves a pixel and the hit queue, as the benchmark's headline), depth limit 5.  The
+scenes: demo2 with scene and camera turned so that the floor's normal is +x, -x, +y (demo2 itself), -y, +z, -z -- a turn by right angles
+is a signed permutation of the coordinates, so the stored normal stays exact, with zeros of either sign; a floor tilted about z (a unit
+normal on no axis: classified "none", the switch must change nothing); the floor followed by a tilted back wall (the axis-aligned plane
+first: the reduced form runs, the wall goes through the later-planes loop) and the wall followed by the floor (the first plane is on no
+axis).  CPU side: tests/test_plane_axis.py."""
+import copy
+
+import numpy as np
+import pytest
+
+from conftest import small_scene
+
+pytestmark = pytest.mark.gpu
+
+N, DEPTH, SEED = 128, 5, 4
+TURNS = {  # name -> where (x, y, z) goes; each takes the floor's normal (0, 1, 0) to the axis in the name
+    "floor_normal_plus_y": lambda v: (v[0], v[1], v[2]),
+    "floor_normal_minus_y": lambda v: (-v[0], -v[1], v[2]),
+    "floor_normal_plus_x": lambda v: (v[1], -v[0], v[2]),
+    "floor_normal_minus_x": lambda v: (-v[1], v[0], v[2]),
+    "floor_normal_plus_z": lambda v: (v[0], -v[2], v[1]),
+    "floor_normal_minus_z": lambda v: (v[0], v[2], -v[1]),
+}
+CASES = list(TURNS) + ["tilted_floor", "floor_then_tilted_wall", "tilted_wall_then_floor"]
+KERNELS = {"hit_queue": {}, "ray_queue": {"FLUX_SPLIT_HITQ_CAP": "0"}, "general_phase_a": {"FLUX_SPLIT_UNIFORM_A": "0"}}
+SWITCHES = ("FLUX_PLANE_AXIS", "FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_UNIFORM_A")
+
+
+def _turned(flux, sd, turn):
+    sd = copy.deepcopy(sd)
+    for s in sd.shapes:
+        if isinstance(s, flux.SphereData):
+            s.center = turn(s.center)
+        else:
+            assert isinstance(s, flux.PlaneData)
+            s.point, s.normal = turn(s.point), turn(s.normal)
+    cs = sd.camera_settings
+    cs.eye, cs.look_at, cs.up = turn(cs.eye), turn(cs.look_at), turn(cs.up)
+    return sd
+
+
+def _cases(flux, demo2):
+    base = small_scene(demo2, 8, 6)
+    floor = next(s for s in base.shapes if isinstance(s, flux.PlaneData))
+    others = [s for s in base.shapes if s is not floor]
+    assert tuple(floor.normal) == (0.0, 1.0, 0.0) and sum(isinstance(s, flux.PlaneData) for s in base.shapes) == 1
+
+    def scene(shapes):
+        sd = copy.deepcopy(base)
+        sd.shapes = copy.deepcopy(shapes)
+        return sd
+
+    cases = {name: _turned(flux, base, turn) for name, turn in TURNS.items()}
+    for name, axis in (("plus_y", (0.0, 1.0, 0.0)), ("minus_y", (0.0, -1.0, 0.0)), ("plus_x", (1.0, 0.0, 0.0)), ("minus_x", (-1.0, 0.0, 0.0)),
+                       ("plus_z", (0.0, 0.0, 1.0)), ("minus_z", (0.0, 0.0, -1.0))):
+        plane = next(s for s in cases["floor_normal_" + name].shapes if isinstance(s, flux.PlaneData))
+        assert tuple(plane.normal) == axis  # (compares equal: a zero of either sign)
+    cases["tilted_floor"] = scene(others + [flux.PlaneData(floor.point, (0.6, 0.8, 0.0), floor.material)])
+    # a wall behind the spheres that leans towards the eye: a unit normal on no axis
+    wall = flux.PlaneData((0.0, 0.0, 12.0), (0.0, 0.6, -0.8), floor.material)
+    cases["floor_then_tilted_wall"] = scene(others + [floor, wall])
+    cases["tilted_wall_then_floor"] = scene(others + [wall, floor])
+    assert sorted(cases) == sorted(CASES)
+    return cases
+
+
+_oracle = {}
+
+
+def _oracle_frame(flux, oracle_mod, sd, case):
+    """The oracle's frame and statistics of a case: computed once, read by every kernel."""
+    if case not in _oracle:
+        o = oracle_mod.Oracle(sd, flux.JobConfiguration(N, DEPTH, 50), seed=SEED)
+        o.stats(reset=True)
+        want = o.render_frame(threads=8)
+        want.setflags(write=False)
+        _oracle[case] = (want, o.stats())
+    return _oracle[case]
+
+
+def _render(flux, sd):
+    """The frame of the instantiation without statistics (the benchmark's), then frame and statistics of the one that counts."""
+    with flux.Renderer(sd, flux.JobConfiguration(N, DEPTH, 50), seed=SEED) as r:
+        r.set_kernel(flux.KERNEL_SPLIT)
+        plain = r.render_frame()
+        r.enable_stats(True)
+        r.stats(reset=True)
+        img = r.render_frame()
+        return plain, img, r.stats(), r.launch_plan()
+
+
+@pytest.fixture
+def switches(monkeypatch):
+    def set_switches(**env):
+        for name in SWITCHES:
+            if name in env:
+                monkeypatch.setenv(name, env[name])
+            else:
+                monkeypatch.delenv(name, raising=False)
+    set_switches()
+    yield set_switches
+    set_switches()
+
+
+@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("case", CASES)
+def test_reduced_plane_test_changes_no_bit(flux, oracle_mod, demo2, switches, case, kernel):
+    sd = _cases(flux, demo2)[case]
+    want, o_stats = _oracle_frame(flux, oracle_mod, sd, case)
+    switches(**KERNELS[kernel])
+    plain, got, gs, plan = _render(flux, sd)
+    switches(FLUX_PLANE_AXIS="0", **KERNELS[kernel])
+    plain_general, general, es, plan_general = _render(flux, sd)
+    switches(FLUX_SPLIT_HITQ_CAP="0")
+    ray_queue_lds = _render(flux, sd)[3]["lds"]
+    switches()
+    # which kernel ran: the split kernel, four waves a pixel; with the hit queue unless the case takes it away (the ray queue's 64
+    # entries a wave are the smaller allocation)
+    assert plan == plan_general
+    assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == 4
+    assert (plan["lds"] == ray_queue_lds) == (kernel == "ray_queue")
+    err = float(np.abs(got - want).max())
+    print(f"{case} {kernel}: |split - oracle| {err:.3e}  bits equal to the general form: {np.array_equal(got, general)}  "
+          f"segments {gs['segments']}")
+    assert np.array_equal(got, general)
+    assert np.array_equal(plain, plain_general)
+    assert gs == es, (gs, es)
+    assert {k: gs[k] for k in o_stats} == o_stats
+    assert err < 1e-4
