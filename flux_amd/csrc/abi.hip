@@ -405,11 +405,9 @@ static int effective_math(const flux_ctx *ctx) {
 // STRICT keeps the (f,s) recursion stack, 4 doubles per level per lane; mesh scenes the BVH traversal stack, one int per
 // level per lane -- 64 lanes in the FAST state-machine kernel, the block's in the others --; the split kernel its path
 // queues), plus the few static words of the refill / split kernels.  64 KiB per block is the launch limit.
-enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2 };  // which kernel family a launch runs (an adaptive pass: plan_moments' LDS)
-static int check_lds_budget(const flux_ctx *ctx, const flux::RenderParams &p, const char *what, Pass pass = kPassRender) {
-    const size_t dyn = pass == kPassAov       ? flux::plan_aov(p, effective_math(ctx)).lds
-                       : pass == kPassMoments ? flux::plan_moments(p, effective_math(ctx)).lds
-                                              : flux::plan_render(p, ctx->variant, effective_math(ctx)).lds;
+using flux::Pass;  // (an adaptive pass is checked as kPassMoments: the same LDS, and no work list to size it by yet)
+static int check_lds_budget(const flux_ctx *ctx, const flux::RenderParams &p, const char *what, Pass pass = flux::kPassRender) {
+    const size_t dyn = flux::plan_pass(pass, p, ctx->variant, effective_math(ctx)).lds;
     const size_t fixed = 512;
     if (dyn + fixed > 64 * 1024)
         return fail(FLUX_E_INVALID, "%s: %zu B of LDS per block (max_trace_depth %u%s, BVH depth %llu) exceed the 64 KiB limit; use %s", what,
@@ -574,32 +572,52 @@ int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, in
 
 // the launch of the render calls, of the feature-buffer calls and of the moments calls (`pass`), between the context's two events
 // (flux_ctx_last_kernel_ms); `what` names the caller in the LDS refusal
-static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, Pass pass = kPassRender) {
+static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, Pass pass = flux::kPassRender) {
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
     if (int rc = check_lds_budget(ctx, p, what, pass)) return rc;
     HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(pass == kPassAov       ? flux::launch_aov(p, effective_math(ctx), stream)
-            : pass == kPassMoments ? flux::launch_moments(p, effective_math(ctx), stream)
-                                   : flux::launch_render(p, ctx->variant, effective_math(ctx), stream));
+    HIP_TRY(flux::launch_pass(pass, p, ctx->variant, effective_math(ctx), stream));
     HIP_TRY(hipEventRecord(ctx->ev1, stream));
     ctx->timed = true;
     return FLUX_OK;
 }
 
-int flux_render_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
-                            void *d_out_rgb, void *hip_stream) {
-    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+// Every row uses every sample set (trace.rs:64-69): the refusal of a context that holds a share of them, in the caller's words
+static int check_all_sets(const flux_ctx *ctx, const char *who_needs, const char *instead) {
+    if (holds_all_sets(ctx)) return FLUX_OK;
+    return fail(FLUX_E_INVALID, "%s all sample sets; this context holds the share %u + k*%u (flux_ctx_create_sets)%s", who_needs,
+                ctx->sets.first, ctx->sets.stride, instead);
+}
+// The checks the device row calls share, in the order they fire: no rows are in order before the output pointer is looked at (the
+// caller then returns), then the pointer, the stride, the share of the sets -- for the calls that name `who_needs`; the moments and
+// adaptive calls have refused a share before they get here --, and the rows.
+static int check_rows_call(const flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, const void *out,
+                           const char *who_needs = nullptr, const char *instead = nullptr) {
     if (num_rows == 0) return FLUX_OK;
-    if (!d_out_rgb) return fail(FLUX_E_INVALID, "null output pointer");
+    if (!out) return fail(FLUX_E_INVALID, "null output pointer");
     if (row_stride < 1) return fail(FLUX_E_INVALID, "row_stride must be >= 1");
-    if (!holds_all_sets(ctx))  // every row uses every sample set (trace.rs:64-69)
-        return fail(FLUX_E_INVALID, "rendering rows needs all sample sets; this context holds the share %u + k*%u "
-                    "(flux_ctx_create_sets): use flux_render_sets_device", ctx->sets.first, ctx->sets.stride);
+    if (who_needs)
+        if (int rc = check_all_sets(ctx, who_needs, instead)) return rc;
     if (first_row >= ctx->H || first_row + (num_rows - 1) * row_stride >= ctx->H)
         return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
                     (unsigned long long)first_row, (unsigned long long)row_stride,
                     (unsigned long long)num_rows, ctx->H);
+    return FLUX_OK;
+}
+// ... and what a per-pixel pass launches behind them: rows_params with the statistics off -- these kernels keep none
+static int launch_pass_rows(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *d_out, const char *what,
+                            void *hip_stream, Pass pass) {
+    flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out);
+    p.stats = nullptr;
+    return launch_timed(ctx, p, what, (hipStream_t)hip_stream, pass);
+}
+
+int flux_render_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
+                            void *d_out_rgb, void *hip_stream) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    if (int rc = check_rows_call(ctx, first_row, row_stride, num_rows, d_out_rgb, "rendering rows needs", ": use flux_render_sets_device")) return rc;
+    if (num_rows == 0) return FLUX_OK;
     return launch_timed(ctx, rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out_rgb), "flux_render_rows", (hipStream_t)hip_stream);
 }
 
@@ -622,112 +640,65 @@ int flux_render_sets_device(flux_ctx *ctx, uint64_t first_set, uint64_t set_stri
     return launch_timed(ctx, sets_params(ctx, first_set, set_stride, num_sets, (double *)d_out_rgb), "flux_render_sets_device", (hipStream_t)hip_stream);
 }
 
-int flux_render_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out_rgb) {
-    if (!ctx) return fail(FLUX_E_INVALID, "null context");
-    if (!out_rgb) return fail(FLUX_E_INVALID, "null output pointer");
+// The host entry points' rows: [row_start, row_end] within the image (`unit`: the caller's word in front of "rows")
+static int check_row_range(const flux_ctx *ctx, uint64_t row_start, uint64_t row_end, const char *unit) {
     if (row_end < row_start || row_end >= ctx->H)
-        return fail(FLUX_E_INVALID, "work unit rows [%llu,%llu] outside image height %u",
+        return fail(FLUX_E_INVALID, "%srows [%llu,%llu] outside image height %u", unit,
                     (unsigned long long)row_start, (unsigned long long)row_end, ctx->H);
+    return FLUX_OK;
+}
+// ... and their path: the checks, the device made current, the call's own scratch grown to rows x W x channels doubles, the device
+// entry point run on it, the result copied back.  (Each call has a scratch buffer of its own: none resizes or aliases another's.)
+typedef int (*RowsDeviceEntry)(flux_ctx *, uint64_t, uint64_t, uint64_t, void *, void *);
+static int rows_to_host(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, const char *unit, flux::Scratch<double> flux_ctx::*scratch,
+                        size_t channels, double *out, RowsDeviceEntry device_entry) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    if (!out) return fail(FLUX_E_INVALID, "null output pointer");
+    if (int rc = check_row_range(ctx, row_start, row_end, unit)) return rc;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
     const uint64_t rows = row_end - row_start + 1;
-    const size_t doubles = (size_t)rows * ctx->W * 3;
-    if (doubles > ctx->d_out_doubles) {
-        ctx->d_out_doubles = 0;  // (stays 0 if the new allocation fails: the old one is released first)
-        HIP_TRY(ctx->d_out.alloc(doubles));
-        ctx->d_out_doubles = doubles;
-    }
-    int rc = flux_render_rows_device(ctx, row_start, 1, rows, ctx->d_out, nullptr);
-    if (rc != FLUX_OK) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, ctx->d_out, doubles * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t doubles = (size_t)rows * ctx->W * channels;
+    flux::Scratch<double> &d_buf = ctx->*scratch;
+    HIP_TRY(d_buf.reserve(doubles));
+    if (int rc = device_entry(ctx, row_start, 1, rows, d_buf, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out, d_buf, doubles * sizeof(double), hipMemcpyDeviceToHost));
     return FLUX_OK;
 }
 
-// The feature buffers (aov_body.inc): the argument checks of flux_render_rows_device, then rows_params with the statistics off --
-// the kernel keeps none -- and the traversal the context is set to.
+int flux_render_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out_rgb) {
+    return rows_to_host(ctx, row_start, row_end, "work unit ", &flux_ctx::d_out, 3, out_rgb, flux_render_rows_device);
+}
+
+// The feature buffers (aov_body.inc)
 int flux_render_aov_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *d_out,
                                 void *hip_stream) {
     if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    if (int rc = check_rows_call(ctx, first_row, row_stride, num_rows, d_out, "feature buffers need", ", which no feature-buffer call serves")) return rc;
     if (num_rows == 0) return FLUX_OK;
-    if (!d_out) return fail(FLUX_E_INVALID, "null output pointer");
-    if (row_stride < 1) return fail(FLUX_E_INVALID, "row_stride must be >= 1");
-    if (!holds_all_sets(ctx))  // every row uses every sample set (trace.rs:64-69)
-        return fail(FLUX_E_INVALID, "feature buffers need all sample sets; this context holds the share %u + k*%u "
-                    "(flux_ctx_create_sets), which no feature-buffer call serves", ctx->sets.first, ctx->sets.stride);
-    if (first_row >= ctx->H || first_row + (num_rows - 1) * row_stride >= ctx->H)
-        return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
-                    (unsigned long long)first_row, (unsigned long long)row_stride,
-                    (unsigned long long)num_rows, ctx->H);
-    flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out);
-    p.stats = nullptr;
-    return launch_timed(ctx, p, "flux_render_aov_rows", (hipStream_t)hip_stream, kPassAov);
+    return launch_pass_rows(ctx, first_row, row_stride, num_rows, d_out, "flux_render_aov_rows", hip_stream, flux::kPassAov);
 }
 
-// (a scratch buffer of its own, d_aov: the framebuffer of flux_render_rows, d_out, is neither resized nor aliased)
 int flux_render_aov_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out) {
-    if (!ctx) return fail(FLUX_E_INVALID, "null context");
-    if (!out) return fail(FLUX_E_INVALID, "null output pointer");
-    if (row_end < row_start || row_end >= ctx->H)
-        return fail(FLUX_E_INVALID, "rows [%llu,%llu] outside image height %u",
-                    (unsigned long long)row_start, (unsigned long long)row_end, ctx->H);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    const uint64_t rows = row_end - row_start + 1;
-    const size_t doubles = (size_t)rows * ctx->W * FLUX_AOV_CHANNELS;
-    if (doubles > ctx->d_aov_doubles) {
-        ctx->d_aov_doubles = 0;  // (stays 0 if the new allocation fails: the old one is released first)
-        HIP_TRY(ctx->d_aov.alloc(doubles));
-        ctx->d_aov_doubles = doubles;
-    }
-    int rc = flux_render_aov_rows_device(ctx, row_start, 1, rows, ctx->d_aov, nullptr);
-    if (rc != FLUX_OK) return rc;
-    HIP_TRY(hipMemcpy(out, ctx->d_aov, doubles * sizeof(double), hipMemcpyDeviceToHost));
-    return FLUX_OK;
+    return rows_to_host(ctx, row_start, row_end, "", &flux_ctx::d_aov, FLUX_AOV_CHANNELS, out, flux_render_aov_rows_device);
 }
 
-// The per-pixel sample moments (moments_body.inc): the argument checks of the feature-buffer calls, and one more -- a single sample
-// has no variance.  Statistics off: the kernel keeps none.
+// The per-pixel sample moments (moments_body.inc): a share of the sets is refused first, and one more thing -- a single sample has
+// no variance.
 int flux_render_moments_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *d_out,
                                     void *hip_stream) {
     if (!ctx) return fail(FLUX_E_INVALID, "null context");
-    if (!holds_all_sets(ctx))  // every row uses every sample set (trace.rs:64-69)
-        return fail(FLUX_E_INVALID, "sample moments need all sample sets; this context holds the share %u + k*%u "
-                    "(flux_ctx_create_sets), which no moments call serves", ctx->sets.first, ctx->sets.stride);
+    if (int rc = check_all_sets(ctx, "sample moments need", ", which no moments call serves")) return rc;
     if (ctx->N < 2)
         return fail(FLUX_E_INVALID, "sample moments need sample_root >= 2: one sample per pixel has no variance; flux_denoise "
                     "estimates the variance from the frame itself");
+    if (int rc = check_rows_call(ctx, first_row, row_stride, num_rows, d_out)) return rc;
     if (num_rows == 0) return FLUX_OK;
-    if (!d_out) return fail(FLUX_E_INVALID, "null output pointer");
-    if (row_stride < 1) return fail(FLUX_E_INVALID, "row_stride must be >= 1");
-    if (first_row >= ctx->H || first_row + (num_rows - 1) * row_stride >= ctx->H)
-        return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
-                    (unsigned long long)first_row, (unsigned long long)row_stride,
-                    (unsigned long long)num_rows, ctx->H);
-    flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out);
-    p.stats = nullptr;
-    return launch_timed(ctx, p, "flux_render_moments_rows", (hipStream_t)hip_stream, kPassMoments);
+    return launch_pass_rows(ctx, first_row, row_stride, num_rows, d_out, "flux_render_moments_rows", hip_stream, flux::kPassMoments);
 }
 
-// (a scratch buffer of its own, d_moments: neither the framebuffer of flux_render_rows nor the feature buffers' is resized or aliased)
 int flux_render_moments_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out) {
-    if (!ctx) return fail(FLUX_E_INVALID, "null context");
-    if (!out) return fail(FLUX_E_INVALID, "null output pointer");
-    if (row_end < row_start || row_end >= ctx->H)
-        return fail(FLUX_E_INVALID, "rows [%llu,%llu] outside image height %u",
-                    (unsigned long long)row_start, (unsigned long long)row_end, ctx->H);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    const uint64_t rows = row_end - row_start + 1;
-    const size_t doubles = (size_t)rows * ctx->W * FLUX_MOMENT_CHANNELS;
-    if (doubles > ctx->d_moments_doubles) {
-        ctx->d_moments_doubles = 0;  // (stays 0 if the new allocation fails: the old one is released first)
-        HIP_TRY(ctx->d_moments.alloc(doubles));
-        ctx->d_moments_doubles = doubles;
-    }
-    int rc = flux_render_moments_rows_device(ctx, row_start, 1, rows, ctx->d_moments, nullptr);
-    if (rc != FLUX_OK) return rc;
-    HIP_TRY(hipMemcpy(out, ctx->d_moments, doubles * sizeof(double), hipMemcpyDeviceToHost));
-    return FLUX_OK;
+    return rows_to_host(ctx, row_start, row_end, "", &flux_ctx::d_moments, FLUX_MOMENT_CHANNELS, out, flux_render_moments_rows_device);
 }
 
 // ---- adaptive sampling (adaptive_body.inc, adaptive.hip) -------------------------------------------------------
@@ -748,9 +719,7 @@ static int check_adaptive_params(const char *what, const flux_adaptive_params *a
 // ... and the ones that need the context but no device
 static int check_adaptive_ctx(const char *what, const flux_ctx *ctx, const flux_adaptive_params *a) {
     if (!ctx) return fail(FLUX_E_INVALID, "%s: null context", what);
-    if (!holds_all_sets(ctx))  // every row uses every sample set (trace.rs:64-69)
-        return fail(FLUX_E_INVALID, "adaptive sampling needs all sample sets; this context holds the share %u + k*%u "
-                    "(flux_ctx_create_sets), which no adaptive call serves", ctx->sets.first, ctx->sets.stride);
+    if (int rc = check_all_sets(ctx, "adaptive sampling needs", ", which no adaptive call serves")) return rc;
     if (ctx->N < 2)
         return fail(FLUX_E_INVALID, "adaptive sampling needs sample_root >= 2: one sample per pass has no variance to decide by");
     if (a->max_passes > ctx->S)
@@ -771,11 +740,7 @@ int flux_render_adaptive_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t
     if (info) info[0] = info[1] = info[2] = info[3] = 0;
     if (num_rows == 0) return FLUX_OK;
     if (!d_out_moments || !d_out_passes) return fail(FLUX_E_INVALID, "%s: null output pointer", what);
-    if (row_stride < 1) return fail(FLUX_E_INVALID, "row_stride must be >= 1");
-    if (first_row >= ctx->H || first_row + (num_rows - 1) * row_stride >= ctx->H)
-        return fail(FLUX_E_INVALID, "rows %llu + k*%llu (k<%llu) exceed image height %u",
-                    (unsigned long long)first_row, (unsigned long long)row_stride,
-                    (unsigned long long)num_rows, ctx->H);
+    if (int rc = check_rows_call(ctx, first_row, row_stride, num_rows, d_out_moments)) return rc;
     const uint64_t pixels = num_rows * ctx->W;
     if (pixels > 0x7fffffffull) return fail(FLUX_E_INVALID, "%s: %llu pixels exceed 2^31 - 1", what, (unsigned long long)pixels);
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -783,16 +748,15 @@ int flux_render_adaptive_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
     flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, nullptr);
     p.stats = nullptr;
-    if (int rc = check_lds_budget(ctx, p, "flux_render_adaptive_rows", kPassMoments)) return rc;
-    if (pixels > ctx->d_adapt_pixels) {
-        ctx->d_adapt_pixels = 0;  // (stays 0 if a new allocation fails: the old ones are released first)
-        HIP_TRY(ctx->d_adapt_sums.alloc((size_t)pixels * flux::kAdaptiveSums));
-        HIP_TRY(ctx->d_adapt_passes.alloc((size_t)pixels));
-        HIP_TRY(ctx->d_adapt_list.alloc((size_t)pixels));
-        HIP_TRY(ctx->d_adapt_hot.alloc((size_t)pixels));
-        HIP_TRY(ctx->d_adapt_counts.alloc(2));
-        ctx->d_adapt_pixels = (size_t)pixels;
-    }
+    if (int rc = check_lds_budget(ctx, p, "flux_render_adaptive_rows", flux::kPassMoments)) return rc;
+    HIP_TRY(ctx->d_adapt_pixels.grow((size_t)pixels, [&] {
+        hipError_t e = ctx->d_adapt_sums.alloc((size_t)pixels * flux::kAdaptiveSums);
+        if (e == hipSuccess) e = ctx->d_adapt_passes.alloc((size_t)pixels);
+        if (e == hipSuccess) e = ctx->d_adapt_list.alloc((size_t)pixels);
+        if (e == hipSuccess) e = ctx->d_adapt_hot.alloc((size_t)pixels);
+        if (e == hipSuccess) e = ctx->d_adapt_counts.alloc(2);
+        return e;
+    }));
     const int math = effective_math(ctx);
     flux::AdaptiveWork work{};
     work.sums = ctx->d_adapt_sums;
@@ -848,19 +812,15 @@ int flux_render_adaptive_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_en
     if (int rc = check_adaptive_params(what, a)) return rc;
     if (int rc = check_adaptive_ctx(what, ctx, a)) return rc;
     if (!out_moments || !out_passes) return fail(FLUX_E_INVALID, "%s: null output pointer", what);
-    if (row_end < row_start || row_end >= ctx->H)
-        return fail(FLUX_E_INVALID, "rows [%llu,%llu] outside image height %u",
-                    (unsigned long long)row_start, (unsigned long long)row_end, ctx->H);
+    if (int rc = check_row_range(ctx, row_start, row_end, "")) return rc;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
     const uint64_t rows = row_end - row_start + 1;
     const size_t pixels = (size_t)rows * ctx->W;
-    if (pixels > ctx->d_adapt_out_pixels) {
-        ctx->d_adapt_out_pixels = 0;  // (stays 0 if a new allocation fails: the old ones are released first)
-        HIP_TRY(ctx->d_adapt_out.alloc(pixels * FLUX_MOMENT_CHANNELS));
-        HIP_TRY(ctx->d_adapt_map.alloc(pixels));
-        ctx->d_adapt_out_pixels = pixels;
-    }
+    HIP_TRY(ctx->d_adapt_out_pixels.grow(pixels, [&] {
+        const hipError_t e = ctx->d_adapt_out.alloc(pixels * FLUX_MOMENT_CHANNELS);
+        return e == hipSuccess ? ctx->d_adapt_map.alloc(pixels) : e;
+    }));
     int rc = flux_render_adaptive_rows_device(ctx, row_start, 1, rows, params, ctx->d_adapt_out, ctx->d_adapt_map, info, nullptr);
     if (rc != FLUX_OK) return rc;
     HIP_TRY(hipMemcpy(out_moments, ctx->d_adapt_out, pixels * FLUX_MOMENT_CHANNELS * sizeof(double), hipMemcpyDeviceToHost));

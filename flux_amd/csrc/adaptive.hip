@@ -21,6 +21,7 @@
 //                           ONE address, a frame whose every pixel is at the limit cost 0.7 ms at 800 x 600: 60 000 serialised adds.)
 #include <hip/hip_runtime.h>
 
+#include "flux_moments.h"
 #include "flux_tables.h"
 
 namespace flux {
@@ -85,30 +86,9 @@ __global__ __launch_bounds__(kBlock) void adaptive_finish_kernel(uint32_t nsamp,
         const double *s = sums + p * kAdaptiveSums;
         const uint32_t c = passes[p];
         const double count = (double)((uint64_t)nsamp * c);
-        const double denom = 1.0 / count;  // (IEEE: with c = 1 the host's RenderParams::pixel_denom bit for bit)
-        // moments_kernel's epilogue with n for N: * 1/n, Color::max_to_one (color.rs:35-44), the one-pass variance
-        const double mr = s[0] * denom, mg = s[1] * denom, mb = s[2] * denom;
-        double r = mr, g = mg, b = mb, k = 1.0;
-        const double mx1 = r > g ? r : g;
-        const double mx2 = mx1 > b ? mx1 : b;
-        if (mx2 > 1.0) {
-            k = 1.0 / mx2;
-            r *= k;
-            g *= k;
-            b *= k;
-        }
-        const double d = s[4] - (s[3] * s[3]) / count;
-        const double s2 = (d < 0.0 ? 0.0 : d) / (count - 1.0);  // (a NaN stays a NaN)
-        const double var = (s2 / count) * (k * k);
-        double v = r;
-        v = ch == 1u ? g : v;
-        v = ch == 2u ? b : v;
-        v = ch == 3u ? var : v;
-        v = ch == 4u ? mr : v;
-        v = ch == 5u ? mg : v;
-        v = ch == 6u ? mb : v;
-        v = ch == 7u ? s2 : v;
-        out[p * 8 + ch] = v;
+        double m[8];  // (IEEE: with c = 1 the denominator is the host's RenderParams::pixel_denom bit for bit)
+        moments_of_sums(s[0], s[1], s[2], s[3], s[4], count, 1.0 / count, m);
+        out[p * 8 + ch] = pick(ch, m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
         if (ch == 0u) out_passes[p] = c;
     }
 }

@@ -1,8 +1,8 @@
 // aov_body.inc -- the first-hit feature buffers (include/flux_abi.h flux_render_aov_rows*, DESIGN.md section 5e): per pixel the mean
 // albedo, the mean shading normal, the mean hit distance and the coverage of the N primary rays the render kernels trace for it.
 // Included by render.hip behind render_body.inc in the STRICT and the FAST copy (not the one with the dielectric lobe: a first hit
-// runs no lobe, so a scene with a Dielectric uses the FAST copy); everything it calls -- primary_ray, scene_hit, map_wave, wave_sum1 --
-// is render_body.inc's, so a sample's ray, its first hit and its normal are the ones the render kernels and flux_debug_shade compute.
+// runs no lobe, so a scene with a Dielectric uses the FAST copy); everything it calls -- primary_ray, scene_hit, map_wave,
+// lane_group, group_totals -- is render_body.inc's, so a sample's ray, its first hit and its normal are the ones the render kernels and flux_debug_shade compute.
 //
 // What a sample contributes (shade_hit's fields of the hit, nothing of its bounce):
 //   normal  the shading normal as the bounce would use it: a sphere's ((o - c) + t d) invert / radius, a plane's, disk's or triangle's
@@ -72,37 +72,29 @@ __device__ __forceinline__ void first_hit_fields(const RenderParams &P, const Ra
 }
 
 // One wave per pixel from 64 samples on (lane l takes samples l, l + 64, ...; pixels in map_wave's order, so a set's tables stay in
-// one XCD's L2), 64 / N pixels per wave in lane groups below (render_static_kernel's two layouts).  The eight per-lane sums are
-// combined in a fixed order -- wave_sum1's tree, or lane order within a group -- so the buffers are bit-reproducible and do not depend
-// on how rows are grouped into calls; the pixel's 64 bytes are then written as one line, a double per lane.  No atomics, no
-// statistics.  P.out: [num_rows][W][FLUX_AOV_CHANNELS].  Dynamic LDS: the per-lane BVH stack [entry][thread] of a mesh scene, at the
-// base in both copies (no recursion stack in front of it here, unlike bvh_stack_base's STRICT layout): launch_plan.cpp plan_aov.
+// one XCD's L2), lane_group's groups in row-major order below (render_body.inc).  The eight per-lane sums are combined by
+// group_totals and the pixel's 64 bytes written as one line, a double per lane.  No atomics, no statistics.
+// P.out: [num_rows][W][FLUX_AOV_CHANNELS].  Dynamic LDS: the per-lane BVH stack [entry][thread] of a mesh scene, at the
+// base in both copies (no recursion stack in front of it here, unlike bvh_stack_base's STRICT layout): launch_plan.cpp plan_pass.
 template <bool TRIS>
 __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void aov_kernel(const RenderParams P) {
     extern __shared__ double lds_stack[];
     const int tid = threadIdx.x;
-    const uint32_t lane = tid & 63;
     const int stride = blockDim.x;
     int *tstack = reinterpret_cast<int *>(lds_stack) + tid;
 
     const uint32_t N = P.nsamp;
-    const uint32_t lpp = N >= 64u ? 64u : N;  // lanes per pixel
-    const uint32_t ppw = 64u / lpp;           // pixels per wave
-    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (tid >> 6);
-    const uint32_t slot = lane / lpp;
-    const uint32_t seg_base = slot * lpp;
-    const uint32_t i0 = lane - seg_base;
-
+    const LaneGroup G = lane_group(N);
     int row = 0, col = 0;
     uint32_t set = 0;
     uint64_t pixel = 0;
     bool lane_on;
-    if (lpp == 64u) {
+    if (G.whole_wave) {
         int lrow;
-        lane_on = map_wave(P, wave, lrow, col, row, set, pixel);
+        lane_on = map_wave(P, G.wave, lrow, col, row, set, pixel);
     } else {
-        pixel = wave * ppw + slot;
-        lane_on = slot < ppw && pixel < (uint64_t)P.num_rows * P.img_w;
+        pixel = G.unit();
+        lane_on = G.on((uint64_t)P.num_rows * P.img_w);
         if (lane_on) {
             const uint64_t lrow = pixel / P.img_w;
             col = (int)(pixel - lrow * P.img_w);
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void aov_kernel(
     double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // albedo, normal, t, hits
     const uint32_t nchunks = (N + 63u) / 64u;
     for (uint32_t c = 0; c < nchunks; ++c) {
-        const uint32_t i = i0 + c * 64u;
+        const uint32_t i = G.i0 + c * 64u;
         if (lane_on && i < N) {
             const double2 sq = P.pix[(size_t)set * N + i];
             const double2 lens = P.disc[(size_t)set * N + i];
@@ -141,23 +133,13 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void aov_kernel(
         }
     }
     double tot[8];
-    if (lpp == 64u) {  // wave-uniform: the whole wave is one pixel
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tot[k] = wave_sum1(s[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tot[k] = 0.0;
-        for (uint32_t j = 0; j < lpp; ++j) {
-            const int src = (int)((seg_base + j) & 63u);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) tot[k] += __shfl(s[k], src);
-        }
-    }
-    // lane j of the pixel's group writes channels j, j + lpp, ...: from 8 samples on, lanes 0..7 one double each
+    group_totals<8>(G, s, tot);
     if (lane_on) {
         const double count = (double)N;
         double *o = P.out + pixel * 8;
-        for (uint32_t ch = i0; ch < 8u; ch += lpp) {
+        for (uint32_t ch = G.i0; ch < 8u; ch += G.lpp) {
+            // (the select as a loop over the array, not pick's chain over values: the compiler keeps this kernel's eight totals in
+            // scratch and indexes them, and with the chain it spilled 55 SGPRs for 23 and ran 6 to 9 % longer on demo2)
             double v = tot[0];
 #pragma unroll
             for (int k = 1; k < 8; ++k) v = ch == (uint32_t)k ? tot[k] : v;

@@ -88,6 +88,25 @@ template <class T> struct DevBuf : Owner<T *, free_device<T>> {  // a hipMalloc 
     }
     hipError_t alloc(size_t count) { return alloc_bytes(count * sizeof(T)); }
 };
+// What grow-only device scratch holds, in its owner's units.  grow(want, alloc) runs alloc() -- which allocates everything sized by
+// this capacity -- where `want` exceeds it.  The capacity is 0 while alloc() runs and stays 0 if it fails: a DevBuf releases what it
+// held before it allocates.
+struct Capacity {
+    size_t n = 0;
+    template <class F> hipError_t grow(size_t want, F &&alloc) {
+        if (want <= n) return hipSuccess;
+        n = 0;
+        const hipError_t e = alloc();
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+};
+template <class T> struct Scratch : DevBuf<T> {  // one grow-only buffer
+    Capacity held;
+    hipError_t reserve(size_t count) {
+        return held.grow(count, [&] { return this->alloc(count); });
+    }
+};
 struct Stream : Owner<hipStream_t, drain_and_destroy> {
     hipError_t create() { return hipStreamCreateWithFlags(&h_, hipStreamNonBlocking); }
 };
@@ -145,22 +164,16 @@ struct flux_ctx {
     int traversal = FLUX_TRAVERSE_BVH;
     int variant = FLUX_KERNEL_DEFAULT;
     int math = FLUX_MATH_FAST;
-    // scratch framebuffer for the host-output path
-    flux::DevBuf<double> d_out;
-    size_t d_out_doubles = 0;
-    // ... and the feature buffers' own (flux_render_aov_rows)
-    flux::DevBuf<double> d_aov;
-    size_t d_aov_doubles = 0;
-    // ... and the sample moments' own (flux_render_moments_rows)
-    flux::DevBuf<double> d_moments;
-    size_t d_moments_doubles = 0;
+    // scratch framebuffer for the host-output path (flux_render_rows), the feature buffers' own (flux_render_aov_rows) and the sample
+    // moments' own (flux_render_moments_rows): no call resizes or aliases another's
+    flux::Scratch<double> d_out, d_aov, d_moments;
     // ... and the adaptive sampler's state and work list (flux_render_adaptive_rows*), all sized for d_adapt_pixels pixels: the running
     // sums [pixels][kAdaptiveSums], the pass counts, the hot flags, the list, and two counters (active pixels, pixels at max_passes);
-    // d_adapt_out / d_adapt_map stage the host entry point's outputs
+    // d_adapt_out / d_adapt_map stage the host entry point's outputs, sized for d_adapt_out_pixels
     flux::DevBuf<double> d_adapt_sums, d_adapt_out;
     flux::DevBuf<uint32_t> d_adapt_passes, d_adapt_list, d_adapt_counts, d_adapt_map;
     flux::DevBuf<unsigned char> d_adapt_hot;
-    size_t d_adapt_pixels = 0, d_adapt_out_pixels = 0;
+    flux::Capacity d_adapt_pixels, d_adapt_out_pixels;
     flux::Event ev0, ev1;
     bool timed = false;
     uint64_t device_bytes = 0;

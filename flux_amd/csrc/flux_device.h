@@ -24,7 +24,7 @@
 #ifndef FLUX_BVH_WIDE_MAX_STACK
 #define FLUX_BVH_WIDE_MAX_STACK 48
 #endif
-// refill kernel: most waves that share one pixel's samples (launch_render picks K <= this, a power of two)
+// refill kernel: most waves that share one pixel's samples (the launch plan picks K <= this, a power of two)
 #ifndef FLUX_MAX_WAVES_PER_PIXEL
 #define FLUX_MAX_WAVES_PER_PIXEL 4
 #endif

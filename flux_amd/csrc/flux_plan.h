@@ -75,7 +75,7 @@ size_t tput_table_bytes(const RenderParams &p, int *bits = nullptr);
 enum KernelCopy { kCopyStrict = 0, kCopyFast = 1, kCopyFastDiel = 2 };
 KernelCopy kernel_copy(const RenderParams &p, int math);
 
-// Which kernel launch_render runs for these parameters -- which instantiation, with what block size, grid and dynamic LDS: decided
+// Which kernel a render launch runs for these parameters -- which instantiation, with what block size, grid and dynamic LDS: decided
 // in ONE place (launch_plan.cpp plan_render) and asked from there by the launch itself, by the host's LDS budget check and by
 // flux_ctx_launch_plan / flux_ctx_bvh_info, so that they cannot drift apart.  The launch maps these fields to template arguments.
 struct LaunchPlan {
@@ -95,17 +95,18 @@ struct LaunchPlan {
                                    // (render_body.inc shade_primary_hits); FLUX_SPLIT_UNIFORM_A=0: the general step everywhere
 };
 LaunchPlan plan_render(const RenderParams &p, int variant, int math);
-// The same for the feature-buffer kernel (aov_body.inc aov_kernel): `kernel` is 0 (or -1: nothing to do), `copy` never kCopyFastDiel --
-// a first hit runs no lobe --, `lds` the per-lane BVH stack of a mesh scene and nothing else, `blocks` one wave per pixel in
-// map_wave's order from 64 samples on and 64 / N pixels per wave below.
-LaunchPlan plan_aov(const RenderParams &p, int math);
-// The same for the moments kernel (moments_body.inc moments_kernel): block, grid and LDS as plan_render's STATIC branch computes
-// them -- render_static_kernel's two layouts and its per-lane stacks --, `copy` as kernel_copy answers (the kernel runs the lobes),
-// `kernel` 0 (or -1: nothing to do).
-LaunchPlan plan_moments(const RenderParams &p, int math);
-// The same for one pass of the adaptive sampler (adaptive_body.inc adaptive_pass_kernel): plan_moments' block, LDS and copy, with
-// `blocks` sized by the `entries` of the pass's work list instead of the pixel grid (-1: an empty list).
-LaunchPlan plan_adaptive(const RenderParams &p, int math, uint64_t entries);
+// The kernel family a launch runs: the render kernels, or one of the per-pixel passes -- the feature buffers (aov_body.inc
+// aov_kernel), the sample moments (moments_body.inc moments_kernel), one pass of the adaptive sampler over a work list
+// (adaptive_body.inc adaptive_pass_kernel)
+enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2, kPassAdaptive = 3 };
+// The same for any pass (kPassRender: plan_render).  Of a per-pixel pass `kernel` is 0 (or -1: nothing to do) and block, grid and
+// LDS are what plan_render's STATIC branch computes -- render_static_kernel's two layouts and its per-lane stacks --, with
+//   kPassAov       `copy` never kCopyFastDiel -- a first hit runs no lobe --, `lds` the per-lane BVH stack of a mesh scene and nothing
+//                  else, `blocks` one wave per pixel in map_wave's order from 64 samples on;
+//   kPassMoments   `copy` as kernel_copy answers: the kernel runs the lobes;
+//   kPassAdaptive  the same, with `blocks` sized by the `entries` of the pass's work list instead of the pixel grid (-1: an empty list).
+// `variant` counts for kPassRender alone, `entries` for kPassAdaptive alone.
+LaunchPlan plan_pass(Pass pass, const RenderParams &p, int variant, int math, uint64_t entries = 0);
 
 // LDS of the per-lane stacks of `lanes` lanes: the STRICT (f, s) recursion stack, 4 doubles per level, and the BVH traversal stack,
 // one int per level

@@ -29,20 +29,14 @@ hipError_t generate_glossx_table(const double *gloss, size_t count, const double
 hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *out, hipStream_t stream);
 hipError_t hemi_to_aos(size_t SD, size_t N, const double *in, double *out, hipStream_t stream);
 
-// Camera::render (trace.rs:53-97).  variant: FLUX_KERNEL_*; math: FLUX_MATH_FAST / FLUX_MATH_STRICT (render_body.inc).  Runs
-// what plan_render (flux_plan.h) answers for the same arguments.
-hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream);
-
-// The first-hit feature buffers of the rows p names (aov_body.inc): p.out = [num_rows][W][FLUX_AOV_CHANNELS].  Runs what plan_aov
-// (flux_plan.h) answers for the same arguments.
-hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream);
-
-// The per-pixel sample moments of the rows p names (moments_body.inc): p.out = [num_rows][W][FLUX_MOMENT_CHANNELS].  Runs what
-// plan_moments (flux_plan.h) answers for the same arguments.
-hipError_t launch_moments(const RenderParams &p, int math, hipStream_t stream);
+// The rows p names by the kernels of `pass` (flux_plan.h; not kPassAdaptive): Camera::render (trace.rs:53-97) for kPassRender --
+// variant: FLUX_KERNEL_*, which counts for it alone --, the first-hit feature buffers (aov_body.inc, p.out =
+// [num_rows][W][FLUX_AOV_CHANNELS]) or the per-pixel sample moments (moments_body.inc, p.out = [num_rows][W][FLUX_MOMENT_CHANNELS]).
+// math: FLUX_MATH_FAST / FLUX_MATH_STRICT (render_body.inc).  Runs what plan_pass answers for the same arguments.
+hipError_t launch_pass(Pass pass, const RenderParams &p, int variant, int math, hipStream_t stream);
 
 // One pass of the adaptive sampler over the work list `a` names (adaptive_body.inc), for the rows p names: N more samples of every
-// listed pixel added to a.sums, a.passes counted up.  Runs what plan_adaptive (flux_plan.h) answers for (p, math, a.count).
+// listed pixel added to a.sums, a.passes counted up.  Runs what plan_pass (flux_plan.h) answers for kPassAdaptive and a.count entries.
 hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int math, hipStream_t stream);
 
 // What the adaptive sampler runs between and after its passes (adaptive.hip; no lobe code).  `pixels` = rows * width of the call.

@@ -79,6 +79,11 @@ size_t tput_table_bytes(const RenderParams &p, int *bits_out) {
     return bytes;
 }
 
+// The waves of a launch in the grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
+static uint64_t grouped_waves(const RenderParams &p) {
+    return 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows + ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
+}
+
 LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     LaunchPlan L;
     L.copy = kernel_copy(p, math);
@@ -93,10 +98,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     const uint32_t lpp = N >= 64u ? 64u : N;
     const uint32_t ppw = 64u / lpp;
     uint64_t waves = (npix + ppw - 1) / ppw;
-    // grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
-    if (variant != FLUX_KERNEL_STATIC && p.num_sets == (uint32_t)p.img_w)
-        waves = 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows +
-                        ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
+    if (variant != FLUX_KERNEL_STATIC && p.num_sets == (uint32_t)p.img_w) waves = grouped_waves(p);
     // refill kernel: K waves per pixel (block = pixel), K from the sample count only
     unsigned K = variant != FLUX_KERNEL_STATIC ? waves_per_pixel(N) : 1u;
     const bool tris = p.n_tris > 0;
@@ -170,64 +172,42 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     return L;
 }
 
-// The feature-buffer kernel: render_static_kernel's two layouts with the refill kernels' pixel order from 64 samples on.  No
-// recursion stack whatever the arithmetic, so the BVH stack starts at the LDS base (aov_body.inc).
-LaunchPlan plan_aov(const RenderParams &p, int math) {
+// A per-pixel pass (aov_body.inc, moments_body.inc, adaptive_body.inc): `units` pixels or work-list entries in lane_group's layout
+// (render_body.inc) -- 64 / N units per wave below 64 samples, one from there on, in the order given --, or the pixels in map_wave's
+// order (`grouped`); FLUX_BLOCK_THREADS lanes a block, each with the (f, s) stack `stack_math` needs for `depth` levels and the BVH
+// stack of a mesh scene.  `kernel` is 0, or -1 where there is nothing to do.
+static LaunchPlan plan_pixel_pass(const RenderParams &p, KernelCopy copy, uint64_t units, int stack_math, size_t depth, bool grouped) {
     LaunchPlan L;
-    L.copy = math == FLUX_MATH_STRICT ? kCopyStrict : kCopyFast;
+    L.copy = copy;
     const uint32_t N = p.nsamp;
-    const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
-    if (npix == 0 || p.set_count <= 0 || N == 0) return L;
+    if (units == 0 || p.set_count <= 0 || N == 0) return L;
     const uint32_t ppw = N >= 64u ? 1u : 64u / N;
-    uint64_t waves = (npix + ppw - 1) / ppw;
-    // grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
-    if (N >= 64u && p.num_sets == (uint32_t)p.img_w)
-        waves = 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows +
-                        ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
+    const uint64_t waves = grouped ? grouped_waves(p) : (units + ppw - 1) / ppw;
     const unsigned wpb = FLUX_BLOCK_THREADS / 64;
     L.kernel = 0;
     L.block = FLUX_BLOCK_THREADS;
     L.blocks = (waves + wpb - 1) / wpb;
     L.tris = p.n_tris > 0 ? 1 : 0;
-    L.lds = lane_stacks_lds(FLUX_MATH_FAST, 0, L.tris != 0, (size_t)p.bvh_stack, L.block);
+    L.lds = lane_stacks_lds(stack_math, depth, L.tris != 0, (size_t)p.bvh_stack, L.block);
     return L;
 }
 
-// The moments kernel: plan_render's STATIC branch at every sample count -- pixels in row-major order, FLUX_BLOCK_THREADS lanes a block,
-// the STRICT (f, s) stack and the BVH stack per lane --, in the copy a render of the job runs.
-LaunchPlan plan_moments(const RenderParams &p, int math) {
-    LaunchPlan L;
-    L.copy = kernel_copy(p, math);
-    const uint32_t N = p.nsamp;
+LaunchPlan plan_pass(Pass pass, const RenderParams &p, int variant, int math, uint64_t entries) {
     const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
-    if (npix == 0 || p.set_count <= 0 || N == 0) return L;
-    const uint32_t ppw = N >= 64u ? 1u : 64u / N;
-    const uint64_t waves = (npix + ppw - 1) / ppw;
-    const unsigned wpb = FLUX_BLOCK_THREADS / 64;
-    L.kernel = 0;
-    L.block = FLUX_BLOCK_THREADS;
-    L.blocks = (waves + wpb - 1) / wpb;
-    L.tris = p.n_tris > 0 ? 1 : 0;
-    L.lds = lane_stacks_lds(math, (size_t)p.max_depth, L.tris != 0, (size_t)p.bvh_stack, L.block);
-    return L;
-}
-
-// One pass of the adaptive sampler: plan_moments with the work list's entries in place of the pixel grid -- 64 / N entries per wave
-// below 64 samples, one from there on --, the same block, LDS and copy.
-LaunchPlan plan_adaptive(const RenderParams &p, int math, uint64_t entries) {
-    LaunchPlan L;
-    L.copy = kernel_copy(p, math);
-    const uint32_t N = p.nsamp;
-    if (entries == 0 || p.set_count <= 0 || N == 0) return L;
-    const uint32_t ppw = N >= 64u ? 1u : 64u / N;
-    const uint64_t waves = (entries + ppw - 1) / ppw;
-    const unsigned wpb = FLUX_BLOCK_THREADS / 64;
-    L.kernel = 0;
-    L.block = FLUX_BLOCK_THREADS;
-    L.blocks = (waves + wpb - 1) / wpb;
-    L.tris = p.n_tris > 0 ? 1 : 0;
-    L.lds = lane_stacks_lds(math, (size_t)p.max_depth, L.tris != 0, (size_t)p.bvh_stack, L.block);
-    return L;
+    switch (pass) {
+        case kPassRender: break;
+        // the feature buffers: the refill kernels' pixel order from 64 samples on; a first hit runs no lobe (never the copy with the
+        // dielectric one) and keeps no recursion stack whatever the arithmetic, so the BVH stack starts at the LDS base
+        case kPassAov:
+            return plan_pixel_pass(p, math == FLUX_MATH_STRICT ? kCopyStrict : kCopyFast, npix, FLUX_MATH_FAST, 0,
+                                   p.nsamp >= 64u && p.num_sets == (uint32_t)p.img_w);
+        // the sample moments: plan_render's STATIC branch at every sample count -- row-major pixels, the STRICT (f, s) stack and the
+        // BVH stack per lane --, in the copy a render of the job runs
+        case kPassMoments: return plan_pixel_pass(p, kernel_copy(p, math), npix, math, (size_t)p.max_depth, false);
+        // one pass of the adaptive sampler: the same with the work list's entries in place of the pixel grid
+        case kPassAdaptive: return plan_pixel_pass(p, kernel_copy(p, math), entries, math, (size_t)p.max_depth, false);
+    }
+    return plan_render(p, variant, math);
 }
 
 }  // namespace flux

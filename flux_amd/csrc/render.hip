@@ -35,7 +35,7 @@
 // The loop body (render_body.inc) is compiled three times: STRICT under `#pragma clang fp contract(off)` with the
 // reference's operation order, FAST under contract(fast) with flux_math.h (see render_body.inc's header), and FAST again with the
 // dielectric lobe.  Which copy, kernel and instantiation a call runs, with what block, grid and LDS, is the launch plan's decision
-// (launch_plan.cpp plan_render, host code compiled once); launch_render below only maps the plan to a kernel.  The instantiations:
+// (launch_plan.cpp plan_render, host code compiled once); launch_pass below only maps the plan to a kernel.  The instantiations:
 //  * render_static_kernel<STATS, TRIS>, render_refill_kernel<STATS, TRIS>: every copy;
 //  * render_split_kernel<STATS, MAX32, TYP, HQ, AXIS>: FAST -- TYP (the usual analytic scene) only with MAX32, and in the copy with the
 //    dielectric lobe neither TYP nor HQ (the hit queue), which the plan never picks for a scene with a dielectric; AXIS (the first scan
@@ -43,15 +43,16 @@
 //  * render_bvh_kernel<STATS>, render_bvh4_kernel<STATS, LDS_SCENE, TYP>: FAST -- TYP only with LDS_SCENE, and not in the copy
 //    with the dielectric lobe;
 //  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy;
-//  * aov_kernel<TRIS> (aov_body.inc, the first-hit feature buffers: launch_plan.cpp plan_aov): STRICT and FAST, not the copy with the
+//  * aov_kernel<TRIS> (aov_body.inc, the first-hit feature buffers: launch_plan.cpp plan_pass): STRICT and FAST, not the copy with the
 //    dielectric lobe -- a first hit runs no lobe;
-//  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments: launch_plan.cpp plan_moments): every copy -- it runs the lobes;
-//  * adaptive_pass_kernel<TRIS> (adaptive_body.inc, one pass of the adaptive sampler over a work list: launch_plan.cpp plan_adaptive):
+//  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments): every copy -- it runs the lobes;
+//  * adaptive_pass_kernel<TRIS> (adaptive_body.inc, one pass of the adaptive sampler over a work list):
 //    every copy, as moments_kernel.
 #include "flux_device.h"
 #include "flux_plan.h"
 #include "flux_tables.h"
 #include "flux_math.h"
+#include "flux_moments.h"
 #include "../../include/flux_abi.h"
 
 // Tunables: NUMBERS only (overridable with -D, scripts/sweep_variants.py).  Every either/or of rounds 1-5 -- 45 boolean FLUX_*
@@ -236,59 +237,44 @@ hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *o
     return hipGetLastError();
 }
 
-// the kernel the launch planner names (launch_plan.cpp), in the copy of render_body.inc it names
-hipError_t launch_render(const RenderParams &p, int variant, int math, hipStream_t stream) {
-    const LaunchPlan L = plan_render(p, variant, math);
+// `call` in the copy of the kernel bodies the plan names
+#define FLUX_IN_COPY(L, call)                           \
+    switch ((L).copy) {                                 \
+        case kCopyStrict: return strict::call;          \
+        case kCopyFast: return fast::call;              \
+        case kCopyFastDiel: return fast_diel::call;     \
+    }                                                   \
+    return hipErrorInvalidValue
+
+// the kernel the launch planner names for the pass (launch_plan.cpp plan_pass), in the copy it names
+hipError_t launch_pass(Pass pass, const RenderParams &p, int variant, int math, hipStream_t stream) {
+    const LaunchPlan L = plan_pass(pass, p, variant, math);
     if (L.kernel < 0) return hipSuccess;
-    switch (L.copy) {
-        case kCopyStrict: return strict::launch_render_impl(L, p, stream);
-        case kCopyFast: return fast::launch_render_impl(L, p, stream);
-        case kCopyFastDiel: return fast_diel::launch_render_impl(L, p, stream);
+    switch (pass) {
+        case kPassRender: FLUX_IN_COPY(L, launch_render_impl(L, p, stream));
+        case kPassMoments: FLUX_IN_COPY(L, launch_moments_impl(L, p, stream));
+        // (a scene with a Dielectric runs the FAST copy: no lobe behind a first hit)
+        case kPassAov: return L.copy == kCopyStrict ? strict::launch_aov_impl(L, p, stream) : fast::launch_aov_impl(L, p, stream);
+        case kPassAdaptive: break;  // (launch_adaptive: it needs the work list)
     }
     return hipErrorInvalidValue;
 }
 
-// the feature-buffer kernel as plan_aov lays it out; a scene with a Dielectric runs the FAST copy (no lobe behind a first hit)
-hipError_t launch_aov(const RenderParams &p, int math, hipStream_t stream) {
-    const LaunchPlan L = plan_aov(p, math);
-    if (L.kernel < 0) return hipSuccess;
-    return L.copy == kCopyStrict ? strict::launch_aov_impl(L, p, stream) : fast::launch_aov_impl(L, p, stream);
-}
-
-// the moments kernel as plan_moments lays it out, in the copy a render of the same job runs
-hipError_t launch_moments(const RenderParams &p, int math, hipStream_t stream) {
-    const LaunchPlan L = plan_moments(p, math);
-    if (L.kernel < 0) return hipSuccess;
-    switch (L.copy) {
-        case kCopyStrict: return strict::launch_moments_impl(L, p, stream);
-        case kCopyFast: return fast::launch_moments_impl(L, p, stream);
-        case kCopyFastDiel: return fast_diel::launch_moments_impl(L, p, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-// one pass of the adaptive sampler as plan_adaptive lays it out, in the copy a render of the same job runs
+// one pass of the adaptive sampler, in the copy a render of the same job runs
 hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int math, hipStream_t stream) {
-    const LaunchPlan L = plan_adaptive(p, math, a.count);
+    const LaunchPlan L = plan_pass(kPassAdaptive, p, 0, math, a.count);
     if (L.kernel < 0) return hipSuccess;
-    switch (L.copy) {
-        case kCopyStrict: return strict::launch_adaptive_impl(L, p, a, stream);
-        case kCopyFast: return fast::launch_adaptive_impl(L, p, a, stream);
-        case kCopyFastDiel: return fast_diel::launch_adaptive_impl(L, p, a, stream);
-    }
-    return hipErrorInvalidValue;
+    FLUX_IN_COPY(L, launch_adaptive_impl(L, p, a, stream));
 }
 
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream) {
     const size_t lds = shade_rays_lds(p, math);
-    switch (kernel_copy(p, math)) {
-        case kCopyStrict: return strict::launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
-        case kCopyFast: return fast::launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
-        case kCopyFastDiel: return fast_diel::launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream);
-    }
-    return hipErrorInvalidValue;
+    LaunchPlan L;
+    L.copy = kernel_copy(p, math);
+    FLUX_IN_COPY(L, launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream));
 }
+#undef FLUX_IN_COPY
 
 // ---- flux_math.h under test: out[i] = fn(a[i], b[i]) computed on the device ----------------------
 __global__ void fastmath_probe_kernel(int fn, const double *a, const double *b, double *out, size_t n) {

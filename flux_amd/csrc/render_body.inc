@@ -1838,6 +1838,57 @@ __device__ __forceinline__ void wave_sum3(double sr, double sg, double sb, doubl
     b = wave_sum1(sb);
 }
 
+// ---- the pieces of a per-pixel pass (aov_kernel, moments_kernel, adaptive_pass_kernel) ----
+// (render_static_kernel and finish_pixel below hold the same layout and combine in their own text: seen in a function of their own,
+// the layout's two divisions are narrowed to 8 bits by the compiler, and the product kernel's instruction stream is kept as it is)
+// The two layouts of a pass whose unit of work -- a pixel, or an entry of a work list -- takes N samples.  From 64 samples on a wave
+// is one unit and lane l takes samples l, l + 64, ...; below, 64 / N consecutive units share a wave in groups of N lanes, and the
+// 64 % N lanes behind the last group idle (N = 9: seven groups, one idle lane).
+struct LaneGroup {
+    bool whole_wave;    // N >= 64 (wave-uniform): the wave is one unit
+    uint32_t lpp;       // lanes per unit
+    uint32_t ppw;       // units per wave
+    uint32_t slot;      // the lane's group within the wave (>= ppw: an idle lane)
+    uint32_t seg_base;  // the group's first lane
+    uint32_t i0;        // the lane within its group: its first sample, and the first channel it stores
+    uint64_t wave;      // the wave within the grid
+    __device__ __forceinline__ uint64_t unit() const { return wave * ppw + slot; }
+    __device__ __forceinline__ bool on(uint64_t units) const { return slot < ppw && unit() < units; }  // not an idle lane, and work left
+};
+__device__ __forceinline__ LaneGroup lane_group(uint32_t N) {
+    LaneGroup G;
+    const int tid = threadIdx.x;
+    const uint32_t lane = tid & 63;
+    G.whole_wave = N >= 64u;
+    G.lpp = G.whole_wave ? 64u : N;
+    G.ppw = 64u / G.lpp;
+    G.wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (tid >> 6);
+    G.slot = lane / G.lpp;
+    G.seg_base = G.slot * G.lpp;
+    G.i0 = lane - G.seg_base;
+    return G;
+}
+// A unit's K totals from its lanes' partial sums, in a fixed order -- a whole wave: wave_sum1's tree; a lane group: in lane order --,
+// so what a pass writes is bit-reproducible and does not depend on how rows are grouped into calls.  Every lane of the group ends
+// with the totals.
+template <int K>
+__device__ __forceinline__ void group_totals(const LaneGroup &G, const double (&s)[K], double (&tot)[K]) {
+    if (G.whole_wave) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) tot[k] = wave_sum1(s[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) tot[k] = 0.0;
+        for (uint32_t j = 0; j < G.lpp; ++j) {
+            const int src = (int)((G.seg_base + j) & 63u);
+#pragma unroll
+            for (int k = 0; k < K; ++k) tot[k] += __shfl(s[k], src);
+        }
+    }
+}
+// A pass stores a unit's K channels as `for (ch = G.i0; ch < K; ch += G.lpp) o[ch] = pick(ch, v0, v1, ...)` (flux_moments.h): lane j of the
+// group writes channels j, j + lpp, ... -- from 8 samples on, eight lanes write a 64-byte line, a double each.
+
 // Sum the per-lane partials of one pixel (a whole wave: wave_sum3's tree; a lane group of a wave that holds several
 // pixels: in lane order), then trace.rs:85-87: * 1/n^2, max_to_one, store (leader = first lane of the pixel's group).
 __device__ __forceinline__ void finish_pixel(const RenderParams &P, bool lane_on, uint32_t lane,
@@ -2031,7 +2082,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, TRIS ? FLUX_WPE_WIDE
     // One BLOCK = one pixel; its K = blockDim/64 waves take K contiguous slices of the pixel's sample list, so a
     // 16384-spp pixel is 4 work items of a quarter the length (the ragged end of a launch -- slots idling
     // while the last long pixels finish -- shrinks accordingly, which is what limits an 8-GPU frame).  K depends
-    // on the sample count only (launch_render), so the summation order, hence the image, does not depend on how
+    // on the sample count only (launch_plan.cpp), so the summation order, hence the image, does not depend on how
     // the frame is split over launches or GPUs.
     const uint32_t N = P.nsamp;
     const uint32_t K = blockDim.x >> 6, sub = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);  // a scalar: see render_split_kernel
@@ -2918,7 +2969,7 @@ template <bool STATS>
 __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_BVH) void render_bvh_kernel(const RenderParams P0) {
     const RenderParams &P = P0;  // (inside the pass loop: shadowed by the re-read view)
     extern __shared__ double lds_stack[];
-    const int tid = threadIdx.x;  // one wave per block (launch_render)
+    const int tid = threadIdx.x;  // one wave per block (launch_plan.cpp)
     const uint32_t lane = tid & 63;
     // traversal stack [entry][lane] in LDS, addressed by BYTE offset (`sp` counts bytes: +-256 per entry, no multiply)
     char *tstack = reinterpret_cast<char *>(lds_stack) + tid * 4;

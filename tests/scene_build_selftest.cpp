@@ -4,7 +4,8 @@
 // text, <out dir>/<scene>.scalars.txt: the test pins their SHA-256.  The scenes are the shipped ones loaded through the C++ host
 // layer and a generated height field whose triangles need the threaded record pool and the forked BVH build.  Small inline
 // scenes cover each branch of the derived flags.  It also writes <out dir>/plans.txt: the launch planner's answer (flux_plan.h
-// plan_render: kernel, instantiation, block, grid, LDS) for every scene over a grid of jobs, one line each, which the test pins too.
+// plan_render: kernel, instantiation, block, grid, LDS) for every scene over a grid of jobs, one line each, which the test pins too,
+// and <out dir>/pass_plans.txt: the same for the per-pixel passes (feature buffers, sample moments, an adaptive pass).
 // Prints one "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
 #include <cstdio>
@@ -135,6 +136,38 @@ static void plans(const std::string &name, const flux::HostScene &h, const char 
                     }
 }
 
+// The plans of the per-pixel passes (flux_plan.h plan_pass) of one scene, for <out dir>/pass_plans.txt: sample roots
+// below, at and above one wave x arithmetic x traversal x pass -- the adaptive pass over a one-entry list and over a seventh of
+// the frame.  The jobs' other fields as in plans().
+static std::string g_pass_plans;
+static void pass_plans(const std::string &name, const flux::HostScene &h) {
+    static const flux::DevNode4Q nodes4_placeholder{};
+    static const char *kTraversal[] = {"bvh", "brute", "binary"};
+    static const char *kPass[] = {"aov", "moments", "adaptive1", "adaptive7th"};
+    char buf[300];
+    for (const uint32_t root : {2u, 3u, 8u, 10u, 16u})
+        for (const int math : {FLUX_MATH_FAST, FLUX_MATH_STRICT})
+            for (const int trav : {FLUX_TRAVERSE_BVH, FLUX_TRAVERSE_BRUTE, FLUX_TRAVERSE_BVH_BINARY})
+                for (int pass = 0; pass < 4; pass++) {
+                    flux::RenderParams p = h.rp;
+                    p.max_depth = 5;
+                    p.nsamp = root * root;
+                    p.nodes4 = h.arena.empty() ? nullptr : &nodes4_placeholder;
+                    p.num_rows = p.img_h;
+                    if (trav == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
+                    if (trav == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
+                    const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
+                    const flux::LaunchPlan L = pass == 0   ? flux::plan_pass(flux::kPassAov, p, FLUX_KERNEL_DEFAULT, math)
+                                               : pass == 1 ? flux::plan_pass(flux::kPassMoments, p, FLUX_KERNEL_DEFAULT, math)
+                                                           : flux::plan_pass(flux::kPassAdaptive, p, FLUX_KERNEL_DEFAULT, math,
+                                                                             pass == 2 ? 1 : npix / 7 + 1);
+                    std::snprintf(buf, sizeof(buf), "%s root=%u math=%s traversal=%s pass=%s copy=%d tris=%d block=%u blocks=%llu lds=%zu\n",
+                                  name.c_str(), root, math == FLUX_MATH_STRICT ? "strict" : "fast", kTraversal[trav], kPass[pass], L.copy,
+                                  L.tris, L.block, (unsigned long long)L.blocks, L.lds);
+                    g_pass_plans += buf;
+                }
+}
+
 static int dump(const std::string &name, const flux_scene_desc &desc) {
     flux::HostScene h;
     CHECK(build(desc, h) == FLUX_OK);
@@ -147,6 +180,7 @@ static int dump(const std::string &name, const flux_scene_desc &desc) {
           write_vec(name + ".tris.bin", h.tris) && write_vec(name + ".nodes.bin", h.nodes) && write_vec(name + ".nodesq.bin", h.nodesq) &&
           write_vec(name + ".arena.bin", h.arena) && write_file(name + ".scalars.txt", sc.data(), sc.size()));
     plans(name, h, "");
+    pass_plans(name, h);
     setenv("FLUX_SPLIT_HITQ_CAP", "0", 1);  // the split kernel without its hit queue
     plans(name, h, "+hitq_cap0");
     unsetenv("FLUX_SPLIT_HITQ_CAP");
@@ -287,6 +321,7 @@ int main(int argc, char **argv) {
     CHECK(!h.filter32 && h.rp.n_uni == 0 && h.rp.env_short == 0 && h.rp.f32_groups == 0 && h.f32_half == -1 && h.f32_top == 0);
     std::printf("ok no f32 filter\n");
     CHECK(write_file("plans.txt", g_plans.data(), g_plans.size()));
+    CHECK(write_file("pass_plans.txt", g_pass_plans.data(), g_pass_plans.size()));
     std::printf("ok plans\n");
     std::printf("all ok\n");
     return 0;

@@ -61,6 +61,9 @@ DIGESTS = {
 # plans.txt: 5 scenes x sample roots 4 / 8 / 16 / 128 x 4 kernel variants x FAST / STRICT x 3 traversals x a rows and a sets launch,
 # then the same under FLUX_SPLIT_HITQ_CAP=0 (one line each)
 PLANS_SHA256 = "12f2966b8918c2997213ead19f3703bc8454ff8affb538bf20b229de6838fa32"
+# pass_plans.txt: 5 scenes x sample roots 2 / 3 / 8 / 10 / 16 x FAST / STRICT x 3 traversals x the passes aov, moments, adaptive
+# over one list entry and adaptive over npix / 7 + 1 entries: copy, tris, block, blocks and lds (one line each)
+PASS_PLANS_SHA256 = "f030afc9ade51a7de2755ff925caa85ca01339619a6d61196532ec8b3c092fef"
 
 
 @pytest.fixture(scope="module")
@@ -134,6 +137,13 @@ def _plans(out_dir):
             head, _, rest = line.partition(" kernel=")
             rows[head] = dict(kv.split("=") for kv in ("kernel=" + rest).split())
     return rows
+
+
+def test_pass_plans_are_pinned(default_run, default_out):
+    with open(os.path.join(default_out, "pass_plans.txt"), "rb") as f:
+        text = f.read()
+    assert len(text.splitlines()) == 5 * 5 * 2 * 3 * 4
+    assert hashlib.sha256(text).hexdigest() == PASS_PLANS_SHA256
 
 
 def test_launch_plans_are_pinned(default_run, default_out):
