@@ -234,16 +234,20 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     // the throughput product table (RenderParams::tput) where the job's renders would take parked hits from the hit queue and the
     // table stays within its cap (flux_plan.h); FLUX_THROUGHPUT_TABLE=0 builds the context without it (tests and A/B runs: the take then
     // multiplies the list up).  A switch of its own: what FLUX_SAMPLE_TABLES=0 removes from a context is the sample tables' bytes.
+    // Whether every throughput product of the job is finite (RenderParams::tput_finite, the depth cut's condition: launch_plan.cpp
+    // split_cut_depth) is judged on the host's table either way: the switch removes the device's copy, not what a frame is made of.
     int tput_bits = 0;
+    bool tput_finite = false;
     {
         RenderParams job = h.rp;
         job.nsamp = c->N;
         job.max_depth = (int32_t)c->D;
         const char *tput_env = std::getenv("FLUX_THROUGHPUT_TABLE");
-        if (!(tput_env && std::atoi(tput_env) == 0) && tput_table_bytes(job, &tput_bits)) {
+        if (tput_table_bytes(job, &tput_bits)) {
             std::vector<double> tput;
             build_tput_table(h, tput_bits, (int)c->D, tput);
-            alloc_copy(c->d_tput, tput);
+            tput_finite = tput_products_finite(h, tput_bits, (int)c->D, tput);
+            if (!(tput_env && std::atoi(tput_env) == 0)) alloc_copy(c->d_tput, tput);
         }
     }
     // the lobe-frame table (RenderParams::lobe_frame): 48 B per hit record, filled by the device below; FLUX_LOBE_FRAMES=0 builds the
@@ -317,6 +321,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.gx_stride = gx_stride;
     rp.tput = c->d_tput;
     rp.tput_bits = c->d_tput ? tput_bits : 0;
+    rp.tput_finite = tput_finite ? 1 : 0;
     rp.lobe_frame = c->d_lobe;
     // the first plane's axis (RenderParams::plane_axis); FLUX_PLANE_AXIS=0 builds the context without it (tests and A/B runs: both scans
     // then form the first plane's dot products in full)

@@ -293,6 +293,15 @@ struct RenderParams {
     // kernel's instantiation for that axis (render_split_kernel<.., AXIS>): the peeled first-plane test of both scans is then
     // num = p_a - o_a, den = d_a in every wave whose vote admits it (render_body.inc).
     int32_t plane_axis;
+    // split kernel with the hit queue: 1 = every throughput a parked hit of this job can carry, and its product with one more bounce
+    // weight, is finite -- judged on the host's throughput table where the context builds it (scene_build.cpp tput_products_finite),
+    // whether or not `tput` holds the device's copy; 0 also for a job that gets no table.  What the depth cut needs (launch_plan.cpp
+    // split_cut_depth).
+    int32_t tput_finite;
+    // split kernel: the depth at which phase B ends a path whose hit would bounce (flux_plan.h LaunchPlan::cut_depth, kNoDepthCut for
+    // none): the launch's, set from its plan -- here and not a kernel argument of its own, so that the pass loop reads it where it is
+    // used like every other field and holds no scalar register for it
+    int32_t cut_depth;
 };
 // bytes per hit record of RenderParams::lobe_frame
 constexpr size_t kLobeFrameBytes = 6 * sizeof(double);

@@ -70,6 +70,10 @@ constexpr uint32_t tput_index(uint32_t list_bits, uint32_t ml) { return (1u << l
 // would exceed the cap.  `bits`: the hit queue's bits per list entry the table is laid out for.
 size_t tput_table_bytes(const RenderParams &p, int *bits = nullptr);
 
+// "No depth cut" as the split kernel's cut depth: a depth no live path holds -- above every depth limit, below the 0x7fffffff that
+// marks a lane without a path (render_body.inc kDeadDepth)
+constexpr int kNoDepthCut = 0x7ffffffe;
+
 // The copy of render_body.inc a launch runs (render.hip): the STRICT arithmetic, the FAST one, or the FAST one with the dielectric
 // lobe (RenderParams::has_diel)
 enum KernelCopy { kCopyStrict = 0, kCopyFast = 1, kCopyFastDiel = 2 };
@@ -93,7 +97,10 @@ struct LaunchPlan {
     int max32 = 0;                 // kernel 2: at most 32 spheres, one group of the sphere filter (MAX32)
     int uniform_a = 1;             // kernel 2: phase A shades a wave whose primaries all hit one shape from that shape's record as a scalar
                                    // (render_body.inc shade_primary_hits); FLUX_SPLIT_UNIFORM_A=0: the general step everywhere
+    int cut_depth = kNoDepthCut;   // kernel 2: phase B ends a path whose hit at this depth would bounce (split_cut_depth): max_depth, or kNoDepthCut
 };
+// The split kernel's depth cut for a launch of `p` with plan `L` (its hq_cap and hq_bits): the job's max_depth, or kNoDepthCut
+int split_cut_depth(const RenderParams &p, const LaunchPlan &L);
 LaunchPlan plan_render(const RenderParams &p, int variant, int math);
 // The kernel family a launch runs: the render kernels, or one of the per-pixel passes -- the feature buffers (aov_body.inc
 // aov_kernel), the sample moments (moments_body.inc moments_kernel), one pass of the adaptive sampler over a work list

@@ -79,6 +79,27 @@ size_t tput_table_bytes(const RenderParams &p, int *bits_out) {
     return bytes;
 }
 
+// The depth cut.  A hit at depth max_depth that bounces has a child beyond the limit, which ends with L = 0 (scene.rs:164-165): the
+// path adds 0 * throughput to its lane's sums and counts as depth_exhausted, and its last ray is never traced.  Phase B may end it
+// where it classifies the hit.
+//   The ray queue (no hit queue planned): phase B has run the bounce already, so the zero is folded with the very throughput the later
+//   pass would fold it with -- a NaN product included -- and the bounce's counters are counted.  Admitted for every job; what goes is
+//   the pass the lane would hold the dead path through.
+//   The hit queue: the hit is not parked, so its take and its bounce go too, and the zero is folded with the throughput BEFORE that
+//   bounce.  That is the same sum exactly when both throughputs are finite: +-0 added to a sum that started at +0.0 changes nothing,
+//   0 * inf = NaN does.  So the launch needs the context's word that every such product is finite (RenderParams::tput_finite, judged
+//   on the throughput table where the context builds it); a job that gets no table keeps parking.  The word is about the scene's
+//   weights, not about the device's copy of the table: a context built with FLUX_THROUGHPUT_TABLE=0 multiplies the same products up
+//   in the take and renders the same frame, bit for bit, as one with the table.  The statistics build counts the skipped bounce by the
+//   record's material kind (no Dielectric: such a scene has no hit queue, plan_hitq).
+// FLUX_SPLIT_DEPTH_CUT=0 (tests, A/B runs): no cut in either loop.
+int split_cut_depth(const RenderParams &p, const LaunchPlan &L) {
+    if (const char *e = std::getenv("FLUX_SPLIT_DEPTH_CUT"))
+        if (std::atoi(e) == 0) return kNoDepthCut;
+    if (L.hq_cap == 0) return p.max_depth;
+    return p.tput_finite != 0 ? p.max_depth : kNoDepthCut;
+}
+
 // The waves of a launch in the grouped order (map_wave): 8 XCD slots x (floor(S/8) sets x rows + an eighth of the last S % 8 sets' rows)
 static uint64_t grouped_waves(const RenderParams &p) {
     return 8ull * ((uint64_t)(p.set_count / 8) * (uint64_t)p.num_rows + ((uint64_t)(p.set_count % 8) * (uint64_t)p.num_rows + 7u) / 8u);
@@ -162,6 +183,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
             L.hq_bits = bits;
             L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
         }
+        L.cut_depth = split_cut_depth(p, L);
         return L;
     }
     L.kernel = variant == FLUX_KERNEL_STATIC ? 0 : 1;

@@ -2634,6 +2634,18 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 else
                     scan_shapes_fast<true, true, MAX32, TYP, 0, true, AXIS>(P, p.r, p.self, hit, t, nullptr, fsph_lds, &facing);
                 cont = shade_hit_fast<STATS, false, true, TYP, false, false, true>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds, facing);
+                // The depth cut (launch_plan.cpp split_cut_depth): the child of a bounce at the depth limit ends with L = 0 untraced, so
+                // the path ends here with the zeros above -- nothing parked, no take, no bounce, no pass spent on finding it dead.
+                if (cont && p.depth == P.cut_depth) {
+                    cont = false;
+                    if (STATS) {  // what the skipped bounce and the skipped pass counted
+                        const int kind = recs[hit].mat_kind;
+                        if (kind == kMatMatte) st.c[2]++;
+                        if (kind == kMatGlossy) st.c[3]++;
+                        if (kind == kMatReflective) st.c[4]++;
+                        st.c[7]++;
+                    }
+                }
             }
             if (live && !cont) {
                 if (STATS && !trace) st.c[7]++;
@@ -2828,6 +2840,12 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 else
                     scan_shapes_fast<true, true, MAX32, TYP, 0, false, AXIS>(P, p.r, p.self, hit, t, lap, fsph_lds);
                 cont = shade_hit_fast<STATS, false, true, TYP>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds);
+                // The depth cut (launch_plan.cpp split_cut_depth), as phase A's: a child beyond the depth limit ends here with the zeros
+                // above, folded below with the throughput its bounce left -- the lane is free a pass earlier.
+                if (cont && p.depth > P.cut_depth) {
+                    cont = false;
+                    if (STATS) st.c[7]++;
+                }
             }
             if (live && !cont) {
                 if (STATS && !trace) st.c[7]++;
@@ -3716,6 +3734,7 @@ static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p,
         // (the throughput product table only where it is laid out for this plan's list entries)
         RenderParams ps = p;
         if (!hq || ps.tput_bits != bits) ps.tput = nullptr;
+        ps.cut_depth = L.cut_depth;
 #define FLUX_LAUNCH_SPLIT_AXIS(MAX32, TYP, HQ, AXIS)                                                                  \
     do {                                                                                                             \
         if (stats) render_split_kernel<true, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);  \

@@ -337,6 +337,23 @@ void build_tput_table(const HostScene &h, int bits, int max_depth, std::vector<d
     }
 }
 
+bool tput_products_finite(const HostScene &h, int bits, int max_depth, const std::vector<double> &table) {
+    const size_t entries = (size_t)2 << (bits * (max_depth - 1));
+    if (max_depth < 2 || table.size() != entries * 3) return false;
+    for (const double v : table)
+        if (!std::isfinite(v)) return false;
+    const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(h.fscene.data() + h.fs.rec);
+    const uint32_t n_rec = (uint32_t)hit_records(h.rp);
+    double top[3] = {0.0, 0.0, 0.0}, weight[3] = {0.0, 0.0, 0.0};
+    for (size_t at = entries / 2; at < entries; at++)  // the lists of max_depth - 1 entries (tput_index: the table's upper half)
+        for (int ch = 0; ch < 3; ch++) top[ch] = std::max(top[ch], std::fabs(table[at * 3 + ch]));
+    for (uint32_t e = 0; e < n_rec; e++) {
+        const double f[3] = {rec[e].fr, rec[e].fg, rec[e].fb};
+        for (int ch = 0; ch < 3; ch++) weight[ch] = std::max(weight[ch], std::fabs(f[ch]));
+    }
+    return std::isfinite(top[0] * weight[0]) && std::isfinite(top[1] * weight[1]) && std::isfinite(top[2] * weight[2]);
+}
+
 namespace {
 // The extension's meshes: one triangle record per triangle (hit order: after all shapes), the binary BVH, its quantised nodes and the
 // 4-wide arena

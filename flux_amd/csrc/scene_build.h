@@ -63,6 +63,11 @@ int build_host_scene(const flux_scene_desc &scene, HostScene &out, std::string &
 // ((R[e0].f * R[e1].f) * ...) * R[e(n-1)].f per channel -- plain IEEE products in the order of the split kernel's loop, so bit for
 // bit its result; entries whose list names a record the scene does not have stay zero.
 void build_tput_table(const HostScene &h, int bits, int max_depth, std::vector<double> &out);
+// Whether every throughput a path of this job can hold is finite (RenderParams::tput_finite): every entry of `table` -- the scene's,
+// as build_tput_table made it for `bits` and `max_depth` -- and the product of every longest list's entry with one more record's
+// weight, the throughput of the bounce at the depth limit.  The last is bounded, not enumerated: per channel, the largest magnitude
+// among the longest lists' entries times the largest weight's; a product of smaller magnitudes rounds to no larger a value.
+bool tput_products_finite(const HostScene &h, int bits, int max_depth, const std::vector<double> &table);
 
 // The lobe-frame table (RenderParams::lobe_frame) of the scene: which hit records get an entry -- has_entry[k] = 1 for every record
 // whose shape stores its normal (a plane, a disk, a box face), 0 for a sphere, in scan order as the records -- and the table's size in
