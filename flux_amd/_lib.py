@@ -26,6 +26,12 @@ BVH_INFO_WORDS = 16
 PLAN_WORDS = 8
 PLAN_NONE, PLAN_STATIC, PLAN_REFILL, PLAN_SPLIT, PLAN_BVH_BINARY, PLAN_BVH4 = -1, 0, 1, 2, 3, 4
 ROUTE_NONE, ROUTE_TO_STRICT, ROUTE_KEPT_FAST = 0, 1, 2
+# the plan's word 7, "flags" (include/flux_abi.h FLUX_PLAN_FLAG_*): the instantiation the launch runs
+PLAN_FLAG_TYP, PLAN_FLAG_MAX32, PLAN_FLAG_HITQ, PLAN_FLAG_TPUT_TABLE = 0x1, 0x2, 0x4, 0x8
+PLAN_FLAG_DEPTH_CUT, PLAN_FLAG_UNIFORM_A, PLAN_FLAG_LDS_SCENE, PLAN_FLAG_TRIS = 0x10, 0x20, 0x40, 0x80
+PLAN_FLAG_AXIS_SHIFT, PLAN_FLAG_AXIS_MASK = 8, 0x300        # 0 none, 1 x, 2 y, 3 z
+PLAN_FLAG_HQ_BITS_SHIFT, PLAN_FLAG_HQ_BITS_MASK = 10, 0xfc00
+PLAN_FLAG_COPY_SHIFT, PLAN_FLAG_COPY_MASK = 16, 0x30000   # 0 STRICT, 1 FAST, 2 FAST with the dielectric lobe
 CREATE_TIMING_WORDS = 8
 CREATE_TIMING_NAMES = ("total", "host", "runtime", "alloc", "upload", "tables", "free", "other")
 SHARD_AUTO, SHARD_SETS, SHARD_ROWS = 0, 1, 2

@@ -571,7 +571,7 @@ int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, in
     // why the arithmetic is not the requested one, or why it SHOULD not be: a FAST job on a scene with a non-unit plane normal
     out[6] = (ctx->math == FLUX_MATH_FAST && ctx->rp.glossy_long) ? (strict_fits_lds(ctx) ? FLUX_ROUTE_TO_STRICT : FLUX_ROUTE_KEPT_FAST)
                                                                  : FLUX_ROUTE_NONE;
-    out[7] = 0;
+    out[7] = (int64_t)flux::plan_flags(p, L);
     return FLUX_OK;
 }
 

@@ -102,6 +102,11 @@ struct LaunchPlan {
 // The split kernel's depth cut for a launch of `p` with plan `L` (its hq_cap and hq_bits): the job's max_depth, or kNoDepthCut
 int split_cut_depth(const RenderParams &p, const LaunchPlan &L);
 LaunchPlan plan_render(const RenderParams &p, int variant, int math);
+// The instantiation a render launch of `p` with plan `L` runs, as one word (flux_ctx_launch_plan's word 7: FLUX_PLAN_FLAG_* in
+// include/flux_abi.h): the fields of `L` the launch maps to template arguments, and what it takes from `p` beside them -- the
+// throughput table, where the context holds one laid out for this plan's list entries, and the first plane's axis of a TYP launch
+// (render_body.inc launch_render reads the same two fields).  0 where there is nothing to launch.
+uint32_t plan_flags(const RenderParams &p, const LaunchPlan &L);
 // The kernel family a launch runs: the render kernels, or one of the per-pixel passes -- the feature buffers (aov_body.inc
 // aov_kernel), the sample moments (moments_body.inc moments_kernel), one pass of the adaptive sampler over a work list
 // (adaptive_body.inc adaptive_pass_kernel)

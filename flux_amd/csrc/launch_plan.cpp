@@ -194,6 +194,26 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     return L;
 }
 
+uint32_t plan_flags(const RenderParams &p, const LaunchPlan &L) {
+    if (L.kernel < 0) return 0;
+    const bool split = L.kernel == 2;
+    const bool hq = split && L.hq_cap > 0;
+    uint32_t f = 0;
+    if ((split || L.kernel == 4) && L.typ) f |= FLUX_PLAN_FLAG_TYP;
+    if (split && L.max32) f |= FLUX_PLAN_FLAG_MAX32;
+    if (hq) f |= FLUX_PLAN_FLAG_HITQ;
+    // (the launch drops a table that is not laid out for this plan's list entries: render_body.inc launch_render)
+    if (hq && p.tput != nullptr && p.tput_bits == L.hq_bits) f |= FLUX_PLAN_FLAG_TPUT_TABLE;
+    if (split && L.cut_depth != kNoDepthCut) f |= FLUX_PLAN_FLAG_DEPTH_CUT;
+    if (split && L.uniform_a) f |= FLUX_PLAN_FLAG_UNIFORM_A;
+    if (L.kernel == 4 && L.lds_scene) f |= FLUX_PLAN_FLAG_LDS_SCENE;
+    if ((L.kernel == 0 || L.kernel == 1) && L.tris) f |= FLUX_PLAN_FLAG_TRIS;
+    if (split && L.typ) f |= ((uint32_t)p.plane_axis << FLUX_PLAN_FLAG_AXIS_SHIFT) & FLUX_PLAN_FLAG_AXIS_MASK;
+    if (hq) f |= ((uint32_t)L.hq_bits << FLUX_PLAN_FLAG_HQ_BITS_SHIFT) & FLUX_PLAN_FLAG_HQ_BITS_MASK;
+    f |= ((uint32_t)L.copy << FLUX_PLAN_FLAG_COPY_SHIFT) & FLUX_PLAN_FLAG_COPY_MASK;
+    return f;
+}
+
 // A per-pixel pass (aov_body.inc, moments_body.inc, adaptive_body.inc): `units` pixels or work-list entries in lane_group's layout
 // (render_body.inc) -- 64 / N units per wave below 64 samples, one from there on, in the order given --, or the pixels in map_wave's
 // order (`grouped`); FLUX_BLOCK_THREADS lanes a block, each with the (f, s) stack `stack_math` needs for `depth` levels and the BVH

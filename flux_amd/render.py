@@ -279,13 +279,15 @@ class Renderer:
                  "leaf_records", "fused_leaves", "wide_stack", "wide_node_bytes", "leaf_record_bytes", "wide_in_use")
         return dict(zip(names, [int(x) for x in buf]))
 
-    def launch_plan(self, num_rows=None, num_sets: int = 0) -> dict:
+    def launch_plan(self, num_rows=None, num_sets: int = 0, flags: bool = False) -> dict:
         """What a render call would launch with the current settings (flux_ctx_launch_plan: the library's own launch
         planner): `num_rows` rows of all sets (flux_render_rows*), or `num_sets` of this context's sets over all rows
-        (flux_render_sets_device) when num_sets > 0."""
+        (flux_render_sets_device) when num_sets > 0.  `flags`: the dict also holds "flags", the instantiation of the kernel
+        (_lib.PLAN_FLAG_*, word 7).  On request only: the other words say what is launched and stay equal under the switches that
+        take one choice of the instantiation away (FLUX_PLANE_AXIS=0, FLUX_THROUGHPUT_TABLE=0, ...), which callers compare plans by."""
         buf = (C.c_int64 * _lib.PLAN_WORDS)()
         _lib.check(_lib.lib.flux_ctx_launch_plan(self._handle(), self.height if num_rows is None else num_rows, num_sets, buf))
-        names = ("kernel", "block", "blocks", "lds", "waves_per_pixel", "math", "route")
+        names = ("kernel", "block", "blocks", "lds", "waves_per_pixel", "math", "route") + (("flags",) if flags else ())
         return dict(zip(names, [int(x) for x in buf]))
 
     def table(self, which: int) -> np.ndarray:

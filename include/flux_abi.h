@@ -502,7 +502,23 @@ int flux_ctx_bvh_info(flux_ctx *ctx, uint64_t *out, uint64_t out_words);
  * scene, but max_trace_depth (and the mesh's BVH depth) leave no room for STRICT's LDS recursion stack, so the job stays FAST
  * with the reference's long-form glossy weights -- its pixels can differ from the reference's NaN pixels in the rarest orderings
  * of an overflow and a zero.  The decision depends on the job alone, not on flux_ctx_set_traversal.
- * [7] reserved (0). */
+ * [7] FLUX_PLAN_FLAG_*: the instantiation of that kernel the launch runs (0 for FLUX_PLAN_NONE; the word was reserved, 0, before
+ * the flags were added).  Which bits can be set depends on the kernel; the environment switches that take a choice away
+ * (FLUX_SPLIT_HITQ_CAP, FLUX_THROUGHPUT_TABLE, FLUX_SPLIT_DEPTH_CUT, FLUX_SPLIT_UNIFORM_A, FLUX_PLANE_AXIS) clear its bit. */
+#define FLUX_PLAN_FLAG_TYP 0x1u          /* SPLIT, BVH4: the instantiation for the usual analytic scene (TYP) */
+#define FLUX_PLAN_FLAG_MAX32 0x2u        /* SPLIT: at most 32 spheres, one group of the sphere filter (MAX32) */
+#define FLUX_PLAN_FLAG_HITQ 0x4u         /* SPLIT: the hit queue (clear: the ray queue) */
+#define FLUX_PLAN_FLAG_TPUT_TABLE 0x8u   /* SPLIT with the hit queue: the take reads the context's throughput table (clear: it multiplies the list up) */
+#define FLUX_PLAN_FLAG_DEPTH_CUT 0x10u   /* SPLIT: phase B ends a path whose hit at the depth limit would bounce */
+#define FLUX_PLAN_FLAG_UNIFORM_A 0x20u   /* SPLIT: phase A shades a one-shape wave from scalar registers */
+#define FLUX_PLAN_FLAG_LDS_SCENE 0x40u   /* BVH4: the analytic set's records and the materials in LDS */
+#define FLUX_PLAN_FLAG_TRIS 0x80u        /* STATIC, REFILL: the instantiation with the mesh */
+#define FLUX_PLAN_FLAG_AXIS_SHIFT 8      /* bits 8-9, SPLIT with TYP: the first plane's axis the launch instantiates, 0 none, 1 x, 2 y, 3 z */
+#define FLUX_PLAN_FLAG_AXIS_MASK 0x300u
+#define FLUX_PLAN_FLAG_HQ_BITS_SHIFT 10  /* bits 10-15, SPLIT with the hit queue: bits per entry of a parked hit's bounce list */
+#define FLUX_PLAN_FLAG_HQ_BITS_MASK 0xfc00u
+#define FLUX_PLAN_FLAG_COPY_SHIFT 16     /* bits 16-17, every kernel: the copy of the kernels, 0 STRICT, 1 FAST, 2 FAST with the dielectric lobe */
+#define FLUX_PLAN_FLAG_COPY_MASK 0x30000u
 #define FLUX_ROUTE_NONE 0
 #define FLUX_ROUTE_TO_STRICT 1
 #define FLUX_ROUTE_KEPT_FAST 2

@@ -6,6 +6,8 @@
 // scenes cover each branch of the derived flags.  It also writes <out dir>/plans.txt: the launch planner's answer (flux_plan.h
 // plan_render: kernel, instantiation, block, grid, LDS) for every scene over a grid of jobs, one line each, which the test pins too,
 // and <out dir>/pass_plans.txt: the same for the per-pixel passes (feature buffers, sample moments, an adaptive pass).
+// The instantiation word of flux_ctx_launch_plan (flux_plan.h plan_flags) is pinned for the headline job -- demo2, 800 x 600,
+// sample root 128, depth 5 -- and for box_room at depths 5 and 3.
 // Prints one "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
 #include <cstdio>
@@ -168,6 +170,32 @@ static void pass_plans(const std::string &name, const flux::HostScene &h) {
                 }
 }
 
+// The plan's flags word (flux_plan.h plan_flags) of a full-frame FAST render of the scene at sample root 128 with the default kernel,
+// as a context of that job would report it: the throughput table and the word on its products as abi.hip's upload decides them.
+static int job_flags(const char *scenes, const char *name, int depth, uint32_t &flags) {
+    static const flux::DevScanSphere32 fsph32_placeholder{};
+    static const double tput_placeholder = 0.0;
+    const AbiScene abi(scene_from_yaml_file(std::string(scenes) + "/" + name + ".yml"));
+    flux::HostScene h;
+    CHECK(build(abi.desc, h) == FLUX_OK);
+    flux::RenderParams p = h.rp;
+    p.max_depth = depth;
+    p.nsamp = 128u * 128u;
+    p.fsph32 = h.filter32 ? &fsph32_placeholder : nullptr;
+    p.num_rows = p.img_h;
+    int bits = 0;
+    if (flux::tput_table_bytes(p, &bits)) {
+        std::vector<double> table;
+        flux::build_tput_table(h, bits, depth, table);
+        p.tput_finite = flux::tput_products_finite(h, bits, depth, table) ? 1 : 0;
+        p.tput = &tput_placeholder;
+        p.tput_bits = bits;
+    }
+    flags = flux::plan_flags(p, flux::plan_render(p, FLUX_KERNEL_DEFAULT, FLUX_MATH_FAST));
+    std::printf("flags %s depth %d 0x%x\n", name, depth, flags);
+    return 0;
+}
+
 static int dump(const std::string &name, const flux_scene_desc &desc) {
     flux::HostScene h;
     CHECK(build(desc, h) == FLUX_OK);
@@ -323,6 +351,21 @@ int main(int argc, char **argv) {
     CHECK(write_file("plans.txt", g_plans.data(), g_plans.size()));
     CHECK(write_file("pass_plans.txt", g_pass_plans.data(), g_pass_plans.size()));
     std::printf("ok plans\n");
+    {
+        const uint32_t fast = 1u << FLUX_PLAN_FLAG_COPY_SHIFT;
+        const uint32_t hitq = FLUX_PLAN_FLAG_HITQ | FLUX_PLAN_FLAG_UNIFORM_A | FLUX_PLAN_FLAG_MAX32 | fast;
+        const uint32_t table_cut = FLUX_PLAN_FLAG_TPUT_TABLE | FLUX_PLAN_FLAG_DEPTH_CUT;
+        uint32_t f = 0;
+        // the headline: TYP with MAX32, the hit queue with 4 bits an entry, the table, the cut, the uniform phase-A step, the floor's axis y
+        if (job_flags(argv[1], "demo2", 5, f)) return 1;
+        CHECK(f == (FLUX_PLAN_FLAG_TYP | hitq | table_cut | 2u << FLUX_PLAN_FLAG_AXIS_SHIFT | 4u << FLUX_PLAN_FLAG_HQ_BITS_SHIFT));
+        // box_room's 17 records, 5 bits an entry: at depth 5 no table (48 MiB) and so no cut, at depth 3 both; boxes: never TYP
+        if (job_flags(argv[1], "box_room", 5, f)) return 1;
+        CHECK(f == (hitq | 5u << FLUX_PLAN_FLAG_HQ_BITS_SHIFT));
+        if (job_flags(argv[1], "box_room", 3, f)) return 1;
+        CHECK(f == (hitq | table_cut | 5u << FLUX_PLAN_FLAG_HQ_BITS_SHIFT));
+        std::printf("ok flags\n");
+    }
     std::printf("all ok\n");
     return 0;
 }

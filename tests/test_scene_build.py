@@ -2,7 +2,8 @@
 records, the FAST scene image, the mesh's triangles and trees and the scene-derived RenderParams of four shipped scenes and a
 height field, and this test pins the SHA-256 of every buffer.  The digests are the bytes the kernels read: a change to any of
 them changes what a context uploads.  The same program asks the launch planner (flux_amd/csrc/launch_plan.cpp) which kernel
-instantiation, block, grid and LDS each of those scenes gets over a grid of jobs; the table is pinned too."""
+instantiation, block, grid and LDS each of those scenes gets over a grid of jobs; the table is pinned too, and so is the
+instantiation word of the headline job (demo2, 800 x 600, 16384 spp, depth 5) and of box_room at depths 5 and 3 ("ok flags")."""
 import hashlib
 import os
 import subprocess
@@ -114,7 +115,7 @@ def default_run(selftest, default_out):
 def test_selftest_checks(default_run):
     stdout, _ = default_run
     for name in ("unit normal", "non-unit plane normal", "sphere beyond 1e3", "one emissive invert sphere", "two invert spheres",
-                 "group walk", "no f32 filter", "plans") + tuple(f"dump {s}" for s in SCENE_NAMES):
+                 "group walk", "no f32 filter", "plans", "flags") + tuple(f"dump {s}" for s in SCENE_NAMES):
         assert f"ok {name}" in stdout
     assert "all ok" in stdout
 
