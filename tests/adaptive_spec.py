@@ -202,9 +202,19 @@ SPECIAL = {
     "single-3x2": ("open", 2, dict(threshold=0.5, max_passes=3, dilate=0), (3, 2)),
     "round1-2": ("open", 2, dict(threshold=1.2, max_passes=6, dilate=1), (ms.W, ms.H)),
 }
+# ... and three frames of more than one selection block (adaptive.hip kSelectBlock = 1024 pixels), scene `open` at other sizes.  At 192
+# pixels adaptive_select_kernel is one block of three waves and adaptive_count_kernel never strides; here a block's base comes from
+# another block's atomic add, an empty block sits beside a non-empty one, and the 130 x 127 frame is more than the 64 x 256 pixels
+# the count kernel covers without striding.  tests/test_adaptive.py asserts what each reaches from the reference alone.
+BLOCK_CASES = {
+    "blocks-41x27-2": ("open", 2, dict(threshold=0.2, max_passes=6, dilate=1), (41, 27)),
+    "blocks-67x47-3": ("open", 3, dict(threshold=0.15, max_passes=4, dilate=2), (67, 47)),
+    "blocks-130x127-2": ("open", 2, dict(threshold=0.2, max_passes=3, dilate=1), (130, 127)),
+}
 DEPTH, SEED = ms.DEPTH, ms.SEED
 _traced = {}
 _runs = {}
+_row_runs = {}
 
 
 @atexit.register
@@ -228,7 +238,7 @@ def traced(flux, scene_name, root, w=ms.W, h=ms.H):
 def case(flux, name):
     """(scene, parameters with the defaults filled in, Result) of a case, computed once and shared, read-only."""
     if name not in _runs:
-        scene_name, root, par, size = CASES[name] + ((ms.W, ms.H),) if name in CASES else SPECIAL[name]
+        scene_name, root, par, size = CASES[name] + ((ms.W, ms.H),) if name in CASES else SPECIAL.get(name) or BLOCK_CASES[name]
         par = dict(DEFAULTS, **par)
         tp = traced(flux, scene_name, root, *size)
         res = tp.run(**par)
@@ -247,3 +257,47 @@ def counts(res, par):
             only_dilated += int(np.count_nonzero(res.active[r] & ~hot))
     return (int(np.count_nonzero(res.passes < par["max_passes"])), int(np.count_nonzero(res.passes == par["max_passes"])),
             only_dilated, len(np.unique(res.passes)))
+
+
+def rows_case(flux, name, rows, **over):
+    """(scene, parameters, Result) of a case's rule run over the global `rows` alone -- the neighbourhood is the call's --, the
+    parameters of the case with `over` on top; computed once and shared, read-only."""
+    key = (name, tuple(int(r) for r in rows), tuple(sorted(over.items())))
+    if key not in _row_runs:
+        sd, par, _ = case(flux, name)
+        scene_name, root, _, size = BLOCK_CASES[name]
+        par = dict(par, **over)
+        res = traced(flux, scene_name, root, *size).run(rows=np.asarray(rows), **par)
+        res.moments.setflags(write=False)
+        res.passes.setflags(write=False)
+        _row_runs[key] = (sd, par, res)
+    return _row_runs[key]
+
+
+def block_counts(res, block):
+    """Per round, the active pixels in each run of `block` consecutive pixels of the call (row-major: the selection's blocks)."""
+    return [[int(a.ravel()[b:b + block].sum()) for b in range(0, a.size, block)] for a in res.active]
+
+
+def block_waves(res, block, wave=64):
+    """Per round and block, the number of the block's `wave`-pixel runs that hold an active pixel."""
+    return [[sum(bool(a.ravel()[w:min(w + wave, b + block)].any()) for w in range(b, min(b + block, a.size), wave))
+             for b in range(0, a.size, block)] for a in res.active]
+
+
+def assert_close_where_finite(got, got_passes, want, label, N):
+    """assert_close for a reference that may hold non-finite values (moments_spec.assert_close_where_finite): the pass map equal,
+    the same finite mask per channel, the bounds wherever the reference is finite."""
+    assert got.shape == want.moments.shape and got_passes.shape == want.passes.shape
+    differ = int(np.count_nonzero(got_passes != want.passes))
+    print(f"adaptive {label}: pass maps differ in {differ} pixels")
+    assert differ == 0, label
+    with np.errstate(all="ignore"):
+        err = ms.group_errors(got, want.moments, ms.lum(want.moments[..., ms.MEAN]) ** 2, N * want.passes.astype(np.float64),
+                              ms.max_to_one_factor(want.moments))
+    odd = int(np.count_nonzero(~np.isfinite(want.moments)))
+    print(f"adaptive {label}: max error rgb {err['rgb']:.2e} mean {err['mean']:.2e} (absolute), var {err['var']:.2e} s2 {err['s2']:.2e} "
+          f"(relative to ref + scale) where the reference is finite; {odd} non-finite values in it")
+    for ch in range(ms.CHANNELS):
+        assert np.array_equal(np.isfinite(got[..., ch]), np.isfinite(want.moments[..., ch])), (label, "finite mask of channel", ch)
+    assert all(e <= ms.TOL for e in err.values()), (label, err)

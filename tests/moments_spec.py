@@ -132,3 +132,38 @@ def assert_close(got, want, rad, label):
           f"(relative to ref + scale)")
     assert np.isfinite(got).all(), label
     assert all(e <= TOL for e in err.values()), (label, err)
+
+
+def group_errors(got, want, m2, n, k):
+    """errors()' four figures over the entries where `want` is finite, for references that hold a NaN or an inf (a scene whose
+    normals are not unit vectors).  m2: the squared mean luminance [H, W]; n: the sample count, a number or [H, W]; k: max_to_one's
+    factor [H, W].  Where the reference is finite and ref + scale is not a positive number, only an equal value is no error."""
+    finite = np.isfinite(want)
+    with np.errstate(all="ignore"):
+        diff = np.where(finite, np.abs(np.asarray(got) - want), 0.0)
+
+        def rel(ch, scale):
+            den = want[..., ch] + scale
+            e = np.where(den > 0.0, diff[..., ch] / den, np.where(diff[..., ch] == 0.0, 0.0, np.inf))
+            return float(np.where(finite[..., ch], e, 0.0).max())
+        return {"rgb": float(diff[..., RGB].max()), "mean": float(diff[..., MEAN].max()), "var": rel(VAR, m2 * k * k / n), "s2": rel(S2, m2)}
+
+
+def max_to_one_factor(want):
+    with np.errstate(all="ignore"):
+        mx = want[..., MEAN].max(axis=2)
+        return np.where(mx > 1.0, 1.0 / np.maximum(mx, 1.0), 1.0)
+
+
+def assert_close_where_finite(got, want, rad, label):
+    """assert_close for a reference that may hold non-finite values: the SAME finite mask in each of the eight channels, and
+    assert_close's bounds wherever the reference is finite; prints the figures first.  On a finite reference it is assert_close."""
+    assert got.shape == want.shape
+    with np.errstate(all="ignore"):
+        err = group_errors(got, want, mean_lum(rad) ** 2, float(rad.shape[2]), max_to_one_factor(want))
+    odd = int(np.count_nonzero(~np.isfinite(want)))
+    print(f"moments {label}: max error rgb {err['rgb']:.2e} mean {err['mean']:.2e} (absolute), var {err['var']:.2e} s2 {err['s2']:.2e} "
+          f"(relative to ref + scale) where the reference is finite; {odd} non-finite values in it")
+    for ch in range(CHANNELS):
+        assert np.array_equal(np.isfinite(got[..., ch]), np.isfinite(want[..., ch])), (label, "finite mask of channel", ch)
+    assert all(e <= TOL for e in err.values()), (label, err)

@@ -194,6 +194,114 @@ def test_row_tiles_equal_the_frame_without_dilation(flux):
     assert tiled.shape == whole.passes.shape
 
 
+# ---- the cases beyond one selection block ---------------------------------------------------------------------------------------------
+
+SELECT_BLOCK = 1024            # flux_amd/csrc/adaptive.hip kSelectBlock: the pixels adaptive_select_kernel compacts per block
+COUNT_BLOCK, COUNT_BLOCKS = 256, 64   # ... kBlock and launch_adaptive_count's largest grid: beyond their product the count kernel strides
+# name -> (rounds, active pixels per selection block and round (None: too many to list), pass histogram (None: not pinned)), measured
+# on the reference alone
+BLOCK_FIGURES = {
+    "blocks-41x27-2": (6, [[1024, 83], [411, 38], [302, 24], [305, 0], [307, 0], [304, 0]], {1: 618, 2: 146, 3: 35, 4: 18, 5: 29, 6: 261}),
+    "blocks-67x47-3": (4, [[1024, 1024, 1024, 77], [450, 500, 475, 25], [403, 452, 366, 21], [403, 463, 376, 21]], None),
+    "blocks-130x127-2": (3, None, {1: 11097, 2: 1187, 3: 4226}),
+}
+STRIDED_ROWS = np.arange(1, 47, 2)    # of blocks-67x47-3: tests/test_gpu_adaptive.py's strided device call
+TILE_ROWS = 10                        # ... and its row tiles, with dilate 1
+
+
+def test_the_block_constants_are_the_kernels():
+    src = open(os.path.join(ROOT, "flux_amd", "csrc", "adaptive.hip")).read()
+    assert f"constexpr unsigned kSelectBlock = {SELECT_BLOCK}," in src and f"constexpr unsigned kBlock = {COUNT_BLOCK};" in src
+    assert f"blocks < {COUNT_BLOCKS} ? blocks : {COUNT_BLOCKS}" in src
+
+
+@pytest.mark.parametrize("name", list(asp.BLOCK_CASES))
+def test_block_case_conditions(flux, name):
+    """test_gpu_case_conditions' margins for the frames of more than one selection block, and what each frame is there to reach."""
+    _, par, res = asp.case(flux, name)
+    w, h = asp.BLOCK_CASES[name][3]
+    rounds, per_block, hist = BLOCK_FIGURES[name]
+    blocks, waves = asp.block_counts(res, SELECT_BLOCK), asp.block_waves(res, SELECT_BLOCK)
+    got_hist = {int(c): int(k) for c, k in zip(*np.unique(res.passes, return_counts=True))}
+    print(f"adaptive case {name}: {w * h} pixels, rounds {len(res.active)}, pass histogram {got_hist}, decision margin "
+          f"{res.decision_margin:.2e}, path margin {res.path_margin:.2e}; active pixels per block and round "
+          f"{blocks if len(blocks[0]) <= 4 else [sum(b) for b in blocks]}")
+    assert res.decision_margin >= 1e-9
+    assert res.path_margin >= ms.MIN_MARGIN
+    assert res.passes.shape == (h, w) and len(res.active) == rounds
+    assert len(blocks[0]) == -(-w * h // SELECT_BLOCK) > 1
+    if per_block is not None:
+        assert blocks == per_block
+    if hist is not None:
+        assert got_hist == hist
+    assert any(16 in wv for wv in waves[1:])   # a selection (rounds >= 1) with a block whose 16 waves all hold an active pixel
+    assert np.isfinite(res.moments).all()
+    assert w % 16 and w % 7                    # no width is a multiple of the pixels a wave holds (16 at root 2, 7 at root 3)
+    if name == "blocks-41x27-2":
+        assert all(wv[0] == 16 for wv in waves)   # ... here the first block, in every round
+    if name == "blocks-130x127-2":
+        assert w * h > COUNT_BLOCKS * COUNT_BLOCK and len(blocks[0]) == 17
+
+
+def test_some_round_has_an_empty_selection_block_beside_a_non_empty_one(flux):
+    found = [(name, r) for name in asp.BLOCK_CASES for r, b in enumerate(asp.block_counts(asp.case(flux, name)[2], SELECT_BLOCK))
+             if r >= 1 and 0 in b and any(b)]
+    assert ("blocks-41x27-2", 3) in found and ("blocks-41x27-2", 5) in found, found
+
+
+def test_strided_rows_and_row_tiles_have_a_neighbourhood_of_their_own(flux):
+    """What the GPU suite's strided and tiled calls with dilation rest on: the rule over rows 1, 3, ... 45 of the 67 x 47 frame
+    (dilate 2) and over its tiles of 10 rows (dilate 1) keeps the margins, fills two selection blocks, and gives ANOTHER pass map
+    than the frame's run does on those rows -- a kernel that dilates in global rows cannot pass both."""
+    _, par, whole = asp.case(flux, "blocks-67x47-3")
+    _, _, sub = asp.rows_case(flux, "blocks-67x47-3", STRIDED_ROWS)
+    differ = int(np.count_nonzero(sub.passes != whole.passes[STRIDED_ROWS]))
+    blocks = asp.block_counts(sub, SELECT_BLOCK)
+    print(f"adaptive strided rows of blocks-67x47-3: {sub.passes.size} pixels, active per block and round {blocks}, pass map differs from "
+          f"the frame's rows in {differ} pixels; decision margin {sub.decision_margin:.2e}, path margin {sub.path_margin:.2e}")
+    assert sub.passes.size == 1541 and blocks == [[1024, 517], [470, 244], [415, 176], [422, 184]]
+    assert differ == 200
+    assert sub.decision_margin >= 1e-9 and sub.path_margin >= ms.MIN_MARGIN
+    _, par1, whole1 = asp.rows_case(flux, "blocks-67x47-3", np.arange(47), dilate=1)
+    assert par1["dilate"] == 1 and whole1.decision_margin >= 1e-9
+    tiles = [asp.rows_case(flux, "blocks-67x47-3", np.arange(a, min(a + TILE_ROWS, 47)), dilate=1)[2] for a in range(0, 47, TILE_ROWS)]
+    for t in tiles:
+        assert t.decision_margin >= 1e-9 and t.path_margin >= ms.MIN_MARGIN
+    tiled = np.concatenate([t.passes for t in tiles])
+    differ1 = int(np.count_nonzero(tiled != whole1.passes))
+    print(f"adaptive tiles of {TILE_ROWS} rows of blocks-67x47-3, dilate 1: pass map differs from the frame's in {differ1} pixels")
+    assert tiled.shape == whole1.passes.shape and differ1 > 0
+    assert [t.passes.shape[0] for t in tiles] == [10, 10, 10, 10, 7]
+
+
+def test_the_comparison_for_non_finite_references(flux):
+    """moments_spec.assert_close_where_finite and adaptive_spec's: assert_close on a finite reference; with a NaN and an inf in the
+    reference they demand them in the same places, and the bounds elsewhere."""
+    _, want, rad, _, _ = ms.reference(flux, "open", 2)
+    got = want.copy()
+    got[..., ms.S2] *= 1.0 + 4e-10
+    assert ms.group_errors(got, want, ms.mean_lum(rad) ** 2, 4.0, ms.max_to_one_factor(want)) == ms.errors(got, want, rad)
+    ms.assert_close_where_finite(got, want, rad, "finite")
+    poisoned = want.copy()
+    poisoned[2, 3, :], poisoned[5, 6, 4], poisoned[5, 6, 0] = np.nan, np.inf, np.nan
+    got = poisoned.copy()
+    got[5, 6, 4] = np.nan     # (another non-finite value in the same place: the mask is what is compared)
+    ms.assert_close_where_finite(got, poisoned, rad, "poisoned")
+    for y, x, ch, v in ((2, 3, 1, 0.5), (0, 0, 7, np.nan), (5, 6, 0, 0.0), (1, 1, 5, want[1, 1, 5] + 1e-8), (4, 4, 7, want[4, 4, 7] * 1.001 + 1e-8)):
+        bad = poisoned.copy()
+        bad[y, x, ch] = v
+        with pytest.raises(AssertionError):
+            ms.assert_close_where_finite(bad, poisoned, rad, "bad")
+    _, par, res = asp.case(flux, "open-2")
+    asp.assert_close_where_finite(res.moments, res.passes, res, "finite", 4)
+    bad = res.moments.copy()
+    bad[3, 3, 7] = bad[3, 3, 7] * 1.001 + 1e-8
+    with pytest.raises(AssertionError):
+        asp.assert_close_where_finite(bad, res.passes, res, "bad", 4)
+    with pytest.raises(AssertionError):
+        asp.assert_close_where_finite(res.moments, res.passes + np.uint32(1), res, "bad", 4)
+
+
 # ---- the quality table of DESIGN.md section 5h ----------------------------------------------------------------------------------------
 
 # scene -> the bound asserted on relMSE(adaptive) / relMSE(uniform), the measured ratio plus 10 %; None: adaptive is NOT better there

@@ -2,8 +2,9 @@
 in numpy (tests/adaptive_spec.py over tests/path_spec.py): parity in both arithmetics and all three kernel copies, meshes in the three
 traversals, the calls, the state, the refusals, the absence of side effects, the denoiser behind it and the command-line tool.
 
-All scenes are 16 x 12 at seed 7, depth 5, so S = 16; tests/test_adaptive.py asserts on the CPU that no hot decision and no path
-decision of a case sits at rounding level, so the pass map must be EQUAL.  Tolerance on the eight channels: moments_spec's -- 1e-9
+The scenes are 16 x 12 at seed 7, depth 5, so S = 16, but for section 2b's frames of 41 x 27, 67 x 47 and 130 x 127 pixels, which fill
+more than one selection block; tests/test_adaptive.py asserts on the CPU that no hot decision and no path decision of a case sits
+at rounding level, so the pass map must be EQUAL.  The generated scenes: tests/test_gpu_pass_fuzz.py.  Tolerance on the eight channels: moments_spec's -- 1e-9
 absolute on channels 0-2 and 4-6, 1e-9 (ref + scale) on channels 3 and 7 with scale = m² for s2 and m² k² / n for var, n = N c."""
 import os
 
@@ -212,6 +213,87 @@ def test_no_side_effects(flux, demo2):
         assert np.array_equal(r.render_moments(), mom) and np.array_equal(r.render_aov(), aov)
         again = r.render_adaptive(threshold=0.05, max_passes=4)
         assert np.array_equal(again[0], got[0]) and np.array_equal(again[1], got[1])
+
+
+# ---- 2b. more than one selection block ------------------------------------------------------------------------------------------------
+# adaptive_spec.BLOCK_CASES: scene `open` at 41 x 27, 67 x 47 and 130 x 127.  tests/test_adaptive.py asserts their margins and, from the
+# reference alone, what each reaches in adaptive.hip: block bases that come from another block's atomic add, an empty selection block
+# beside a non-empty one, blocks whose sixteen waves all hold an active pixel, a count kernel that strides.
+
+@pytest.mark.parametrize("math", MATHS)
+@pytest.mark.parametrize("name", list(asp.BLOCK_CASES))
+def test_parity_with_the_spec_beyond_one_selection_block(flux, name, math):
+    sd, par, want = asp.case(flux, name)
+    root = asp.BLOCK_CASES[name][1]
+    got, passes, info = gpu_adaptive(flux, sd, root, par, math)
+    asp.assert_close(got, passes, want, f"{name} {math}", root * root)
+    assert info["rounds"] == len(want.active) and info["pixel_passes"] == int(want.passes.sum()) == int(passes.sum())
+    assert info["pixels_at_max_passes"] == int(np.count_nonzero(want.passes == par["max_passes"]))
+    assert info["samples"] == root * root * int(passes.sum())
+    assert np.all(got[..., ms.S2] >= 0.0) and np.all(got[..., ms.VAR] >= 0.0)
+    if name == "blocks-130x127-2":   # the count kernel's verdict on the map it was given, the spec aside
+        assert passes.size > 64 * 256
+        assert info["pixels_at_max_passes"] == int(np.count_nonzero(passes == par["max_passes"]))
+        assert info["pixel_passes"] == int(passes.astype(np.int64).sum())
+
+
+def test_strided_rows_with_dilation_against_the_spec(flux):
+    """Rows 1, 3, ... 45 of the 67 x 47 frame with dilate 2 through the device entry on a non-default stream: 1541 pixels in two
+    selection blocks, the neighbourhood in the call's LOCAL row index.  tests/test_adaptive.py asserts that the frame's own run gives
+    another pass map on these rows."""
+    import torch
+    name = "blocks-67x47-3"
+    w, h = asp.BLOCK_CASES[name][3]
+    rows = np.arange(1, h, 2)
+    sd, par, want = asp.rows_case(flux, name, rows)
+    assert par["dilate"] == 2 and len(rows) == 23
+    k, guard = len(rows) * w, 64
+    with renderer(flux, sd, 3) as r:
+        stream = torch.cuda.Stream(device="cuda:0")
+        dmom = torch.full((k * 8 + guard,), -7.0, dtype=torch.float64, device="cuda:0")
+        dmap = torch.full((k + guard,), 0x5a5a5a5a, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        r.render_adaptive_device(1, 2, len(rows), dmom.data_ptr(), dmap.data_ptr(), stream=stream.cuda_stream, **par)
+        stream.synchronize()
+        info = dict(r.last_adaptive_info)
+        hm, hp = dmom.cpu().numpy(), dmap.cpu().numpy()
+    assert np.all(hm[k * 8:] == -7.0) and np.all(hp[k:] == 0x5a5a5a5a)
+    passes = hp[:k].reshape(len(rows), w).view(np.uint32)
+    asp.assert_close(hm[:k * 8].reshape(len(rows), w, 8), passes, want, f"{name} rows 1, 3, ... 45", 9)
+    assert info == {"rounds": len(want.active), "pixel_passes": int(want.passes.sum()), "samples": 9 * int(want.passes.sum()),
+                    "pixels_at_max_passes": int(np.count_nonzero(want.passes == par["max_passes"]))}
+
+
+def test_row_tiles_with_dilation_against_the_spec(flux):
+    """Tiles of 10 rows of the 67 x 47 frame with dilate 1, each against the rule run over that tile's rows alone."""
+    name = "blocks-67x47-3"
+    w, h = asp.BLOCK_CASES[name][3]
+    sd = asp.case(flux, name)[0]
+    with renderer(flux, sd, 3) as r:
+        for a in range(0, h, 10):
+            rows = np.arange(a, min(a + 10, h))
+            _, par, want = asp.rows_case(flux, name, rows, dilate=1)
+            got, passes = r.render_adaptive(row_start=int(rows[0]), row_end=int(rows[-1]), **par)
+            asp.assert_close(got, passes, want, f"{name} rows {rows[0]}..{rows[-1]} dilate 1", 9)
+            assert r.last_adaptive_info["rounds"] == len(want.active) and r.last_adaptive_info["pixel_passes"] == int(want.passes.sum())
+
+
+def test_one_context_through_calls_of_growing_and_shrinking_size(flux):
+    """One row, the frame, five rows, the frame: d_adapt_pixels and d_adapt_out_pixels grow once, and the later calls find a list
+    buffer that holds a longer, older list.  Each result is what a fresh context returns for the same call, bit for bit."""
+    name = "blocks-41x27-2"
+    sd, par, want = asp.case(flux, name)
+    w, h = asp.BLOCK_CASES[name][3]
+    calls = [(3, 3), (0, h - 1), (0, 4), (0, h - 1)]
+    with renderer(flux, sd, 2) as r:
+        got = [r.render_adaptive(row_start=a, row_end=b, **par) + (dict(r.last_adaptive_info),) for a, b in calls]
+    for (a, b), (mom, passes, info) in zip(calls, got):
+        with renderer(flux, sd, 2) as fresh:
+            fmom, fpasses = fresh.render_adaptive(row_start=a, row_end=b, **par)
+            assert mom.shape == (b - a + 1, w, 8) and fmom.tobytes() == mom.tobytes() and np.array_equal(fpasses, passes), (a, b)
+            assert fresh.last_adaptive_info == info, (a, b)
+    for k in (1, 3):
+        asp.assert_close(got[k][0], got[k][1], want, f"{name} call {k + 1} of one context", 4)
 
 
 # ---- 3. end to end --------------------------------------------------------------------------------------------------------------
