@@ -461,19 +461,31 @@ def _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a):
     return (C.c_double * _lib.DENOISE_PARAM_WORDS)(levels, sigma_l, sigma_n, sigma_z, sigma_a, 0.0, 0.0, 0.0)
 
 
+def _denoise_host(name, what, channels, x, aov, device, params):
+    """denoise and denoise_moments as `name`: flux_<name> over the input `x` [H, W, channels], which the error text calls `what`."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    aov = np.ascontiguousarray(aov, dtype=np.float64)
+    if x.ndim != 3 or x.shape[2] != channels or aov.shape != x.shape[:2] + (_lib.AOV_CHANNELS,):
+        raise _lib.FluxError(_lib.E_INVALID, f"{name}: {what} {x.shape} and aov {aov.shape} are not "
+                                             f"[H, W, {channels}] and [H, W, {_lib.AOV_CHANNELS}]")
+    out = np.empty(x.shape[:2] + (3,), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    _lib.check(getattr(_lib.lib, "flux_" + name)(int(device), x.shape[1], x.shape[0], x.ctypes.data_as(dp), aov.ctypes.data_as(dp), params,
+                                                 out.ctypes.data_as(dp)))
+    return out
+
+
+def _denoise_device(name, width, height, d_in_ptr, d_aov_ptr, d_out_ptr, d_work_ptr, work_doubles, stream, device, params):
+    """denoise_device and denoise_moments_device as `name`: flux_<name> on device addresses."""
+    _lib.check(getattr(_lib.lib, "flux_" + name)(int(device), width, height, C.c_void_p(d_in_ptr), C.c_void_p(d_aov_ptr), params,
+                                                 C.c_void_p(d_out_ptr), C.c_void_p(d_work_ptr), work_doubles, C.c_void_p(stream)))
+
+
 def denoise(rgb, aov, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1) -> np.ndarray:
     """The feature-guided a-trous filter of flux_denoise (include/flux_abi.h) over a frame `rgb` [H, W, 3] of
     render_frame() and its feature buffers `aov` [H, W, 8] of render_aov(): the filtered frame, on `device`.  Meant for noisy
     previews (1-16 spp); a frame that is already clean can come out worse."""
-    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
-    aov = np.ascontiguousarray(aov, dtype=np.float64)
-    if rgb.ndim != 3 or rgb.shape[2] != 3 or aov.shape != rgb.shape[:2] + (_lib.AOV_CHANNELS,):
-        raise _lib.FluxError(_lib.E_INVALID, f"denoise: rgb {rgb.shape} and aov {aov.shape} are not [H, W, 3] and [H, W, {_lib.AOV_CHANNELS}]")
-    out = np.empty_like(rgb)
-    dp = C.POINTER(C.c_double)
-    _lib.check(_lib.lib.flux_denoise(int(device), rgb.shape[1], rgb.shape[0], rgb.ctypes.data_as(dp), aov.ctypes.data_as(dp),
-                                     _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a), out.ctypes.data_as(dp)))
-    return out
+    return _denoise_host("denoise", "rgb", 3, rgb, aov, device, _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a))
 
 
 def denoise_work_doubles(width: int, height: int) -> int:
@@ -485,26 +497,16 @@ def denoise_device(width: int, height: int, d_rgb_ptr: int, d_aov_ptr: int, d_ou
                    stream: int = 0, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1):
     """Asynchronous device-resident filter (see flux_denoise_device): device addresses of the frame, the feature buffers, the
     output frame and `work_doubles` >= denoise_work_doubles(width, height) doubles of scratch; `stream` a hipStream_t."""
-    _lib.check(_lib.lib.flux_denoise_device(int(device), width, height, C.c_void_p(d_rgb_ptr), C.c_void_p(d_aov_ptr),
-                                            _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a), C.c_void_p(d_out_ptr),
-                                            C.c_void_p(d_work_ptr), work_doubles, C.c_void_p(stream)))
+    _denoise_device("denoise_device", width, height, d_rgb_ptr, d_aov_ptr, d_out_ptr, d_work_ptr, work_doubles, stream, device,
+                    _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a))
 
 
 def denoise_moments(moments, aov, device: int = 0, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1) -> np.ndarray:
     """flux_denoise_moments (include/flux_abi.h): the a-trous filter of `denoise` guided by the measured
     variance -- `moments` [H, W, 8] of render_moments(), whose channels 0..2 are the frame and channel 3 its variance, and `aov`
     [H, W, 8] of render_aov(): the filtered frame [H, W, 3], on `device`."""
-    moments = np.ascontiguousarray(moments, dtype=np.float64)
-    aov = np.ascontiguousarray(aov, dtype=np.float64)
-    if moments.ndim != 3 or moments.shape[2] != _lib.MOMENT_CHANNELS or aov.shape != moments.shape[:2] + (_lib.AOV_CHANNELS,):
-        raise _lib.FluxError(_lib.E_INVALID, f"denoise_moments: moments {moments.shape} and aov {aov.shape} are not "
-                                             f"[H, W, {_lib.MOMENT_CHANNELS}] and [H, W, {_lib.AOV_CHANNELS}]")
-    out = np.empty(moments.shape[:2] + (3,), dtype=np.float64)
-    dp = C.POINTER(C.c_double)
-    _lib.check(_lib.lib.flux_denoise_moments(int(device), moments.shape[1], moments.shape[0], moments.ctypes.data_as(dp),
-                                             aov.ctypes.data_as(dp), _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a),
-                                             out.ctypes.data_as(dp)))
-    return out
+    return _denoise_host("denoise_moments", "moments", _lib.MOMENT_CHANNELS, moments, aov, device,
+                         _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a))
 
 
 def denoise_moments_device(width: int, height: int, d_moments_ptr: int, d_aov_ptr: int, d_out_ptr: int, d_work_ptr: int,
@@ -512,9 +514,8 @@ def denoise_moments_device(width: int, height: int, d_moments_ptr: int, d_aov_pt
                            sigma_a=0.1):
     """Asynchronous device-resident filter (see flux_denoise_moments_device): device addresses of the moments, the feature buffers,
     the output frame and `work_doubles` >= denoise_work_doubles(width, height) doubles of scratch; `stream` a hipStream_t."""
-    _lib.check(_lib.lib.flux_denoise_moments_device(int(device), width, height, C.c_void_p(d_moments_ptr), C.c_void_p(d_aov_ptr),
-                                                    _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a),
-                                                    C.c_void_p(d_out_ptr), C.c_void_p(d_work_ptr), work_doubles, C.c_void_p(stream)))
+    _denoise_device("denoise_moments_device", width, height, d_moments_ptr, d_aov_ptr, d_out_ptr, d_work_ptr, work_doubles, stream, device,
+                    _denoise_params(levels, sigma_l, sigma_n, sigma_z, sigma_a))
 
 
 def debug_fastmath(fn: int, a, b=None, device: int = 0) -> np.ndarray:

@@ -349,7 +349,7 @@ int flux_render_moments_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t 
  * a pixel refuse every neighbour.  Argument checks as flux_denoise. */
 int flux_denoise_moments(int device, uint64_t width, uint64_t height, const double *moments, const double *aov,
                          const double *params, double *out_rgb);
-/* The same on device pointers of `device`, asynchronously on `hip_stream`: 3 + L kernel launches.  d_moments and d_aov are only
+/* The same on device pointers of `device`, asynchronously on `hip_stream`: 2 + L kernel launches.  d_moments and d_aov are only
  * read.  flux_denoise_work_doubles is the scratch size for this call too.  Checked as flux_denoise_device (d_out_rgb may be neither
  * d_moments nor d_work). */
 int flux_denoise_moments_device(int device, uint64_t width, uint64_t height, void *d_moments, void *d_aov, const double *params,

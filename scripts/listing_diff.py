@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Kernel by kernel, the device listings of two checkouts compared, without a GPU: `hipcc -S --cuda-device-only` of csrc/render.hip
-and csrc/adaptive.hip with the build's flags (scripts/kernel_asm.py's compile, one per file and tree), then for every kernel whether
+and csrc/adaptive.hip (or the files of --files) with the build's flags (scripts/kernel_asm.py's compile, one per file and tree), then for every kernel whether
 the instruction stream is the same text (comments dropped, labels renumbered) and what the compiler reports for it.
-usage: scripts/listing_diff.py <parent checkout> [<branch checkout>] [--keep dir] > table.md
-   --keep dir: keep the four listings and the remarks there (and reuse the ones already there)
+usage: scripts/listing_diff.py <parent checkout> [<branch checkout>] [--keep dir] [--files a.hip,b.hip] > table.md
+   --keep dir: keep the listings and the remarks there (and reuse the ones already there)
+   --files:    the files of flux_amd/csrc to compare instead of render.hip,adaptive.hip
 Exit status 1 if a kernel exists in one tree only."""
 import os
 import re
@@ -37,10 +38,10 @@ def listing(tree, name, keep):
     return open(asm).read(), open(rem).read()
 
 
-def kernels(tree, keep):
+def kernels(tree, keep, files):
     """demangled name -> (normalised instruction stream, resources)"""
     out = {}
-    for name in FILES:
+    for name in files:
         text, remarks = listing(tree, name, keep)
         syms = re.findall(r"^\s*\.globl\s+(_Z\S+)", text, flags=re.M)
         dem = subprocess.run(["c++filt"] + syms, capture_output=True, text=True).stdout.splitlines()
@@ -75,13 +76,18 @@ def main():
         k = args.index("--keep")
         keep = os.path.abspath(args[k + 1])
         del args[k:k + 2]
+    files = FILES
+    if "--files" in args:
+        k = args.index("--files")
+        files = args[k + 1].split(",")
+        del args[k:k + 2]
     trees = [args[0], args[1] if len(args) > 1 else ROOT]
     with tempfile.TemporaryDirectory() as td:
         sides = []
         for side, tree in zip(("parent", "branch"), trees):
             d = os.path.join(keep or td, side)
             os.makedirs(d, exist_ok=True)
-            sides.append(kernels(tree, d))
+            sides.append(kernels(tree, d, files))
     parent, branch = sides
     fmt = lambda r, n: "{} / {} / {} / {} / {} / {}".format(r.get("vgprs"), r.get("vgpr_spill"), r.get("sgpr_spill"), r.get("scratch"), r.get("occupancy"), n)  # noqa: E731
     print("| kernel | stream | parent: VGPRs / VGPR spills / SGPR spills / scratch B / occupancy / instructions | branch: the same |")

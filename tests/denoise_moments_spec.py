@@ -4,7 +4,7 @@ prefiltered over the step-1 taps with the guide weights, var_p = sum w v_q / sum
 `prefilter=False` skips the prefilter (var_p = v_p): not an entry point of the library, only the middle column of §5g's table."""
 import numpy as np
 
-from denoise_spec import E_MAX, H5, SD_FLOOR, _shifted, guide, lum, max_to_one, usable
+from denoise_spec import filter_levels, usable
 
 
 def usable_moments(rgb, v, aov):
@@ -15,47 +15,21 @@ def usable_moments(rgb, v, aov):
 def denoise_moments(moments, aov, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1, prefilter=True):
     moments = np.asarray(moments, dtype=np.float64)
     aov = np.asarray(aov, dtype=np.float64)
+    assert moments.ndim == 3 and moments.shape[2] == 8
     rgb, v = np.array(moments[..., 0:3]), moments[..., 3]
-    h, w, _ = rgb.shape
-    assert moments.shape == (h, w, 8) and aov.shape == (h, w, 8) and 1 <= levels <= 8
     ok = usable_moments(rgb, v, aov)
-    a, n, z = aov[..., 0:3], aov[..., 3:6], aov[..., 6]
-    sn2, sz2, sa2 = sigma_n * sigma_n, sigma_z * sigma_z, sigma_a * sigma_a
-    c = np.where(ok[..., None], rgb, 0.0)
     v = np.where(ok, v, 0.0)
-    zero = np.zeros((h, w))
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        if prefilter:
-            s0, s1 = zero.copy(), zero.copy()
-            for j in range(-2, 3):
-                for i in range(-2, 3):
-                    (vq, aq, nq, zq, okq), on = _shifted([v, a, n, z, ok], j, i, h, w)
-                    valid = on & okq & ok
-                    wt = np.where(valid, np.exp2(-np.minimum(guide(a, n, z, aq, nq, zq, sn2, sz2, sa2), E_MAX)), 0.0)
-                    s0 += wt
-                    s1 += np.where(valid, wt * vq, 0.0)
-            var = np.where(ok, s1 / s0, 0.0)
-        else:
-            var = v
-        for k in range(levels):
-            s = 1 << k
-            sd = sigma_l * np.sqrt(var) + SD_FLOOR
-            l = lum(c)
-            num, den, vnum = np.zeros_like(c), zero.copy(), zero.copy()
-            for j in range(-2, 3):
-                for i in range(-2, 3):
-                    (cq, lq, vq, aq, nq, zq, okq), on = _shifted([c, l, var, a, n, z, ok], j * s, i * s, h, w)
-                    valid = on & okq & ok
-                    e = np.minimum(guide(a, n, z, aq, nq, zq, sn2, sz2, sa2) + np.abs(l - lq) / sd, E_MAX)
-                    wt = np.where(valid, (H5[j + 2] * H5[i + 2]) * np.exp2(-e), 0.0)
-                    num += np.where(valid[..., None], wt[..., None] * cq, 0.0)
-                    den += wt
-                    vnum += np.where(valid, (wt * wt) * vq, 0.0)
-            c = np.where(ok[..., None], num / den[..., None], 0.0)
-            var = np.where(ok, vnum / (den * den), 0.0)
-    out = max_to_one(c)
-    out[~ok] = rgb[~ok]  # bit for bit
-    return out
+
+    def variance(c, taps):
+        if not prefilter:
+            return v
+        s0, s1 = np.zeros(ok.shape), np.zeros(ok.shape)
+        for valid, wt, vq in taps(v):
+            s0 += wt
+            s1 += np.where(valid, wt * vq, 0.0)
+        return s1 / s0
+
+    return filter_levels(rgb, aov, ok, variance, levels, sigma_l, sigma_n, sigma_z, sigma_a)
 
 
 def synthetic(h, w, seed=3):

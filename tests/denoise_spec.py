@@ -53,34 +53,27 @@ def guide(a, n, z, aq, nq, zq, sn2, sz2, sa2):
         return (en + ez) + ea
 
 
-def denoise(rgb, aov, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1):
-    rgb = np.array(rgb, dtype=np.float64)
-    aov = np.asarray(aov, dtype=np.float64)
+def filter_levels(rgb, aov, ok, variance, levels, sigma_l, sigma_n, sigma_z, sigma_a):
+    """The filter over the frame `rgb`, given which pixels are usable and where the variance comes from that the first level starts
+    from: variance(c, taps) with c the frame, unusable pixels zeroed, and taps(x) the walk over the step-1 taps, rows outer, that
+    yields (valid, wt, xq) per tap -- whether a pixel may use it, its weight from the guides alone (0 where it may not) and x read
+    at the tap."""
     h, w, _ = rgb.shape
     assert aov.shape == (h, w, 8) and 1 <= levels <= 8
-    ok = usable(rgb, aov)
     a, n, z = aov[..., 0:3], aov[..., 3:6], aov[..., 6]
     sn2, sz2, sa2 = sigma_n * sigma_n, sigma_z * sigma_z, sigma_a * sigma_a
     c = np.where(ok[..., None], rgb, 0.0)
     zero = np.zeros((h, w))
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        # the variance of the luminance over the 5 x 5 neighbourhood, weighted by the guides alone: two passes
-        l = lum(c)
-        taps, s0, s1 = [], zero.copy(), zero.copy()
+
+    def taps(x):
         for j in range(-2, 3):
             for i in range(-2, 3):
-                (lq, aq, nq, zq, okq), on = _shifted([l, a, n, z, ok], j, i, h, w)
+                (xq, aq, nq, zq, okq), on = _shifted([x, a, n, z, ok], j, i, h, w)
                 valid = on & okq & ok
-                wt = np.where(valid, np.exp2(-np.minimum(guide(a, n, z, aq, nq, zq, sn2, sz2, sa2), E_MAX)), 0.0)
-                s0 += wt
-                s1 += np.where(valid, wt * lq, 0.0)
-                taps.append((valid, wt, lq))
-        m = np.where(ok, s1 / s0, 0.0)
-        s2 = zero.copy()
-        for valid, wt, lq in taps:
-            d = lq - m
-            s2 += np.where(valid, wt * (d * d), 0.0)
-        var = np.where(ok, s2 / s0, 0.0)
+                yield valid, np.where(valid, np.exp2(-np.minimum(guide(a, n, z, aq, nq, zq, sn2, sz2, sa2), E_MAX)), 0.0), xq
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        var = np.where(ok, variance(c, taps), 0.0)
         for k in range(levels):
             s = 1 << k
             sd = sigma_l * np.sqrt(var) + SD_FLOOR
@@ -100,6 +93,28 @@ def denoise(rgb, aov, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=
     out = max_to_one(c)
     out[~ok] = rgb[~ok]  # bit for bit
     return out
+
+
+def denoise(rgb, aov, levels=5, sigma_l=2.0, sigma_n=0.35, sigma_z=0.1, sigma_a=0.1):
+    rgb = np.array(rgb, dtype=np.float64)
+    aov = np.asarray(aov, dtype=np.float64)
+    ok = usable(rgb, aov)
+
+    def variance(c, taps):
+        """Of the luminance over the 5 x 5 neighbourhood, weighted by the guides alone: two passes."""
+        seen, s0, s1 = [], np.zeros(ok.shape), np.zeros(ok.shape)
+        for valid, wt, lq in taps(lum(c)):
+            s0 += wt
+            s1 += np.where(valid, wt * lq, 0.0)
+            seen.append((valid, wt, lq))
+        m = np.where(ok, s1 / s0, 0.0)
+        s2 = np.zeros(ok.shape)
+        for valid, wt, lq in seen:
+            d = lq - m
+            s2 += np.where(valid, wt * (d * d), 0.0)
+        return s2 / s0
+
+    return filter_levels(rgb, aov, ok, variance, levels, sigma_l, sigma_n, sigma_z, sigma_a)
 
 
 def synthetic(h, w, seed=3):

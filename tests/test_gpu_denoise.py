@@ -2,53 +2,22 @@
 (tests/denoise_spec.py): parity on synthetic inputs at every size and level count at which the kernels take another path,
 determinism, the device-resident call, the renderer's end-to-end call with its quality bound, and the command-line tool.
 
-Tolerance: |gpu - spec| <= 1e-10 on usable pixels, unusable pixels bit for bit.  The kernels repeat the specification's operations
-in its order (no contraction, IEEE division and sqrt); the one difference is fexp2 (flux_math.h) against np.exp2, at most 2 ulp: about
-25 taps x 8 levels x a few ulp ~ 1e-13 on values <= 1.2.  A dropped or misplaced tap moves a pixel by at least 1/256 of a colour
-difference.  Measured: DESIGN.md §5f."""
+Tolerance (tests/denoise_checks.py, with the helpers both denoiser suites share): |gpu - spec| <= 1e-10 on usable pixels, unusable
+pixels bit for bit."""
 import os
 
 import numpy as np
 import pytest
 
+import denoise_checks
 import denoise_spec
 from conftest import SCENES, small_scene
+from denoise_checks import SIZES, SPATIAL, TOL
 from extension_checks import cli_frame, host_bins, small_yaml
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-10
-# (W, H): one tile; not a tile multiple, several tiles both ways, level-4 taps at +-32 inside the image; one pixel; one column (five
-# tiles high); smaller than a filter
-SIZES = [(16, 12), (70, 45), (1, 1), (1, 40), (3, 2)]
-_inputs, _specs = {}, {}
-
-
-def inputs(w, h):
-    if (w, h) not in _inputs:
-        rgb, aov = denoise_spec.synthetic(h, w)
-        rgb.setflags(write=False)
-        aov.setflags(write=False)
-        _inputs[(w, h)] = (rgb, aov)
-    return _inputs[(w, h)]
-
-
-def spec(w, h, **params):
-    """The specification's frame for the synthetic input of this size, computed once per parameter set and shared, read-only."""
-    key = (w, h, tuple(sorted(params.items())))
-    if key not in _specs:
-        _specs[key] = denoise_spec.denoise(*inputs(w, h), **params)
-        _specs[key].setflags(write=False)
-    return _specs[key]
-
-
-def assert_matches(got, want, rgb, aov, label):
-    ok = denoise_spec.usable(rgb, aov)
-    assert got[~ok].tobytes() == rgb[~ok].tobytes(), f"{label}: an unusable pixel was not copied bit for bit"
-    assert np.isfinite(got[ok]).all(), label
-    err = float(np.max(np.abs(got[ok] - want[ok]))) if ok.any() else 0.0
-    print(f"denoise {label}: max |gpu - spec| = {err:.2e} over {int(ok.sum())} usable pixels, {int((~ok).sum())} unusable")
-    assert err <= TOL, (label, err)
+inputs, spec, assert_matches = SPATIAL.inputs, SPATIAL.spec, SPATIAL.assert_matches
 
 
 # ---- 1. parity with the spec --------------------------------------------------------------------------------------------------
@@ -74,17 +43,7 @@ def test_parity_with_other_sigmas(flux):
 
 @pytest.mark.parametrize("w,h,levels", [(70, 45, 5), (16, 12, 8), (1, 40, 3)])
 def test_lds_tiles_give_the_bits_of_the_gathers(flux, monkeypatch, w, h, levels):
-    """The level kernel exists twice (global gathers; one residue class of the step's lattice per block through LDS, chosen per
-    level by FLUX_DENOISE_LDS_LEVELS for the measurement of DESIGN.md §5f): the same taps in the same order."""
-    rgb, aov = inputs(w, h)
-    monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", "0")
-    gathers = flux.denoise(rgb, aov, levels=levels)
-    monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", "8")
-    tiles = flux.denoise(rgb, aov, levels=levels)
-    monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", "2")
-    mixed = flux.denoise(rgb, aov, levels=levels)
-    assert gathers.tobytes() == tiles.tobytes() == mixed.tobytes()
-    assert_matches(tiles, spec(w, h, levels=levels), rgb, aov, f"{w}x{h} levels {levels} through LDS")
+    denoise_checks.lds_tiles_give_the_bits_of_the_gathers(SPATIAL, flux, monkeypatch, w, h, levels)
 
 
 # ---- 2. determinism and the device-resident call ----------------------------------------------------------------------------------
@@ -95,25 +54,7 @@ def test_two_runs_are_bit_equal(flux):
 
 
 def test_device_call_on_a_stream_equals_the_host_call_and_leaves_its_inputs(flux):
-    import torch
-    w, h = 70, 45
-    rgb, aov = inputs(w, h)
-    want = flux.denoise(rgb, aov)
-    dev = torch.device("cuda", 0)
-    need = flux.denoise_work_doubles(w, h)
-    d_rgb, d_aov = torch.from_numpy(rgb.copy()).to(dev), torch.from_numpy(aov.copy()).to(dev)
-    d_out = torch.full((h, w, 3), -7.0, dtype=torch.float64, device=dev)
-    d_work = torch.full((need + 16,), -3.0, dtype=torch.float64, device=dev)  # exactly `need` is handed over; a guard band behind it
-    stream = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(stream):
-        flux.denoise_device(w, h, d_rgb.data_ptr(), d_aov.data_ptr(), d_out.data_ptr(), d_work.data_ptr(), need, stream=stream.cuda_stream)
-    stream.synchronize()
-    assert d_out.cpu().numpy().tobytes() == want.tobytes()
-    assert d_rgb.cpu().numpy().tobytes() == rgb.tobytes() and d_aov.cpu().numpy().tobytes() == aov.tobytes()
-    assert bool((d_work[need:] == -3.0).all())  # nothing is written past work_doubles
-    with pytest.raises(flux.FluxError):
-        flux.denoise_device(w, h, d_rgb.data_ptr(), d_aov.data_ptr(), d_out.data_ptr(), d_work.data_ptr(), need - 1)
+    denoise_checks.device_call_on_a_stream_equals_the_host_call_and_leaves_its_inputs(SPATIAL, flux)
 
 
 # ---- 3. end to end ----------------------------------------------------------------------------------------------------------------

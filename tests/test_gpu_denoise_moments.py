@@ -3,53 +3,23 @@ specification in numpy (tests/denoise_moments_spec.py): parity on synthetic inpu
 kernels take another path, determinism, the device-resident call, the renderer's end-to-end call with its quality bounds, and the
 command-line tool.
 
-Tolerance: |gpu - spec| <= 1e-10 on usable pixels, unusable pixels bit for bit -- the bound of tests/test_gpu_denoise.py, for its
-reason: the kernels repeat the specification's operations in its order, and the one difference is fexp2 against np.exp2 (<= 2 ulp)."""
+Tolerance (tests/denoise_checks.py, with the helpers both denoiser suites share): |gpu - spec| <= 1e-10 on usable pixels, unusable
+pixels bit for bit -- the bound of tests/test_gpu_denoise.py, for its reason."""
 import os
 
 import numpy as np
 import pytest
 
+import denoise_checks
 import denoise_moments_spec as dms
 import denoise_spec
 from conftest import SCENES, small_scene
+from denoise_checks import MEASURED, SIZES, TOL
 from extension_checks import cli_frame, host_bins, small_yaml
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-10
-# (W, H): one tile; not a tile multiple, several tiles both ways; one pixel; one column (five tiles high); smaller than a filter
-SIZES = [(16, 12), (70, 45), (1, 1), (1, 40), (3, 2)]
-_inputs, _specs = {}, {}
-
-
-def inputs(w, h):
-    if (w, h) not in _inputs:
-        mom, aov = dms.synthetic(h, w)
-        mom.setflags(write=False)
-        aov.setflags(write=False)
-        _inputs[(w, h)] = (mom, aov)
-    return _inputs[(w, h)]
-
-
-def spec(w, h, **params):
-    """The specification's frame for the synthetic input of this size, computed once per parameter set and shared, read-only."""
-    key = (w, h, tuple(sorted(params.items())))
-    if key not in _specs:
-        _specs[key] = dms.denoise_moments(*inputs(w, h), **params)
-        _specs[key].setflags(write=False)
-    return _specs[key]
-
-
-def assert_matches(got, want, mom, aov, label):
-    rgb = mom[..., 0:3]
-    ok = dms.usable_moments(rgb, mom[..., 3], aov)
-    assert got.shape == rgb.shape
-    assert got[~ok].tobytes() == rgb[~ok].tobytes(), f"{label}: an unusable pixel was not copied bit for bit"
-    assert np.isfinite(got[ok]).all(), label
-    err = float(np.max(np.abs(got[ok] - want[ok]))) if ok.any() else 0.0
-    print(f"denoise_moments {label}: max |gpu - spec| = {err:.2e} over {int(ok.sum())} usable pixels, {int((~ok).sum())} unusable")
-    assert err <= TOL, (label, err)
+inputs, spec, assert_matches = MEASURED.inputs, MEASURED.spec, MEASURED.assert_matches
 
 
 # ---- 1. parity with the spec --------------------------------------------------------------------------------------------------
@@ -73,6 +43,31 @@ def test_parity_with_other_sigmas_and_an_even_level_count(flux):
     got = flux.denoise_moments(mom, aov, **params)
     assert_matches(got, spec(70, 45, **params), mom, aov, f"70x45 {params}")
     assert not np.array_equal(got, flux.denoise_moments(mom, aov, levels=4), equal_nan=True)  # the parameters arrive
+
+
+# (70, 45, 4): an even count, so the last level reads the other plane set; (3, 2, 1): the last level is also the first
+@pytest.mark.parametrize("w,h,levels", [(70, 45, 5), (70, 45, 4), (16, 12, 8), (1, 40, 3), (3, 2, 1)])
+def test_lds_tiles_give_the_bits_of_the_gathers(flux, monkeypatch, w, h, levels):
+    """Where the image has room these inputs hold the 7 unusable pixels of dms.synthetic, so both level kernels copy pixels from a
+    buffer of 8 doubles per pixel."""
+    denoise_checks.lds_tiles_give_the_bits_of_the_gathers(MEASURED, flux, monkeypatch, w, h, levels)
+
+
+@pytest.mark.parametrize("levels", [1, 2])
+def test_unusable_pixels_come_back_as_channels_0_to_2_bit_for_bit(flux, monkeypatch, levels):
+    """Channels 4..7 of the unusable pixels hold values found nowhere else: a copy with another stride than 8 or another channel
+    offset than 0 brings one of them, or another pixel's colour, into the output.  Through the gathers and through LDS."""
+    mom, aov = (np.array(a) for a in inputs(16, 12))
+    ok = dms.usable_moments(mom[..., 0:3], mom[..., 3], aov)
+    assert (~ok).sum() == 7
+    marks = -1000.0 - np.arange(7 * 4, dtype=np.float64).reshape(7, 4)
+    mom[~ok, 4:8] = marks
+    for lds in ("0", "8"):
+        monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", lds)
+        got = flux.denoise_moments(mom, aov, levels=levels)
+        assert got[~ok].tobytes() == mom[~ok, 0:3].tobytes()
+        assert not np.isin(got, marks).any()
+    assert_matches(got, spec(16, 12, levels=levels), mom, aov, f"16x12 levels {levels}, marked channels 4..7")
 
 
 def test_the_variance_channel_is_what_guides_the_filter(flux):
@@ -99,26 +94,7 @@ def test_two_runs_are_bit_equal(flux):
 
 @pytest.mark.parametrize("levels", [5, 2])
 def test_device_call_on_a_stream_equals_the_host_call_and_leaves_its_inputs(flux, levels):
-    import torch
-    w, h = 70, 45
-    mom, aov = inputs(w, h)
-    want = flux.denoise_moments(mom, aov, levels=levels)
-    dev = torch.device("cuda", 0)
-    need = flux.denoise_work_doubles(w, h)
-    d_mom, d_aov = torch.from_numpy(mom.copy()).to(dev), torch.from_numpy(aov.copy()).to(dev)
-    d_out = torch.full((h, w, 3), -7.0, dtype=torch.float64, device=dev)
-    d_work = torch.full((need + 16,), -3.0, dtype=torch.float64, device=dev)  # exactly `need` is handed over; a guard band behind it
-    stream = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(stream):
-        flux.denoise_moments_device(w, h, d_mom.data_ptr(), d_aov.data_ptr(), d_out.data_ptr(), d_work.data_ptr(), need,
-                                    stream=stream.cuda_stream, levels=levels)
-    stream.synchronize()
-    assert d_out.cpu().numpy().tobytes() == want.tobytes()
-    assert d_mom.cpu().numpy().tobytes() == mom.tobytes() and d_aov.cpu().numpy().tobytes() == aov.tobytes()
-    assert bool((d_work[need:] == -3.0).all())  # nothing is written past work_doubles
-    with pytest.raises(flux.FluxError):
-        flux.denoise_moments_device(w, h, d_mom.data_ptr(), d_aov.data_ptr(), d_out.data_ptr(), d_work.data_ptr(), need - 1)
+    denoise_checks.device_call_on_a_stream_equals_the_host_call_and_leaves_its_inputs(MEASURED, flux, levels=levels)
 
 
 # ---- 3. end to end ----------------------------------------------------------------------------------------------------------------
