@@ -135,6 +135,8 @@ SYMBOLS = {
                                     C.POINTER(C.c_double)]),
     "flux_debug_fastmath": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.c_uint64]),
+    "flux_debug_plane_div": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_uint64]),
     "flux_ctx_bvh_info": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_uint64]),
     "flux_ctx_launch_plan": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64)]),
     "flux_ctx_last_kernel_ms": (C.c_double, [_P]),

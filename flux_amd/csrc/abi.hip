@@ -521,6 +521,30 @@ int flux_debug_fastmath(int device, int fn, const double *a, const double *b, do
     return FLUX_OK;
 }
 
+int flux_debug_plane_div(int device, const double *num, const double *den, double *out_unscaled, double *out_quotient, int32_t *out_admit,
+                         uint64_t n) {
+    if (!num || !den || !out_unscaled || !out_quotient || !out_admit) return fail(FLUX_E_INVALID, "null argument");
+    if (int rc = flux::require_device(device)) return rc;
+    DeviceGuard guard(device);
+    if (n == 0) return FLUX_OK;
+    flux::DevBuf<double> dn, dd, du, dq;
+    flux::DevBuf<int32_t> da;
+    const size_t bytes = (size_t)n * sizeof(double);
+    hipError_t e = dn.alloc((size_t)n);
+    if (e == hipSuccess) e = dd.alloc((size_t)n);
+    if (e == hipSuccess) e = du.alloc((size_t)n);
+    if (e == hipSuccess) e = dq.alloc((size_t)n);
+    if (e == hipSuccess) e = da.alloc((size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(dn, num, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dd, den, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = flux::launch_plane_div_probe(dn, dd, du, dq, da, (size_t)n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out_unscaled, du, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_quotient, dq, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_admit, da, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FLUX_E_DEVICE, "plane division probe: %s", hipGetErrorString(e));
+    return FLUX_OK;
+}
+
 // The work fields of a launch: ONE place per entry point, shared by the render call and flux_ctx_launch_plan.
 static flux::RenderParams apply_context(const flux_ctx *ctx, flux::RenderParams p) {
     p.stats = ctx->stats_on ? ctx->d_stats : nullptr;

@@ -302,6 +302,11 @@ struct RenderParams {
     // none): the launch's, set from its plan -- here and not a kernel argument of its own, so that the pass loop reads it where it is
     // used like every other field and holds no scalar register for it
     int32_t cut_depth;
+    // split kernel, TYP instantiations: {max_depth, cut_depth} once more, as an aligned pair that phase B reads with ONE load in front
+    // of its scan (render_body.inc split_depths), set by the launch beside cut_depth.  Read where it is used, behind the scan, the cut's
+    // depth was a load and its whole wait between the classification and the park, every pass.  (A copy, and the two fields where they
+    // were: laying them side by side moved four other instantiations' scalar spills -- profiles/r16_plane_div/registers.txt.)
+    alignas(8) int32_t depth_pair[2];
 };
 // bytes per hit record of RenderParams::lobe_frame
 constexpr size_t kLobeFrameBytes = 6 * sizeof(double);

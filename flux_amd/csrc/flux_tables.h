@@ -61,5 +61,8 @@ hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_ra
 // flux_math.h under test: out[i] = fn(a[i], b[i]) on the device (b may be null).
 hipError_t launch_fastmath_probe(int fn, const double *a, const double *b, double *out, size_t n,
                                  hipStream_t stream);
+// flux_plane_axis.h on the device (render.hip plane_div_probe_kernel): plane_div_unscaled, num / den, and the votes' word on den
+hipError_t launch_plane_div_probe(const double *num, const double *den, double *unscaled, double *quotient, int32_t *admit, size_t n,
+                                  hipStream_t stream);
 
 }  // namespace flux

@@ -305,4 +305,23 @@ hipError_t launch_fastmath_probe(int fn, const double *a, const double *b, doubl
     return hipGetLastError();
 }
 
+// ---- flux_plane_axis.h under test: the reduced arms' unscaled division, IEEE `/` and the votes' word on den, on the device ----
+// admit[i]: bit 0 the predicate as a function of the lane's den, bit 1 the lane's bit of the mask the split kernel's votes take
+__global__ void plane_div_probe_kernel(const double *num, const double *den, double *unscaled, double *quotient, int32_t *admit, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = num[i], y = den[i];
+    unscaled[i] = plane_div_unscaled(x, y);
+    quotient[i] = x / y;
+    const unsigned long long lanes = fast::plane_div_admits_lanes(y);
+    admit[i] = (plane_div_admits(y) ? 1 : 0) | ((lanes >> (threadIdx.x & 63)) & 1ull ? 2 : 0);
+}
+
+hipError_t launch_plane_div_probe(const double *num, const double *den, double *unscaled, double *quotient, int32_t *admit, size_t n,
+                                  hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    plane_div_probe_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(num, den, unscaled, quotient, admit, n);
+    return hipGetLastError();
+}
+
 }  // namespace flux

@@ -52,10 +52,44 @@ __device__ __forceinline__ const RenderParams &relaunder_params(uint32_t tick) {
     return *(const RenderParams *)p;
 }
 
+// The depth limit and the depth cut's depth as phase B takes them.  PAIR (split_depth_pair: the TYP instantiations of render_split_kernel):
+// RenderParams::depth_pair, ONE 64-bit scalar load where phase B needs the limit, in front of its scan.  Two field reads are two loads to
+// the compiler, and it places the cut's at its use, behind the scan and the shading step: a scalar load and its full wait between the
+// classification and the park, in every pass.  It costs the TYP instantiations no register -- the headline stays at 84 vector and 96
+// scalar registers, the others drop two scalar ones.  The instantiations without TYP stand at the scalar-register limit and spill to
+// vector lanes as they are; one more value held across the scan is two to four more spills there, so they read the two fields where
+// they use them, the parent's code (profiles/r16_plane_div/registers.txt).
+struct SplitDepths {
+    int max_depth, cut_depth;
+};
+constexpr bool split_depth_pair(bool TYP) { return TYP; }
+template <bool PAIR>
+__device__ __forceinline__ SplitDepths split_depths(const RenderParams &P) {
+    if (!PAIR) return SplitDepths{0, 0};  // (not read: split_max_depth, split_cut_depth below)
+    // (a typed 64-bit load: a byte copy is a load of alignment 1, which no scalar load serves -- it came out a vector load)
+    typedef unsigned long long __attribute__((may_alias)) DepthPair;
+    const DepthPair both = *reinterpret_cast<const DepthPair *>(P.depth_pair);
+    return SplitDepths{(int)(uint32_t)both, (int)(uint32_t)(both >> 32)};
+}
+// (without PAIR: the field, read where the value is used)
+template <bool PAIR>
+__device__ __forceinline__ int split_max_depth(const RenderParams &P, const SplitDepths &d) { return PAIR ? d.max_depth : P.max_depth; }
+template <bool PAIR>
+__device__ __forceinline__ int split_cut_depth(const RenderParams &P, const SplitDepths &d) { return PAIR ? d.cut_depth : P.cut_depth; }
+
 // wave votes straight from the compare's lane mask (hip's __ballot / __any / __all go through a 0/1 select and a second compare)
 __device__ __forceinline__ unsigned long long ballot64(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 __device__ __forceinline__ bool any64(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0ull; }
 __device__ __forceinline__ bool all64(bool b) { return __builtin_amdgcn_ballot_w64(!b) == 0ull; }
+// The active lanes whose d_a plane_div_admits (flux_plane_axis.h: its f32 image a normal number), as the votes of both scans take it:
+// ONE class test that writes the lane mask (the bits of lanes that are not active are zero).  Written out because a ballot of
+// __builtin_isnormal is the class test, a 0/1 select and a compare of that -- and its mask a vector register; the probe kernel
+// holds this mask to the function lane by lane (render.hip plane_div_probe_kernel, tests/test_gpu_plane_div.py).
+__device__ __forceinline__ unsigned long long plane_div_admits_lanes(double da) {
+    unsigned long long m;
+    asm("v_cmp_class_f32_e64 %0, %1, %2" : "=s"(m) : "v"((float)da), "s"(0x108));  // 0x108: -normal | +normal
+    return m;
+}
 
 // A gather from a table in GLOBAL memory: wave-uniform base + 32-bit per-lane byte offset.  A base that comes out of a record in memory
 // (DevSetRows) is a generic pointer to the compiler: flat_load with a 64-bit address per lane, formed by two or three VALU instructions
@@ -610,7 +644,9 @@ __device__ __forceinline__ void scan_shapes_fast(const RenderParams &P, const Ra
             num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
             den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
         }
-        const double t = num / den;
+        // (AXIS: the vote has also put d_a where the division needs neither its operands scaled nor its result fixed up -- plane_div_admits,
+        // plane_div_unscaled: the bits of num / den without three of its eleven instructions)
+        const double t = PLANE_AXIS ? plane_div_unscaled(num, den) : num / den;
         const bool take = t > tmin;
         best = take ? P.n_sph : -1;
         best_id = S.id;
@@ -2273,11 +2309,12 @@ __device__ __forceinline__ void pixel_sphere_mask(const RenderParams &P, int row
 // compiler merges the two.)
 // AXIS (the instantiation for a first plane whose normal lies on that axis): the reduced plane test of ZF = 0 also needs, of every lane
 // (flux_plane_axis.h plane_axis_admits, plane_axis_admits_b -- the CPU test holds this vote to that predicate),
-//     d_a != 0                 for a z plane the vote above; else one more compare;
+//     plane_div_admits(d_a)    d_a not zero and of a size the reduced arm's unscaled division takes: one class test of (float)d_a,
+//                              which the filter forms anyway;
 //     d_x, d_y, d_z finite     |o.u| < 3e38 in f32, one compare of a value the filter forms anyway: an infinite or NaN component of d
 //                              (or one beyond f32) times a finite o_i is infinite or -- o_i = 0 -- NaN, and the fused sum that takes it
 //                              in stays infinite or NaN.  A NaN d_a fails here.
-// Two more vector instructions a pass for demo2's y plane, one for a z plane.
+// Two more vector instructions a pass.
 template <int AXIS>
 __device__ __forceinline__ unsigned long long split_rare_lanes(const Ray &r) {
     const float ofx = (float)r.ox, ofy = (float)r.oy, ofz = (float)r.oz;
@@ -2286,8 +2323,7 @@ __device__ __forceinline__ unsigned long long split_rare_lanes(const Ray &r) {
     if (AXIS != kPlaneAxisNone) {
         const float ou32 = __builtin_fmaf(ofz, (float)r.dz, __builtin_fmaf(ofy, (float)r.dy, ofx * (float)r.dx));
         rare |= ballot64(!(__builtin_fabsf(ou32) < 3.0e38f));
-        if (AXIS == kPlaneAxisY) rare |= ballot64(r.dy == 0.0);
-        if (AXIS == kPlaneAxisX) rare |= ballot64(r.dx == 0.0);
+        rare |= ballot64(true) & ~plane_div_admits_lanes(AXIS == kPlaneAxisX ? r.dx : AXIS == kPlaneAxisY ? r.dy : r.dz);
     }
     return rare;
 }
@@ -2306,7 +2342,8 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
     if (P.n_pln > 0) {  // the first plane: one compare and one select (scan_shapes_fast)
         const DevScanPlane &S = P.fpln[0];
         // AXIS (the instantiation for a plane whose stored normal lies on that axis): num = p_a - o_a, den = d_a, the general t bit for
-        // bit (flux_plane_axis.h) in a wave whose valid lanes all hold |d_a| > 0 -- ONE compare a pass; a NaN fails it.  The rest of
+        // bit (flux_plane_axis.h) in a wave whose valid lanes all hold a d_a of ordinary size (plane_div_admits: its f32 image a normal
+        // number, which a zero, a NaN and an infinity are not) -- one conversion and ONE class test a pass.  The rest of
         // the predicate is the host's: it sets the axis only for a camera of finite scalars below 1e60 (plane_axis_camera_ok), the sample
         // tables hold points of the unit square and the unit disc, so primary_ray_px's origin is finite and of that size, and its
         // direction is a finite vector times ONE frsqrt -- finite in all three components or NaN in all three, and a NaN d_a has failed
@@ -2314,16 +2351,17 @@ __device__ __forceinline__ void scan_shapes_primary(const RenderParams &P, const
         bool reduced = false;
         if (AXIS != kPlaneAxisNone) {
             const double da = AXIS == kPlaneAxisX ? r.dx : AXIS == kPlaneAxisY ? r.dy : r.dz;
-            reduced = (valid_m & ballot64(!(__builtin_fabs(da) > 0.0))) == 0ull;
+            reduced = (valid_m & ~plane_div_admits_lanes(da)) == 0ull;
         }
-        double num, den;
+        double num, den, t;
         if (AXIS != kPlaneAxisNone && reduced) {
             plane_axis_num_den(AXIS, S.px, S.py, S.pz, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, num, den);
+            t = plane_div_unscaled(num, den);  // (the vote: no operand of this division is scaled, nothing is fixed up)
         } else {
             num = (S.px - r.ox) * S.nx + (S.py - r.oy) * S.ny + (S.pz - r.oz) * S.nz;
             den = r.dx * S.nx + r.dy * S.ny + r.dz * S.nz;
+            t = num / den;
         }
-        const double t = num / den;
         best = t > tmin ? P.n_sph : -1;
         best_id = S.id;
         tb = t;
@@ -2620,7 +2658,8 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             //      added to the lane's sums, a path that continues is parked
             FLUX_TRIP(P, 10);
             const bool live = p.depth != kDeadDepth;
-            const bool trace = p.depth <= P.max_depth;  // (live, and) scene.rs:164-165: a path beyond the depth limit ends with L = 0
+            const SplitDepths depths = split_depths<split_depth_pair(TYP)>(P);  // (the limit and the cut's depth: one load, here)
+            const bool trace = p.depth <= split_max_depth<split_depth_pair(TYP)>(P, depths);  // (live, and) scene.rs:164-165: a path beyond the depth limit ends with L = 0
             double Lr = 0.0, Lg = 0.0, Lb = 0.0;
             bool cont = false;
             int hit = -1;
@@ -2636,7 +2675,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 cont = shade_hit_fast<STATS, false, true, TYP, false, false, true>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds, facing);
                 // The depth cut (launch_plan.cpp split_cut_depth): the child of a bounce at the depth limit ends with L = 0 untraced, so
                 // the path ends here with the zeros above -- nothing parked, no take, no bounce, no pass spent on finding it dead.
-                if (cont && p.depth == P.cut_depth) {
+                if (cont && p.depth == split_cut_depth<split_depth_pair(TYP)>(P, depths)) {
                     cont = false;
                     if (STATS) {  // what the skipped bounce and the skipped pass counted
                         const int kind = recs[hit].mat_kind;
@@ -2824,7 +2863,8 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             FLUX_TRIP(P, 10);
             // a sequence of plain `if`s, none with an else, each changing its own part of the loop-carried state (see shade_hit_fast)
             const bool live = p.depth != kDeadDepth;
-            const bool trace = p.depth <= P.max_depth;  // (live, and) scene.rs:164-165: a path beyond the depth limit ends with L = 0
+            const SplitDepths depths = split_depths<split_depth_pair(TYP)>(P);  // (the limit and the cut's depth: one load, here)
+            const bool trace = p.depth <= split_max_depth<split_depth_pair(TYP)>(P, depths);  // (live, and) scene.rs:164-165: a path beyond the depth limit ends with L = 0
             // (Lr = Lg = Lb = 0 are six 64-bit moves a pass as the compiler lowers them -- once per nesting level.  Leaving the three
             // undefined and writing the zeros behind a vote on `depth > max_depth` removes the moves and was measured 1.0 % SLOWER, twice:
             // profiles/r06_experiments/ab_m20_m22_m23_r06z.log, ab_m29_m30_r06ag.log.)
@@ -2842,7 +2882,7 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 cont = shade_hit_fast<STATS, false, true, TYP>(P, p, set_p, i, hit, -1, t, Lr, Lg, Lb, st, 0, frec_lds);
                 // The depth cut (launch_plan.cpp split_cut_depth), as phase A's: a child beyond the depth limit ends here with the zeros
                 // above, folded below with the throughput its bounce left -- the lane is free a pass earlier.
-                if (cont && p.depth > P.cut_depth) {
+                if (cont && p.depth > split_cut_depth<split_depth_pair(TYP)>(P, depths)) {
                     cont = false;
                     if (STATS) st.c[7]++;
                 }
@@ -3735,6 +3775,8 @@ static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p,
         RenderParams ps = p;
         if (!hq || ps.tput_bits != bits) ps.tput = nullptr;
         ps.cut_depth = L.cut_depth;
+        ps.depth_pair[0] = ps.max_depth;  // (the two once more, for the TYP instantiations' one load: split_depths)
+        ps.depth_pair[1] = L.cut_depth;
 #define FLUX_LAUNCH_SPLIT_AXIS(MAX32, TYP, HQ, AXIS)                                                                  \
     do {                                                                                                             \
         if (stats) render_split_kernel<true, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);  \

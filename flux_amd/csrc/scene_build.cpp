@@ -224,6 +224,11 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
     rp.n_pln = (int32_t)fpln.size();
     // the first scan plane's axis, from the normal and the point as stored (flux_plane_axis.h); the camera's side: build_host_scene
     rp.plane_axis = fpln.empty() ? kPlaneAxisNone : plane_axis_of(fpln[0].nx, fpln[0].ny, fpln[0].nz, fpln[0].px, fpln[0].py, fpln[0].pz);
+    if (rp.plane_axis != kPlaneAxisNone) {
+        // ... and the axis component of its point, which the reduced arms' division needs of ordinary size (plane_div_point_ok)
+        const double pa = rp.plane_axis == kPlaneAxisX ? fpln[0].px : rp.plane_axis == kPlaneAxisY ? fpln[0].py : fpln[0].pz;
+        if (!plane_div_point_ok(pa)) rp.plane_axis = kPlaneAxisNone;
+    }
     rp.n_dsk = (int32_t)fdsk.size();
     rp.n_box = (int32_t)fbox.size();
     // The glossy lobe's angle table (RenderParams::glossx): a slot for every distinct 1 / (exponent + 1) among the glossy records --

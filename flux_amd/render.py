@@ -532,6 +532,19 @@ def debug_fastmath(fn: int, a, b=None, device: int = 0) -> np.ndarray:
     return out
 
 
+def debug_plane_div(num, den, device: int = 0):
+    """The split kernel's unscaled first-plane division, num / den and the votes' word on den, evaluated on the device by
+    csrc/flux_plane_axis.h (test hook, include/flux_abi.h flux_debug_plane_div): (unscaled, quotient, admit)."""
+    num = np.ascontiguousarray(num, dtype=np.float64)
+    den = np.ascontiguousarray(den, dtype=np.float64)
+    assert num.shape == den.shape
+    unscaled, quotient, admit = np.empty_like(num), np.empty_like(num), np.empty(num.shape, dtype=np.int32)
+    pd = C.POINTER(C.c_double)
+    _lib.check(_lib.lib.flux_debug_plane_div(device, num.ctypes.data_as(pd), den.ctypes.data_as(pd), unscaled.ctypes.data_as(pd),
+                                             quotient.ctypes.data_as(pd), admit.ctypes.data_as(C.POINTER(C.c_int32)), num.size))
+    return unscaled, quotient, admit
+
+
 def sampler_grid(kind: int, sample_root: int, seed: int = 1, hemi: bool = False, device: int = 0):
     """One set of a samplers-crate generator computed on the device (include/flux_abi.h flux_sampler_grid):
     (n*n, 2) array, plus its to_hemisphere(.., 0.0) image (n*n, 3) when hemi=True."""

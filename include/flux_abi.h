@@ -587,6 +587,12 @@ int flux_debug_shade(flux_ctx *ctx, uint64_t n, const double *rays, uint64_t dep
  * 4 fexp2, 5 fpow_pos, 6 sin(2 pi a), 7 cos(2 pi a), 8 raw v_rsq_f64, 9 raw v_rcp_f64. */
 int flux_debug_fastmath(int device, int fn, const double *a, const double *b, double *out, uint64_t n);
 
+/* Test hook for csrc/flux_plane_axis.h: for n operand pairs (host pointers), evaluated ON THE DEVICE, out_unscaled[i] = the split
+ * kernel's unscaled first-plane division of num[i] by den[i], out_quotient[i] = num[i] / den[i], out_admit[i] = what the kernel's votes
+ * say of den[i]: bit 0 the predicate (plane_div_admits), bit 1 the lane's bit of the wave mask the votes take. */
+int flux_debug_plane_div(int device, const double *num, const double *den, double *out_unscaled, double *out_quotient,
+                         int32_t *out_admit, uint64_t n);
+
 /* ---- one frame on the GPUs of one node ------------------------------------------------------------------------------
  * Replaces, for GPUs in ONE process, what RenderManager does with a job: the fan-out of the job to every worker
  * (fluxcore/src/manager.rs:156-162: one clone of the job per worker handle) and ImageBuilder's gather of their rows into
