@@ -601,15 +601,21 @@ int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, in
 
 // the launch of the render calls, of the feature-buffer calls and of the moments calls (`pass`), between the context's two events
 // (flux_ctx_last_kernel_ms); `what` names the caller in the LDS refusal
-static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, Pass pass = flux::kPassRender) {
+// (`launch(math)`: the pass's launch in that arithmetic -- launch_pass for the passes RenderParams describes whole, a launcher of its
+// own for one that takes a further argument)
+extern "C++" template <class Launch>
+static int launch_timed_by(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, Pass pass, Launch &&launch) {
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
     if (int rc = check_lds_budget(ctx, p, what, pass)) return rc;
     HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(flux::launch_pass(pass, p, ctx->variant, effective_math(ctx), stream));
+    HIP_TRY(launch(effective_math(ctx)));
     HIP_TRY(hipEventRecord(ctx->ev1, stream));
     ctx->timed = true;
     return FLUX_OK;
+}
+static int launch_timed(flux_ctx *ctx, const flux::RenderParams &p, const char *what, hipStream_t stream, Pass pass = flux::kPassRender) {
+    return launch_timed_by(ctx, p, what, stream, pass, [&](int math) { return flux::launch_pass(pass, p, ctx->variant, math, stream); });
 }
 
 // Every row uses every sample set (trace.rs:64-69): the refusal of a context that holds a share of them, in the caller's words
@@ -678,9 +684,10 @@ static int check_row_range(const flux_ctx *ctx, uint64_t row_start, uint64_t row
 }
 // ... and their path: the checks, the device made current, the call's own scratch grown to rows x W x channels doubles, the device
 // entry point run on it, the result copied back.  (Each call has a scratch buffer of its own: none resizes or aliases another's.)
-typedef int (*RowsDeviceEntry)(flux_ctx *, uint64_t, uint64_t, uint64_t, void *, void *);
+// (`device_entry`: a device entry point, or a callable with its arguments -- one that binds a further argument of its call)
+extern "C++" template <class DeviceEntry>
 static int rows_to_host(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, const char *unit, flux::Scratch<double> flux_ctx::*scratch,
-                        size_t channels, double *out, RowsDeviceEntry device_entry) {
+                        size_t channels, double *out, DeviceEntry &&device_entry) {
     if (!ctx) return fail(FLUX_E_INVALID, "null context");
     if (!out) return fail(FLUX_E_INVALID, "null output pointer");
     if (int rc = check_row_range(ctx, row_start, row_end, unit)) return rc;
@@ -728,6 +735,54 @@ int flux_render_moments_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t 
 
 int flux_render_moments_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, double *out) {
     return rows_to_host(ctx, row_start, row_end, "", &flux_ctx::d_moments, FLUX_MOMENT_CHANNELS, out, flux_render_moments_rows_device);
+}
+
+// The feature buffers at the first non-specular hit (aov_chain_body.inc).  The checks that need no context come
+// first, each with its own message: the context and a max_chain no job can reach here, the output pointer, the stride and the order
+// of the host entry's rows in the entry points.
+static int check_chain_call(const char *what, const flux_ctx *ctx, uint32_t max_chain) {
+    if (!ctx) return fail(FLUX_E_INVALID, "%s: null context", what);
+    if (max_chain > 256) return fail(FLUX_E_INVALID, "%s: max_chain %u exceeds 256, the largest max_trace_depth of any job", what, max_chain);
+    return FLUX_OK;
+}
+// ... then the ones that read it: a share of the sets, and a chain deeper than the job traces -- the hemisphere table holds no u for
+// such a segment, and the render never traces one
+static int check_chain_ctx(const char *what, const flux_ctx *ctx, uint32_t max_chain) {
+    if (int rc = check_all_sets(ctx, "chain feature buffers need", ", which no feature-buffer call serves")) return rc;
+    if (max_chain > ctx->D)
+        return fail(FLUX_E_INVALID, "%s: max_chain %u exceeds the job's max_trace_depth %u (0 means max_trace_depth)", what, max_chain, ctx->D);
+    return FLUX_OK;
+}
+
+int flux_render_aov_chain_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, uint32_t max_chain,
+                                      void *d_out, void *hip_stream) {
+    const char *what = "flux_render_aov_chain_rows_device";
+    // (no rows are in order before the output pointer is looked at, as in the other row calls)
+    if (int rc = check_chain_call(what, ctx, max_chain)) return rc;
+    if (num_rows == 0) return FLUX_OK;
+    if (!d_out) return fail(FLUX_E_INVALID, "%s: null output pointer", what);
+    if (row_stride < 1) return fail(FLUX_E_INVALID, "%s: row_stride must be >= 1", what);
+    if (int rc = check_chain_ctx(what, ctx, max_chain)) return rc;
+    if (int rc = check_rows_call(ctx, first_row, row_stride, num_rows, d_out)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    flux::RenderParams p = rows_params(ctx, first_row, row_stride, num_rows, (double *)d_out);
+    p.stats = nullptr;
+    const int limit = (int)(max_chain == 0 ? ctx->D : max_chain);
+    return launch_timed_by(ctx, p, what, stream, flux::kPassAovChain,
+                           [&](int math) { return flux::launch_aov_chain(p, limit, math, stream); });
+}
+
+// (a staging buffer of its own, d_aov_chain: no other call's scratch is resized or aliased)
+int flux_render_aov_chain_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, uint32_t max_chain, double *out) {
+    const char *what = "flux_render_aov_chain_rows";
+    if (int rc = check_chain_call(what, ctx, max_chain)) return rc;
+    if (!out) return fail(FLUX_E_INVALID, "%s: null output pointer", what);
+    if (row_end < row_start)
+        return fail(FLUX_E_INVALID, "%s: row_end %llu is below row_start %llu", what, (unsigned long long)row_end, (unsigned long long)row_start);
+    return rows_to_host(ctx, row_start, row_end, "", &flux_ctx::d_aov_chain, FLUX_AOV_CHANNELS, out,
+                        [max_chain](flux_ctx *c, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, void *d_out, void *hip_stream) {
+                            return flux_render_aov_chain_rows_device(c, first_row, row_stride, num_rows, max_chain, d_out, hip_stream);
+                        });
 }
 
 // ---- adaptive sampling (adaptive_body.inc, adaptive.hip) -------------------------------------------------------

@@ -165,8 +165,9 @@ struct flux_ctx {
     int variant = FLUX_KERNEL_DEFAULT;
     int math = FLUX_MATH_FAST;
     // scratch framebuffer for the host-output path (flux_render_rows), the feature buffers' own (flux_render_aov_rows) and the sample
-    // moments' own (flux_render_moments_rows): no call resizes or aliases another's
-    flux::Scratch<double> d_out, d_aov, d_moments;
+    // moments' own (flux_render_moments_rows), the chain feature buffers' own (flux_render_aov_chain_rows): no call resizes or
+    // aliases another's
+    flux::Scratch<double> d_out, d_aov, d_moments, d_aov_chain;
     // ... and the adaptive sampler's state and work list (flux_render_adaptive_rows*), all sized for d_adapt_pixels pixels: the running
     // sums [pixels][kAdaptiveSums], the pass counts, the hot flags, the list, and two counters (active pixels, pixels at max_passes);
     // d_adapt_out / d_adapt_map stage the host entry point's outputs, sized for d_adapt_out_pixels

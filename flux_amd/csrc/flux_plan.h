@@ -109,14 +109,15 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math);
 uint32_t plan_flags(const RenderParams &p, const LaunchPlan &L);
 // The kernel family a launch runs: the render kernels, or one of the per-pixel passes -- the feature buffers (aov_body.inc
 // aov_kernel), the sample moments (moments_body.inc moments_kernel), one pass of the adaptive sampler over a work list
-// (adaptive_body.inc adaptive_pass_kernel)
-enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2, kPassAdaptive = 3 };
+// (adaptive_body.inc adaptive_pass_kernel), the feature buffers at the first non-specular hit (aov_chain_body.inc aov_chain_kernel)
+enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2, kPassAdaptive = 3, kPassAovChain = 4 };
 // The same for any pass (kPassRender: plan_render).  Of a per-pixel pass `kernel` is 0 (or -1: nothing to do) and block, grid and
 // LDS are what plan_render's STATIC branch computes -- render_static_kernel's two layouts and its per-lane stacks --, with
 //   kPassAov       `copy` never kCopyFastDiel -- a first hit runs no lobe --, `lds` the per-lane BVH stack of a mesh scene and nothing
 //                  else, `blocks` one wave per pixel in map_wave's order from 64 samples on;
 //   kPassMoments   `copy` as kernel_copy answers: the kernel runs the lobes;
-//   kPassAdaptive  the same, with `blocks` sized by the `entries` of the pass's work list instead of the pixel grid (-1: an empty list).
+//   kPassAdaptive  the same, with `blocks` sized by the `entries` of the pass's work list instead of the pixel grid (-1: an empty list);
+//   kPassAovChain  as kPassMoments: the kernel runs the delta lobes and, in STRICT, keeps their (f, s) stack.
 // `variant` counts for kPassRender alone, `entries` for kPassAdaptive alone.
 LaunchPlan plan_pass(Pass pass, const RenderParams &p, int variant, int math, uint64_t entries = 0);
 

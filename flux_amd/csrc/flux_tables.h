@@ -38,6 +38,8 @@ hipError_t launch_pass(Pass pass, const RenderParams &p, int variant, int math, 
 // One pass of the adaptive sampler over the work list `a` names (adaptive_body.inc), for the rows p names: N more samples of every
 // listed pixel added to a.sums, a.passes counted up.  Runs what plan_pass (flux_plan.h) answers for kPassAdaptive and a.count entries.
 hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int math, hipStream_t stream);
+// the feature buffers at the first non-specular hit (aov_chain_body.inc), chains of at most `max_chain` >= 1 segments
+hipError_t launch_aov_chain(const RenderParams &p, int max_chain, int math, hipStream_t stream);
 
 // What the adaptive sampler runs between and after its passes (adaptive.hip; no lobe code).  `pixels` = rows * width of the call.
 struct AdaptiveRule {

@@ -245,7 +245,9 @@ LaunchPlan plan_pass(Pass pass, const RenderParams &p, int variant, int math, ui
                                    p.nsamp >= 64u && p.num_sets == (uint32_t)p.img_w);
         // the sample moments: plan_render's STATIC branch at every sample count -- row-major pixels, the STRICT (f, s) stack and the
         // BVH stack per lane --, in the copy a render of the job runs
-        case kPassMoments: return plan_pixel_pass(p, kernel_copy(p, math), npix, math, (size_t)p.max_depth, false);
+        // (the chain pass beside it: it runs the delta lobes of the same copy and keeps the same stacks)
+        case kPassMoments:
+        case kPassAovChain: return plan_pixel_pass(p, kernel_copy(p, math), npix, math, (size_t)p.max_depth, false);
         // one pass of the adaptive sampler: the same with the work list's entries in place of the pixel grid
         case kPassAdaptive: return plan_pixel_pass(p, kernel_copy(p, math), entries, math, (size_t)p.max_depth, false);
     }

@@ -47,7 +47,9 @@
 //    dielectric lobe -- a first hit runs no lobe;
 //  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments): every copy -- it runs the lobes;
 //  * adaptive_pass_kernel<TRIS> (adaptive_body.inc, one pass of the adaptive sampler over a work list):
-//    every copy, as moments_kernel.
+//    every copy, as moments_kernel;
+//  * aov_chain_kernel<TRIS> (aov_chain_body.inc, the feature buffers at the first non-specular hit): every copy -- a Dielectric
+//    bounce runs the dielectric lobe.
 #include "flux_device.h"
 #include "flux_plan.h"
 #include "flux_tables.h"
@@ -110,6 +112,7 @@ namespace strict {
 #include "aov_body.inc"
 #include "moments_body.inc"
 #include "adaptive_body.inc"
+#include "aov_chain_body.inc"
 }  // namespace strict
 }  // namespace flux
 #undef FLUX_FAST
@@ -128,6 +131,7 @@ namespace fast {
 #include "aov_body.inc"
 #include "moments_body.inc"
 #include "adaptive_body.inc"
+#include "aov_chain_body.inc"
 }  // namespace fast
 }  // namespace flux
 #undef FLUX_DIEL
@@ -138,8 +142,10 @@ namespace fast {
 namespace flux {
 namespace fast_diel {
 #include "render_body.inc"
+#include "aov_body.inc"  // (for first_hit_fields, which aov_chain_body.inc ends a chain with: aov_kernel itself is never launched from this copy)
 #include "moments_body.inc"
 #include "adaptive_body.inc"
+#include "aov_chain_body.inc"
 }  // namespace fast_diel
 }  // namespace flux
 #undef FLUX_DIEL
@@ -256,6 +262,7 @@ hipError_t launch_pass(Pass pass, const RenderParams &p, int variant, int math, 
         // (a scene with a Dielectric runs the FAST copy: no lobe behind a first hit)
         case kPassAov: return L.copy == kCopyStrict ? strict::launch_aov_impl(L, p, stream) : fast::launch_aov_impl(L, p, stream);
         case kPassAdaptive: break;  // (launch_adaptive: it needs the work list)
+        case kPassAovChain: break;  // (launch_aov_chain: it needs the chain limit)
     }
     return hipErrorInvalidValue;
 }
@@ -265,6 +272,13 @@ hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int mat
     const LaunchPlan L = plan_pass(kPassAdaptive, p, 0, math, a.count);
     if (L.kernel < 0) return hipSuccess;
     FLUX_IN_COPY(L, launch_adaptive_impl(L, p, a, stream));
+}
+
+// the feature buffers at the first non-specular hit, chains of at most `max_chain` segments, in the copy a render of the same job runs
+hipError_t launch_aov_chain(const RenderParams &p, int max_chain, int math, hipStream_t stream) {
+    const LaunchPlan L = plan_pass(kPassAovChain, p, 0, math);
+    if (L.kernel < 0) return hipSuccess;
+    FLUX_IN_COPY(L, launch_aov_chain_impl(L, p, max_chain, stream));
 }
 
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,

@@ -5,7 +5,7 @@
 // wait (:92-94), ImageBuilder writes "<scene_name>.ppm" into the cwd and prints the total time
 // (manager.rs:326-335).  -n/--node ADDRESS[:PORT] adds NetworkWorkers (flux_node processes, flux_net.hpp) and
 // -L leaves the local GPUs out, as in main.rs:37-66.  Additions: --seed (the reference seeds from OS
-// entropy), --gpus, --outdir, --split, --aov, --denoise, --denoise-variance, --adaptive, --adaptive-max-passes.  Not carried over: -g (SDL preview), rejected.
+// entropy), --gpus, --outdir, --split, --aov, --aov-chain, --denoise, --denoise-variance, --denoise-guides, --adaptive, --adaptive-max-passes.  Not carried over: -g (SDL preview), rejected.
 //
 // --split sets|rows|units: how the local GPUs share a frame.  `units` is the reference's scheme -- one worker per device pulling
 // WorkUnits from the shared channel (manager.rs:100) --, `sets` / `rows` hand the node's GPUs to ONE MultiGpuWorker (flux_multi_*:
@@ -18,6 +18,10 @@
 // --denoise: the finished frame and the feature buffers of the same job go through the a-trous filter (flux_abi.h flux_denoise) on
 // local device 0 and the result is written beside the frame as <scene_name>.denoised.ppm; refused like --aov without a local GPU.
 // With --aov as well the feature buffers are rendered once and all five files are written.
+// --aov-chain K: the feature buffers at the first non-specular hit (flux_render_aov_chain_rows, chains of at most K segments, 0 = the
+// tracing depth) as <scene_name>.chain_albedo.ppm, .chain_normal.ppm, .chain_depth.ppm and .chain_coverage.ppm, mapped as --aov maps
+// them.  --denoise-guides first|chain says which buffers steer --denoise (default first).  A K beyond the tracing depth, another word
+// for the guides, --denoise-guides without --denoise, and either flag without a local GPU end the run with status 2 before any job.
 // --denoise-variance measured|spatial (with --denoise; default spatial): `measured` renders the job's per-pixel sample moments on local
 // device 0 (flux_render_moments_rows: the frame again, with the variance of its samples) and writes <scene_name>.denoised.ppm from
 // them through flux_denoise_moments, which takes the noise from the samples instead of guessing it from the frame.  Without
@@ -63,6 +67,9 @@ struct Config {  // flux/src/main.rs:115-124
     bool aov = false;
     bool denoise = false;
     std::string denoise_variance;  // "" (not given), "spatial" or "measured"
+    std::string denoise_guides;    // "" (not given), "first" or "chain"
+    bool aov_chain = false;
+    size_t aov_chain_limit = 0;    // --aov-chain K: 0 = the tracing depth
     bool adaptive = false;
     double adaptive_threshold = 0.0;
     size_t adaptive_max_passes = 0;  // 0: not given
@@ -79,6 +86,11 @@ void usage() {
                  "                     GPU 0 (for noisy previews of 1-16 samples per pixel; a clean frame may lose detail)\n\nOPTIONS:\n"
                  "        --denoise-variance <measured|spatial>  with --denoise: where the filter takes a pixel's noise from [default spatial:\n"
                  "                     the frame's neighbourhood; measured: the variance of the pixel's samples, from one more render pass]\n"
+                 "        --denoise-guides <first|chain>  with --denoise: the feature buffers that steer the filter [default first: what a pixel\n"
+                 "                     sees first; chain: what it sees through mirrors and glass, the first non-specular hit]\n"
+                 "        --aov-chain <K>  Also write <scene_name>.chain_albedo.ppm, .chain_normal.ppm, .chain_depth.ppm and .chain_coverage.ppm:\n"
+                 "                     the feature buffers at the first non-specular hit, Reflective and Dielectric bounces followed for at\n"
+                 "                     most K segments (0: the tracing depth; at most the tracing depth), rendered on local GPU 0\n"
                  "        --adaptive <THRESHOLD>   Also write <scene_name>.adaptive.ppm and <scene_name>.passes.ppm: the job with adaptive sampling on\n"
                  "                     local GPU 0 -- further passes of ROOT^2 samples only where the relative standard error exceeds THRESHOLD\n"
                  "        --adaptive-max-passes <M>  with --adaptive: most passes a pixel takes [default 8; at most the image width]\n"
@@ -146,6 +158,15 @@ Config config_from_args(int argc, char **argv) {
                 std::fprintf(stderr, "error: invalid value '%s' for '--denoise-variance' (measured, spatial)\n", c.denoise_variance.c_str());
                 std::exit(2);
             }
+        } else if (a == "--denoise-guides") {
+            c.denoise_guides = need("--denoise-guides");
+            if (c.denoise_guides != "first" && c.denoise_guides != "chain") {
+                std::fprintf(stderr, "error: invalid value '%s' for '--denoise-guides' (first, chain)\n", c.denoise_guides.c_str());
+                std::exit(2);
+            }
+        } else if (a == "--aov-chain") {
+            c.aov_chain_limit = parse_usize("--aov-chain", need("--aov-chain"));
+            c.aov_chain = true;
         } else if (a == "--adaptive") {
             const char *v = need("--adaptive");
             char *end = nullptr;
@@ -183,6 +204,15 @@ Config config_from_args(int argc, char **argv) {
         std::fprintf(stderr, "error: --denoise-variance says how --denoise measures the noise and needs that flag\n");
         std::exit(2);
     }
+    if (!c.denoise_guides.empty() && !c.denoise) {
+        std::fprintf(stderr, "error: --denoise-guides says which feature buffers steer --denoise and needs that flag\n");
+        std::exit(2);
+    }
+    if (c.aov_chain && c.aov_chain_limit > c.max_depth) {  // (after the loop: --depth may follow the flag)
+        std::fprintf(stderr, "error: invalid value '%zu' for '--aov-chain' (at most the tracing depth %zu; 0 means the tracing depth)\n",
+                     c.aov_chain_limit, c.max_depth);
+        std::exit(2);
+    }
     if (c.adaptive_max_passes != 0 && !c.adaptive) {
         std::fprintf(stderr, "error: --adaptive-max-passes bounds the passes of --adaptive and needs that flag\n");
         std::exit(2);
@@ -212,6 +242,10 @@ int main(int argc, char **argv) {
     }
     if (config.aov && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
         std::fprintf(stderr, "error: --aov renders the feature buffers on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
+        return 2;
+    }
+    if (config.aov_chain && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
+        std::fprintf(stderr, "error: --aov-chain renders the feature buffers on a local GPU, and this run has none (-L, --gpus 0 or no HIP device visible)\n");
         return 2;
     }
     if (config.denoise && (!config.use_local_worker || config.gpus == 0 || flux_device_count() < 1)) {
@@ -306,11 +340,30 @@ int main(int argc, char **argv) {
         std::printf("wrote %s (%.1f Msamples/s incl. context creation)\n", image_builder.written_path.c_str(),
                     image_builder.total_time_s > 0 ? samples / image_builder.total_time_s / 1e6 : 0.0);
     }
-    if (rc == 0 && (config.aov || config.denoise) && !image_builder.written_path.empty()) {
-        const char *flag = config.aov ? "--aov" : "--denoise";
+    if (rc == 0 && (config.aov || config.aov_chain || config.denoise) && !image_builder.written_path.empty()) {
+        const char *flag = config.aov ? "--aov" : config.aov_chain ? "--aov-chain" : "--denoise";
         try {
-            const std::vector<double> aov = render_feature_buffers(s, job_config, config.seed, 0);
             const size_t w = s.output_settings.image_width, h = s.output_settings.image_height;
+            const bool chain_guides = config.denoise && config.denoise_guides == "chain";
+            // (each buffer is rendered only where a flag asks for it: the first-hit one, the chain one of --aov-chain's K, and the
+            // full-depth chain one that steers the filter -- the same buffer where K says the tracing depth)
+            std::vector<double> aov, chain, guides;
+            if (config.aov || (config.denoise && !chain_guides)) aov = render_feature_buffers(s, job_config, config.seed, 0);
+            if (config.aov_chain) {
+                flag = "--aov-chain";
+                chain.resize(w * h * FLUX_AOV_CHANNELS);
+                render_aov_chain(s, job_config, config.seed, 0, (uint32_t)config.aov_chain_limit, chain);
+            }
+            if (chain_guides) {
+                flag = "--denoise";
+                if (config.aov_chain && (config.aov_chain_limit == 0 || config.aov_chain_limit == job_config.max_trace_depth)) {
+                    guides = chain;
+                } else {
+                    guides.resize(w * h * FLUX_AOV_CHANNELS);
+                    render_aov_chain(s, job_config, config.seed, 0, 0, guides);
+                }
+            }
+            const std::vector<double> &steer = chain_guides ? guides : aov;
             const auto write = [&](const char *name, const std::vector<double> &img) {
                 const std::string path = config.outdir + "/" + s.scene_name + "." + name + ".ppm";
                 if (flux_write_ppm(path.c_str(), img.data(), w, h, nullptr) != FLUX_OK) throw FluxError(FLUX_E_IO, flux_last_error());
@@ -321,12 +374,17 @@ int main(int argc, char **argv) {
                     {AovKind::Albedo, "albedo"}, {AovKind::Normal, "normal"}, {AovKind::Depth, "depth"}, {AovKind::Coverage, "coverage"}};
                 for (const auto &o : outs) write(o.name, aov_image(aov.data(), w, h, o.kind));
             }
+            if (config.aov_chain) {
+                const struct { AovKind kind; const char *name; } outs[] = {{AovKind::Albedo, "chain_albedo"}, {AovKind::Normal, "chain_normal"},
+                                                                       {AovKind::Depth, "chain_depth"}, {AovKind::Coverage, "chain_coverage"}};
+                for (const auto &o : outs) write(o.name, aov_image(chain.data(), w, h, o.kind));
+            }
             if (config.denoise) {
                 flag = "--denoise";
                 if (config.denoise_variance == "measured")
-                    write("denoised", denoise_moments_frame(render_moments(s, job_config, config.seed, 0), aov, w, h, 0));
+                    write("denoised", denoise_moments_frame(render_moments(s, job_config, config.seed, 0), steer, w, h, 0));
                 else
-                    write("denoised", denoise_frame(image_builder.image, aov, w, h, 0));
+                    write("denoised", denoise_frame(image_builder.image, steer, w, h, 0));
             }
         } catch (const FluxError &e) {
             std::fprintf(stderr, "error: %s: %s\n", flag, e.what());

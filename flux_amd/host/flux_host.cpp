@@ -264,6 +264,23 @@ std::vector<double> render_feature_buffers(const SceneData &scene_data, const Jo
     return aov;
 }
 
+void render_aov_chain(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device, uint32_t max_chain,
+                      std::vector<double> &out) {
+    const size_t w = scene_data.output_settings.image_width, h = scene_data.output_settings.image_height;
+    if (out.size() != w * h * FLUX_AOV_CHANNELS)
+        throw FluxError(FLUX_E_INVALID, "render_aov_chain: the buffer holds " + std::to_string(out.size()) + " doubles, the frame needs " +
+                                            std::to_string(w * h * FLUX_AOV_CHANNELS));
+    if (max_chain > config.max_trace_depth)
+        throw FluxError(FLUX_E_INVALID, "render_aov_chain: max_chain " + std::to_string(max_chain) + " exceeds max_trace_depth " +
+                                            std::to_string(config.max_trace_depth));
+    if (w == 0 || h == 0) throw FluxError(FLUX_E_INVALID, "render_aov_chain: an empty frame");
+    int rc = FLUX_OK;
+    const CtxPtr ctx = create_ctx(scene_data, config, seed, device, &rc);
+    if (!ctx) throw FluxError(rc, flux_last_error());
+    rc = flux_render_aov_chain_rows(ctx.get(), 0, h - 1, max_chain, out.data());
+    if (rc != FLUX_OK) throw FluxError(rc, flux_last_error());  // (the message is copied before the context goes)
+}
+
 std::vector<double> render_moments(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device) {
     int rc = FLUX_OK;
     const CtxPtr ctx = create_ctx(scene_data, config, seed, device, &rc);

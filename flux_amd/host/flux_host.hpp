@@ -385,6 +385,12 @@ struct AbiScene {
 // flux_render_aov_rows over the frame, the context dropped.  Throws FluxError with the library's message.
 std::vector<double> render_feature_buffers(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device);
 
+// The same buffers at the first non-specular hit (include/flux_abi.h flux_render_aov_chain_rows), chains of at most `max_chain`
+// segments (0: max_trace_depth), into `out`, which must hold width * height * FLUX_AOV_CHANNELS doubles: a buffer of another size and
+// a max_chain beyond the job's max_trace_depth are refused before any context exists.  Throws FluxError with the library's message.
+void render_aov_chain(const SceneData &scene_data, const JobConfiguration &config, uint64_t seed, int device, uint32_t max_chain,
+                      std::vector<double> &out);
+
 // One channel group of such a frame as an image for flux_write_ppm: [H][W] RGB in [0, 1].
 //   Albedo    min(1, x) per channel
 //   Normal    0.5 + 0.5 n / |n| (the zero vector: 0.5)

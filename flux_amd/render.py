@@ -142,6 +142,33 @@ class Renderer:
         _lib.check(_lib.lib.flux_render_aov_rows_device(self._handle(), first_row, row_stride, num_rows,
                                                         C.c_void_p(d_out_ptr), C.c_void_p(stream)))
 
+    # -- feature buffers at the first non-specular hit ---------------------------
+    def render_aov_chain(self, max_chain: int = 0, row_start: int = 0, row_end=None) -> np.ndarray:
+        """render_aov()'s buffers taken where each sample's chain of Reflective / Dielectric bounces ends, [rows, W, 8]:
+        flux_render_aov_chain_rows.  max_chain: the most segments a chain has (0: max_trace_depth; 1 is render_aov() bit for bit)."""
+        if row_end is None:
+            row_end = self.height - 1
+        if row_start < 0 or row_end < row_start:
+            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        self._check_max_chain(max_chain)
+        out = np.empty((row_end - row_start + 1, self.width, _lib.AOV_CHANNELS), dtype=np.float64)
+        _lib.check(_lib.lib.flux_render_aov_chain_rows(self._handle(), row_start, row_end, max_chain,
+                                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    @staticmethod
+    def _check_max_chain(max_chain):
+        # (the parameter is a uint32_t: ctypes would wrap 2**32 to 0, which means the full depth)
+        if not 0 <= int(max_chain) <= 0xFFFFFFFF:
+            raise _lib.FluxError(_lib.E_INVALID, f"max_chain {max_chain} is outside 0 .. 2**32 - 1 (0 means max_trace_depth)")
+
+    def render_aov_chain_device(self, first_row: int, row_stride: int, num_rows: int, d_out_ptr: int, max_chain: int = 0,
+                                stream: int = 0):
+        """Asynchronous device-resident form (see flux_render_aov_chain_rows_device): num_rows * W * 8 doubles."""
+        self._check_max_chain(max_chain)
+        _lib.check(_lib.lib.flux_render_aov_chain_rows_device(self._handle(), first_row, row_stride, num_rows, max_chain,
+                                                              C.c_void_p(d_out_ptr), C.c_void_p(stream)))
+
     # -- per-pixel sample moments ------------------------------------------------
     def render_moments(self, row_start: int = 0, row_end=None) -> np.ndarray:
         """The frame and its measured variance for rows [row_start, row_end] inclusive (default: the frame), [rows, W, 8]:
@@ -207,15 +234,20 @@ class Renderer:
                                                              C.c_void_p(stream)))
         self._keep_adaptive_info(info)
 
-    def render_denoised(self, variance: str = "spatial", **params) -> np.ndarray:
+    def render_denoised(self, variance: str = "spatial", guides: str = "first", **params) -> np.ndarray:
         """The denoised frame on this renderer's device; `params` are flux_amd.denoise's.  variance="spatial" (the default):
         render_frame() + render_aov() + flux_amd.denoise, which estimates the noise from the frame.  variance="measured":
-        render_moments() + render_aov() + flux_amd.denoise_moments -- one render, whose per-sample variance guides the filter."""
+        render_moments() + render_aov() + flux_amd.denoise_moments -- one render, whose per-sample variance guides the filter.
+        guides="first" (the default): render_aov(); guides="chain": render_aov_chain(), the features behind mirrors and glass."""
+        if guides not in ("first", "chain"):
+            raise _lib.FluxError(_lib.E_INVALID, f"render_denoised: guides must be 'first' or 'chain', got {guides!r}")
+        if variance not in ("spatial", "measured"):
+            raise _lib.FluxError(_lib.E_INVALID, f"render_denoised: variance must be 'spatial' or 'measured', got {variance!r}")
+        frame = self.render_frame() if variance == "spatial" else self.render_moments()
+        aov = self.render_aov() if guides == "first" else self.render_aov_chain()
         if variance == "spatial":
-            return denoise(self.render_frame(), self.render_aov(), device=self.device, **params)
-        if variance == "measured":
-            return denoise_moments(self.render_moments(), self.render_aov(), device=self.device, **params)
-        raise _lib.FluxError(_lib.E_INVALID, f"render_denoised: variance must be 'spatial' or 'measured', got {variance!r}")
+            return denoise(frame, aov, device=self.device, **params)
+        return denoise_moments(frame, aov, device=self.device, **params)
 
     def debug_shade(self, origins, directions, depth: int = 1, set_index: int = 0, sample_index: int = 0):
         """Scene::shade on the device for the given rays (flux_debug_shade): (rgb [n,3], first-hit index [n], t [n])."""

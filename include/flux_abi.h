@@ -272,6 +272,40 @@ int flux_render_aov_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, do
 int flux_render_aov_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows,
                                 void *d_out, void *hip_stream);
 
+/* Feature buffers at the first NON-SPECULAR hit (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol):
+ * the same FLUX_AOV_CHANNELS doubles per pixel, taken where a sample's chain of delta bounces ends, so that what a mirror or a pane
+ * of glass shows has edges a denoiser can follow.  DESIGN.md section 5i; tests/aov_chain_spec.py states the rule in numpy.
+ * The frame is that of the first-hit buffers above: a context that holds every sample set, pixel (row, col), set =
+ * row_perm(row)[col] % S, N = sample_root^2, the context's arithmetic (the routing to STRICT for non-unit plane normals included)
+ * and traversal.  max_chain sets the chain limit K: 0 means K = max_trace_depth, 1..max_trace_depth is K itself, a larger value is
+ * FLUX_E_INVALID (the hemisphere table holds no u for a deeper segment, and the render never traces one).  Per sample i:
+ *   1. the primary ray the render builds for (row, col, set, i); k = 1, tsum = 0;
+ *   2. the nearest hit exactly as the render finds it: Scene::hit with T_MIN, ties to the lowest YAML index, triangles after all
+ *      shapes, and in FAST the skip of the sphere a segment leaves outwards;
+ *   3. a miss ends the chain uncovered: albedo fold(background), normal 0, no depth term;
+ *   4. a hit on a Reflective or a Dielectric with k < K bounces, bit for bit as the render kernels bounce at that vertex -- the
+ *      mirror direction with weight reflect_amount * reflect_color and scale (n.wi) / pdf as the render evaluates it; for a
+ *      Dielectric u = hemi_sets[set][k-1][i].z and the Fresnel choice of FLUX_MAT_DIELECTRIC, weight 1 for a reflection and
+ *      transmit_color for a transmission --, then tsum += t, k += 1, and step 2 again;
+ *   5. any other hit ends the chain covered -- Matte, Glossy, Emissive, and a Reflective or Dielectric reached at k == K, whose own
+ *      a(m) is used: albedo fold(a(m)) with a(m) as above and the emissive facing test taken with THIS segment's direction, the
+ *      shading normal of this hit by the rule above (in world space, not unfolded through the mirror), depth term tsum + t.
+ * fold(x) is the render's fold of the path's bounces applied to x in place of the end-of-path radiance: in STRICT (f * x) * s from
+ * the deepest bounce outward, in FAST the front-to-back throughput product times x.  Nothing is clamped: a NaN scale at a grazing
+ * mirror hit passes through, and so does a plane's +inf hit.  GlossyReflective is NOT followed: it is a sampled lobe of finite
+ * width.  The pixel's doubles, their means and the fixed combination order are those of the first-hit buffers.
+ * Three identities: max_chain = 1 gives flux_render_aov_rows bit for bit; so does every max_chain on a scene without Reflective
+ * and Dielectric; and on a scene whose other materials are all Emissive, with max_chain = 0, the albedo of a pixel none of whose
+ * samples ends on a delta material at k == K is the unclamped mean radiance of the frame (which is why it carries the throughput).
+ * Host entry: rows [row_start, row_end] inclusive, (row_end-row_start+1) * image_width * FLUX_AOV_CHANNELS doubles, synchronous,
+ * staged through a device buffer of its own.  Argument checks as flux_render_aov_rows, plus the max_chain range. */
+int flux_render_aov_chain_rows(flux_ctx *ctx, uint64_t row_start, uint64_t row_end, uint32_t max_chain, double *out);
+/* Device-resident, asynchronously on `hip_stream`; argument checks as flux_render_aov_rows_device, plus the max_chain range.  One
+ * kernel beside the render kernels, with no atomics and no effect on flux_ctx_stats; its launch is recorded between the context's
+ * two events.  A job whose STRICT stacks exceed the LDS of a block is refused as flux_render_moments_rows_device refuses it. */
+int flux_render_aov_chain_rows_device(flux_ctx *ctx, uint64_t first_row, uint64_t row_stride, uint64_t num_rows, uint32_t max_chain,
+                                      void *d_out, void *hip_stream);
+
 /* A feature-guided a-trous denoiser for low-sample frames (extension; FLUX_ABI_VERSION unchanged -- a client detects support by
  * the symbol).  DESIGN.md section 5f; tests/denoise_spec.py states the same filter in numpy.
  * Inputs: rgb [H][W][3] as flux_render_rows returns it, aov [H][W][FLUX_AOV_CHANNELS] as flux_render_aov_rows returns it, of
