@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "flux_amd", "csrc")
 HIP_SOURCES = ["abi.hip", "multi.hip", "tables.hip", "render.hip", "denoise.hip", "adaptive.hip", "bvh.cpp", "scene_build.cpp", "launch_plan.cpp"]
 HIP_HEADERS = ["flux_ctx.h", "scene_build.h", "joining_thread.h", "flux_device.h", "flux_plan.h", "flux_rng.h", "flux_tables.h", "flux_bvh.h", "flux_math.h",
-               "flux_math_coeffs.h", "flux_env_verdict.h", "flux_plane_axis.h", "flux_moments.h", "render_body.inc", "aov_body.inc", "moments_body.inc", "adaptive_body.inc", "aov_chain_body.inc"]
+               "flux_math_coeffs.h", "flux_env_verdict.h", "flux_plane_axis.h", "flux_sample_order.h", "flux_moments.h", "render_body.inc", "aov_body.inc", "moments_body.inc", "adaptive_body.inc", "aov_chain_body.inc"]
 HIP_LIB = os.path.join(ROOT, "flux_amd", "libflux_hip.so")
 
 # -ffp-contract=off is the translation units' default: host arithmetic, the table generator and the STRICT render kernels keep
@@ -42,7 +42,7 @@ def _hipcc():
 
 # the sources that become DEVICE code (the render / table kernels): their hash is the `kernels:` half of flux_build_id()
 KERNEL_FILES = ["render.hip", "render_body.inc", "aov_body.inc", "moments_body.inc", "adaptive_body.inc", "aov_chain_body.inc", "tables.hip", "denoise.hip", "adaptive.hip", "flux_device.h", "flux_plan.h", "flux_bvh.h", "flux_math.h",
-                "flux_math_coeffs.h", "flux_rng.h", "flux_tables.h", "flux_env_verdict.h", "flux_plane_axis.h", "flux_moments.h"]
+                "flux_math_coeffs.h", "flux_rng.h", "flux_tables.h", "flux_env_verdict.h", "flux_plane_axis.h", "flux_sample_order.h", "flux_moments.h"]
 
 
 def build_id(extra_flags=()):

@@ -255,6 +255,9 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     std::vector<unsigned char> lobe_entries;
     const size_t lobe_bytes = lobe_frame_table(h, lobe_entries);
     if (lobe_bytes) alloc(c->d_lobe, lobe_bytes);
+    alloc(c->d_order, own * c->N * sizeof(uint32_t));
+    alloc(c->d_pix_o, pix_bytes);
+    alloc(c->d_disc_o, pix_bytes);
     alloc(c->d_setrows, own * sizeof(DevSetRows));
     alloc(c->d_rowperm, perm_bytes);
     alloc(c->d_invperm, perm_bytes);
@@ -282,6 +285,14 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         if (e == hipSuccess && c->d_lobe)
             e = generate_lobe_frame_table(reinterpret_cast<const DevHitRec *>(c->d_fscene + h.fs.rec), (int)lobe_entries.size(), c->d_lobe, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        // the split kernel's sample order, from the hemi rows just written; FLUX_SAMPLE_ORDER=0 fills it with the identity (tests and
+        // A/B runs: the same kernel code then traces a pixel's samples in index order)
+        const char *order_env = std::getenv("FLUX_SAMPLE_ORDER");
+        if (e == hipSuccess)
+            e = generate_sample_order(c->sets.count, c->D, c->n, c->d_hemi, c->d_order, order_env && std::atoi(order_env) == 0, nullptr, tab_ms);
+        // ... and the two primary-ray tables in that order, for phase A's consecutive reads (under the switch: plain copies)
+        if (e == hipSuccess)
+            e = generate_order_copies((size_t)c->sets.count * c->N, c->N, c->d_order, c->d_pix, c->d_disc, c->d_pix_o, c->d_disc_o, nullptr);
     }
     laps.lap(FLUX_CREATE_MS_TABLES);
     // the generator's scratch (the permutations of every grid: 262 MB at 16384 spp) is allocation, not table work
@@ -297,6 +308,9 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
             rows[m].disc = c->d_disc + m * c->N;
             rows[m].hemi = c->d_hemi + m * c->D * c->N * kHemiDoubles;
             rows[m].gloss = c->d_gloss + m * c->N * 4;
+            rows[m].order = c->d_order + m * c->N;
+            rows[m].pix_o = c->d_pix_o + m * c->N;
+            rows[m].disc_o = c->d_disc_o + m * c->N;
             rows[m].glossx = gx_stride ? c->d_glossx + m * c->N * (size_t)(gx_stride / 16) : nullptr;
         }
         copy(c->d_setrows, rows);
@@ -987,6 +1001,15 @@ int flux_ctx_copy_table(flux_ctx *ctx, int which, double *out, uint64_t out_doub
         if (e == hipSuccess) e = hipMemcpy(out, tmp, total * sizeof(double), hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(FLUX_E_DEVICE, "hemi copy: %s", hipGetErrorString(e));
         return FLUX_OK;
+    }
+    if (which == FLUX_TABLE_ORDER) {  // (sample indices, below 2^24: exact as doubles)
+        if (out_doubles < SN) return fail(FLUX_E_INVALID, "output too small: need %zu doubles", SN);
+        return flux::no_throw([&]() -> int {
+            std::vector<uint32_t> tmp(SN);
+            HIP_TRY(hipMemcpy(tmp.data(), ctx->d_order, SN * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < SN; k++) out[k] = (double)tmp[k];
+            return FLUX_OK;
+        });
     }
     return fail(FLUX_E_INVALID, "unknown table %d", which);
 }

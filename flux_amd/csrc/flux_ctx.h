@@ -151,6 +151,8 @@ struct flux_ctx {
     flux::DevBuf<int32_t> d_gxoff;    // RenderParams::gx_off, with d_glossx
     flux::DevBuf<double> d_tput;      // RenderParams::tput, or empty
     flux::DevBuf<double> d_lobe;      // RenderParams::lobe_frame, or empty
+    flux::DevBuf<double2> d_pix_o, d_disc_o;  // [slots held][N]: pix and disc in the order of d_order, what the split kernel's phase A reads
+    flux::DevBuf<uint32_t> d_order;  // [slots held][N]: the split kernel's sample order (flux_sample_order.h)
     flux::DevBuf<flux::DevSetRows> d_setrows;  // per table slot: where the set's rows of the sample tables start
     flux::DevBuf<int32_t> d_rowperm, d_invperm;
     flux::DevBuf<unsigned long long> d_stats;

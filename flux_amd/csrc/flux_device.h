@@ -160,7 +160,8 @@ struct DevSetRows {
     const double2 *pix, *disc;
     const double *hemi, *gloss;
     const double2 *glossx;  // the set's rows of RenderParams::glossx, or nullptr
-    const void *pad[3];
+    const uint32_t *order;  // the set's row of the split kernel's sample order (flux_sample_order.h): a permutation of 0 .. N-1
+    const double2 *pix_o, *disc_o;  // pix_o[k] = pix[order[k]], disc_o[k] = disc[order[k]]
 };
 static_assert(sizeof(DevSetRows) == 64, "DevSetRows layout");
 

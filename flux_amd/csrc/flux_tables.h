@@ -13,6 +13,15 @@ namespace flux {
 hipError_t generate_tables(uint64_t seed, uint32_t S, SetRange sets, uint32_t D, uint32_t n, uint32_t H,
                            double2 *pix, double2 *disc, double *hemi, int32_t *rowperm, int32_t *invperm,
                            hipStream_t stream, double *phase_ms = nullptr);
+// The split kernel's sample order (flux_sample_order.h) of `sets` held sets: order[slot][k] = the k-th sample index phase A traces, from
+// depth row 0 of the slot's hemi rows alone -- so a set's row is the same in whichever context holds it.  Sorted on the device
+// (a stable segmented radix sort of (key, index) pairs: a permutation of 0 .. n n - 1 by construction), then dealt.  identity:
+// order[slot][k] = k (FLUX_SAMPLE_ORDER=0).  Synchronises `stream`; phase_ms as generate_tables.
+hipError_t generate_sample_order(uint32_t sets, uint32_t D, uint32_t n, const double *hemi, uint32_t *order, bool identity,
+                                 hipStream_t stream, double *phase_ms = nullptr);
+// pix_o[t] = pix[set's row][order[t]], disc_o likewise, for the `count` = sets * N held samples (DevSetRows::pix_o, disc_o).  Synchronises `stream`.
+hipError_t generate_order_copies(size_t count, uint32_t N, const uint32_t *order, const double2 *pix, const double2 *disc, double2 *pix_o,
+                                 double2 *disc_o, hipStream_t stream);
 // One set of a samplers-crate generator (0 regular, 1 jittered, 2 multi-jittered, 3 correlated MJ) and,
 // if d_hemi != nullptr, its to_hemisphere(.., 0.0) image [N][3].  Synchronises `stream`.
 hipError_t generate_sampler_grid(int kind, uint64_t seed, uint32_t n, double *d_xy, double *d_hemi,

@@ -2553,20 +2553,27 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
             if (run_a) {
                 FLUX_TRIP(P, 12);
                 FLUX_CENSUS(P, 0);
-                const uint32_t ia = next + lane;
-                const bool valid = ia < s_hi;
-                const unsigned long long valid_m = ballot64(ia < s_hi);
+                // the batch's samples: slots next .. next+63 of the set's processing order (flux_sample_order.h: a permutation of 0 .. N-1,
+                // so every sample is still traced once).  `valid`, the cursor and the primary ray's two tables (the set's copies in this order,
+                // DevSetRows::pix_o / disc_o) go by the SLOT; the shading step's tables, the parked hit's sample word and the statistics by
+                // the sample index ia read from it.  Lanes past the slice's end read the slice's
+                // last slot (see the ray-queue loop below).
+                const uint32_t slot_a = next + lane;
+                const bool valid = slot_a < s_hi;
+                const unsigned long long valid_m = ballot64(slot_a < s_hi);
+                const uint32_t kc_a = slot_a < s_hi ? slot_a : s_hi - 1u;
+                const uint32_t ia = gather_global<uint32_t>(set_rows_of(P, set_p).order, kc_a << 2);
                 next = (s_hi - next) > 64u ? next + 64u : s_hi;
                 bool cont = false;
-                const double2 *pix = set_rows_of(P, set_p).pix;
-                const double2 *disc = set_rows_of(P, set_p).disc;
+                // (the two primary-ray tables in processing order: consecutive slots, consecutive 16-byte entries)
+                const double2 *pix = set_rows_of(P, set_p).pix_o;
+                const double2 *disc = set_rows_of(P, set_p).disc_o;
                 const char *pxc_b = reinterpret_cast<const char *>(P.pxc);
                 const PixelConsts PX = PixelConsts{*reinterpret_cast<const double *>(pxc_b + ((uint32_t)col << 3)),
                                                    *reinterpret_cast<const double *>(pxc_b + ((uint32_t)(P.img_w + row) << 3)), P.fwx, P.fwy, P.fwz};
                 {
-                    const uint32_t ic = ia < s_hi ? ia : s_hi - 1u;  // (lanes past the slice's end: see the loop below)
-                    p.sq = gather_global_d2(pix, ic << 4);
-                    p.r = primary_ray_px(P, PX, p.sq, gather_global_d2(disc, ic << 4));
+                    p.sq = gather_global_d2(pix, kc_a << 4);
+                    p.r = primary_ray_px(P, PX, p.sq, gather_global_d2(disc, kc_a << 4));
                     if (STATS && valid) {
                         st.c[0]++;
                         st.c[1]++;
@@ -2780,9 +2787,16 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 // ---- phase A: primary segments of samples next .. next+63
                 FLUX_TRIP(P, 12);
                 FLUX_CENSUS(P, 0);
-                const uint32_t ia = next + lane;
-                const bool valid = ia < s_hi;
-                const unsigned long long valid_m = ballot64(ia < s_hi);
+                // (the batch's samples by the set's processing order, as in the hit-queue loop above: the slot decides `valid` and the
+                // cursor, the sample index ia everything downstream)
+                const uint32_t slot_a = next + lane;
+                const bool valid = slot_a < s_hi;
+                const unsigned long long valid_m = ballot64(slot_a < s_hi);
+                // Lanes past the slice's end (the last pass of a slice only) take the slice's last slot: every lane has a ray, there is no
+                // masked region and no default ray -- seven 64-bit moves a pass -- to define for the others; what such a lane computes is
+                // never used (`valid` gates the shading step, `valid_m` the votes).
+                const uint32_t kc_a = slot_a < s_hi ? slot_a : s_hi - 1u;
+                const uint32_t ia = gather_global<uint32_t>(set_rows_of(P, set_p).order, kc_a << 2);
                 next = (s_hi - next) > 64u ? next + 64u : s_hi;
                 bool cont = false;
                 Path pa;
@@ -2790,8 +2804,9 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 pa.sq = make_double2(0.5, 0.5);
                 pa.r = Ray{0, 0, 0, 0, 0, 1};
                 // (the pixel's rows of the two sample tables: addresses formed here, not held across the loop)
-                const double2 *pix = set_rows_of(P, set_p).pix;
-                const double2 *disc = set_rows_of(P, set_p).disc;
+                // (the two primary-ray tables in processing order: consecutive slots, consecutive 16-byte entries)
+                const double2 *pix = set_rows_of(P, set_p).pix_o;
+                const double2 *disc = set_rows_of(P, set_p).disc_o;
                 // primary_ray's per-pixel and per-frame constants, read where they are used (scalar loads from the context's tables and the
                 // kernel arguments): held in scalar registers across the pass loop they were 10 of the 29 registers the allocator spilled
                 // to VGPR lanes, and came back through v_readlane_b32 in every ray-generation step
@@ -2800,12 +2815,8 @@ __global__ __launch_bounds__(64 * FLUX_MAX_WAVES_PER_PIXEL, FLUX_WPE_SPLIT) void
                 const PixelConsts PX = PixelConsts{*reinterpret_cast<const double *>(pxc_b + ((uint32_t)col << 3)),
                                                    *reinterpret_cast<const double *>(pxc_b + ((uint32_t)(P.img_w + row) << 3)), P.fwx, P.fwy, P.fwz};
                 {
-                    // Lanes past the slice's end (the last pass of a slice only) take the slice's last sample: every lane has a ray, there
-                    // is no masked region and no default ray -- seven 64-bit moves a pass -- to define for the others; what such a lane
-                    // computes is never used (`valid` gates the shading step, `valid_m` the votes).
-                    const uint32_t ic = ia < s_hi ? ia : s_hi - 1u;
-                    pa.sq = gather_global_d2(pix, ic << 4);
-                    pa.r = primary_ray_px(P, PX, pa.sq, gather_global_d2(disc, ic << 4));
+                    pa.sq = gather_global_d2(pix, kc_a << 4);
+                    pa.r = primary_ray_px(P, PX, pa.sq, gather_global_d2(disc, kc_a << 4));
                     if (STATS && valid) {
                         st.c[0]++;
                         st.c[1]++;

@@ -326,7 +326,7 @@ class Renderer:
         S = len(range(self.set_share[0], self.width, self.set_share[1]))  # the sets held, in slot order
         N = self.config.sample_root ** 2
         D = self.config.max_trace_depth
-        shape = (S, N, 2) if which in (_lib.TABLE_PIXEL, _lib.TABLE_DISC) else (S, D, N, 3)
+        shape = (S, N, 2) if which in (_lib.TABLE_PIXEL, _lib.TABLE_DISC) else (S, N) if which == _lib.TABLE_ORDER else (S, D, N, 3)
         out = np.empty(shape, dtype=np.float64)
         _lib.check(_lib.lib.flux_ctx_copy_table(self._handle(), which, out.ctypes.data_as(C.POINTER(C.c_double)),
                                                 out.size))

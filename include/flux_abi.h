@@ -571,6 +571,9 @@ int flux_ctx_launch_plan(flux_ctx *ctx, uint64_t num_rows, uint64_t num_sets, in
 #define FLUX_TABLE_PIXEL 0
 #define FLUX_TABLE_DISC 1
 #define FLUX_TABLE_HEMI 2
+/* 3 = the split kernel's sample order [S][N]: the k-th sample index a pixel of the set traces, as doubles (a permutation of 0 .. N-1
+ * per set; the identity under FLUX_SAMPLE_ORDER=0) */
+#define FLUX_TABLE_ORDER 3
 int flux_ctx_copy_table(flux_ctx *ctx, int which, double *out, uint64_t out_doubles);
 int flux_ctx_copy_row_perm(flux_ctx *ctx, uint64_t row, int32_t *out, uint64_t out_len);
 int flux_ctx_camera_basis(flux_ctx *ctx, double uvw[9]); /* CameraBasis::new scene.rs:28-35 */
