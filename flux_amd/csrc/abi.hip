@@ -15,7 +15,6 @@
 #include <memory>
 #include <new>
 #include <algorithm>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -25,6 +24,7 @@
 #include "flux_math_coeffs.h"  // kExp2Poly -> RenderParams::exp2c
 
 #include "flux_ctx.h"
+#include "flux_switches.h"
 
 namespace flux {
 
@@ -168,6 +168,11 @@ int build_host(const flux_scene_desc &scene, HostScene &host) {
 int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int device, uint64_t first_set, uint64_t set_stride,
            CreateLaps &laps, flux_ctx **out) {
     *out = nullptr;
+    // the creation switches (flux_switches.h), each named where it acts below
+    const bool no_sample_tables = switch_off(kEnvSampleTables);
+    const bool no_tput_table = switch_off(kEnvThroughputTable);
+    const bool identity_order = switch_off(kEnvSampleOrder);
+    const bool no_plane_axis = switch_off(kEnvPlaneAxis);
     DeviceGuard guard(device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", device);
     (void)hipFree(nullptr);  // the runtime's lazy per-device initialisation, booked under its own word (zero once the process has used the device)
@@ -225,8 +230,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     alloc(c->d_gloss, pix_bytes * 2);
     // the glossy lobe's angle table (RenderParams::glossx) where the host scene assigned its exponents slots; FLUX_SAMPLE_TABLES=0
     // builds the context without it (tests and A/B runs: every glossy bounce then keeps the arithmetic in the loop)
-    const char *tables_env = std::getenv("FLUX_SAMPLE_TABLES");
-    const int gx_stride = (tables_env && std::atoi(tables_env) == 0) ? 0 : h.rp.gx_stride;
+    const int gx_stride = no_sample_tables ? 0 : h.rp.gx_stride;
     if (gx_stride) {
         alloc(c->d_glossx, own * c->N * (size_t)gx_stride);
         alloc_copy(c->d_gxoff, h.gx_off);
@@ -242,12 +246,11 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         RenderParams job = h.rp;
         job.nsamp = c->N;
         job.max_depth = (int32_t)c->D;
-        const char *tput_env = std::getenv("FLUX_THROUGHPUT_TABLE");
         if (tput_table_bytes(job, &tput_bits)) {
             std::vector<double> tput;
             build_tput_table(h, tput_bits, (int)c->D, tput);
             tput_finite = tput_products_finite(h, tput_bits, (int)c->D, tput);
-            if (!(tput_env && std::atoi(tput_env) == 0)) alloc_copy(c->d_tput, tput);
+            if (!no_tput_table) alloc_copy(c->d_tput, tput);
         }
     }
     // the lobe-frame table (RenderParams::lobe_frame): 48 B per hit record, filled by the device below; FLUX_LOBE_FRAMES=0 builds the
@@ -287,9 +290,8 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         // the split kernel's sample order, from the hemi rows just written; FLUX_SAMPLE_ORDER=0 fills it with the identity (tests and
         // A/B runs: the same kernel code then traces a pixel's samples in index order)
-        const char *order_env = std::getenv("FLUX_SAMPLE_ORDER");
         if (e == hipSuccess)
-            e = generate_sample_order(c->sets.count, c->D, c->n, c->d_hemi, c->d_order, order_env && std::atoi(order_env) == 0, nullptr, tab_ms);
+            e = generate_sample_order(c->sets.count, c->D, c->n, c->d_hemi, c->d_order, identity_order, nullptr, tab_ms);
         // ... and the two primary-ray tables in that order, for phase A's consecutive reads (under the switch: plain copies)
         if (e == hipSuccess)
             e = generate_order_copies((size_t)c->sets.count * c->N, c->N, c->d_order, c->d_pix, c->d_disc, c->d_pix_o, c->d_disc_o, nullptr);
@@ -339,10 +341,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     rp.lobe_frame = c->d_lobe;
     // the first plane's axis (RenderParams::plane_axis); FLUX_PLANE_AXIS=0 builds the context without it (tests and A/B runs: both scans
     // then form the first plane's dot products in full)
-    {
-        const char *axis_env = std::getenv("FLUX_PLANE_AXIS");
-        if (axis_env && std::atoi(axis_env) == 0) rp.plane_axis = kPlaneAxisNone;
-    }
+    if (no_plane_axis) rp.plane_axis = kPlaneAxisNone;
     rp.set_rows = c->d_setrows;
     rp.rowperm = c->d_rowperm;
     rp.invperm = c->d_invperm;

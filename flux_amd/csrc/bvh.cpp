@@ -5,6 +5,7 @@
 // f32 so that the device slab test never rejects a box whose triangle the f64 Moeller-Trumbore test
 // would accept.  The traversal must return exactly the brute-force nearest hit (lowest id on ties).
 #include "flux_bvh.h"
+#include "flux_switches.h"
 #include "joining_thread.h"
 
 #include <algorithm>
@@ -289,9 +290,7 @@ void build_bvh(std::vector<DevTri> &tris, std::vector<DevNode> &nodes, BvhInfo &
     // Large meshes are built by several threads (build_inner's fork; FLUX_BUILD_THREADS, default: the hardware's, at most 16): the tree,
     // hence everything that follows from it, is THE SAME as the one-thread build's (tests/bvh_selftest.cpp compares them bit for bit).
     // 1 M triangles on the GPU box's host: 420 ms with one thread (DESIGN.md "Context creation").
-    unsigned threads = std::thread::hardware_concurrency();
-    if (const char *env = std::getenv("FLUX_BUILD_THREADS")) threads = (unsigned)std::max(1, std::atoi(env));
-    threads = std::min(std::max(threads, 1u), 16u);
+    const unsigned threads = build_threads();
     int fork = 0;
     if (tris.size() >= 65536)
         while ((1u << fork) < 2u * threads && fork < 6) fork++;  // about two leaf builders per thread (splits are not exactly even)

@@ -29,6 +29,7 @@
 #include "../../include/flux_abi.h"
 #include "flux_ctx.h"
 #include "flux_math.h"
+#include "flux_switches.h"
 
 namespace flux {
 namespace denoise {
@@ -397,8 +398,7 @@ static hipError_t launch(Frame f, int levels, bool moments, uint64_t width, uint
         hipLaunchKernelGGL(denoise_pack_kernel<false>, grid, block, 0, stream, f, d_in, d_aov);
         hipLaunchKernelGGL(denoise_variance_kernel, grid, block, 0, stream, f);
     }
-    const char *e = std::getenv("FLUX_DENOISE_LDS_LEVELS");
-    const int lds_levels = e ? std::atoi(e) : kDefaultLdsLevels;
+    const int lds_levels = denoise_lds_levels(kDefaultLdsLevels);
     const int in_stride = moments ? FLUX_MOMENT_CHANNELS : 3;
     for (int k = 0; k < levels; k++) {
         f.step = 1 << k;

@@ -2,9 +2,9 @@
 // Plain host code, compiled once: render.hip launches what it answers, abi.hip checks its LDS against the limit and reports it
 // (flux_ctx_launch_plan), and tests/scene_build_selftest.cpp pins its answers for the shipped scenes on the CPU.
 #include <algorithm>
-#include <cstdlib>
 
 #include "flux_plan.h"
+#include "flux_switches.h"
 #include "../../include/flux_abi.h"
 
 namespace flux {
@@ -56,9 +56,9 @@ static bool plan_hitq(const RenderParams &p, unsigned K, size_t scene_lds, uint3
     const size_t granules = (size_t)128 * K / (4 * FLUX_WPE_SPLIT);
     const size_t per_wave = granules * 1280 > scene_lds + 96 ? (granules * 1280 - scene_lds - 96) / K : 0;
     cap = (uint32_t)(per_wave / kHitQBytesPerSlot) & ~1u;  // (even: the next wave's queue stays 8-byte aligned)
-    if (const char *e = std::getenv("FLUX_SPLIT_HITQ_CAP")) cap = std::min(cap, (uint32_t)std::max(0, std::atoi(e)) & ~1u);
+    cap = hitq_cap(cap);
     th = cap > 64u + FLUX_HITQ_MIN_TAKE ? std::min(64u, cap - 64u) : FLUX_HITQ_MIN_TAKE;
-    if (const char *e = std::getenv("FLUX_SPLIT_HITQ_TAKE_AT")) th = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
+    th = hitq_take_at(th);
     bits = 1;
     while ((1 << bits) < hit_records(p)) ++bits;
     return cap >= 64u + th && bits * p.max_depth <= 32;
@@ -94,8 +94,7 @@ size_t tput_table_bytes(const RenderParams &p, int *bits_out) {
 //   record's material kind (no Dielectric: such a scene has no hit queue, plan_hitq).
 // FLUX_SPLIT_DEPTH_CUT=0 (tests, A/B runs): no cut in either loop.
 int split_cut_depth(const RenderParams &p, const LaunchPlan &L) {
-    if (const char *e = std::getenv("FLUX_SPLIT_DEPTH_CUT"))
-        if (std::atoi(e) == 0) return kNoDepthCut;
+    if (switch_off(kEnvSplitDepthCut)) return kNoDepthCut;
     if (L.hq_cap == 0) return p.max_depth;
     return p.tput_finite != 0 ? p.max_depth : kNoDepthCut;
 }
@@ -166,7 +165,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
         L.typ = split_typ(p) ? 1 : 0;
         L.max32 = p.n_sph <= 32 ? 1 : 0;
         // FLUX_SPLIT_UNIFORM_A=0 (tests, A/B runs): phase A's general shading step for every wave (render_body.inc shade_primary_hits)
-        if (const char *e = std::getenv("FLUX_SPLIT_UNIFORM_A")) L.uniform_a = std::atoi(e) != 0 ? 1 : 0;
+        if (switch_off(kEnvSplitUniformA)) L.uniform_a = 0;
         // The hit queue: as many slots as the LDS leaves a wave at FLUX_WPE_SPLIT waves/SIMD -- the CU's 128 granules of
         // 1280 B shared by 4 * FLUX_WPE_SPLIT / K blocks, less the scene copy and the 96 B of `part` (demo2, K = 4: 25 granules, 7 568 B
         // a wave, 110 slots of 68 B; H = 46).  A scene that leaves fewer than 64 + H slots (H at least FLUX_HITQ_MIN_TAKE), or whose bounce list does not fit 32 bits or does

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "flux_ctx.h"
+#include "flux_switches.h"
 #include "joining_thread.h"
 
 using flux::DeviceGuard;
@@ -55,7 +56,7 @@ Rccl g_rccl;
 bool rccl_load(std::string &err) {
     if (g_rccl.handle) return true;
     std::vector<std::pair<std::string, int>> tries;
-    if (const char *env = std::getenv("FLUX_RCCL_LIB")) tries.push_back({env, RTLD_NOW | RTLD_LOCAL});
+    if (const char *env = flux::rccl_lib()) tries.push_back({env, RTLD_NOW | RTLD_LOCAL});
     // a copy the process has mapped already (SONAME librccl.so.1 in both ROCm's and PyTorch's builds) wins: never a second RCCL
     tries.push_back({"librccl.so.1", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD});
     tries.push_back({"librccl.so", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD});

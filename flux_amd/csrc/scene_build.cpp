@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "flux_switches.h"
 #include "joining_thread.h"
 
 namespace flux {
@@ -304,9 +305,8 @@ void build_fast_scene(const flux_scene_desc &scene, HostScene &h) {
 
 size_t lobe_frame_table(const HostScene &h, std::vector<unsigned char> &has_entry) {
     has_entry.clear();
-    const char *env = std::getenv("FLUX_LOBE_FRAMES");
     const size_t n_rec = (size_t)hit_records(h.rp);
-    if ((env && std::atoi(env) == 0) || n_rec == 0) return 0;
+    if (switch_off(kEnvLobeFrames) || n_rec == 0) return 0;
     const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(h.fscene.data() + h.fs.rec);
     has_entry.resize(n_rec);
     for (size_t k = 0; k < n_rec; k++) has_entry[k] = rec[k].shape_kind != kShapeSphere;
@@ -405,9 +405,7 @@ int build_meshes(const flux_scene_desc &scene, HostScene &h, std::string &error)
             t.mat = (int32_t)(ns + m);
         }
     };
-    unsigned threads = std::thread::hardware_concurrency();
-    if (const char *env = std::getenv("FLUX_BUILD_THREADS")) threads = (unsigned)std::max(1, std::atoi(env));
-    threads = std::min(std::max(threads, 1u), 16u);
+    const unsigned threads = build_threads();
     const size_t n = h.tris.size();
     if (threads > 1 && n >= 65536) {
         std::vector<JoiningThread> pool;

@@ -538,7 +538,7 @@ int flux_ctx_bvh_info(flux_ctx *ctx, uint64_t *out, uint64_t out_words);
  * of an overflow and a zero.  The decision depends on the job alone, not on flux_ctx_set_traversal.
  * [7] FLUX_PLAN_FLAG_*: the instantiation of that kernel the launch runs (0 for FLUX_PLAN_NONE; the word was reserved, 0, before
  * the flags were added).  Which bits can be set depends on the kernel; the environment switches that take a choice away
- * (FLUX_SPLIT_HITQ_CAP, FLUX_THROUGHPUT_TABLE, FLUX_SPLIT_DEPTH_CUT, FLUX_SPLIT_UNIFORM_A, FLUX_PLANE_AXIS) clear its bit. */
+ * (the table that opens flux_amd/csrc/flux_switches.h; DESIGN.md "Environment switches") clear its bit. */
 #define FLUX_PLAN_FLAG_TYP 0x1u          /* SPLIT, BVH4: the instantiation for the usual analytic scene (TYP) */
 #define FLUX_PLAN_FLAG_MAX32 0x2u        /* SPLIT: at most 32 spheres, one group of the sphere filter (MAX32) */
 #define FLUX_PLAN_FLAG_HITQ 0x4u         /* SPLIT: the hit queue (clear: the ray queue) */

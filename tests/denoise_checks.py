@@ -12,6 +12,7 @@ import pytest
 
 import denoise_moments_spec as dms
 import denoise_spec
+import switches
 
 TOL = 1e-10
 # (W, H): one tile; not a tile multiple, several tiles both ways, level-4 taps at +-32 inside the image; one pixel; one column (five
@@ -64,11 +65,11 @@ def lds_tiles_give_the_bits_of_the_gathers(path, flux, monkeypatch, w, h, levels
     """The level kernel exists twice (global gathers; one residue class of the step's lattice per block through LDS, chosen per
     level by FLUX_DENOISE_LDS_LEVELS for the measurement of DESIGN.md §5f): the same taps in the same order."""
     x, aov = path.inputs(w, h)
-    monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", "0")
+    switches.set_switches(monkeypatch, FLUX_DENOISE_LDS_LEVELS=0)
     gathers = path.run(flux, x, aov, levels=levels)
-    monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", "8")
+    switches.set_switches(monkeypatch, FLUX_DENOISE_LDS_LEVELS=8)
     tiles = path.run(flux, x, aov, levels=levels)
-    monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", "2")
+    switches.set_switches(monkeypatch, FLUX_DENOISE_LDS_LEVELS=2)
     mixed = path.run(flux, x, aov, levels=levels)
     assert gathers.tobytes() == tiles.tobytes() == mixed.tobytes()
     path.assert_matches(tiles, path.spec(w, h, levels=levels), x, aov, f"{w}x{h} levels {levels} through LDS")

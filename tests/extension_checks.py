@@ -1,6 +1,6 @@
 """What the suites of the extensions (Disk, Dielectric, Box: tests/test_gpu_*.py and tests/test_*_scene.py) share with each other
 and with the headline, parity and host tests: one render with statistics, a frame put together from set shares, row tiles or
-loopback ranks, a shipped YAML scene shrunk as text, the command-line tools writing a frame, and the build and output of a
+loopback ranks, a shipped YAML scene shrunk as text, the command-line tools writing a frame, and the output of a
 tests/*_host_selftest.cpp.  Plain functions: each test states its own scenes, worlds, modes and assertions."""
 import os
 import re
@@ -9,7 +9,7 @@ import time
 
 import numpy as np
 
-from conftest import ROOT, SCENES
+from conftest import ROOT
 
 HOST = os.path.join(ROOT, "flux_amd", "host")
 
@@ -153,26 +153,7 @@ def node_frame(flux_bin, node_bin, scene, args, outdir, tmp_path, stdout_has=())
     return _ppm(scene, outdir)
 
 
-# ---- tests/<name>_host_selftest.cpp -------------------------------------------------------------------------------------
-
-def build_host_selftest(name, exe, compiler="g++", extra_sources=(), extra_flags=()):
-    """tests/<name>_host_selftest.cpp built against the C++ host layer (CPU only: no compute call) as `exe`."""
-    from flux_amd import build
-    build.build_hip()
-    lib = os.path.join(ROOT, "flux_amd")
-    subprocess.run([compiler, "-O2", "-std=c++17", "-pthread", "-Wall", *extra_flags, "-o", exe,
-                    os.path.join(ROOT, "tests", f"{name}_host_selftest.cpp"), *extra_sources,
-                    *[os.path.join(HOST, s) for s in build.HOST_SOURCES],
-                    "-L" + lib, "-lflux_hip", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
-def run_host_selftest(exe):
-    """The selftest's stdout on the shipped scenes; it must exit with status 0."""
-    out = subprocess.run([exe, SCENES], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
-
+# ---- what a tests/<name>_host_selftest.cpp prints (tests/selftest.py builds and runs it) ---------------------------------------------
 
 def cpp_shapes(stdout):
     """The selftest's `shape <i> <fields>` lines as {i: fields}, typed as shape_fields gives them."""

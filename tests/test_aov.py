@@ -10,7 +10,8 @@ import pytest
 
 import aov_spec
 from conftest import ROOT, SCENES
-from extension_checks import build_host_selftest, host_bins
+import selftest
+from extension_checks import host_bins
 
 KINDS = ("albedo", "normal", "depth", "coverage")
 
@@ -50,10 +51,10 @@ def _parse(stdout):
 
 
 def test_cpp_image_mapping_equals_numpy(tmp_path):
-    exe = build_host_selftest("aov", str(tmp_path / "aov_host_selftest"))
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
-    aov, images, flat = _parse(out.stdout)
+    exe = selftest.build(str(tmp_path / "aov_host_selftest"), "aov_host_selftest.cpp", host=True, compiler="g++")
+    out = selftest.run(exe)
+    assert "all ok" in out
+    aov, images, flat = _parse(out)
     # the buffer holds the singled-out cases
     assert np.isinf(aov[..., aov_spec.DEPTH]).any() and (aov[..., aov_spec.ALBEDO] > 1.0).any()
     assert (np.abs(aov[..., aov_spec.NORMAL]).sum(axis=2) == 0.0).any()
@@ -72,12 +73,9 @@ def test_cpp_image_mapping_equals_numpy(tmp_path):
 def test_cpp_image_mapping_under_asan_and_ubsan(tmp_path):
     """The same program as a stand-alone sanitized executable: the host layer it calls is compiled into it with
     -fsanitize=address,undefined."""
-    exe = build_host_selftest("aov", str(tmp_path / "aov_host_selftest_san"),
-                              extra_flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = selftest.build(str(tmp_path / "aov_host_selftest_san"), "aov_host_selftest.cpp", host=True, flags=selftest.SANITIZE,
+                         compiler="g++")
+    assert "all ok" in selftest.run(exe, env=selftest.sanitize_env())
 
 
 # ---- the command-line tool ------------------------------------------------------------------------------------------------------

@@ -20,7 +20,9 @@ import aov_chain_spec as cs
 import aov_spec
 import path_spec
 from conftest import ROOT, SCENES
-from extension_checks import build_host_selftest, host_bins
+import selftest
+import switches
+from extension_checks import host_bins
 
 MARGIN = 1e-9
 CASE_IDS = [(name, root) for name, (_, roots, _) in cs.CASES.items() for root in roots]
@@ -171,21 +173,16 @@ def test_python_refuses_unknown_guides_and_a_max_chain_outside_32_bits(flux):
 
 def test_cpp_render_aov_chain_refuses_wrong_buffers(tmp_path):
     """It is about host code, so the program is shown no device: the call in order ends in FLUX_E_DEVICE everywhere."""
-    exe = build_host_selftest("aov_chain", str(tmp_path / "aov_chain_host_selftest"))
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    out = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    exe = selftest.build(str(tmp_path / "aov_chain_host_selftest"), "aov_chain_host_selftest.cpp", host=True, compiler="g++")
+    assert "all ok" in selftest.run(exe, env=switches.clean_env(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1"))
 
 
 def test_cpp_render_aov_chain_under_asan_and_ubsan(tmp_path):
     """The same program as a stand-alone sanitized executable: the host layer it calls is compiled into it with
     -fsanitize=address,undefined.  It is about host code, so it is shown no device: the call in order ends in FLUX_E_DEVICE."""
-    exe = build_host_selftest("aov_chain", str(tmp_path / "aov_chain_host_selftest_san"),
-                              extra_flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1", HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
-    out = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = selftest.build(str(tmp_path / "aov_chain_host_selftest_san"), "aov_chain_host_selftest.cpp", host=True, flags=selftest.SANITIZE,
+                         compiler="g++")
+    assert "all ok" in selftest.run(exe, env=selftest.sanitize_env(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1"))
 
 
 # ---- the command-line tool ------------------------------------------------------------------------------------------------------

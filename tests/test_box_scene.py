@@ -7,30 +7,27 @@ import copy
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import yaml
 
 import box_spec
+import selftest as st
 from conftest import ROOT, SCENES
-from extension_checks import build_host_selftest, cpp_shapes, run_host_selftest, shape_fields
+from extension_checks import cpp_shapes, shape_fields
 
 BOX_SCENE = os.path.join(SCENES, "box_room.yml")
 
 
 def _build_selftest(exe, extra=()):
-    """tests/box_host_selftest.cpp against the C++ host layer and the host scene build (CPU only: no compute call).  Host-only
-    clang, as for tests/scene_build_selftest.cpp: plain g++ cannot compile flux_device.h's ext_vector_type records."""
-    csrc = [os.path.join(ROOT, "flux_amd", "csrc", s) for s in ("scene_build.cpp", "bvh.cpp", "launch_plan.cpp")]
-    return build_host_selftest("box", exe, "/opt/rocm/llvm/bin/clang++", csrc,
-                               ("-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", *extra))
+    """tests/box_host_selftest.cpp against the C++ host layer and the host scene build (CPU only: no compute call)."""
+    return st.build(exe, "box_host_selftest.cpp", csrc=("scene_build.cpp", "bvh.cpp", "launch_plan.cpp"), flags=extra)
 
 
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
-    return run_host_selftest(_build_selftest(str(tmp_path_factory.mktemp("box") / "box_host_selftest")))
+    return st.run(_build_selftest(str(tmp_path_factory.mktemp("box") / "box_host_selftest")), SCENES)
 
 
 def test_cpp_selftest(selftest):
@@ -42,12 +39,8 @@ def test_cpp_selftest(selftest):
 def test_cpp_selftest_under_asan_and_ubsan(tmp_path):
     """The same program as a stand-alone sanitized executable: the loaders, the codecs and the host scene build it calls are
     compiled into it with -fsanitize=address,undefined."""
-    exe = _build_selftest(str(tmp_path / "box_host_selftest_san"), ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                                                     "-fno-omit-frame-pointer"))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, SCENES], capture_output=True, text=True, env=env)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = _build_selftest(str(tmp_path / "box_host_selftest_san"), st.SANITIZE)
+    assert "all ok" in st.run(exe, SCENES, env=st.sanitize_env())
 
 
 def test_both_loaders_give_the_same_flux_shapes(flux, selftest):

@@ -11,7 +11,8 @@ import pytest
 import aov_spec
 import denoise_spec
 from conftest import SCENES, small_scene
-from extension_checks import build_host_selftest, host_bins
+import selftest
+from extension_checks import host_bins
 
 H, W = 12, 16
 
@@ -223,9 +224,9 @@ def test_python_names(flux):
 # ---- flux_host::denoise_frame ----------------------------------------------------------------------------------------------------------
 
 def test_cpp_denoise_frame_checks_its_buffers(tmp_path):
-    exe = build_host_selftest("denoise", str(tmp_path / "denoise_host_selftest"))
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    exe = selftest.build(str(tmp_path / "denoise_host_selftest"), "denoise_host_selftest.cpp", host=True, compiler="g++")
+    out = selftest.run(exe)
+    assert "all ok" in out
 
 
 # ---- the command-line tool --------------------------------------------------------------------------------------------------------------

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 import yaml
 
+import selftest as st
 from conftest import ROOT, SCENES
-from extension_checks import build_host_selftest, cpp_shapes, run_host_selftest, shape_fields
+from extension_checks import cpp_shapes, shape_fields
 from dielectric_spec import bounce, fresnel, fresnel_cos
 
 GLASS_SCENE = os.path.join(SCENES, "glass.yml")
@@ -21,7 +22,8 @@ GLASS_SCENE = os.path.join(SCENES, "glass.yml")
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
     """tests/dielectric_host_selftest.cpp built against the C++ host layer (CPU only: no compute call)."""
-    return run_host_selftest(build_host_selftest("dielectric", str(tmp_path_factory.mktemp("dielectric") / "dielectric_host_selftest")))
+    exe = st.build(str(tmp_path_factory.mktemp("dielectric") / "dielectric_host_selftest"), "dielectric_host_selftest.cpp", host=True, compiler="g++")
+    return st.run(exe, SCENES)
 
 
 def test_cpp_selftest(selftest):

@@ -10,8 +10,9 @@ import re
 import pytest
 import yaml
 
+import selftest as st
 from conftest import ROOT, SCENES
-from extension_checks import build_host_selftest, cpp_shapes, run_host_selftest, shape_fields
+from extension_checks import cpp_shapes, shape_fields
 
 DISK_SCENE = os.path.join(SCENES, "disk_light.yml")
 
@@ -19,7 +20,8 @@ DISK_SCENE = os.path.join(SCENES, "disk_light.yml")
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
     """tests/disk_host_selftest.cpp built against the C++ host layer (CPU only: no compute call)."""
-    return run_host_selftest(build_host_selftest("disk", str(tmp_path_factory.mktemp("disk") / "disk_host_selftest")))
+    exe = st.build(str(tmp_path_factory.mktemp("disk") / "disk_host_selftest"), "disk_host_selftest.cpp", host=True, compiler="g++")
+    return st.run(exe, SCENES)
 
 
 def test_cpp_selftest(selftest):

@@ -3,29 +3,22 @@ kernel's own header and holds it against the exact predicate -- the signs of c =
 long double -- over a few million rays: never a wrong "wins" or "loses", every clear case of demo2's environment decided, and every
 decided case one the f64 shortcut decides alike.  The program is run once more as a stand-alone executable under AddressSanitizer
 and UBSan."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import selftest
 
 CHECKS = ("random rays", "around the margins", "special distances", "cap")
 
 
-def _build(exe, extra=()):
-    """Host-only clang and -ffp-contract=off: the header spells out every fused multiply-add."""
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", *extra, "-o", exe,
-                    os.path.join(ROOT, "tests", "env_verdict_selftest.cpp")], check=True)
-    return exe
+def _build(exe, flags=()):
+    """(-ffp-contract=off: the header spells out every fused multiply-add)"""
+    return selftest.build(exe, "env_verdict_selftest.cpp", flags=flags)
 
 
 @pytest.fixture(scope="module")
 def selftest_out(tmp_path_factory):
     exe = _build(str(tmp_path_factory.mktemp("env32") / "env_verdict_selftest"))
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    return selftest.run(exe)
 
 
 def test_verdict_against_the_exact_predicate(selftest_out):
@@ -35,9 +28,5 @@ def test_verdict_against_the_exact_predicate(selftest_out):
 
 
 def test_selftest_under_asan_and_ubsan(tmp_path):
-    exe = _build(str(tmp_path / "env_verdict_selftest_san"),
-                 ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = _build(str(tmp_path / "env_verdict_selftest_san"), selftest.SANITIZE)
+    assert "all ok" in selftest.run(exe, env=selftest.sanitize_env(), timeout=600)

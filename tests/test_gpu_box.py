@@ -12,6 +12,7 @@ import pytest
 import box_spec
 from conftest import SCENES, small_scene
 from extension_checks import box_as_mesh as _as_mesh, cli_frame, host_bins, loopback_frames, math_mode, node_frame, render, row_tiles, set_sharded_frame, small_yaml
+from switches import switches  # noqa: F401 (the fixture)
 from test_box_scene import C0, C1, spec_rays
 
 pytestmark = pytest.mark.gpu
@@ -318,24 +319,23 @@ def test_kernels_agree(flux, scene):
 
 
 @pytest.mark.parametrize("scene", ["box_room", "glass"])
-def test_hit_queue_on_and_off(flux, monkeypatch, scene):
+def test_hit_queue_on_and_off(flux, switches, scene):
     """sample_root 128 on 8 x 6: four waves a pixel, the split kernel with its hit queue (box_room; a scene with glass keeps the ray
     queue either way) against FLUX_SPLIT_HITQ_CAP=0."""
     sd = _box_room(flux, 8, 6) if scene == "box_room" else _glass_room(flux, 8, 6)
-    monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
     a, sa, pa = render(flux, sd, 128, flux.MATH_FAST)
-    monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", "0")
+    switches(FLUX_SPLIT_HITQ_CAP=0)
     b, sb, pb = render(flux, sd, 128, flux.MATH_FAST)
-    monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
+    switches()
     assert pa["kernel"] == pb["kernel"] == flux._lib.PLAN_SPLIT
     assert sa == sb and np.abs(a - b).max() <= 1e-12
     # that the queue was on in the first run shows in the plan's LDS: 4 waves x C slots of 68 B against 4 ray queues of 5 120 B,
     # each beside the records (20 x 96 B and one 32-B scan sphere)
     with flux.Renderer(sd, flux.JobConfiguration(128, 5, 50), seed=1) as r:
         on = r.launch_plan()
-        monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", "0")
+        switches(FLUX_SPLIT_HITQ_CAP=0)
         off = r.launch_plan()
-        monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
+        switches()
     assert on["waves_per_pixel"] == off["waves_per_pixel"] == 4 and off["lds"] == 4 * QUEUE_BYTES + ROOM_RECORDS
     if scene == "box_room":
         slots, rest = divmod(on["lds"] - ROOM_RECORDS, 4 * HITQ_SLOT_BYTES)

@@ -13,6 +13,7 @@ import pytest
 import denoise_checks
 import denoise_moments_spec as dms
 import denoise_spec
+import switches
 from conftest import SCENES, small_scene
 from denoise_checks import MEASURED, SIZES, TOL
 from extension_checks import cli_frame, host_bins, small_yaml
@@ -63,7 +64,7 @@ def test_unusable_pixels_come_back_as_channels_0_to_2_bit_for_bit(flux, monkeypa
     marks = -1000.0 - np.arange(7 * 4, dtype=np.float64).reshape(7, 4)
     mom[~ok, 4:8] = marks
     for lds in ("0", "8"):
-        monkeypatch.setenv("FLUX_DENOISE_LDS_LEVELS", lds)
+        switches.set_switches(monkeypatch, FLUX_DENOISE_LDS_LEVELS=lds)
         got = flux.denoise_moments(mom, aov, levels=levels)
         assert got[~ok].tobytes() == mom[~ok, 0:3].tobytes()
         assert not np.isin(got, marks).any()

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from conftest import small_scene
+from switches import queue, switches as env_switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,16 +85,8 @@ def _cases(flux, demo2):
 
 
 @pytest.fixture
-def switches(monkeypatch):
-    def set_switches(q, cut):
-        for name, value in (("FLUX_SPLIT_HITQ_CAP", None if q is None else q[0]), ("FLUX_SPLIT_HITQ_TAKE_AT", None if q is None else q[1]),
-                            ("FLUX_SPLIT_DEPTH_CUT", None if cut else 0)):
-            if value is None:
-                monkeypatch.delenv(name, raising=False)
-            else:
-                monkeypatch.setenv(name, str(value))
-    yield set_switches
-    set_switches(None, True)
+def switches(env_switches):
+    return lambda q, cut: env_switches(FLUX_SPLIT_DEPTH_CUT=None if cut else 0, **queue(q))
 
 
 def _render(flux, sd, n, depth, kernel, rows=None):

@@ -16,6 +16,7 @@ import pytest
 
 from conftest import SCENES, small_scene
 from dielectric_spec import bounce, fresnel_cos
+from switches import switches  # noqa: F401 (the fixture)
 from extension_checks import cli_frame, host_bins, loopback_frames, math_mode, render, row_tiles, set_sharded_frame, small_yaml
 
 pytestmark = pytest.mark.gpu
@@ -349,7 +350,7 @@ def _glass_mesh(flux):
 
 
 @pytest.mark.parametrize("math_name", ["fast", "strict"])
-def test_static_refill_split_agree(flux, demo2, monkeypatch, math_name):
+def test_static_refill_split_agree(flux, demo2, switches, math_name):
     sd = _glass()
     m = math_mode(flux, math_name)
     n = 16
@@ -357,14 +358,11 @@ def test_static_refill_split_agree(flux, demo2, monkeypatch, math_name):
     assert sbase["dielectric_reflections"] > 0 and sbase["dielectric_transmissions"] > 0
     for kernel in (flux.KERNEL_REFILL, flux.KERNEL_SPLIT):
         for cap in (None, "0", "96"):
-            if cap is None:
-                monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
-            else:
-                monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", cap)
+            switches(FLUX_SPLIT_HITQ_CAP=cap)
             img, st, plan = render(flux, sd, n, m, kernel)
             assert st == sbase, (kernel, cap, st, sbase)
             assert np.abs(img - base).max() <= 1e-12, (kernel, cap)
-    monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
+    switches()
     if math_name == "fast":
         # the launch plan reports what runs: a glass scene keeps the split kernel's ray queue (the LDS of the queue-less plan, which
         # a hit queue would enlarge), where demo2 parks its hits (at 16384 spp: four waves per pixel leave the queue its slots)
@@ -372,13 +370,10 @@ def test_static_refill_split_agree(flux, demo2, monkeypatch, math_name):
         plans = {}
         for name, s in (("glass", sd), ("demo2", small_scene(demo2, 64, 48))):
             for cap in (None, "0"):
-                if cap is None:
-                    monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
-                else:
-                    monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", cap)
+                switches(FLUX_SPLIT_HITQ_CAP=cap)
                 with flux.Renderer(s, flux.JobConfiguration(n, 5, 50), seed=1) as r:
                     plans[name, cap] = r.launch_plan()
-        monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
+        switches()
         assert plans["glass", None]["kernel"] == flux._lib.PLAN_SPLIT
         assert plans["glass", None] == plans["glass", "0"]
         assert plans["demo2", None]["lds"] > plans["demo2", "0"]["lds"]

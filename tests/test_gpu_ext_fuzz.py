@@ -15,6 +15,7 @@ import pytest
 
 import aov_spec
 import path_spec
+import switches
 from conftest import SCENES
 
 pytestmark = pytest.mark.gpu
@@ -243,11 +244,7 @@ def forced_queue_fits(flux, sd, D):
 
 
 def _forced_queue(monkeypatch, take_at):
-    for key, v in (("FLUX_SPLIT_HITQ_CAP", 66), ("FLUX_SPLIT_HITQ_TAKE_AT", take_at)):
-        if take_at is None:
-            monkeypatch.delenv(key, raising=False)
-        else:
-            monkeypatch.setenv(key, str(v))
+    switches.set_switches(monkeypatch, **switches.queue(None if take_at is None else (66, take_at)))
 
 
 def _queue_is_on(flux, sd, plan):

@@ -27,6 +27,8 @@ import os
 import numpy as np
 import pytest
 
+import switches
+from switches import switches as env_switches  # noqa: F401 (the fixture)
 from conftest import SCENES, small_scene
 
 pytestmark = pytest.mark.gpu
@@ -85,16 +87,8 @@ def _has_dielectric(flux, sd):
 
 
 @pytest.fixture
-def queue(monkeypatch):
-    def set_queue(name):
-        cap, take_at = QUEUES[name]
-        for key, v in (("FLUX_SPLIT_HITQ_CAP", cap), ("FLUX_SPLIT_HITQ_TAKE_AT", take_at)):
-            if v is None:
-                monkeypatch.delenv(key, raising=False)
-            else:
-                monkeypatch.setenv(key, str(v))
-    yield set_queue
-    set_queue("plan")
+def queue(env_switches):
+    return lambda name: env_switches(**switches.queue(QUEUES[name]))
 
 
 def _render(flux, sd, n, depth, kernel, seed=1):
@@ -114,7 +108,7 @@ def references(flux, oracle_mod, scenes, scenes_8x6):
 
     def get(name, n, depth):
         if (name, n, depth) not in out:
-            assert "FLUX_SPLIT_HITQ_CAP" not in os.environ and "FLUX_SPLIT_HITQ_TAKE_AT" not in os.environ
+            assert not any(n in os.environ for n in switches.NAMES)
             sd = (scenes_8x6 if n == 128 else scenes)[name]
             img, st, _ = _render(flux, sd, n, depth, flux.KERNEL_STATIC)
             img.setflags(write=False)

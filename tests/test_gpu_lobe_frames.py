@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from conftest import small_scene
+from switches import queue, switches as env_switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -118,17 +119,9 @@ def _references(flux, oracle_mod, demo2, case):
 
 
 @pytest.fixture
-def switches(monkeypatch):
-    def set_switches(q=None, table=True, uniform=True):
-        for name, value in (("FLUX_SPLIT_HITQ_CAP", None if q is None else q[0]), ("FLUX_SPLIT_HITQ_TAKE_AT", None if q is None else q[1]),
-                            ("FLUX_LOBE_FRAMES", None if table else 0), ("FLUX_SPLIT_UNIFORM_A", None if uniform else 0)):
-            if value is None:
-                monkeypatch.delenv(name, raising=False)
-            else:
-                monkeypatch.setenv(name, str(value))
-    set_switches()
-    yield set_switches
-    set_switches()
+def switches(env_switches):
+    return lambda q=None, table=True, uniform=True: env_switches(FLUX_LOBE_FRAMES=None if table else 0,
+                                                                 FLUX_SPLIT_UNIFORM_A=None if uniform else 0, **queue(q))
 
 
 @pytest.mark.parametrize("q", QUEUES)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import small_scene
+from switches import switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +33,6 @@ TURNS = {  # name -> where (x, y, z) goes; each takes the floor's normal (0, 1, 
 }
 CASES = list(TURNS) + ["tilted_floor", "floor_then_tilted_wall", "tilted_wall_then_floor"]
 KERNELS = {"hit_queue": {}, "ray_queue": {"FLUX_SPLIT_HITQ_CAP": "0"}, "general_phase_a": {"FLUX_SPLIT_UNIFORM_A": "0"}}
-SWITCHES = ("FLUX_PLANE_AXIS", "FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_UNIFORM_A")
 
 
 def _turned(flux, sd, turn):
@@ -96,19 +96,6 @@ def _render(flux, sd):
         r.stats(reset=True)
         img = r.render_frame()
         return plain, img, r.stats(), r.launch_plan()
-
-
-@pytest.fixture
-def switches(monkeypatch):
-    def set_switches(**env):
-        for name in SWITCHES:
-            if name in env:
-                monkeypatch.setenv(name, env[name])
-            else:
-                monkeypatch.delenv(name, raising=False)
-    set_switches()
-    yield set_switches
-    set_switches()
 
 
 @pytest.mark.parametrize("kernel", list(KERNELS))

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 from conftest import small_scene
+from switches import switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +39,6 @@ TURNS = {  # name -> where (x, y, z) goes; each takes the floor's normal (0, 1, 
     "minus_z": lambda v: (v[0], v[2], -v[1]),
 }
 JOBS = ((16, 5), (16, 1), (23, 5), (23, 1))  # (sample root, depth limit)
-SWITCHES = ("FLUX_PLANE_AXIS", "FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_DEPTH_CUT")
 KERNELS = [dict(FLUX_SPLIT_DEPTH_CUT=cut, **queue) for queue in ({}, {"FLUX_SPLIT_HITQ_CAP": "0"}) for cut in ("0", "1")]
 
 NUM_LOW, NUM_HIGH, SMALL = 2.0 ** -894, 2.0 ** 499, 2.0 ** -764
@@ -161,19 +161,6 @@ def _render(flux, sd, root, depth):
         r.stats(reset=True)
         img = r.render_frame()
         return plain, img, r.stats(), r.launch_plan()
-
-
-@pytest.fixture
-def switches(monkeypatch):
-    def set_switches(**env):
-        for name in SWITCHES:
-            if name in env:
-                monkeypatch.setenv(name, env[name])
-            else:
-                monkeypatch.delenv(name, raising=False)
-    set_switches()
-    yield set_switches
-    set_switches()
 
 
 def _check(flux, oracle_mod, switches, sd, key, root, depth):

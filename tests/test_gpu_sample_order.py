@@ -24,6 +24,7 @@ import pytest
 
 import sample_order_ref as ref
 import split_sweep as sw
+from switches import switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +33,6 @@ JOBS = sw.JOBS + ((16, 5), (17, 5))
 SCENE_NAMES = ("floor", "glossy_no_floor", "no_environment")
 FRAMES = {"floor": (5, 3), "glossy_no_floor": (4, 3), "no_environment": (7, 3)}
 MODES = ({}, {"FLUX_SPLIT_HITQ_CAP": "0"}, {"FLUX_SPLIT_UNIFORM_A": "0"})
-SWITCHES = ("FLUX_SAMPLE_ORDER", "FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_UNIFORM_A")
 
 
 @functools.lru_cache(maxsize=None)
@@ -94,17 +94,10 @@ def _split(flux, r):
     return plain, img, st, r.launch_plan(flags=True)
 
 
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in SWITCHES:
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
-
-
 # ---- (a) the table: before any render in this file ---------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("root", (8, 9, 16, 17, 128))
-def test_table_is_the_restated_order_of_the_hemi_rows(flux, clean_env, root):
+def test_table_is_the_restated_order_of_the_hemi_rows(flux, switches, root):
     sd = copy.deepcopy(_scene("no_environment")[0])   # 7 sets: rank 1 of 3 holds sets 1 and 4
     cfg = flux.JobConfiguration(root, 3, 50)
     N, T = root * root, flux._lib.TABLE_ORDER
@@ -121,14 +114,14 @@ def test_table_is_the_restated_order_of_the_hemi_rows(flux, clean_env, root):
             keys = ref.key(hemi[0, 0, :, 0], hemi[0, 0, :, 1])[order[0].astype(np.int64)].reshape(-1, 64)
             assert np.all(np.diff(keys.astype(np.int64), axis=1) >= 0)
         assert not np.array_equal(order[0], np.arange(N))
-    clean_env.setenv("FLUX_SAMPLE_ORDER", "0")
+    switches(FLUX_SAMPLE_ORDER="0")
     with flux.Renderer(sd, cfg, seed=11) as off:
         assert np.array_equal(off.table(T), np.broadcast_to(np.arange(N, dtype=np.float64), (7, N)))
 
 
 # ---- (b) renders -------------------------------------------------------------------------------------------------------------------
 
-def test_jobs_run_one_two_and_four_waves_a_pixel(flux, clean_env):
+def test_jobs_run_one_two_and_four_waves_a_pixel(flux, switches):
     sd, seed = _scene("floor")
     seen = set()
     for root, depth in JOBS:
@@ -143,26 +136,24 @@ def test_jobs_run_one_two_and_four_waves_a_pixel(flux, clean_env):
 
 @pytest.mark.parametrize("job", JOBS, ids=lambda j: f"root{j[0]}-depth{j[1]}")
 @pytest.mark.parametrize("name", SCENE_NAMES)
-def test_sorted_order_renders_the_same_samples(flux, clean_env, name, job):
+def test_sorted_order_renders_the_same_samples(flux, switches, name, job):
     root, depth = job
     sd, seed = _scene(name)
     cfg = flux.JobConfiguration(root, depth, 50)
     want, ost = _oracle(name, root, depth)
     for mode in MODES:
         tag = f"{name} root {root} depth {depth} {mode}"
-        for k, v in mode.items():
-            clean_env.setenv(k, v)
+        switches(**mode)
         try:
             with flux.Renderer(sd, cfg, seed=seed) as r:
                 static, ss = _with_stats(flux, r, flux.KERNEL_STATIC)
                 refill, rs = _with_stats(flux, r, flux.KERNEL_REFILL)
                 plain, got, gs, plan = _split(flux, r)
-            clean_env.setenv("FLUX_SAMPLE_ORDER", "0")
+            switches(FLUX_SAMPLE_ORDER="0", **mode)
             with flux.Renderer(sd, cfg, seed=seed) as r:
                 plain0, got0, gs0, plan0 = _split(flux, r)
         finally:
-            for k in tuple(mode) + ("FLUX_SAMPLE_ORDER",):
-                clean_env.delenv(k, raising=False)
+            switches()
         assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == sw.waves_per_pixel(root), (tag, plan)
         assert plan == plan0, f"{tag}: the switch changes the plan"   # (no bit of the flags word belongs to the order)
         hitq = bool(plan["flags"] & flux._lib.PLAN_FLAG_HITQ)
@@ -182,7 +173,7 @@ def test_sorted_order_renders_the_same_samples(flux, clean_env, name, job):
 
 
 @pytest.mark.parametrize("name", SCENE_NAMES)
-def test_three_loopback_ranks_render_the_same_bits(flux, clean_env, name):
+def test_three_loopback_ranks_render_the_same_bits(flux, switches, name):
     sd, seed = _scene(name)
     cfg = flux.JobConfiguration(*sw.HEADLINE_JOB, 50)
     with flux.Renderer(sd, cfg, seed=seed) as r:

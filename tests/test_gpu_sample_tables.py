@@ -6,12 +6,13 @@ FLUX_SPLIT_HITQ_TAKE_AT; 16384 spp on a few pixels: the plan's own), the refill 
 one, three and five exponents (five: past the cap, no table), exponent 0, and with and without a lens.  One case per kernel is also
 held against the oracle at test_gpu_parity.py's bounds.  tests/sample_tables_selftest.cpp looks at the table itself."""
 import copy
-import subprocess
 
 import numpy as np
 import pytest
 
+import selftest
 from conftest import max_abs_diff, small_scene
+from switches import queue, switches  # noqa: F401 (the fixture)
 from test_sample_table_slots import build_selftest
 
 pytestmark = pytest.mark.gpu
@@ -59,16 +60,14 @@ def _render(flux, sd, root, seed=3):
 @pytest.mark.parametrize("lens", [0.0, 0.3])
 @pytest.mark.parametrize("root", [16, 8, 4])
 @pytest.mark.parametrize("name", ["one", "three", "five", "zero", "plane"])
-def test_frames_do_not_depend_on_the_table(flux, demo2, monkeypatch, name, root, lens):
+def test_frames_do_not_depend_on_the_table(flux, demo2, switches, name, root, lens):
     sd = _scene(flux, demo2, name, lens)
-    monkeypatch.delenv("FLUX_SAMPLE_TABLES", raising=False)
-    if root == 16:  # a one-wave block's LDS holds 88 slots for this scene: the plan takes the hit queue from H = 24 down
-        monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", "80")
-        monkeypatch.setenv("FLUX_SPLIT_HITQ_TAKE_AT", "16")
+    q = queue((80, 16) if root == 16 else None)  # a one-wave block's LDS holds 88 slots for this scene: the plan takes the hit queue from H = 24 down
+    switches(**q)
     got, gs, gplan, gbytes = _render(flux, sd, root)
-    monkeypatch.setenv("FLUX_SAMPLE_TABLES", "0")
+    switches(FLUX_SAMPLE_TABLES=0, **q)
     want, ws, wplan, wbytes = _render(flux, sd, root)
-    monkeypatch.delenv("FLUX_SAMPLE_TABLES")
+    switches(**q)
     assert gplan["kernel"] == wplan["kernel"] == getattr(flux._lib, KERNEL_OF_ROOT[root])
     if root == 16:
         # the hit queue (68 B a slot), both times -- not the ray queue (5120 B a wave)
@@ -83,12 +82,11 @@ def test_frames_do_not_depend_on_the_table(flux, demo2, monkeypatch, name, root,
     assert gbytes - wbytes == table
 
 
-def test_headline_plan_reads_the_table(flux, demo2, monkeypatch):
+def test_headline_plan_reads_the_table(flux, demo2, switches):
     """16384 spp, the plan's own hit queue (four waves a pixel, 110 slots of 68 B a wave for demo2's records), demo2 itself."""
     sd = small_scene(demo2, 8, 6)
-    monkeypatch.delenv("FLUX_SAMPLE_TABLES", raising=False)
     got, gs, gplan, gbytes = _render(flux, sd, 128)
-    monkeypatch.setenv("FLUX_SAMPLE_TABLES", "0")
+    switches(FLUX_SAMPLE_TABLES=0)
     want, ws, wplan, wbytes = _render(flux, sd, 128)
     assert gplan["kernel"] == wplan["kernel"] == flux._lib.PLAN_SPLIT and gplan["waves_per_pixel"] == 4
     n_sph = sum(isinstance(s, flux.SphereData) for s in sd.shapes)
@@ -114,11 +112,8 @@ def oracle_frames(flux, oracle_mod, demo2):
 
 
 @pytest.mark.parametrize("root", [16, 8, 4])
-def test_against_the_oracle(flux, demo2, oracle_frames, monkeypatch, root):
-    monkeypatch.delenv("FLUX_SAMPLE_TABLES", raising=False)
-    if root == 16:  # the hit queue, as above
-        monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", "80")
-        monkeypatch.setenv("FLUX_SPLIT_HITQ_TAKE_AT", "16")
+def test_against_the_oracle(flux, demo2, oracle_frames, switches, root):
+    switches(**queue((80, 16) if root == 16 else None))  # the hit queue, as above
     want, ost = oracle_frames(root)
     got, gs, plan, _ = _render(flux, _scene(flux, demo2, "three", 0.3), root)
     assert plan["kernel"] == getattr(flux._lib, KERNEL_OF_ROOT[root])
@@ -127,9 +122,8 @@ def test_against_the_oracle(flux, demo2, oracle_frames, monkeypatch, root):
     assert np.percentile(np.abs(got - want), 99.9) < TOL_TIGHT
 
 
-def test_glossy_plane_against_the_oracle(flux, demo2, oracle_frames, monkeypatch):
+def test_glossy_plane_against_the_oracle(flux, demo2, oracle_frames, switches):
     """The glossy floor: most primary hits read the table through a record behind the spheres'."""
-    monkeypatch.delenv("FLUX_SAMPLE_TABLES", raising=False)
     want, ost = oracle_frames(8, "plane")
     got, gs, plan, _ = _render(flux, _scene(flux, demo2, "plane", 0.3), 8)
     assert {k: gs[k] for k in ost} == ost
@@ -139,8 +133,7 @@ def test_glossy_plane_against_the_oracle(flux, demo2, oracle_frames, monkeypatch
 
 def test_table_entries_and_set_share(tmp_path):
     exe = build_selftest(tmp_path)
-    out = subprocess.run([exe, "gpu"], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    out = selftest.run(exe, "gpu", timeout=60)
     for name in ("table values", "set rows", "set share", "one exponent", "past the cap", "switch"):
-        assert f"ok {name}" in out.stdout
-    assert "all ok" in out.stdout
+        assert f"ok {name}" in out
+    assert "all ok" in out

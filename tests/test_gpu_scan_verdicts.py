@@ -10,6 +10,8 @@ import copy
 import numpy as np
 import pytest
 
+import switches
+from switches import switches as env_switches  # noqa: F401 (the fixture)
 from conftest import small_scene
 from test_gpu_parity import _env_cases
 
@@ -103,16 +105,8 @@ def _references(flux, oracle_mod, demo2, case):
 
 
 @pytest.fixture
-def queue(monkeypatch):
-    def set_queue(q):
-        if q is None:
-            monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
-            monkeypatch.delenv("FLUX_SPLIT_HITQ_TAKE_AT", raising=False)
-        else:
-            monkeypatch.setenv("FLUX_SPLIT_HITQ_CAP", str(q[0]))
-            monkeypatch.setenv("FLUX_SPLIT_HITQ_TAKE_AT", str(q[1]))
-    yield set_queue
-    set_queue(None)
+def queue(env_switches):
+    return lambda q: env_switches(**switches.queue(q))
 
 
 @pytest.mark.parametrize("q", QUEUES)

@@ -38,6 +38,7 @@ import numpy as np
 import pytest
 
 import split_sweep as sw
+from switches import switches  # noqa: F401 (the fixture)
 from test_gpu_ext_fuzz import check_run
 
 pytestmark = pytest.mark.gpu
@@ -92,9 +93,7 @@ def _check_plan(flux, plan, sd, root, depth, tag, env=None):
 
 @pytest.mark.parametrize("index", range(sw.SCENES_PER_CLASS))
 @pytest.mark.parametrize("cls", sw.CLASSES)
-def test_split_kernel_on_a_generated_scene(flux, monkeypatch, cls, index):
-    for name in SWITCHES:
-        monkeypatch.delenv(name, raising=False)
+def test_split_kernel_on_a_generated_scene(flux, switches, cls, index):
     sd, seed = sw.scene(cls, index)
     draw = sw.DRAWS.get(cls, {}).get(index, 0)
     headline = {}
@@ -130,12 +129,12 @@ def test_split_kernel_on_a_generated_scene(flux, monkeypatch, cls, index):
     if index < 2:
         for name, (value, how) in SWITCHES.items():
             tag = f"{cls} {index} {name}={value}"
-            monkeypatch.setenv(name, value)   # before the context: its tables are made at creation
+            switches(**{name: value})   # before the context: its tables are made at creation
             try:
                 with flux.Renderer(sd, cfg, seed=seed) as r:
                     plain, img, st, plan = _split(flux, r)
             finally:
-                monkeypatch.delenv(name)
+                switches()
             _check_plan(flux, plan, sd, root, depth, tag, {name: value})
             assert st == headline["stats"], (tag, st, headline["stats"])
             assert _same_bits(plain, img), tag

@@ -18,6 +18,8 @@ import os
 import numpy as np
 import pytest
 
+import switches
+from switches import switches as env_switches  # noqa: F401 (the fixture)
 from conftest import SCENES, small_scene
 
 pytestmark = pytest.mark.gpu
@@ -45,17 +47,8 @@ def scenes(flux, demo2):
 
 
 @pytest.fixture
-def env(monkeypatch):
-    def set_env(take_at=None, tables=True):
-        for key, v in (("FLUX_SPLIT_HITQ_TAKE_AT", take_at), ("FLUX_THROUGHPUT_TABLE", None if tables else 0)):
-            if v is None:
-                monkeypatch.delenv(key, raising=False)
-            else:
-                monkeypatch.setenv(key, str(v))
-        monkeypatch.delenv("FLUX_SPLIT_HITQ_CAP", raising=False)
-    set_env()
-    yield set_env
-    set_env()
+def env(env_switches):
+    return lambda take_at=None, tables=True: env_switches(FLUX_SPLIT_HITQ_TAKE_AT=take_at, FLUX_THROUGHPUT_TABLE=None if tables else 0)
 
 
 def _render(flux, sd, n, depth, kernel):
@@ -74,7 +67,7 @@ def references(flux, oracle_mod, scenes):
 
     def get(name, n, depth):
         if (name, n, depth) not in out:
-            assert "FLUX_SPLIT_HITQ_TAKE_AT" not in os.environ and "FLUX_THROUGHPUT_TABLE" not in os.environ
+            assert not any(n in os.environ for n in switches.NAMES)
             img, st, _, _ = _render(flux, scenes[name], n, depth, flux.KERNEL_STATIC)
             img.setflags(write=False)
             ost = None

@@ -2,12 +2,10 @@
 -- the array-of-structures pool keeps the bytes, the hit-queue / ray-queue decision and the reported fields the field-major queue had
 -- and checks the pool's arithmetic (flux_plan.h, the functions the kernel's pass loop calls): entries lie inside the pool, clear of
 each other, and phase A is never admitted with less than 64 * 68 B free, for every pool size from the floor to the cap."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT, SCENES
+import selftest
+from conftest import SCENES
 
 # scene, sample root -> kernel, TYP, C, H, bits per bounce, waves per pixel, LDS of the queues per wave.  The values of the field-major
 # queue: C slots of 68 B (demo2 at 16384 spp: 110, H = 46), or the 5120-byte ray queue (glass: a dielectric's weight is not in its record;
@@ -23,22 +21,9 @@ PLANS = {
 
 @pytest.fixture(scope="module")
 def selftest_out(tmp_path_factory):
-    from flux_amd import build
-    build.build_hip()
-    exe = str(tmp_path_factory.mktemp("hitq_pool") / "hitq_pool_selftest")
-    host = os.path.join(ROOT, "flux_amd", "host")
-    csrc = os.path.join(ROOT, "flux_amd", "csrc")
-    # (host-only clang and -ffp-contract=off: as tests/test_scene_build.py)
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
-                    "-I/opt/rocm/include", "-pthread", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "hitq_pool_selftest.cpp"),
-                    os.path.join(csrc, "scene_build.cpp"), os.path.join(csrc, "bvh.cpp")] +
-                   [os.path.join(host, s) for s in build.HOST_SOURCES] +
-                   ["-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"),
-                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    env = {k: v for k, v in os.environ.items() if k not in ("FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_HITQ_TAKE_AT")}
-    out = subprocess.run([exe, SCENES], capture_output=True, text=True, env=env, timeout=300)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    exe = selftest.build(str(tmp_path_factory.mktemp("hitq_pool") / "hitq_pool_selftest"), "hitq_pool_selftest.cpp",
+                         csrc=("scene_build.cpp", "bvh.cpp"))
+    return selftest.run(exe, SCENES)
 
 
 def test_pool_arithmetic(selftest_out):

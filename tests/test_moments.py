@@ -14,7 +14,8 @@ import denoise_moments_spec as dms
 import denoise_spec
 import moments_spec as ms
 from conftest import ROOT, SCENES, small_scene
-from extension_checks import build_host_selftest, host_bins
+import selftest
+from extension_checks import host_bins
 from path_spec import aov_buffers, PathSpec
 
 H, W = 12, 16
@@ -267,20 +268,17 @@ def test_render_denoised_refuses_an_unknown_variance():
 # ---- flux_host::denoise_moments_frame -------------------------------------------------------------------------------------------------
 
 def test_cpp_denoise_moments_frame_checks_its_buffers(tmp_path):
-    exe = build_host_selftest("moments", str(tmp_path / "moments_host_selftest"))
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+    exe = selftest.build(str(tmp_path / "moments_host_selftest"), "moments_host_selftest.cpp", host=True, compiler="g++")
+    out = selftest.run(exe)
+    assert "all ok" in out
 
 
 def test_cpp_denoise_moments_frame_under_sanitizers(tmp_path):
     """The same program as a stand-alone sanitized executable: the host layer it calls is compiled into it with
     -fsanitize=address,undefined.  It is about host code, so it is shown no device: the valid call ends in FLUX_E_DEVICE everywhere."""
-    exe = build_host_selftest("moments", str(tmp_path / "moments_host_selftest_san"),
-                              extra_flags=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1", HIP_VISIBLE_DEVICES="-1")
-    out = subprocess.run([exe], capture_output=True, text=True, env=env)
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = selftest.build(str(tmp_path / "moments_host_selftest_san"), "moments_host_selftest.cpp", host=True, flags=selftest.SANITIZE,
+                         compiler="g++")
+    assert "all ok" in selftest.run(exe, env=selftest.sanitize_env(HIP_VISIBLE_DEVICES="-1"))
 
 
 # ---- the command-line tool --------------------------------------------------------------------------------------------------------------

@@ -5,29 +5,18 @@ values (zeros, subnormals, 1e-300, 1, 1e300, infinities, NaN) in every component
 sign: bit-equal wherever the predicate admits the ray, the predicate refusing every ray of the grid for which a form differs, the
 kernel's f32 vote implying the predicate, and the classifier.  The program is run once more, on a tenth of the cases, as a stand-alone
 executable under AddressSanitizer and UBSan."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import selftest
 
 CHECKS = ("classifier", "random rays", "special values")
 
 
-def _build(exe, extra=()):
-    """Host-only clang and -ffp-contract=off: the test spells out every fused multiply-add."""
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-Wall", *extra, "-o", exe,
-                    os.path.join(ROOT, "tests", "plane_axis_selftest.cpp")], check=True)
-    return exe
-
-
 @pytest.fixture(scope="module")
 def selftest_out(tmp_path_factory):
-    exe = _build(str(tmp_path_factory.mktemp("plane_axis") / "plane_axis_selftest"))
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    """(-ffp-contract=off: the program spells out every fused multiply-add)"""
+    exe = selftest.build(str(tmp_path_factory.mktemp("plane_axis") / "plane_axis_selftest"), "plane_axis_selftest.cpp")
+    return selftest.run(exe, timeout=600)
 
 
 def test_reduced_form_against_every_general_form(selftest_out):
@@ -38,9 +27,5 @@ def test_reduced_form_against_every_general_form(selftest_out):
 
 
 def test_selftest_under_asan_and_ubsan(tmp_path):
-    exe = _build(str(tmp_path / "plane_axis_selftest_san"),
-                 ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = selftest.build(str(tmp_path / "plane_axis_selftest_san"), "plane_axis_selftest.cpp", flags=selftest.SANITIZE)
+    assert "all ok" in selftest.run(exe, "quick", env=selftest.sanitize_env(), timeout=600)

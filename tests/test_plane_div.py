@@ -13,29 +13,22 @@ plane_div_admits) on the CPU: tests/plane_div_selftest.cpp includes the header t
     guard is needed, and the program prints how many such pairs are bit-equal all the same;
   - holds the votes to the predicate on special values of d_a.
 The program is run once more, on a tenth of the cases, as a stand-alone executable under AddressSanitizer and UBSan."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import selftest
 
 CHECKS = ("predicate", "function", "small nums", "votes")
 
 
-def _build(exe, extra=()):
-    """Host-only clang and -ffp-contract=off, as the library's translation units: every fused multiply-add is spelled out."""
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", *extra, "-o", exe,
-                    os.path.join(ROOT, "tests", "plane_div_selftest.cpp")], check=True)
-    return exe
+def _build(exe, flags=()):
+    """(-ffp-contract=off, as the library's translation units: every fused multiply-add is spelled out)"""
+    return selftest.build(exe, "plane_div_selftest.cpp", flags=flags)
 
 
 @pytest.fixture(scope="module")
 def selftest_out(tmp_path_factory):
     exe = _build(str(tmp_path_factory.mktemp("plane_div") / "plane_div_selftest"))
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    return selftest.run(exe, timeout=600)
 
 
 def test_unscaled_division_against_ieee(selftest_out):
@@ -46,9 +39,5 @@ def test_unscaled_division_against_ieee(selftest_out):
 
 
 def test_selftest_under_asan_and_ubsan(tmp_path):
-    exe = _build(str(tmp_path / "plane_div_selftest_san"),
-                 ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = _build(str(tmp_path / "plane_div_selftest_san"), selftest.SANITIZE)
+    assert "all ok" in selftest.run(exe, "quick", env=selftest.sanitize_env(), timeout=600)

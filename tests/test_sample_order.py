@@ -4,33 +4,19 @@ deal is a bijection whose quarters are the kernel's slices and whose 64-aligned 
 the key clamps NaN, infinities and +-1 into range, equal keys keep index order.  The program's own checks (random and adversarial key
 arrays: the row is a permutation whatever the keys are) run once plain and once as a stand-alone executable under AddressSanitizer
 and UBSan."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import sample_order_ref as ref
-from conftest import ROOT
+import selftest
+from selftest import run as _run
 
 SIZES = (64, 81, 256, 289, 4225, 16384)
 
 
-def _build(exe, extra=()):
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", *extra, "-o", exe,
-                    os.path.join(ROOT, "tests", "sample_order_selftest.cpp")], check=True)
-    return exe
-
-
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    return _build(str(tmp_path_factory.mktemp("sample_order") / "sample_order_selftest"))
-
-
-def _run(exe, *args, stdin=None):
-    out = subprocess.run([exe, *args], input=stdin, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    return out.stdout
+    return selftest.build(str(tmp_path_factory.mktemp("sample_order") / "sample_order_selftest"), "sample_order_selftest.cpp")
 
 
 def _ints(text):
@@ -90,9 +76,5 @@ def test_selftest_checks(exe):
 
 
 def test_selftest_under_asan_and_ubsan(tmp_path):
-    exe = _build(str(tmp_path / "sample_order_selftest_san"),
-                 ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
-    out = subprocess.run([exe, "quick"], capture_output=True, text=True, timeout=600,
-                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert out.returncode == 0 and "all ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    exe = selftest.build(str(tmp_path / "sample_order_selftest_san"), "sample_order_selftest.cpp", flags=selftest.SANITIZE)
+    assert "all ok" in _run(exe, "quick", env=selftest.sanitize_env(), timeout=600)

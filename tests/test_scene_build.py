@@ -6,11 +6,12 @@ instantiation, block, grid and LDS each of those scenes gets over a grid of jobs
 instantiation word of the headline job (demo2, 800 x 600, 16384 spp, depth 5) and of box_room at depths 5 and 3 ("ok flags")."""
 import hashlib
 import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT, SCENES
+import selftest as st
+import switches
+from conftest import SCENES
 
 BUFFERS = ("shapes", "mats", "fscene", "tris", "nodes", "nodesq", "arena", "scalars")
 SCENE_NAMES = ("demo1", "demo2", "disk_light", "glass", "heightfield")
@@ -69,37 +70,20 @@ PASS_PLANS_SHA256 = "f030afc9ade51a7de2755ff925caa85ca01339619a6d61196532ec8b3c0
 
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
-    from flux_amd import build
-    build.build_hip()
-    exe = str(tmp_path_factory.mktemp("scene_build") / "scene_build_selftest")
-    host = os.path.join(ROOT, "flux_amd", "host")
-    csrc = os.path.join(ROOT, "flux_amd", "csrc")
-    # host-only clang: plain g++ cannot compile flux_device.h's ext_vector_type records; -ffp-contract=off as the library's
-    subprocess.run(["/opt/rocm/llvm/bin/clang++", "-O2", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__",
-                    "-I/opt/rocm/include", "-pthread", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "scene_build_selftest.cpp"),
-                    os.path.join(csrc, "scene_build.cpp"), os.path.join(csrc, "bvh.cpp")] +
-                   [os.path.join(host, s) for s in build.HOST_SOURCES] +
-                   ["-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"),
-                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
+    return st.build(str(tmp_path_factory.mktemp("scene_build") / "scene_build_selftest"), "scene_build_selftest.cpp",
+                    csrc=("scene_build.cpp", "bvh.cpp"))
 
 
 def _run(exe, out_dir, threads=None):
-    env = dict(os.environ)
-    for k in ("FLUX_BUILD_THREADS", "FLUX_SPLIT_HITQ_CAP", "FLUX_SPLIT_HITQ_TAKE_AT"):
-        env.pop(k, None)
-    if threads is not None:
-        env["FLUX_BUILD_THREADS"] = str(threads)
     os.makedirs(out_dir, exist_ok=True)
-    out = subprocess.run([exe, SCENES, str(out_dir)], capture_output=True, text=True, env=env)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    stdout = st.run(exe, SCENES, str(out_dir), env=switches.clean_env(FLUX_BUILD_THREADS=threads))
     digests = {}
     for scene in SCENE_NAMES:
         for buf in BUFFERS:
             ext = "txt" if buf == "scalars" else "bin"
             with open(os.path.join(out_dir, f"{scene}.{buf}.{ext}"), "rb") as f:
                 digests[f"{scene}.{buf}"] = hashlib.sha256(f.read()).hexdigest()
-    return out.stdout, digests
+    return stdout, digests
 
 
 @pytest.fixture(scope="module")
