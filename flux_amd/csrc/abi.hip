@@ -24,6 +24,7 @@
 #include "flux_math_coeffs.h"  // kExp2Poly -> RenderParams::exp2c
 
 #include "flux_ctx.h"
+#include "flux_smooth.h"
 #include "flux_switches.h"
 
 namespace flux {
@@ -192,6 +193,8 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     c->sets.stride = (uint32_t)set_stride;
     c->sets.count = first_set < c->S ? (uint32_t)((c->S - first_set + set_stride - 1) / set_stride) : 0u;
     c->bvh = h.bvh;
+    c->mesh_first = h.mesh_first;
+    c->mesh_smooth.assign(h.mesh_first.empty() ? 0 : h.mesh_first.size() - 1, 0);
     for (int a = 0; a < 3; a++) {
         c->U[a] = h.U[a];
         c->V[a] = h.V[a];
@@ -932,6 +935,50 @@ double flux_ctx_last_kernel_ms(flux_ctx *ctx) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) != hipSuccess) return -1.0;
     return (double)ms;
+}
+
+// the checks and the normalisation (flux_smooth.h) before any device call; then the table where the context has none yet, the mesh's
+// normals staged in input order, and the device's own gather into leaf order.  Every allocation precedes the first change.
+int flux_ctx_set_mesh_normals(flux_ctx *ctx, uint64_t mesh, const double *corner_normals, uint64_t num_triangles) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    return flux::no_throw([&] {
+        std::vector<double> normal;
+        std::string error;
+        if (!flux::normalize_corner_normals(ctx->mesh_first, mesh, corner_normals, num_triangles, normal, error))
+            return fail(FLUX_E_INVALID, "%s", error.c_str());
+        const bool set = !normal.empty();
+        const size_t m = (size_t)mesh;
+        const uint64_t own = ctx->mesh_first[m + 1] - ctx->mesh_first[m];
+        if (!set && !ctx->mesh_smooth[m]) return (int)FLUX_OK;  // (a mesh without triangles, or nothing to clear)
+        DeviceGuard guard(ctx->device);
+        if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+        const size_t table_bytes = (size_t)ctx->rp.n_tris * flux::kTriNormalDoubles * sizeof(double);
+        flux::DevBuf<double> fresh, stage;
+        if (set && !ctx->d_tri_normals) {
+            HIP_TRY(fresh.alloc_bytes(table_bytes));
+            HIP_TRY(hipMemset(fresh, 0, table_bytes));
+        }
+        if (set) {
+            HIP_TRY(stage.alloc(normal.size()));
+            HIP_TRY(hipMemcpy(stage, normal.data(), normal.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        double *table = fresh ? fresh : ctx->d_tri_normals;
+        HIP_TRY(flux::gather_tri_normals(ctx->d_tris, ctx->rp.n_tris, ctx->rp.n_shapes + (int)ctx->mesh_first[m], (int)own, stage, table, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if (fresh) {
+            ctx->d_tri_normals = std::move(fresh);
+            ctx->device_bytes += table_bytes;
+        }
+        ctx->mesh_smooth[m] = set ? 1 : 0;
+        bool any = false;
+        for (unsigned char f : ctx->mesh_smooth) any = any || f;
+        if (!any && ctx->d_tri_normals) {  // the last mesh went back to facet normals: the context is as it was created
+            ctx->d_tri_normals.reset();
+            ctx->device_bytes -= table_bytes;
+        }
+        ctx->rp.tri_normals = ctx->d_tri_normals;
+        return (int)FLUX_OK;
+    });
 }
 
 int flux_ctx_enable_stats(flux_ctx *ctx, int on) {

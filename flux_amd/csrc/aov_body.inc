@@ -33,7 +33,8 @@ __device__ __forceinline__ void first_hit_fields(const RenderParams &P, const Ra
         const DevTri &T = P.tris[slot];
         const int mat = T.mat;
         const V3 w = material_weight(P, mat);
-        nx = T.nx; ny = T.ny; nz = T.nz;
+        const V3 tn = tri_shading_normal(P, r, slot);
+        nx = tn.x; ny = tn.y; nz = tn.z;
         wr = w.x; wg = w.y; wb = w.z;
         kind = P.mats[mat].kind;
     } else {
@@ -51,7 +52,7 @@ __device__ __forceinline__ void first_hit_fields(const RenderParams &P, const Ra
     const DevShape *S = P.shapes + (is_tri ? 0 : hit);
     const int mat = is_tri ? P.tris[slot].mat : hit;
     if (is_tri) {
-        n = mk(P.tris[slot].nx, P.tris[slot].ny, P.tris[slot].nz);
+        n = tri_shading_normal(P, r, slot);
     } else if (S->kind == kShapeSphere) {
         const double inv = S->inv, rad = S->radius;
         n = mk(((r.ox - S->px) + t * d.x) * inv / rad, ((r.oy - S->py) + t * d.y) * inv / rad, ((r.oz - S->pz) + t * d.z) * inv / rad);

@@ -15,7 +15,9 @@ struct DevTri {
     int32_t id;            // index in hit order: num_shapes + position in the input meshes.  Right behind the edges: the
     int32_t mat;           // intersection test then reads bytes 0..79 = five 16-B gathers.  mat: index into the materials
     double nx, ny, nz;     // normalize(e1 x e2), never flipped (read when shading only)
-    double pad[3];
+    int32_t smooth;        // 1: the slot's record of RenderParams::tri_normals holds corner normals (flux_ctx_set_mesh_normals); set on
+    int32_t pad0;          // the device, with the table (render.hip gather_tri_normals) -- the host build leaves it 0
+    double pad[2];
 };
 static_assert(sizeof(DevTri) == 128, "DevTri layout");
 

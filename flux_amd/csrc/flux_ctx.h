@@ -9,6 +9,7 @@
 #include <string>
 #include <system_error>
 #include <utility>
+#include <vector>
 
 #include "../../include/flux_abi.h"
 #include "flux_device.h"
@@ -70,6 +71,13 @@ template <class H, hipError_t (*Release)(H)> class Owner {
   public:
     Owner() = default;
     Owner(Owner &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    Owner &operator=(Owner &&o) noexcept {
+        if (this != &o) {
+            reset();
+            h_ = std::exchange(o.h_, nullptr);
+        }
+        return *this;
+    }
     ~Owner() { reset(); }
     void reset() {
         if (H h = std::exchange(h_, nullptr)) (void)Release(h);
@@ -162,6 +170,11 @@ struct flux_ctx {
     flux::DevBuf<flux::DevNode> d_nodes;
     flux::DevBuf<flux::DevNode4A> d_arena;  // the 4-wide tree of the FAST traversal kernel (RenderParams::nodes4), or empty
     flux::DevBuf<flux::DevNodeQ> d_nodesq;
+    // extension: smooth meshes (flux_ctx_set_mesh_normals).  mesh_first: HostScene::mesh_first; mesh_smooth[m]: mesh m has corner
+    // normals in d_tri_normals (RenderParams::tri_normals), which is held while any mesh has
+    std::vector<uint64_t> mesh_first;
+    std::vector<unsigned char> mesh_smooth;
+    flux::DevBuf<double> d_tri_normals;
     flux::BvhInfo bvh{};
     int traversal = FLUX_TRAVERSE_BVH;
     int variant = FLUX_KERNEL_DEFAULT;

@@ -308,7 +308,14 @@ struct RenderParams {
     // depth was a load and its whole wait between the classification and the park, every pass.  (A copy, and the two fields where they
     // were: laying them side by side moved four other instantiations' scalar spills -- profiles/r16_plane_div/registers.txt.)
     alignas(8) int32_t depth_pair[2];
+    // extension: smooth meshes.  One record of kTriNormalDoubles doubles per DevTri slot, in leaf order as
+    // `tris`: the three corner normals {n0, n1, n2} of a triangle whose mesh has them (DevTri::smooth = 1), zeros otherwise.  nullptr:
+    // no mesh of the context has normals -- no kernel then reads DevTri::smooth.  The shading step reads it (render_body.inc
+    // tri_shading_normal), the traversal never.
+    const double *tri_normals;
 };
+// doubles per record of RenderParams::tri_normals: nine used, padded to one aligned 128-B line -- one more line per shaded hit
+constexpr size_t kTriNormalDoubles = 16;
 // bytes per hit record of RenderParams::lobe_frame
 constexpr size_t kLobeFrameBytes = 6 * sizeof(double);
 

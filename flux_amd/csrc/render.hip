@@ -243,6 +243,26 @@ hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *o
     return hipGetLastError();
 }
 
+// The corner-normal records of one mesh, gathered into leaf order (flux_tables.h gather_tri_normals): one thread per DevTri slot
+__global__ void gather_tri_normals_kernel(DevTri *__restrict__ tris, int n_tris, int first_id, int count, const double *__restrict__ stage,
+                                          double *__restrict__ table) {
+    const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= n_tris) return;
+    const int k = tris[s].id - first_id;
+    if (k < 0 || k >= count) return;
+    if (table) {
+        double *o = table + (size_t)s * kTriNormalDoubles;
+        for (int j = 0; j < (int)kTriNormalDoubles; j++) o[j] = (stage && j < 9) ? stage[(size_t)k * 9 + j] : 0.0;
+    }
+    tris[s].smooth = stage ? 1 : 0;
+}
+hipError_t gather_tri_normals(DevTri *tris, int n_tris, int first_id, int count, const double *stage, double *table, hipStream_t stream) {
+    if (n_tris <= 0 || count <= 0) return hipSuccess;
+    if (stage && !table) return hipErrorInvalidValue;
+    gather_tri_normals_kernel<<<dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, stream>>>(tris, n_tris, first_id, count, stage, table);
+    return hipGetLastError();
+}
+
 // `call` in the copy of the kernel bodies the plan names
 #define FLUX_IN_COPY(L, call)                           \
     switch ((L).copy) {                                 \

@@ -290,6 +290,48 @@ __device__ __forceinline__ bool tri_hit(const DevTri &T, const Ray &r, double &t
     return tri_hit_v(mk(T.v0x, T.v0y, T.v0z), mk(T.e1x, T.e1y, T.e1z), mk(T.e2x, T.e2y, T.e2z), r, t);
 }
 
+// extension: smooth meshes (DESIGN.md section 5j; the spec: include/flux_abi.h flux_ctx_set_mesh_normals, tests/smooth_spec.py).
+// The shading normal of the hit of segment r on triangle `slot`: the stored facet normal, or -- for a triangle whose mesh has corner
+// normals -- their interpolation at the hit's barycentrics, recomputed here from the DevTri record with tri_hit_v's own expressions
+// (the traversal keeps no u, v: two registers less through its loop than carrying them would cost).  Every reader of a triangle's
+// normal calls this: the bounce and the facing test (shade_hit_fast, shade_hit), the feature buffers (first_hit_fields).
+// A context without a table (P.tri_normals == nullptr: a scalar branch) runs the stored normal's three loads as before.
+__device__ __forceinline__ V3 tri_shading_normal(const RenderParams &P, const Ray &r, int slot) {
+    const DevTri &T = P.tris[slot];
+    bool flat = true;
+    V3 n;
+    if (P.tri_normals != nullptr && T.smooth != 0) {
+        const V3 e1 = mk(T.e1x, T.e1y, T.e1z), e2 = mk(T.e2x, T.e2y, T.e2z);
+        const V3 d = mk(r.dx, r.dy, r.dz);
+        const V3 p = cross(d, e2);
+        const V3 s = mk(r.ox - T.v0x, r.oy - T.v0y, r.oz - T.v0z);
+#if FLUX_FAST
+        const double inv = fastmath::fdiv(1.0, dot(e1, p));
+#else
+        const double inv = 1.0 / dot(e1, p);
+#endif
+        const double u = dot(s, p) * inv;
+        const double v = dot(d, cross(s, e1)) * inv;
+        const double w = (1.0 - u) - v;
+        // uniform base + 32-bit byte offset (the slot count keeps slot * 128 below 2^32, as for the DevTri records)
+        const double *N = reinterpret_cast<const double *>(reinterpret_cast<const char *>(P.tri_normals) +
+                                                           (uint32_t)slot * (uint32_t)(kTriNormalDoubles * sizeof(double)));
+        const V3 m = mk((w * N[0] + u * N[3]) + v * N[6], (w * N[1] + u * N[4]) + v * N[7], (w * N[2] + u * N[5]) + v * N[8]);
+        const double l2 = (m.x * m.x + m.y * m.y) + m.z * m.z;
+        flat = !(l2 >= 1e-24);  // (true for a NaN too: opposed corner normals and a degenerate hit keep the facet normal)
+#if FLUX_FAST
+        const double il = fastmath::frsqrt(l2);
+        n = mk(m.x * il, m.y * il, m.z * il);
+#else
+        const double len = sqrt(l2);
+        n = mk(m.x / len, m.y / len, m.z / len);
+#endif
+    }
+    // (the stored normal is read behind the interpolation, not in front of it: its six registers are not held across)
+    if (flat) n = mk(T.nx, T.ny, T.nz);
+    return n;
+}
+
 // nearest-hit rule of Scene::hit (scene.rs:156-160 + Hit::compare common.rs:17-23) for candidates
 // visited in ANY order: smaller t wins, equal t keeps the lower hit-order index (what min_by +
 // Hit::compare give for an ordered scan)
@@ -1532,7 +1574,7 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
             const DevTri &T = P.tris[slot];
             const DevMaterial &Mt = P.mats[T.mat];
             p.mat = T.mat;
-            n = mk(T.nx, T.ny, T.nz);
+            n = tri_shading_normal(P, p.r, slot);
             kind = Mt.kind;
             fr = Mt.fr; fg = Mt.fg; fb = Mt.fb; m_inv_e1 = Mt.inv_e1;
             ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
@@ -1637,7 +1679,7 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
         const DevMaterial &Mt = LDS_SCENE ? *reinterpret_cast<const DevMaterial *>(mats_lds + (uint32_t)T.mat * (uint32_t)sizeof(DevMaterial))
                                           : P.mats[T.mat];
         p.mat = T.mat;
-        n = mk(T.nx, T.ny, T.nz);
+        n = tri_shading_normal(P, p.r, slot);
         kind = Mt.kind;
         fr = Mt.fr; fg = Mt.fg; fb = Mt.fb; m_inv_e1 = Mt.inv_e1;
         ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
@@ -1669,7 +1711,7 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
     const DevShape *S = P.shapes + (is_tri ? 0 : hit);
     const DevMaterial *M = P.mats + (is_tri ? P.tris[slot].mat : hit);
     if (is_tri) {
-        n = mk(P.tris[slot].nx, P.tris[slot].ny, P.tris[slot].nz);
+        n = tri_shading_normal(P, p.r, slot);
     } else if (S->kind == kShapeSphere) {
         const double inv = S->inv, rad = S->radius;
         n = mk(((p.r.ox - S->px) + t * d.x) * inv / rad, ((p.r.oy - S->py) + t * d.y) * inv / rad,

@@ -374,6 +374,7 @@ int build_meshes(const flux_scene_desc &scene, HostScene &h, std::string &error)
         error = buf;
         return FLUX_E_INVALID;
     }
+    h.mesh_first.assign(first.begin(), first.end());
     h.tris.assign(first.back(), DevTri{});
     // edges and the geometric normal (a square root and three divisions each).  A million of them take tens of milliseconds on
     // one core, so large meshes are dealt to threads by index range (FLUX_BUILD_THREADS, as for the BVH)

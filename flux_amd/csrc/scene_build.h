@@ -39,6 +39,7 @@ struct HostScene {
     std::vector<DevNodeQ> nodesq;
     std::vector<DevNode4A> arena;  // empty when the arena exceeds its 26-bit unit index: the binary tree's kernel walks the mesh
     BvhInfo bvh;
+    std::vector<uint64_t> mesh_first;  // [meshes + 1]: mesh m holds the triangles mesh_first[m] .. mesh_first[m + 1] - 1 of the input order
     double U[3] = {}, V[3] = {}, W[3] = {};  // CameraBasis::new (scene.rs:28-35)
     // every field of RenderParams the scene decides.  The pointers stay null here; the upload sets them, f32_half and f32_top from
     // the pair indices below.

@@ -23,7 +23,57 @@ from .scene import MatteData, MeshData, PlaneData, SceneData, load_scene
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def heightfield_mesh(nx: int, nz: int, seed: int = 12345) -> MeshData:
+def vertex_normals(vertices, triangles) -> np.ndarray:
+    """Area-weighted vertex normals, float64 [nv][3]: per vertex the sum of (v1 - v0) x (v2 - v0) -- twice the area times the facet
+    normal -- over the triangles that use it, in triangle order, normalised.  A vertex no triangle with an area uses gets (0, 1, 0),
+    so that the result is always a valid MeshData.normals."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    face = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    n = np.zeros_like(v)
+    for c in range(3):
+        np.add.at(n, t[:, c], face)
+    length = np.sqrt((n * n).sum(axis=1))
+    ok = np.isfinite(length) & (length > 0.0)
+    n[~ok] = (0.0, 1.0, 0.0)
+    length[~ok] = 1.0
+    return n / length[:, None]
+
+
+def uv_sphere_mesh(segments: int, rings: int, center=(0.0, 0.0, 0.0), radius: float = 1.0, material=None, smooth: bool = True) -> MeshData:
+    """A latitude / longitude sphere: `segments` around the y axis, `rings` from pole to pole, 2 segments (rings - 1) triangles --
+    a fan of `segments` triangles at each pole and a quad (two triangles sharing their first vertex and an edge, facing outwards)
+    per segment and inner ring.  Vertices: the north pole, (rings - 1) rows of `segments`, the south pole.  smooth: the exact
+    sphere normals (vertex - center) / radius as per-vertex `normals`."""
+    if segments < 3 or rings < 2:
+        raise ValueError("uv_sphere_mesh: segments >= 3 and rings >= 2 required")
+    c = np.asarray(center, dtype=np.float64)
+    theta = np.pi * np.arange(1, rings, dtype=np.float64) / rings
+    phi = 2.0 * np.pi * np.arange(segments, dtype=np.float64) / segments
+    T, P = np.meshgrid(theta, phi, indexing="ij")
+    unit = np.concatenate([[[0.0, 1.0, 0.0]],
+                           np.stack([np.sin(T) * np.cos(P), np.cos(T), np.sin(T) * np.sin(P)], axis=-1).reshape(-1, 3),
+                           [[0.0, -1.0, 0.0]]])
+    south = len(unit) - 1
+
+    def vid(r, s):
+        return 1 + r * segments + s % segments
+    tris = []
+    for s in range(segments):
+        tris.append((0, vid(0, s + 1), vid(0, s)))
+    for r in range(rings - 2):
+        for s in range(segments):
+            a, b, d, e = vid(r, s), vid(r, s + 1), vid(r + 1, s + 1), vid(r + 1, s)
+            tris.append((a, b, d))
+            tris.append((a, d, e))
+    for s in range(segments):
+        tris.append((south, vid(rings - 2, s), vid(rings - 2, s + 1)))
+    if material is None:
+        material = MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0)
+    return MeshData(c + radius * unit, np.array(tris, dtype=np.uint32), material, unit.copy() if smooth else None)
+
+
+def heightfield_mesh(nx: int, nz: int, seed: int = 12345, smooth: bool = False) -> MeshData:
     i = np.arange(nx + 1, dtype=np.float64)
     j = np.arange(nz + 1, dtype=np.float64)
     x = -14.0 + 28.0 * i / nx
@@ -42,14 +92,15 @@ def heightfield_mesh(nx: int, nz: int, seed: int = 12345) -> MeshData:
     tris = np.empty((nx * nz, 2, 3), dtype=np.uint32)
     tris[:, 0, 0], tris[:, 0, 1], tris[:, 0, 2] = v00, v01, v11
     tris[:, 1, 0], tris[:, 1, 1], tris[:, 1, 2] = v00, v11, v10
-    return MeshData(verts, tris.reshape(-1, 3), MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0))
+    tris = tris.reshape(-1, 3)
+    return MeshData(verts, tris, MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0), vertex_normals(verts, tris) if smooth else None)
 
 
-def heightfield_scene(nx: int = 1000, nz: int = 500, seed: int = 12345, base: SceneData = None) -> SceneData:
+def heightfield_scene(nx: int = 1000, nz: int = 500, seed: int = 12345, base: SceneData = None, smooth: bool = False) -> SceneData:
     sd = copy.deepcopy(base) if base is not None else load_scene(os.path.join(_ROOT, "scenes", "demo2.yml"))
     sd.scene_name = f"heightfield_{nx}x{nz}"
     shapes = [s for s in sd.shapes if not isinstance(s, PlaneData)]
     shapes.append(PlaneData((0.0, -1.0, 0.0), (0.0, 1.0, 0.0), MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0)))
-    shapes.append(heightfield_mesh(nx, nz, seed))
+    shapes.append(heightfield_mesh(nx, nz, seed, smooth))
     sd.shapes = shapes
     return sd

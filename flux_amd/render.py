@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult
+from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult, corner_normals, split_shapes
 
 STAT_NAMES = ("samples", "segments", "matte_bounces", "glossy_bounces", "specular_bounces",
               "emissive_hits", "misses", "depth_exhausted", "bvh_nodes", "tris_tested",
@@ -36,6 +36,7 @@ class Renderer:
         _lib.check(_lib.lib.flux_ctx_create_sets(C.byref(self._desc.desc), C.byref(cfg), C.c_uint64(self.seed),
                                                  self.device, self.set_share[0], self.set_share[1], C.byref(h)))
         self._h = h
+        _set_scene_normals(h, scene_data)
         self._warn_if_routed()
 
     def _warn_if_routed(self):
@@ -304,6 +305,15 @@ class Renderer:
         """Extension: 0 = BVH (default), 1 = brute force over the triangles."""
         _lib.check(_lib.lib.flux_ctx_set_traversal(self._handle(), mode))
 
+    def set_mesh_normals(self, mesh_index: int, normals):
+        """Extension: smooth shading for mesh `mesh_index` (in the order of the scene's meshes) -- `normals` as MeshData.normals,
+        [vertices][3] or [triangles][3][3]; None: back to the facet normals (flux_ctx_set_mesh_normals)."""
+        meshes = split_shapes(self.scene_data)[1]
+        if normals is not None and 0 <= mesh_index < len(meshes):
+            import dataclasses
+            normals = corner_normals(dataclasses.replace(meshes[mesh_index], normals=normals), f"mesh {mesh_index}")
+        _set_mesh_normals(self._handle(), mesh_index, normals)
+
     def bvh_info(self) -> dict:
         buf = (C.c_uint64 * _lib.BVH_INFO_WORDS)()
         _lib.check(_lib.lib.flux_ctx_bvh_info(self._handle(), buf, _lib.BVH_INFO_WORDS))
@@ -352,6 +362,25 @@ class Renderer:
         return _create_timing(self._handle())
 
 
+def _set_mesh_normals(handle, mesh_index, corners):
+    """flux_ctx_set_mesh_normals: `corners` [nt][3][3] float64, or None to clear"""
+    if mesh_index < 0:
+        raise _lib.FluxError(_lib.E_INVALID, f"mesh index {mesh_index} out of range")
+    if corners is None:
+        _lib.check(_lib.lib.flux_ctx_set_mesh_normals(handle, mesh_index, None, 0))
+        return
+    c = np.ascontiguousarray(corners, dtype=np.float64)
+    _lib.check(_lib.lib.flux_ctx_set_mesh_normals(handle, mesh_index, c.ctypes.data_as(C.POINTER(C.c_double)), c.size // 9))
+
+
+def _set_scene_normals(handle, scene_data):
+    """the normals of every mesh of the scene that has them, on one context"""
+    for i, m in enumerate(split_shapes(scene_data)[1]):
+        corners = corner_normals(m, f"mesh {i}")
+        if corners is not None and len(corners):
+            _set_mesh_normals(handle, i, corners)
+
+
 def _create_timing(handle) -> dict:
     buf = (C.c_double * _lib.CREATE_TIMING_WORDS)()
     _lib.check(_lib.lib.flux_ctx_create_timing(handle, buf))
@@ -375,6 +404,10 @@ class MultiRenderer:
         _lib.check(_lib.lib.flux_multi_create(C.byref(self._desc.desc), C.byref(cfg), C.c_uint64(self.seed), devs, len(self.devices),
                                               int(shard), C.byref(h)))
         self._h = h
+        for rank in range(len(self.devices)):  # smooth meshes: every rank's context gets the normals (flux_ctx_set_mesh_normals)
+            ctx = C.c_void_p()
+            _lib.check(_lib.lib.flux_multi_ctx(h, rank, C.byref(ctx)))
+            _set_scene_normals(ctx, scene_data)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -453,7 +486,10 @@ class _BorrowedRenderer(Renderer):
 
 def render_frame_multi(scene_data: SceneData, config: JobConfiguration, seed: int = 1, num_devices: int = 0,
                        shard: int = _lib.SHARD_AUTO) -> np.ndarray:
-    """flux_render_frame_multi: create + render + destroy on the first `num_devices` devices (0 = all)."""
+    """flux_render_frame_multi: create + render + destroy on the first `num_devices` devices (0 = all).  The one call has no place
+    for mesh normals (flux_ctx_set_mesh_normals works on a context), so a scene with a smooth mesh is refused: use MultiRenderer."""
+    if any(m.normals is not None for m in split_shapes(scene_data)[1]):
+        raise _lib.FluxError(_lib.E_INVALID, "render_frame_multi renders facet normals only; use MultiRenderer for a mesh with normals")
     desc = SceneDesc(scene_data)
     cfg = _lib.FluxJobCfg(config.sample_root, config.max_trace_depth, config.rows_per_work_unit)
     out = np.empty((scene_data.output_settings.image_height, scene_data.output_settings.image_width, 3), dtype=np.float64)

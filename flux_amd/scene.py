@@ -403,10 +403,14 @@ class MeshData:
     """Indexed triangle mesh.  YAML (extension of the ShapeData enum):
         - Mesh: {vertices: [[x,y,z], ...], triangles: [[i,j,k], ...], material: {...}}
         - Triangle: {v0: [..], v1: [..], v2: [..], material: {...}}      (a one-triangle mesh)
-    Hit order: all Sphere/Plane shapes first (YAML order), then mesh triangles in YAML/index order."""
+    Hit order: all Sphere/Plane shapes first (YAML order), then mesh triangles in YAML/index order.
+    `normals` (optional; YAML `normals: [[x,y,z], ...]`, one per vertex): smooth shading -- [nv][3], one normal per vertex, or
+    [nt][3][3], one per triangle corner.  The renderer interpolates them at the hit (include/flux_abi.h
+    flux_ctx_set_mesh_normals); None: the facet normals.  A Triangle stays flat."""
     vertices: object  # float64 ndarray [nv][3]
     triangles: object  # uint32 ndarray [nt][3]
     material: MaterialData
+    normals: object = None  # float64 ndarray [nv][3] or [nt][3][3], or None
 
 
 def mesh_from_yaml(tag, b, what):
@@ -425,7 +429,44 @@ def mesh_from_yaml(tag, b, what):
         raise SceneError(f"{w}: vertices must be [[x,y,z],...] and triangles [[i,j,k],...]")
     if t.size and (t.min() < 0 or t.max() >= len(v)):
         raise SceneError(f"{w}: triangle index out of range (have {len(v)} vertices)")
-    return MeshData(v, t.astype(np.uint32), mat)
+    mesh = MeshData(v, t.astype(np.uint32), mat)
+    if b.get("normals") is not None:
+        nm = b["normals"]
+        if not isinstance(nm, list) or len(nm) != len(v):
+            raise SceneError(f"{w}.normals: expected one [x,y,z] per vertex ({len(v)}), got "
+                             f"{len(nm) if isinstance(nm, list) else repr(nm)}")
+        mesh.normals = np.array([_vec3(x, f"{w}.normals[{i}]") for i, x in enumerate(nm)], dtype=np.float64).reshape(-1, 3)
+        corner_normals(mesh, w)  # (a zero or non-finite normal is refused where the scene is loaded)
+    return mesh
+
+
+def corner_normals(mesh, what="mesh"):
+    """`mesh.normals` in the layout of flux_ctx_set_mesh_normals, float64 [nt][3 corners][3] (per-vertex normals expanded through
+    `triangles`; not normalised: the library does that), or None for a mesh without normals.  SceneError for a wrong count, a
+    non-numeric entry, or a normal that is not finite with a finite length > 0."""
+    import numpy as np
+    if mesh.normals is None:
+        return None
+    t = np.asarray(mesh.triangles, dtype=np.int64).reshape(-1, 3)
+    nv = len(np.asarray(mesh.vertices).reshape(-1, 3))
+    try:
+        nm = np.asarray(mesh.normals, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SceneError(f"{what}.normals: expected numbers, got {mesh.normals!r}")
+    if nm.shape == (len(t), 3, 3):
+        out = nm
+    elif nm.shape == (nv, 3):
+        out = nm[t]
+    else:
+        raise SceneError(f"{what}.normals: expected [{nv}][3] (per vertex) or [{len(t)}][3][3] (per corner), got shape {nm.shape}")
+    out = np.ascontiguousarray(out, dtype=np.float64).reshape(len(t), 3, 3)
+    with np.errstate(over="ignore", invalid="ignore"):
+        nn = (out[..., 0] * out[..., 0] + out[..., 1] * out[..., 1]) + out[..., 2] * out[..., 2]
+    bad = ~(np.isfinite(out).all(axis=-1) & np.isfinite(nn) & (nn > 0.0))
+    if bad.any():
+        k, c = np.argwhere(bad)[0]
+        raise SceneError(f"{what}.normals: triangle {k}, corner {c}: normal {tuple(float(x) for x in out[k, c])} must be finite with a finite length > 0")
+    return out
 
 
 def split_shapes(sd: SceneData):

@@ -389,6 +389,30 @@ int flux_denoise_moments(int device, uint64_t width, uint64_t height, const doub
 int flux_denoise_moments_device(int device, uint64_t width, uint64_t height, void *d_moments, void *d_aov, const double *params,
                                 void *d_out_rgb, void *d_work, uint64_t work_doubles, void *hip_stream);
 
+/* Smooth meshes (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): three CORNER NORMALS per
+ * triangle of a mesh, interpolated at the hit.  DESIGN.md section 5j; tests/smooth_spec.py states the same rule in numpy.
+ * flux_mesh's layout is pinned, so the normals arrive through this call: corner_normals is a host pointer laid out
+ * [num_triangles][3 corners][3], in the mesh's own triangle and corner order, and num_triangles must equal the mesh's count.
+ * corner_normals == NULL with num_triangles == 0 clears the mesh back to facet normals.
+ *   Checks, on the host at the time of the call and before any device call: every component finite, n.n finite and > 0.  Each
+ *   normal is then normalised in f64, n / sqrt(n.n), IEEE.
+ *   For a hit on triangle (v0, e1, e2) of such a mesh by the segment (o, d) the barycentrics are recomputed when the hit is
+ *   shaded, with the hit test's own expressions:  p = d x e2,  inv = 1 / (e1.p),  s = o - v0,  u = (s.p) inv,  q = s x e1,
+ *   v = (d.q) inv.  Then  w = (1 - u) - v,  m = (w n0 + u n1) + v n2 per component,  l2 = (m.x^2 + m.y^2) + m.z^2,  and the shading
+ *   normal is m / sqrt(l2) if l2 >= 1e-24, otherwise the stored facet normal (opposed corner normals; a NaN).
+ *   That vector stands wherever the stored normal is read: the bounce of every material, the Emissive facing test, the normal
+ *   channel of both feature buffers (and so the guides of both denoisers), flux_debug_shade.  It is never flipped towards the ray.
+ *   A triangle of a mesh without normals keeps its stored normal bit for bit, whatever the scene's other meshes have; the hit
+ *   test, the BVH, ties and t are untouched.
+ * The call is synchronous -- no render of the context may be in flight on a caller's stream --; a table set earlier for the mesh
+ * is replaced; renders before and after are otherwise independent; a failed call leaves the context as it was.
+ * FLUX_E_INVALID, with a message naming the mesh and the first offending triangle and
+ * corner: a null context, mesh >= the scene's num_meshes, a wrong count, a non-finite or zero normal.  Works on the contexts of
+ * flux_ctx_create and flux_ctx_create_sets and on the borrowed contexts of flux_multi_ctx: a flux_multi client sets the normals on
+ * EVERY rank (a frame whose ranks disagree is not defined).  flux_ctx_device_bytes counts the table -- 128 B per triangle of the
+ * scene, held while any mesh has normals. */
+int flux_ctx_set_mesh_normals(flux_ctx *ctx, uint64_t mesh, const double *corner_normals, uint64_t num_triangles);
+
 /* Adaptive sampling (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): further sample sets of
  * N = sample_root^2 samples for the pixels whose measured variance is still high, and only for those.  DESIGN.md section 5h;
  * tests/adaptive_spec.py states the same rule in numpy.  A call covers a list of h rows of W columns of a context that holds every

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Kernel by kernel, the device listings of two checkouts compared, without a GPU: `hipcc -S --cuda-device-only` of csrc/render.hip
 and csrc/adaptive.hip (or the files of --files) with the build's flags (scripts/kernel_asm.py's compile, one per file and tree), then for every kernel whether
-the instruction stream is the same text (comments dropped, labels renumbered) and what the compiler reports for it.
+the instruction stream is the same text (comments dropped, labels renumbered) and what the compiler reports for it.  A stream that
+differs only in the immediate offsets of scalar loads and the kernel-argument size -- what a kernel-argument block that grew moves --
+is reported as "kernarg size and s_load offsets only", with the numbers that changed.
 usage: scripts/listing_diff.py <parent checkout> [<branch checkout>] [--keep dir] [--files a.hip,b.hip] > table.md
    --keep dir: keep the listings and the remarks there (and reuse the ones already there)
    --files:    the files of flux_amd/csrc to compare instead of render.hip,adaptive.hip
@@ -69,6 +71,31 @@ def kernels(tree, keep, files):
     return out
 
 
+SLOAD = re.compile(r"^(s_load_\w+\s+.*,\s*|\.amdhsa_kernarg_size\s+)(0x[0-9a-f]+|\d+)$")
+
+
+def masked(stream):
+    """(the stream with every scalar load's immediate offset and the kernel-argument size masked, those numbers in order)"""
+    lines, offs = [], []
+    for ln in stream.splitlines():
+        m = SLOAD.match(ln)
+        if m:
+            offs.append(m.group(2))
+            ln = m.group(1) + "IMM"
+        lines.append(ln)
+    return "\n".join(lines), offs
+
+
+def verdict(pa, ba):
+    if pa == ba:
+        return "identical"
+    (pm, po), (bm, bo) = masked(pa), masked(ba)
+    if pm != bm:
+        return "DIFFERS"
+    moved = sorted({f"{a} -> {b}" for a, b in zip(po, bo) if a != b})
+    return "kernarg size and s_load offsets only (" + ", ".join(moved) + ")"
+
+
 def main():
     args = sys.argv[1:]
     keep = None
@@ -92,15 +119,18 @@ def main():
     fmt = lambda r, n: "{} / {} / {} / {} / {} / {}".format(r.get("vgprs"), r.get("vgpr_spill"), r.get("sgpr_spill"), r.get("scratch"), r.get("occupancy"), n)  # noqa: E731
     print("| kernel | stream | parent: VGPRs / VGPR spills / SGPR spills / scratch B / occupancy / instructions | branch: the same |")
     print("|---|---|---|---|")
-    same = 0
+    same = offsets = 0
     for name in sorted(set(parent) | set(branch)):
         if name not in parent or name not in branch:
             print(f"| `{name}` | only in {'parent' if name in parent else 'branch'} | | |")
             continue
         (pa, pn, pr), (ba, bn, br) = parent[name], branch[name]
-        same += pa == ba
-        print(f"| `{name}` | {'identical' if pa == ba else 'DIFFERS'} | {fmt(pr, pn)} | {fmt(br, bn)} |")
-    print(f"\n{len(parent)} kernels in the parent, {len(branch)} in the branch, {same} with an identical instruction stream.")
+        v = verdict(pa, ba)
+        same += v == "identical"
+        offsets += v.startswith("kernarg")
+        print(f"| `{name}` | {v} | {fmt(pr, pn)} | {fmt(br, bn)} |")
+    print(f"\n{len(parent)} kernels in the parent, {len(branch)} in the branch, {same} with an identical instruction stream, "
+          f"{offsets} that differ in the kernel-argument size and scalar-load offsets only.")
     return 0 if set(parent) == set(branch) else 1
 
 
