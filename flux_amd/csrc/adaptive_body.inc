@@ -40,11 +40,3 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void adaptive_pa
         if (G.i0 == 0u) A.passes[pixel] = (A.fresh ? 0u : A.passes[pixel]) + 1u;
     }
 }
-
-static hipError_t launch_adaptive_impl(const LaunchPlan &L, const RenderParams &p, const AdaptiveWork &a, hipStream_t stream) {
-    if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const dim3 g((unsigned)L.blocks), b(L.block);
-    if (L.tris) adaptive_pass_kernel<true><<<g, b, L.lds, stream>>>(p, a);
-    else adaptive_pass_kernel<false><<<g, b, L.lds, stream>>>(p, a);
-    return hipGetLastError();
-}

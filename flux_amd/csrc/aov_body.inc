@@ -151,11 +151,3 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void aov_kernel(
         }
     }
 }
-
-static hipError_t launch_aov_impl(const LaunchPlan &L, const RenderParams &p, hipStream_t stream) {
-    if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const dim3 g((unsigned)L.blocks), b(L.block);
-    if (L.tris) aov_kernel<true><<<g, b, L.lds, stream>>>(p);
-    else aov_kernel<false><<<g, b, L.lds, stream>>>(p);
-    return hipGetLastError();
-}

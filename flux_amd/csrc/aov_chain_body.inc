@@ -108,11 +108,3 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void aov_chain_k
         }
     }
 }
-
-static hipError_t launch_aov_chain_impl(const LaunchPlan &L, const RenderParams &p, int max_chain, hipStream_t stream) {
-    if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const dim3 g((unsigned)L.blocks), b(L.block);
-    if (L.tris) aov_chain_kernel<true><<<g, b, L.lds, stream>>>(p, max_chain);
-    else aov_chain_kernel<false><<<g, b, L.lds, stream>>>(p, max_chain);
-    return hipGetLastError();
-}

@@ -81,7 +81,8 @@ KernelCopy kernel_copy(const RenderParams &p, int math);
 
 // Which kernel a render launch runs for these parameters -- which instantiation, with what block size, grid and dynamic LDS: decided
 // in ONE place (launch_plan.cpp plan_render) and asked from there by the launch itself, by the host's LDS budget check and by
-// flux_ctx_launch_plan / flux_ctx_bvh_info, so that they cannot drift apart.  The launch maps these fields to template arguments.
+// flux_ctx_launch_plan / flux_ctx_bvh_info, so that they cannot drift apart.  The launch copies these fields into template and kernel
+// arguments and decides nothing (render_body.inc launch_render_impl); which combinations of them are compiled: kernel_exists below.
 struct LaunchPlan {
     int kernel = -1;  // FLUX_PLAN_* (include/flux_abi.h): 0 static, 1 refill, 2 split, 3 BVH state machine over the binary tree,
                       // 4 the same over the 4-wide tree; -1 nothing to do
@@ -98,14 +99,16 @@ struct LaunchPlan {
     int uniform_a = 1;             // kernel 2: phase A shades a wave whose primaries all hit one shape from that shape's record as a scalar
                                    // (render_body.inc shade_primary_hits); FLUX_SPLIT_UNIFORM_A=0: the general step everywhere
     int cut_depth = kNoDepthCut;   // kernel 2: phase B ends a path whose hit at this depth would bounce (split_cut_depth): max_depth, or kNoDepthCut
+    int tput = 0;                  // kernel 2: the take reads the context's throughput table (RenderParams::tput) -- the hit queue, and a
+                                   // table laid out for this plan's hq_bits; 0: the kernel gets no table
+    int axis = 0;                  // kernel 2, TYP: the first scan plane's axis (RenderParams::plane_axis, the AXIS instantiation); else 0
 };
 // The split kernel's depth cut for a launch of `p` with plan `L` (its hq_cap and hq_bits): the job's max_depth, or kNoDepthCut
 int split_cut_depth(const RenderParams &p, const LaunchPlan &L);
 LaunchPlan plan_render(const RenderParams &p, int variant, int math);
 // The instantiation a render launch of `p` with plan `L` runs, as one word (flux_ctx_launch_plan's word 7: FLUX_PLAN_FLAG_* in
-// include/flux_abi.h): the fields of `L` the launch maps to template arguments, and what it takes from `p` beside them -- the
-// throughput table, where the context holds one laid out for this plan's list entries, and the first plane's axis of a TYP launch
-// (render_body.inc launch_render reads the same two fields).  0 where there is nothing to launch.
+// include/flux_abi.h): the fields of `L` the launch copies into template and kernel arguments -- a function of the plan alone (`p`
+// stays in the signature for its callers).  0 where there is nothing to launch.
 uint32_t plan_flags(const RenderParams &p, const LaunchPlan &L);
 // The kernel family a launch runs: the render kernels, or one of the per-pixel passes -- the feature buffers (aov_body.inc
 // aov_kernel), the sample moments (moments_body.inc moments_kernel), one pass of the adaptive sampler over a work list
@@ -120,6 +123,41 @@ enum Pass { kPassRender = 0, kPassAov = 1, kPassMoments = 2, kPassAdaptive = 3, 
 //   kPassAovChain  as kPassMoments: the kernel runs the delta lobes and, in STRICT, keeps their (f, s) stack.
 // `variant` counts for kPassRender alone, `entries` for kPassAdaptive alone.
 LaunchPlan plan_pass(Pass pass, const RenderParams &p, int variant, int math, uint64_t entries = 0);
+
+// THE statement of which kernel instantiations render.hip compiles: whether `copy` holds the kernel of `pass` -- of kPassRender the
+// one LaunchPlan::kernel names -- with these template arguments (STATS apart: every kernel that counts exists with and without).  An
+// argument the kernel does not take must be 0.  The launcher asks it before it names an instantiation (render_body.inc
+// launch_render_impl), and the CPU test asks it of every plan (plan_exists; tests/scene_build_selftest.cpp), so the planner cannot ask
+// for a kernel that is not there.  A new template flag is a planner rule and a row here.
+//   the per-pixel passes       <TRIS>: aov_kernel, moments_kernel, adaptive_pass_kernel, aov_chain_kernel in every copy, and so is
+//                              shade_rays_kernel (flux_debug_shade, which has no plan).  That includes aov_kernel in the copy with the
+//                              dielectric lobe: aov_chain_kernel ends a chain with its file's first_hit_fields, and the file comes whole;
+//                              plan_pass never names that copy for kPassAov -- a first hit runs no lobe
+//   0 static, 1 refill         <STATS, TRIS>: every copy
+//   2 split                    <STATS, MAX32, TYP, HQ, AXIS>: FAST.  TYP (the usual analytic scene) only with MAX32, any HQ, any
+//                              AXIS (the first scan plane's stored normal lies on that axis); without TYP, AXIS 0, any MAX32 and HQ.
+//                              The copy with the dielectric lobe has neither TYP nor HQ (the hit queue)
+//   3 BVH, binary tree         <STATS>: FAST
+//   4 BVH, 4-wide tree         <STATS, LDS_SCENE, TYP>: FAST.  TYP only with LDS_SCENE, and not in the copy with the dielectric lobe
+constexpr bool kernel_exists(int copy, int pass, int kernel, int tris, int typ, int max32, int hq, int axis, int lds_scene) {
+    const bool flags_ok = (tris | typ | max32 | hq | lds_scene) >> 1 == 0 && axis >= 0 && axis <= 3;
+    if (copy < kCopyStrict || copy > kCopyFastDiel || !flags_ok) return false;
+    const bool fast = copy != kCopyStrict, diel = copy == kCopyFastDiel;
+    const bool split_args = typ || max32 || hq || axis;  // (arguments of the split kernel alone; TYP: the 4-wide tree's too)
+    if (pass != kPassRender) return pass > kPassRender && pass <= kPassAovChain && kernel == 0 && !split_args && !lds_scene;
+    switch (kernel) {
+        case 0:
+        case 1: return !split_args && !lds_scene;
+        case 2: return fast && !tris && !lds_scene && (typ ? max32 && !diel : axis == 0) && !(hq && diel);
+        case 3: return fast && !tris && !split_args && !lds_scene;
+        case 4: return fast && !tris && !max32 && !hq && !axis && (!typ || (lds_scene && !diel));
+    }
+    return false;
+}
+// ... asked of a plan: its fields as the launcher turns them into template arguments (true where there is nothing to launch)
+constexpr bool plan_exists(Pass pass, const LaunchPlan &L) {
+    return L.kernel < 0 || kernel_exists(L.copy, pass, L.kernel, L.tris, L.typ, L.max32, L.hq_cap > 0 ? 1 : 0, L.axis, L.lds_scene);
+}
 
 // LDS of the per-lane stacks of `lanes` lanes: the STRICT (f, s) recursion stack, 4 doubles per level, and the BVH traversal stack,
 // one int per level

@@ -183,6 +183,9 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
             L.lds = (size_t)cap * kHitQBytesPerSlot * K + scene_lds;
         }
         L.cut_depth = split_cut_depth(p, L);
+        // (the throughput product table only where it is laid out for this plan's list entries)
+        L.tput = L.hq_cap > 0 && p.tput != nullptr && p.tput_bits == L.hq_bits ? 1 : 0;
+        L.axis = L.typ ? p.plane_axis : 0;  // (the AXIS instantiations are TYP's)
         return L;
     }
     L.kernel = variant == FLUX_KERNEL_STATIC ? 0 : 1;
@@ -193,7 +196,7 @@ LaunchPlan plan_render(const RenderParams &p, int variant, int math) {
     return L;
 }
 
-uint32_t plan_flags(const RenderParams &p, const LaunchPlan &L) {
+uint32_t plan_flags(const RenderParams &, const LaunchPlan &L) {
     if (L.kernel < 0) return 0;
     const bool split = L.kernel == 2;
     const bool hq = split && L.hq_cap > 0;
@@ -201,13 +204,12 @@ uint32_t plan_flags(const RenderParams &p, const LaunchPlan &L) {
     if ((split || L.kernel == 4) && L.typ) f |= FLUX_PLAN_FLAG_TYP;
     if (split && L.max32) f |= FLUX_PLAN_FLAG_MAX32;
     if (hq) f |= FLUX_PLAN_FLAG_HITQ;
-    // (the launch drops a table that is not laid out for this plan's list entries: render_body.inc launch_render)
-    if (hq && p.tput != nullptr && p.tput_bits == L.hq_bits) f |= FLUX_PLAN_FLAG_TPUT_TABLE;
+    if (L.tput) f |= FLUX_PLAN_FLAG_TPUT_TABLE;
     if (split && L.cut_depth != kNoDepthCut) f |= FLUX_PLAN_FLAG_DEPTH_CUT;
     if (split && L.uniform_a) f |= FLUX_PLAN_FLAG_UNIFORM_A;
     if (L.kernel == 4 && L.lds_scene) f |= FLUX_PLAN_FLAG_LDS_SCENE;
     if ((L.kernel == 0 || L.kernel == 1) && L.tris) f |= FLUX_PLAN_FLAG_TRIS;
-    if (split && L.typ) f |= ((uint32_t)p.plane_axis << FLUX_PLAN_FLAG_AXIS_SHIFT) & FLUX_PLAN_FLAG_AXIS_MASK;
+    f |= ((uint32_t)L.axis << FLUX_PLAN_FLAG_AXIS_SHIFT) & FLUX_PLAN_FLAG_AXIS_MASK;
     if (hq) f |= ((uint32_t)L.hq_bits << FLUX_PLAN_FLAG_HQ_BITS_SHIFT) & FLUX_PLAN_FLAG_HQ_BITS_MASK;
     f |= ((uint32_t)L.copy << FLUX_PLAN_FLAG_COPY_SHIFT) & FLUX_PLAN_FLAG_COPY_MASK;
     return f;

@@ -80,11 +80,3 @@ __global__ __launch_bounds__(FLUX_BLOCK_THREADS, FLUX_WPE_WIDE) void moments_ker
         for (uint32_t ch = G.i0; ch < 8u; ch += G.lpp) o[ch] = pick(ch, m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
     }
 }
-
-static hipError_t launch_moments_impl(const LaunchPlan &L, const RenderParams &p, hipStream_t stream) {
-    if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const dim3 g((unsigned)L.blocks), b(L.block);
-    if (L.tris) moments_kernel<true><<<g, b, L.lds, stream>>>(p);
-    else moments_kernel<false><<<g, b, L.lds, stream>>>(p);
-    return hipGetLastError();
-}

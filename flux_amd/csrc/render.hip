@@ -35,21 +35,10 @@
 // The loop body (render_body.inc) is compiled three times: STRICT under `#pragma clang fp contract(off)` with the
 // reference's operation order, FAST under contract(fast) with flux_math.h (see render_body.inc's header), and FAST again with the
 // dielectric lobe.  Which copy, kernel and instantiation a call runs, with what block, grid and LDS, is the launch plan's decision
-// (launch_plan.cpp plan_render, host code compiled once); launch_pass below only maps the plan to a kernel.  The instantiations:
-//  * render_static_kernel<STATS, TRIS>, render_refill_kernel<STATS, TRIS>: every copy;
-//  * render_split_kernel<STATS, MAX32, TYP, HQ, AXIS>: FAST -- TYP (the usual analytic scene) only with MAX32, and in the copy with the
-//    dielectric lobe neither TYP nor HQ (the hit queue), which the plan never picks for a scene with a dielectric; AXIS (the first scan
-//    plane's stored normal lies on that axis, RenderParams::plane_axis) other than 0 only with TYP;
-//  * render_bvh_kernel<STATS>, render_bvh4_kernel<STATS, LDS_SCENE, TYP>: FAST -- TYP only with LDS_SCENE, and not in the copy
-//    with the dielectric lobe;
-//  * shade_rays_kernel<TRIS> (flux_debug_shade): every copy;
-//  * aov_kernel<TRIS> (aov_body.inc, the first-hit feature buffers: launch_plan.cpp plan_pass): STRICT and FAST, not the copy with the
-//    dielectric lobe -- a first hit runs no lobe;
-//  * moments_kernel<TRIS> (moments_body.inc, the per-pixel sample moments): every copy -- it runs the lobes;
-//  * adaptive_pass_kernel<TRIS> (adaptive_body.inc, one pass of the adaptive sampler over a work list):
-//    every copy, as moments_kernel;
-//  * aov_chain_kernel<TRIS> (aov_chain_body.inc, the feature buffers at the first non-specular hit): every copy -- a Dielectric
-//    bounce runs the dielectric lobe.
+// (launch_plan.cpp plan_render, host code compiled once); the launchers below only map the plan to a kernel.  Which instantiations
+// each copy holds is stated once: flux_plan.h kernel_exists.
+#include <type_traits>
+
 #include "flux_device.h"
 #include "flux_plan.h"
 #include "flux_tables.h"
@@ -98,6 +87,15 @@ static_assert(FLUX_BVH4_EARLY_AT >= FLUX_BVH_REFILL_AT,
 #endif                                 // render_refill_kernel (15 spilled): 4 waves/SIMD, nothing spilled (round 5; they shared the cap tuned
                                        // for the refill kernel in round 1)
 
+// A run-time value as a compile-time constant: f(std::integral_constant<int, v>{}) for the v in [LO, LO + N) that `v` is, found by
+// halving the range; a `v` outside it is an error.  How the launchers turn plan fields into template arguments.
+namespace flux {
+template <int N, int LO = 0, class F>
+static hipError_t with_const(int v, F &&f) {
+    if constexpr (N == 1) return v == LO ? f(std::integral_constant<int, LO>{}) : hipErrorInvalidValue;
+    else return v < LO + N / 2 ? with_const<N / 2, LO>(v, f) : with_const<N - N / 2, LO + N / 2>(v, f);
+}
+}  // namespace flux
 
 // The loop itself lives in render_body.inc and is compiled twice (see its header): the STRICT
 // arithmetic (reference operation order, no contraction) and the FAST arithmetic (FMA + flux_math.h).
@@ -263,13 +261,23 @@ hipError_t gather_tri_normals(DevTri *tris, int n_tris, int first_id, int count,
     return hipGetLastError();
 }
 
-// `call` in the copy of the kernel bodies the plan names
-#define FLUX_IN_COPY(L, call)                           \
-    switch ((L).copy) {                                 \
-        case kCopyStrict: return strict::call;          \
-        case kCopyFast: return fast::call;              \
-        case kCopyFastDiel: return fast_diel::call;     \
-    }                                                   \
+// The launcher of the <TRIS> kernels -- the per-pixel passes and flux_debug_shade, which every copy compiles both ways
+// (flux_plan.h kernel_exists): the plan's grid, block, LDS and TRIS, the copy's kernel pair, and what the kernel takes
+template <class... A>
+static hipError_t launch_tris_pair(const LaunchPlan &L, hipStream_t stream, void (*plain)(A...), void (*tris)(A...), const A &...args) {
+    if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)L.blocks), b(L.block);
+    (L.tris ? tris : plain)<<<g, b, L.lds, stream>>>(args...);
+    return hipGetLastError();
+}
+
+// `call` with the names of the copy of the kernel bodies the plan names
+#define FLUX_IN_COPY(L, call)                                             \
+    switch ((L).copy) {                                                   \
+        case kCopyStrict: { using namespace strict; return call; }        \
+        case kCopyFast: { using namespace fast; return call; }            \
+        case kCopyFastDiel: { using namespace fast_diel; return call; }   \
+    }                                                                     \
     return hipErrorInvalidValue
 
 // the kernel the launch planner names for the pass (launch_plan.cpp plan_pass), in the copy it names
@@ -278,9 +286,8 @@ hipError_t launch_pass(Pass pass, const RenderParams &p, int variant, int math, 
     if (L.kernel < 0) return hipSuccess;
     switch (pass) {
         case kPassRender: FLUX_IN_COPY(L, launch_render_impl(L, p, stream));
-        case kPassMoments: FLUX_IN_COPY(L, launch_moments_impl(L, p, stream));
-        // (a scene with a Dielectric runs the FAST copy: no lobe behind a first hit)
-        case kPassAov: return L.copy == kCopyStrict ? strict::launch_aov_impl(L, p, stream) : fast::launch_aov_impl(L, p, stream);
+        case kPassMoments: FLUX_IN_COPY(L, launch_tris_pair(L, stream, moments_kernel<false>, moments_kernel<true>, p));
+        case kPassAov: FLUX_IN_COPY(L, launch_tris_pair(L, stream, aov_kernel<false>, aov_kernel<true>, p));
         case kPassAdaptive: break;  // (launch_adaptive: it needs the work list)
         case kPassAovChain: break;  // (launch_aov_chain: it needs the chain limit)
     }
@@ -291,22 +298,27 @@ hipError_t launch_pass(Pass pass, const RenderParams &p, int variant, int math, 
 hipError_t launch_adaptive(const RenderParams &p, const AdaptiveWork &a, int math, hipStream_t stream) {
     const LaunchPlan L = plan_pass(kPassAdaptive, p, 0, math, a.count);
     if (L.kernel < 0) return hipSuccess;
-    FLUX_IN_COPY(L, launch_adaptive_impl(L, p, a, stream));
+    FLUX_IN_COPY(L, launch_tris_pair(L, stream, adaptive_pass_kernel<false>, adaptive_pass_kernel<true>, p, a));
 }
 
 // the feature buffers at the first non-specular hit, chains of at most `max_chain` segments, in the copy a render of the same job runs
 hipError_t launch_aov_chain(const RenderParams &p, int max_chain, int math, hipStream_t stream) {
     const LaunchPlan L = plan_pass(kPassAovChain, p, 0, math);
     if (L.kernel < 0) return hipSuccess;
-    FLUX_IN_COPY(L, launch_aov_chain_impl(L, p, max_chain, stream));
+    FLUX_IN_COPY(L, launch_tris_pair(L, stream, aov_chain_kernel<false>, aov_chain_kernel<true>, p, max_chain));
 }
 
+// flux_debug_shade has no planner entry: 64-lane blocks, one ray a lane, the per-lane stacks
 hipError_t launch_shade_rays(const RenderParams &p, int math, const double *d_rays, int n, int depth, uint32_t set,
                              uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream) {
-    const size_t lds = shade_rays_lds(p, math);
+    if (n <= 0) return hipSuccess;
     LaunchPlan L;
     L.copy = kernel_copy(p, math);
-    FLUX_IN_COPY(L, launch_shade_rays_impl(p, lds, d_rays, n, depth, set, index, d_rgb, d_hit, d_t, stream));
+    L.blocks = ((uint64_t)n + 63) / 64;
+    L.lds = shade_rays_lds(p, math);
+    L.tris = p.n_tris > 0 ? 1 : 0;
+    FLUX_IN_COPY(L, launch_tris_pair(L, stream, shade_rays_kernel<false>, shade_rays_kernel<true>, p, d_rays, n, depth, set, index, d_rgb,
+                                     d_hit, d_t));
 }
 #undef FLUX_IN_COPY
 

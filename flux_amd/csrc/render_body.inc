@@ -3773,103 +3773,40 @@ __global__ __launch_bounds__(64, 1) void shade_rays_kernel(const RenderParams P,
     out_rgb[3 * k + 2] = Lb;
 }
 
-static hipError_t launch_shade_rays_impl(const RenderParams &p, size_t lds, const double *d_rays, int n, int depth, uint32_t set,
-                                         uint32_t index, double *d_rgb, int *d_hit, double *d_t, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    const dim3 g((unsigned)((n + 63) / 64)), b(64);
-    if (p.n_tris > 0) shade_rays_kernel<true><<<g, b, lds, stream>>>(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t);
-    else shade_rays_kernel<false><<<g, b, lds, stream>>>(p, d_rays, n, depth, set, index, d_rgb, d_hit, d_t);
-    return hipGetLastError();
-}
+// This copy of the bodies, as kernel_exists (flux_plan.h) names it
+constexpr KernelCopy kThisCopy = !FLUX_FAST ? kCopyStrict : FLUX_DIEL ? kCopyFastDiel : kCopyFast;
 
-// Runs the kernel the launch plan names (launch_plan.cpp plan_render): its fields become template arguments, nothing is decided here.
+// Runs the render kernel the launch plan names (launch_plan.cpp plan_render).  Nothing is decided here: the plan's fields become
+// template arguments -- all of them as ONE compile-time constant (with_const, render.hip) -- and kernel arguments, and each kernel is
+// named once, behind kernel_exists' word (flux_plan.h) that this copy compiles it with those arguments.  A plan that names another
+// is hipErrorInvalidValue before anything is launched.  `p.stats` is a property of the call, not of the plan.
 static hipError_t launch_render_impl(const LaunchPlan &L, const RenderParams &p, hipStream_t stream) {
-    if (L.blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const bool tris = L.tris != 0;
-    const bool stats = p.stats != nullptr;
+    if (L.blocks > 0x7fffffffull || !plan_exists(kPassRender, L)) return hipErrorInvalidValue;
     const dim3 g((unsigned)L.blocks), b(L.block);
     const size_t lds = L.lds;
-#define FLUX_LAUNCH(K)                                                     \
-    do {                                                                   \
-        if (stats && tris) K<true, true><<<g, b, lds, stream>>>(p);        \
-        else if (stats) K<true, false><<<g, b, lds, stream>>>(p);          \
-        else if (tris) K<false, true><<<g, b, lds, stream>>>(p);           \
-        else K<false, false><<<g, b, lds, stream>>>(p);                    \
-    } while (0)
-#if FLUX_FAST
-    // The copy with the dielectric lobe has no TYP and no hit-queue instantiation: the planner never asks for one for a scene with a
-    // dielectric, and a plan that does is a planner bug.
-    if (L.kernel == 3) {
-        if (stats) render_bvh_kernel<true><<<g, b, lds, stream>>>(p);
-        else render_bvh_kernel<false><<<g, b, lds, stream>>>(p);
-        return hipGetLastError();
-    }
-    if (L.kernel == 4) {
-        if (L.typ) {
-#if FLUX_DIEL
-            return hipErrorInvalidValue;
-#else
-            if (stats) render_bvh4_kernel<true, true, true><<<g, b, lds, stream>>>(p);
-            else render_bvh4_kernel<false, true, true><<<g, b, lds, stream>>>(p);
+    RenderParams ps = p;  // the split kernel's
+    ps.tput = L.tput ? p.tput : nullptr;
+    ps.cut_depth = L.cut_depth;
+    ps.depth_pair[0] = ps.max_depth;  // (the two once more, for the TYP instantiations' one load: split_depths)
+    ps.depth_pair[1] = L.cut_depth;
+    const int args = (p.stats != nullptr ? 1 : 0) | L.tris << 1 | L.typ << 2 | L.max32 << 3 | (L.hq_cap > 0 ? 1 : 0) << 4 | L.lds_scene << 5 | L.axis << 6;
+    return with_const<256>(args, [&](auto c) {
+        constexpr int I = decltype(c)::value, AXIS = I >> 6;
+        constexpr bool STATS = I & 1, TRIS = I & 2, TYP = I & 4, MAX32 = I & 8, HQ = I & 16, LDS_SCENE = I & 32;
+        constexpr auto here = [](int kernel) { return kernel_exists(kThisCopy, kPassRender, kernel, TRIS, TYP, MAX32, HQ, AXIS, LDS_SCENE); };
+        if constexpr (here(0))
+            if (L.kernel == 0) render_static_kernel<STATS, TRIS><<<g, b, lds, stream>>>(p);
+        if constexpr (here(1))
+            if (L.kernel == 1) render_refill_kernel<STATS, TRIS><<<g, b, lds, stream>>>(p);
+#if FLUX_FAST  // (the STRICT copy does not declare these)
+        if constexpr (here(2))
+            if (L.kernel == 2) render_split_kernel<STATS, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, L.hq_cap, L.hq_th, L.hq_bits, L.uniform_a);
+        if constexpr (here(3))
+            if (L.kernel == 3) render_bvh_kernel<STATS><<<g, b, lds, stream>>>(p);
+        if constexpr (here(4))
+            if (L.kernel == 4) render_bvh4_kernel<STATS, LDS_SCENE, TYP><<<g, b, lds, stream>>>(p);
 #endif
-        } else if (L.lds_scene) {
-            if (stats) render_bvh4_kernel<true, true, false><<<g, b, lds, stream>>>(p);
-            else render_bvh4_kernel<false, true, false><<<g, b, lds, stream>>>(p);
-        } else {
-            if (stats) render_bvh4_kernel<true, false, false><<<g, b, lds, stream>>>(p);
-            else render_bvh4_kernel<false, false, false><<<g, b, lds, stream>>>(p);
-        }
         return hipGetLastError();
-    }
-    if (L.kernel == 2) {
-        const int c = L.hq_cap, h = L.hq_th, bits = L.hq_bits;
-        const bool hq = L.hq_cap > 0;
-        // (the throughput product table only where it is laid out for this plan's list entries)
-        RenderParams ps = p;
-        if (!hq || ps.tput_bits != bits) ps.tput = nullptr;
-        ps.cut_depth = L.cut_depth;
-        ps.depth_pair[0] = ps.max_depth;  // (the two once more, for the TYP instantiations' one load: split_depths)
-        ps.depth_pair[1] = L.cut_depth;
-#define FLUX_LAUNCH_SPLIT_AXIS(MAX32, TYP, HQ, AXIS)                                                                  \
-    do {                                                                                                             \
-        if (stats) render_split_kernel<true, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);  \
-        else render_split_kernel<false, MAX32, TYP, HQ, AXIS><<<g, b, lds, stream>>>(ps, c, h, bits, L.uniform_a);   \
-    } while (0)
-#define FLUX_LAUNCH_SPLIT(MAX32, TYP, HQ) FLUX_LAUNCH_SPLIT_AXIS(MAX32, TYP, HQ, 0)
-// (TYP: the instantiation of the first plane's axis, RenderParams::plane_axis)
-#define FLUX_LAUNCH_SPLIT_TYP(HQ)                                                         \
-    do {                                                                                  \
-        if (ps.plane_axis == kPlaneAxisY) FLUX_LAUNCH_SPLIT_AXIS(true, true, HQ, kPlaneAxisY);       \
-        else if (ps.plane_axis == kPlaneAxisX) FLUX_LAUNCH_SPLIT_AXIS(true, true, HQ, kPlaneAxisX);  \
-        else if (ps.plane_axis == kPlaneAxisZ) FLUX_LAUNCH_SPLIT_AXIS(true, true, HQ, kPlaneAxisZ);  \
-        else FLUX_LAUNCH_SPLIT(true, true, HQ);                                           \
-    } while (0)
-#if FLUX_DIEL
-        if (L.typ || hq) return hipErrorInvalidValue;
-#else
-        if (L.typ) {
-            if (hq) FLUX_LAUNCH_SPLIT_TYP(true);
-            else FLUX_LAUNCH_SPLIT_TYP(false);
-            return hipGetLastError();
-        }
-        if (hq) {
-            if (L.max32) FLUX_LAUNCH_SPLIT(true, false, true);
-            else FLUX_LAUNCH_SPLIT(false, false, true);
-            return hipGetLastError();
-        }
-#endif
-        if (L.max32) FLUX_LAUNCH_SPLIT(true, false, false);
-        else FLUX_LAUNCH_SPLIT(false, false, false);
-#undef FLUX_LAUNCH_SPLIT_TYP
-#undef FLUX_LAUNCH_SPLIT
-#undef FLUX_LAUNCH_SPLIT_AXIS
-        return hipGetLastError();
-    }
-#endif
-    if (L.kernel == 0)
-        FLUX_LAUNCH(render_static_kernel);
-    else
-        FLUX_LAUNCH(render_refill_kernel);
-#undef FLUX_LAUNCH
-    return hipGetLastError();
+    });
 }
+

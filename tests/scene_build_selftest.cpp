@@ -7,7 +7,8 @@
 // plan_render: kernel, instantiation, block, grid, LDS) for every scene over a grid of jobs, one line each, which the test pins too,
 // and <out dir>/pass_plans.txt: the same for the per-pixel passes (feature buffers, sample moments, an adaptive pass).
 // The instantiation word of flux_ctx_launch_plan (flux_plan.h plan_flags) is pinned for the headline job -- demo2, 800 x 600,
-// sample root 128, depth 5 -- and for box_room at depths 5 and 3.
+// sample root 128, depth 5 -- and for box_room at depths 5 and 3.  Every plan it asks for, and every plan of a grid of synthetic jobs
+// (synthetic_plans), must name a kernel instantiation that exists (flux_plan.h kernel_exists).
 // Prints one "ok <name>" per passed check and "all ok" at the end; exits 1 on the first failure.
 #include <cmath>
 #include <cstdio>
@@ -104,7 +105,7 @@ static int build(const flux_scene_desc &desc, flux::HostScene &h) {
 // sample roots x kernel variants x arithmetic x traversal x a rows and a sets launch; max_trace_depth 5 (the job default).  Where the
 // upload sets a pointer the planner tests, a placeholder stands in for it.
 static std::string g_plans;
-static void plans(const std::string &name, const flux::HostScene &h, const char *tag) {
+static int plans(const std::string &name, const flux::HostScene &h, const char *tag) {
     static const flux::DevScanSphere32 fsph32_placeholder{};
     static const flux::DevNode4Q nodes4_placeholder{};
     static const char *kVariant[] = {"default", "static", "refill", "split"};
@@ -128,6 +129,7 @@ static void plans(const std::string &name, const flux::HostScene &h, const char 
                         if (trav == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
                         if (trav == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
                         const flux::LaunchPlan L = flux::plan_render(p, variant, math);
+                        CHECK(flux::plan_exists(flux::kPassRender, L));  // (render.hip compiles the instantiation it names)
                         std::snprintf(buf, sizeof(buf),
                                       "%s%s root=%u variant=%s math=%s traversal=%s launch=%s kernel=%d copy=%d tris=%d typ=%d max32=%d "
                                       "lds_scene=%d hq_cap=%d hq_th=%d hq_bits=%d block=%u blocks=%llu lds=%zu K=%u\n",
@@ -136,13 +138,14 @@ static void plans(const std::string &name, const flux::HostScene &h, const char 
                                       L.hq_cap, L.hq_th, L.hq_bits, L.block, (unsigned long long)L.blocks, L.lds, L.waves_per_pixel);
                         g_plans += buf;
                     }
+    return 0;
 }
 
 // The plans of the per-pixel passes (flux_plan.h plan_pass) of one scene, for <out dir>/pass_plans.txt: sample roots
 // below, at and above one wave x arithmetic x traversal x pass -- the adaptive pass over a one-entry list and over a seventh of
 // the frame.  The jobs' other fields as in plans().
 static std::string g_pass_plans;
-static void pass_plans(const std::string &name, const flux::HostScene &h) {
+static int pass_plans(const std::string &name, const flux::HostScene &h) {
     static const flux::DevNode4Q nodes4_placeholder{};
     static const char *kTraversal[] = {"bvh", "brute", "binary"};
     static const char *kPass[] = {"aov", "moments", "adaptive1", "adaptive7th"};
@@ -159,15 +162,15 @@ static void pass_plans(const std::string &name, const flux::HostScene &h) {
                     if (trav == FLUX_TRAVERSE_BRUTE) p.bvh_stack = 0;
                     if (trav == FLUX_TRAVERSE_BVH_BINARY) p.nodes4 = nullptr;
                     const uint64_t npix = (uint64_t)p.num_rows * (uint64_t)p.img_w;
-                    const flux::LaunchPlan L = pass == 0   ? flux::plan_pass(flux::kPassAov, p, FLUX_KERNEL_DEFAULT, math)
-                                               : pass == 1 ? flux::plan_pass(flux::kPassMoments, p, FLUX_KERNEL_DEFAULT, math)
-                                                           : flux::plan_pass(flux::kPassAdaptive, p, FLUX_KERNEL_DEFAULT, math,
-                                                                             pass == 2 ? 1 : npix / 7 + 1);
+                    const flux::Pass which = pass == 0 ? flux::kPassAov : pass == 1 ? flux::kPassMoments : flux::kPassAdaptive;
+                    const flux::LaunchPlan L = flux::plan_pass(which, p, FLUX_KERNEL_DEFAULT, math, pass < 2 ? 0 : pass == 2 ? 1 : npix / 7 + 1);
+                    CHECK(flux::plan_exists(which, L));
                     std::snprintf(buf, sizeof(buf), "%s root=%u math=%s traversal=%s pass=%s copy=%d tris=%d block=%u blocks=%llu lds=%zu\n",
                                   name.c_str(), root, math == FLUX_MATH_STRICT ? "strict" : "fast", kTraversal[trav], kPass[pass], L.copy,
                                   L.tris, L.block, (unsigned long long)L.blocks, L.lds);
                     g_pass_plans += buf;
                 }
+    return 0;
 }
 
 // The plan's flags word (flux_plan.h plan_flags) of a full-frame FAST render of the scene at sample root 128 with the default kernel,
@@ -196,6 +199,83 @@ static int job_flags(const char *scenes, const char *name, int depth, uint32_t &
     return 0;
 }
 
+// The planner over jobs the shipped scenes do not reach: every answer names an instantiation render.hip compiles (flux_plan.h
+// kernel_exists).  Scene-derived fields as scene_build.cpp ties them (unit_dirs, self_skip = !glossy_long), one plane, an environment
+// sphere among the spheres; a mesh has a tree of 8 levels, `nodes4`: with the 4-wide one; a context that would build the throughput
+// table holds it.  Also the table itself: its rows counted.
+static int synthetic_plans() {
+    static const flux::DevScanSphere32 fsph32_placeholder{};
+    static const flux::DevNode4Q nodes4_placeholder{};
+    static const double tput_placeholder = 0.0;
+    unsigned long long asked = 0;
+    for (const int n_sph : {0, 1, 32, 33, 64, 65})
+        for (int bits = 0; bits < 256; bits++)
+            for (int plane_axis = 0; plane_axis < 4; plane_axis++)
+                for (const uint32_t nsamp : {16u, 64u, 256u, 16384u})
+                    for (const int max_depth : {1, 5, 9}) {
+                        flux::RenderParams p{};
+                        p.img_w = 32;
+                        p.img_h = p.num_rows = 16;
+                        p.num_sets = 32;
+                        p.set_count = 32;
+                        p.row_stride = p.set_stride = p.slot_stride = 1;
+                        p.n_mats = 2;
+                        p.n_sph = n_sph;
+                        p.n_pln = 1;
+                        p.n_dsk = bits & 1;
+                        p.n_box = bits >> 1 & 1;
+                        p.has_diel = bits >> 2 & 1;
+                        p.glossy_long = bits >> 3 & 1;
+                        p.unit_dirs = p.self_skip = !p.glossy_long;
+                        p.n_uni = 1 + (bits >> 4 & 1);
+                        p.env_short = p.n_uni == 1;
+                        p.fsph32 = bits >> 5 & 1 ? &fsph32_placeholder : nullptr;
+                        p.n_tris = bits >> 6 & 1;
+                        p.bvh_stack = p.bvh4_stack = p.n_tris ? 8 : 0;
+                        p.nodes4 = bits >> 7 & 1 ? &nodes4_placeholder : nullptr;
+                        p.n_shapes = flux::hit_records(p);
+                        p.plane_axis = plane_axis;
+                        p.nsamp = nsamp;
+                        p.max_depth = max_depth;
+                        int tb = 0;
+                        if (flux::tput_table_bytes(p, &tb)) {
+                            p.tput = &tput_placeholder;
+                            p.tput_bits = tb;
+                            p.tput_finite = 1;
+                        }
+                        for (const int math : {FLUX_MATH_FAST, FLUX_MATH_STRICT}) {
+                            for (const int variant : {FLUX_KERNEL_DEFAULT, FLUX_KERNEL_STATIC, FLUX_KERNEL_REFILL, FLUX_KERNEL_SPLIT}) {
+                                const flux::LaunchPlan L = flux::plan_render(p, variant, math);
+                                CHECK(L.kernel >= 0 && flux::plan_exists(flux::kPassRender, L));
+                                asked++;
+                            }
+                            for (const flux::Pass pass : {flux::kPassAov, flux::kPassMoments, flux::kPassAdaptive, flux::kPassAovChain}) {
+                                const flux::LaunchPlan L = flux::plan_pass(pass, p, FLUX_KERNEL_DEFAULT, math, 7);
+                                CHECK(L.kernel == 0 && flux::plan_exists(pass, L));
+                                asked++;
+                            }
+                        }
+                    }
+    // The rows of the table, STATS apart.  Every copy: static and refill x TRIS, 4, and the four passes x TRIS, 8.  FAST beside them:
+    // split 2 x 4 with TYP and 2 x 2 without, the binary tree's 1, the 4-wide tree's 3: 28 in all; with the dielectric lobe split 2,
+    // 1 and 2: 17; STRICT 12.  (The render kernels' 33 rows twice, for STATS, the passes' 24, shade_rays_kernel x TRIS per copy and
+    // the six table and probe kernels: render.hip's 102 kernels.)
+    int rows[3] = {0, 0, 0};
+    for (int copy = 0; copy < 3; copy++)
+        for (int pass = flux::kPassRender; pass <= flux::kPassAovChain; pass++)
+            for (int kernel = 0; kernel <= 4; kernel++)
+                for (int a = 0; a < 32; a++)
+                    for (int axis = 0; axis < 4; axis++)
+                        rows[copy] += flux::kernel_exists(copy, pass, kernel, a & 1, a >> 1 & 1, a >> 2 & 1, a >> 3 & 1, axis, a >> 4 & 1);
+    CHECK(rows[flux::kCopyStrict] == 12 && rows[flux::kCopyFast] == 28 && rows[flux::kCopyFastDiel] == 17);
+    static_assert(!flux::kernel_exists(flux::kCopyFastDiel, flux::kPassRender, 2, 0, 1, 1, 0, 0, 0) &&
+                      !flux::kernel_exists(flux::kCopyFast, flux::kPassRender, 2, 0, 0, 1, 0, 2, 0) &&
+                      flux::kernel_exists(flux::kCopyFast, flux::kPassRender, 2, 0, 1, 1, 1, 3, 0),
+                  "kernel_exists is a constant expression: the launchers ask it under if constexpr");
+    std::printf("ok synthetic plans (%llu)\n", asked);
+    return 0;
+}
+
 static int dump(const std::string &name, const flux_scene_desc &desc) {
     flux::HostScene h;
     CHECK(build(desc, h) == FLUX_OK);
@@ -207,10 +287,9 @@ static int dump(const std::string &name, const flux_scene_desc &desc) {
     CHECK(write_vec(name + ".shapes.bin", h.shapes) && write_vec(name + ".mats.bin", mats) && write_vec(name + ".fscene.bin", h.fscene) &&
           write_vec(name + ".tris.bin", h.tris) && write_vec(name + ".nodes.bin", h.nodes) && write_vec(name + ".nodesq.bin", h.nodesq) &&
           write_vec(name + ".arena.bin", h.arena) && write_file(name + ".scalars.txt", sc.data(), sc.size()));
-    plans(name, h, "");
-    pass_plans(name, h);
+    if (plans(name, h, "") || pass_plans(name, h)) return 1;
     setenv("FLUX_SPLIT_HITQ_CAP", "0", 1);  // the split kernel without its hit queue
-    plans(name, h, "+hitq_cap0");
+    if (plans(name, h, "+hitq_cap0")) return 1;
     unsetenv("FLUX_SPLIT_HITQ_CAP");
     std::printf("ok dump %s\n", name.c_str());
     return 0;
@@ -351,6 +430,7 @@ int main(int argc, char **argv) {
     CHECK(write_file("plans.txt", g_plans.data(), g_plans.size()));
     CHECK(write_file("pass_plans.txt", g_pass_plans.data(), g_pass_plans.size()));
     std::printf("ok plans\n");
+    if (synthetic_plans()) return 1;
     {
         const uint32_t fast = 1u << FLUX_PLAN_FLAG_COPY_SHIFT;
         const uint32_t hitq = FLUX_PLAN_FLAG_HITQ | FLUX_PLAN_FLAG_UNIFORM_A | FLUX_PLAN_FLAG_MAX32 | fast;

@@ -3,7 +3,10 @@ records, the FAST scene image, the mesh's triangles and trees and the scene-deri
 height field, and this test pins the SHA-256 of every buffer.  The digests are the bytes the kernels read: a change to any of
 them changes what a context uploads.  The same program asks the launch planner (flux_amd/csrc/launch_plan.cpp) which kernel
 instantiation, block, grid and LDS each of those scenes gets over a grid of jobs; the table is pinned too, and so is the
-instantiation word of the headline job (demo2, 800 x 600, 16384 spp, depth 5) and of box_room at depths 5 and 3 ("ok flags")."""
+instantiation word of the headline job (demo2, 800 x 600, 16384 spp, depth 5) and of box_room at depths 5 and 3 ("ok flags").
+Every one of those plans, and every plan of a grid of synthetic jobs the shipped scenes do not reach ("ok synthetic plans"), must
+name a kernel instantiation that render.hip compiles (flux_plan.h kernel_exists): a planner that asks for one that is not there
+fails here, not at a launch on a GPU.  The program runs once more as a stand-alone executable under AddressSanitizer and UBSan."""
 import hashlib
 import os
 
@@ -99,9 +102,16 @@ def default_run(selftest, default_out):
 def test_selftest_checks(default_run):
     stdout, _ = default_run
     for name in ("unit normal", "non-unit plane normal", "sphere beyond 1e3", "one emissive invert sphere", "two invert spheres",
-                 "group walk", "no f32 filter", "plans", "flags") + tuple(f"dump {s}" for s in SCENE_NAMES):
+                 "group walk", "no f32 filter", "plans", "synthetic plans", "flags") + tuple(f"dump {s}" for s in SCENE_NAMES):
         assert f"ok {name}" in stdout
     assert "all ok" in stdout
+
+
+def test_selftest_under_asan_and_ubsan(tmp_path):
+    """The host build, the planner (compiled into the program) and the walk over its answers with -fsanitize=address,undefined."""
+    exe = st.build(str(tmp_path / "scene_build_selftest_san"), "scene_build_selftest.cpp",
+                   csrc=("scene_build.cpp", "bvh.cpp", "launch_plan.cpp"), flags=st.SANITIZE)
+    assert "all ok" in st.run(exe, SCENES, str(tmp_path), env=st.sanitize_env(), timeout=600)
 
 
 def test_buffers_are_pinned(default_run):
