@@ -22,7 +22,9 @@ import os
 
 import numpy as np
 
+import split_checks as sc
 from conftest import SCENES
+from split_checks import SLOT, scene_lds
 
 SCENES_PER_CLASS = int(os.environ.get("FLUX_SPLIT_SWEEP_SCENES", "6"))   # a longer sweep: FLUX_SPLIT_SWEEP_SCENES=60
 CLASSES = ("typ_axis", "typ_no_axis", "records_17_30", "spheres_33_64", "no_env_shortcut", "beyond_the_guard", "five_exponents",
@@ -38,7 +40,6 @@ JOBS = ((64, 3), (65, 8), (91, 2), (127, 5), (128, 1), (128, 8))
 # which draw of its stream a scene is (default 0): the draws before it fail a condition of tests/test_split_sweep.py, which says which
 DRAWS = {"typ_no_axis": {1: 1}, "spheres_33_64": {4: 1}, "beyond_the_guard": {1: 1}, "disks_and_boxes": {0: 1}, "glass": {0: 1}}
 
-REC, SPH, SLOT = 96, 32, 68           # DevHitRec, DevScanSphere, a hit-queue slot (bytes in LDS)
 EXPONENTS = (0.0, 1.0, 2.5, 10.0, 100.0, 1e4)
 FIVE_EXPONENTS = (0.0, 1.0, 10.0, 100.0, 1e4)   # more than kGlossExpSlots = 4
 AXES = ((1.0, 0.0, 0.0), (-1.0, -0.0, 0.0), (-0.0, 1.0, 0.0), (0.0, -1.0, -0.0), (0.0, -0.0, 1.0), (-0.0, 0.0, -1.0))
@@ -306,10 +307,6 @@ def _records(flux, sd):
     return sum(6 if isinstance(s, flux.BoxData) else 1 for s in sd.shapes)
 
 
-def scene_lds(flux, sd):
-    return _records(flux, sd) * REC + sum(isinstance(s, flux.SphereData) for s in sd.shapes) * SPH
-
-
 def plan_hitq(flux, sd, root, depth, env=None):
     """launch_plan.cpp plan_hitq for the job's K waves a pixel: (C, H, bits an entry), C = 0 for the ray queue"""
     env = env or {}
@@ -406,12 +403,7 @@ def oracle_run(cls, index, draw, root, depth):
     from oracle import oracle
     sd, seed = draws(cls, index, draw + 1)[-1]
     t0 = time.perf_counter()
-    o = oracle.Oracle(sd, flux.JobConfiguration(root, depth, 50), seed=seed)
-    o.stats(reset=True)
-    frame = o.render_frame(threads=8)
-    stats = o.stats()
-    o.close()
-    frame.setflags(write=False)
+    frame, stats = sc.oracle_run(flux, oracle, sd, root, depth, seed)
     return frame, stats, time.perf_counter() - t0
 
 

@@ -18,12 +18,13 @@ import copy
 import numpy as np
 import pytest
 
+import split_checks as sc
 from conftest import small_scene
+from split_checks import QUEUES, TOL_ORACLE, TOL_ORDER
 from switches import queue, switches as env_switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-QUEUES = [None, (86, 22), (66, 1)]
 CASES = ["demo2_depth_1", "demo2_depth_2", "demo2_depth_3", "demo2", "close_to_a_reflective_sphere", "reflective_sphere_depth_2",
          "close_to_a_matte_sphere", "floor_as_a_disk", "floor_as_a_box_depth_3", "floor_as_a_box", "glass_beside_the_balls",
          "partial_last_pass"]
@@ -89,48 +90,27 @@ def switches(env_switches):
     return lambda q, cut: env_switches(FLUX_SPLIT_DEPTH_CUT=None if cut else 0, **queue(q))
 
 
-def _render(flux, sd, n, depth, kernel, rows=None):
-    """frame, statistics, plan -- and, with rows = (first, last), the frame once more and that sub-range from the same context"""
-    with flux.Renderer(sd, flux.JobConfiguration(n, depth, 50), seed=SEED) as r:
-        r.set_kernel(kernel)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        out = img, r.stats(), r.launch_plan()
-        if rows is not None:
-            out += (r.render_frame(), r.render_rows(*rows))
-        return out
-
-
 _refs = {}
 
 
-def _references(flux, oracle_mod, demo2, case):
-    """The oracle's, the refill kernel's and the static kernel's frame and statistics of a case: computed once, read by every queue."""
-    if case not in _refs:
-        sd, oracle_sd, n, depth = _cases(flux, demo2)[case]
-        want, o_stats = None, None
-        if case not in NO_ORACLE:
-            o = oracle_mod.Oracle(oracle_sd, flux.JobConfiguration(n, depth, 50), seed=SEED)
-            o.stats(reset=True)
-            want = o.render_frame(threads=8)
-            o_stats = o.stats()
-            want.setflags(write=False)
-        refill = _render(flux, sd, n, depth, flux.KERNEL_REFILL)
-        static = _render(flux, sd, n, depth, flux.KERNEL_STATIC)
-        for a in (refill[0], static[0]):
-            a.setflags(write=False)
-        _refs[case] = (sd, n, depth, want, o_stats, refill, static)
-    return _refs[case]
+def _case(flux, oracle_mod, demo2, case):
+    """scene, sample root, depth limit, and the oracle's, the refill kernel's and the static kernel's frame and statistics: read by
+    every queue"""
+    sd, oracle_sd, n, depth = _cases(flux, demo2)[case]
+    return (sd, n, depth) + sc.references(_refs, case, flux, oracle_mod, sd, n, depth, SEED,
+                                          oracle_sd=None if case in NO_ORACLE else oracle_sd)
 
 
 def _check(flux, oracle_mod, demo2, switches, case, q):
-    sd, n, depth, want, o_stats, (refill, rs, _), (static, ss, _) = _references(flux, oracle_mod, demo2, case)
+    sd, n, depth, want, o_stats, (refill, rs, *_), (static, ss, *_) = _case(flux, oracle_mod, demo2, case)
     first, last = 5, 11
     switches(q, True)
-    got, gs, plan, again, rows = _render(flux, sd, n, depth, flux.KERNEL_SPLIT, rows=(first, last))
+    # the frame once more and a sub-range of its rows from the same context
+    with flux.Renderer(sd, flux.JobConfiguration(n, depth, 50), seed=SEED) as r:
+        got, gs = sc.with_stats(flux, r, flux.KERNEL_SPLIT)
+        plan, again, rows = r.launch_plan(), r.render_frame(), r.render_rows(first, last)
     switches(q, False)
-    uncut, us, plan_uncut = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    uncut, us, plan_uncut = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches(None, True)
     assert plan["kernel"] == flux._lib.PLAN_SPLIT
     assert plan_uncut == plan
@@ -140,12 +120,12 @@ def _check(flux, oracle_mod, demo2, switches, case, q):
           f"|cut - oracle| {err_oracle:.3e}  depth_exhausted {gs['depth_exhausted']}")
     assert gs == us, (gs, us)
     assert gs == rs == ss, (gs, rs, ss)
-    assert err_uncut <= 1e-12
-    assert err_refill <= 1e-12
-    assert err_static <= 1e-12
+    assert err_uncut <= TOL_ORDER
+    assert err_refill <= TOL_ORDER
+    assert err_static <= TOL_ORDER
     if want is not None:
         assert {k: gs[k] for k in o_stats} == o_stats
-        assert err_oracle < 1e-4
+        assert err_oracle < TOL_ORACLE
     else:
         assert ss["dielectric_reflections"] > 0 and ss["dielectric_transmissions"] > 0 and ss["depth_exhausted"] > 0
     assert np.array_equal(got, again)
@@ -163,15 +143,15 @@ def test_depth_cut_in_the_ray_queue_loop(flux, oracle_mod, demo2, switches):
     _check(flux, oracle_mod, demo2, switches, "ray_queue_job", None)
 
 
-def test_the_cut_has_paths_to_end(flux, oracle_mod, demo2):
+def test_the_cut_has_paths_to_end(flux, oracle_mod, demo2, env_switches):
     """By the oracle's own statistics: at depth 5 demo2 has paths that the depth limit ends, and at depth 2 those are exactly the hits
     that bounce at depth 2 -- every bounce of the depth-2 run but the primaries', which the depth-1 run counts as depth_exhausted."""
-    st = {d: _references(flux, oracle_mod, demo2, "demo2" if d == 5 else f"demo2_depth_{d}")[4] for d in (1, 2, 5)}
+    st = {d: _case(flux, oracle_mod, demo2, "demo2" if d == 5 else f"demo2_depth_{d}")[4] for d in (1, 2, 5)}
     bounces = lambda s: s["matte_bounces"] + s["glossy_bounces"] + s["specular_bounces"]  # noqa: E731
     assert st[5]["depth_exhausted"] > 0
     assert st[1]["depth_exhausted"] == bounces(st[1]) > 0
     assert st[2]["depth_exhausted"] == bounces(st[2]) - bounces(st[1]) > 0
-    mirror = _references(flux, oracle_mod, demo2, "reflective_sphere_depth_2")[4]
+    mirror = _case(flux, oracle_mod, demo2, "reflective_sphere_depth_2")[4]
     assert mirror["specular_bounces"] > 0 and mirror["depth_exhausted"] > 0
 
 
@@ -182,11 +162,11 @@ def test_throughputs_that_are_not_finite_refuse_the_cut(flux, demo2, switches, q
     switch changes nothing -- and the pixels that are finite are the refill kernel's."""
     sd, _, n, depth = _cases(flux, demo2)["floor_of_colour_1e200"]
     switches(q, True)
-    got, gs, plan = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    got, gs, plan = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches(q, False)
-    uncut, us, _ = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    uncut, us = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:2]
     switches(None, True)
-    refill, rs, _ = _render(flux, sd, n, depth, flux.KERNEL_REFILL)
+    refill, rs = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_REFILL)[:2]
     assert plan["kernel"] == flux._lib.PLAN_SPLIT
     assert not np.isfinite(refill).all() and np.isfinite(refill).any()
     assert np.array_equal(got, uncut, equal_nan=True)

@@ -17,10 +17,10 @@ import aov_spec
 import path_spec
 import switches
 from conftest import SCENES
+from split_checks import REC, SLOT, SPH   # a hit record, a hit queue slot, a scan sphere (bytes in LDS)
 
 pytestmark = pytest.mark.gpu
 
-SLOT, REC, SPH = 68, 96, 32   # tests/test_gpu_split_hit_queue.py: a hit queue slot, a hit record, a scan sphere (bytes in LDS)
 TOL, TOL_TIGHT = 1e-4, 1e-9   # the north-star tolerance; tests/test_gpu_parity.py
 REFRACTION_INDICES = [1.0, 1.33, 1.5, 2.4, 0.7]
 EXPONENTS = [0.0, 1.0, 10.0, 100.0, 1e4]

@@ -27,14 +27,15 @@ import os
 import numpy as np
 import pytest
 
+import split_checks as sc
 import switches
 from switches import switches as env_switches  # noqa: F401 (the fixture)
 from conftest import SCENES, small_scene
+from split_checks import RAY_QUEUE, SLOT, TOL_ORDER
 
 pytestmark = pytest.mark.gpu
 
-SLOT, RAY_QUEUE, REC, SPH = 68, 5120, 96, 32   # tests/test_gpu_split_hit_queue.py
-W, H = 16, 12
+W, H, SEED = 16, 12, 1
 SCENE_NAMES = ["demo2", "matte_plane", "glossy", "matte_sphere", "disk_light", "box_room", "glass"]
 NOT_IN_THE_ORACLE = ("disk_light", "box_room", "glass")
 # FLUX_SPLIT_HITQ_CAP, FLUX_SPLIT_HITQ_TAKE_AT
@@ -77,11 +78,6 @@ def _scenes(flux, demo2, W, H):
     return out
 
 
-def _scene_lds(flux, sd):
-    recs = sum(6 if isinstance(s, flux.BoxData) else 1 for s in sd.shapes)  # a box: one record per face
-    return recs * REC + sum(isinstance(s, flux.SphereData) for s in sd.shapes) * SPH
-
-
 def _has_dielectric(flux, sd):
     return any(isinstance(s.material, flux.DielectricData) for s in sd.shapes)
 
@@ -91,37 +87,7 @@ def queue(env_switches):
     return lambda name: env_switches(**switches.queue(QUEUES[name]))
 
 
-def _render(flux, sd, n, depth, kernel, seed=1):
-    with flux.Renderer(sd, flux.JobConfiguration(n, depth, 50), seed=seed) as r:
-        r.set_kernel(kernel)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan()
-
-
-@pytest.fixture(scope="module")
-def references(flux, oracle_mod, scenes, scenes_8x6):
-    """Per scene, sample root and depth limit: the static kernel's frame and statistics and the oracle's statistics, made once (under
-    the plan's own queue: neither reads the overrides)."""
-    out = {}
-
-    def get(name, n, depth):
-        if (name, n, depth) not in out:
-            assert not any(n in os.environ for n in switches.NAMES)
-            sd = (scenes_8x6 if n == 128 else scenes)[name]
-            img, st, _ = _render(flux, sd, n, depth, flux.KERNEL_STATIC)
-            img.setflags(write=False)
-            ost = None
-            if name not in NOT_IN_THE_ORACLE:
-                o = oracle_mod.Oracle(sd, flux.JobConfiguration(n, depth, 50), seed=1)
-                o.stats(reset=True)
-                o.render_frame(threads=8)
-                ost = o.stats()
-                o.close()
-            out[(name, n, depth)] = (img, st, ost)
-        return out[(name, n, depth)]
-    return get
+_refs = {}   # per scene, sample root and depth limit: the oracle's statistics and the static kernel's run, under the plan's own queue
 
 
 def _cases():
@@ -135,14 +101,15 @@ def _cases():
 
 
 @pytest.mark.parametrize("name,n,q,depth", list(_cases()))
-def test_split_equals_static_and_the_oracles_statistics(flux, scenes, scenes_8x6, references, queue, name, n, q, depth):
+def test_split_equals_static_and_the_oracles_statistics(flux, oracle_mod, scenes, scenes_8x6, queue, name, n, q, depth):
     sd = (scenes_8x6 if n == 128 else scenes)[name]
-    want, ws, ost = references(name, n, depth)
+    _, ost, (want, ws, *_) = sc.references(_refs, (name, n, depth), flux, oracle_mod, sd, n, depth, SEED, kernels=("STATIC",),
+                                           oracle_sd=None if name in NOT_IN_THE_ORACLE else sc.SAME)
     queue(q)
-    got, gs, plan = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    got, gs, plan = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:3]
     queue("plan")
     assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == (4 if n == 128 else 1)
-    queues = (plan["lds"] - _scene_lds(flux, sd)) // plan["waves_per_pixel"]
+    queues = (plan["lds"] - sc.scene_lds(flux, sd)) // plan["waves_per_pixel"]
     if _has_dielectric(flux, sd):
         assert queues == RAY_QUEUE
     elif q == "smallest":
@@ -154,7 +121,7 @@ def test_split_equals_static_and_the_oracles_statistics(flux, scenes, scenes_8x6
         assert {k: ws[k] for k in ost} == ost and {k: gs[k] for k in ost} == ost
     if depth > 1 and name != "glossy":
         assert gs["matte_bounces"] > 0
-    assert np.abs(got - want).max() <= 1e-12
+    assert np.abs(got - want).max() <= TOL_ORDER
 
 
 @pytest.mark.parametrize("n,q", [(32, "smallest"), (32, "take1"), (128, "plan")])

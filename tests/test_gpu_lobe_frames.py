@@ -22,19 +22,19 @@ import copy
 import numpy as np
 import pytest
 
+import split_checks as sc
 from conftest import small_scene
+from split_checks import QUEUES, RAY_QUEUE, SLOT, TOL_ORACLE, TOL_ORDER
 from switches import queue, switches as env_switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-QUEUES = [None, (86, 22), (66, 1)]
-SLOT, RAY_QUEUE, REC, SPH = 68, 5120, 96, 32   # tests/test_gpu_split_hit_queue.py
 CASES = ["floor_under_the_environment", "demo2", "plane_with_an_oblique_unit_normal", "ceiling_seen_from_below", "floor_as_a_disk",
          "box_top_and_front_face", "glossy_floor", "reflective_floor", "matte_plane_before_a_coincident_glossy_one",
          "glossy_plane_before_a_coincident_matte_one", "floor_with_a_long_normal", "depth_limit_1", "depth_limit_2"]
 ROUTED_TO_STRICT = ("floor_with_a_long_normal",)
 PLANNED_WITH_THE_RAY_QUEUE = ("demo2",)
-N = 17
+N, SEED = 17, 4
 
 
 def _cases(flux, demo2):
@@ -82,40 +82,13 @@ def _cases(flux, demo2):
     return cases
 
 
-def _scene_lds(flux, sd):
-    records = sum(6 if isinstance(s, flux.BoxData) else 1 for s in sd.shapes)  # a box: one record per face
-    return records * REC + sum(isinstance(s, flux.SphereData) for s in sd.shapes) * SPH
-
-
-def _render(flux, sd, depth, kernel, seed=4):
-    with flux.Renderer(sd, flux.JobConfiguration(N, depth, 50), seed=seed) as r:
-        r.set_kernel(kernel)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan()
-
-
 _refs = {}
 
 
-def _references(flux, oracle_mod, demo2, case):
-    """The oracle's, the refill kernel's and the static kernel's frame and statistics of a case: computed once, read by every queue."""
-    if case not in _refs:
-        sd, oracle_sd, depth = _cases(flux, demo2)[case]
-        want = o_stats = None
-        if oracle_sd is not None:
-            o = oracle_mod.Oracle(oracle_sd, flux.JobConfiguration(N, depth, 50), seed=4)
-            o.stats(reset=True)
-            want = o.render_frame(threads=8)
-            o_stats = o.stats()
-            want.setflags(write=False)
-        refill = _render(flux, sd, depth, flux.KERNEL_REFILL)
-        static = _render(flux, sd, depth, flux.KERNEL_STATIC)
-        for a in (refill[0], static[0]):
-            a.setflags(write=False)
-        _refs[case] = (sd, depth, want, o_stats, refill, static)
-    return _refs[case]
+def _case(flux, oracle_mod, demo2, case):
+    """scene, depth limit, and the oracle's, the refill kernel's and the static kernel's frame and statistics: read by every queue"""
+    sd, oracle_sd, depth = _cases(flux, demo2)[case]
+    return (sd, depth) + sc.references(_refs, case, flux, oracle_mod, sd, N, depth, SEED, oracle_sd=oracle_sd)
 
 
 @pytest.fixture
@@ -128,13 +101,13 @@ def switches(env_switches):
 @pytest.mark.parametrize("case", CASES)
 def test_table_frame_changes_no_bit(flux, oracle_mod, demo2, switches, case, q):
     switches()
-    sd, depth, want, o_stats, (refill, rs, _), (static, ss, _) = _references(flux, oracle_mod, demo2, case)
+    sd, depth, want, o_stats, (refill, rs, *_), (static, ss, *_) = _case(flux, oracle_mod, demo2, case)
     switches(q, table=True)
-    got, gs, plan = _render(flux, sd, depth, flux.KERNEL_SPLIT)
+    got, gs, plan = sc.render(flux, sd, N, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches(q, table=False)
-    computed, cs, plan_computed = _render(flux, sd, depth, flux.KERNEL_SPLIT)
+    computed, cs, plan_computed = sc.render(flux, sd, N, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches(q, table=True, uniform=False)
-    general, es, plan_general = _render(flux, sd, depth, flux.KERNEL_SPLIT)
+    general, es, plan_general = sc.render(flux, sd, N, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches()
     # which instantiation ran: the 64-entry ray queue of the plan's own choice at this sample count, or the hit queue of q[0] slots --
     # one wave a pixel, beside the scene's records (a stored normal that is not unit: STRICT has no split kernel, the refill kernel runs)
@@ -143,12 +116,12 @@ def test_table_frame_changes_no_bit(flux, oracle_mod, demo2, switches, case, q):
         assert plan["kernel"] == flux._lib.PLAN_REFILL
     else:
         assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == 1 and plan["block"] == 64
-        queue = plan["lds"] - _scene_lds(flux, sd)
+        queue = plan["lds"] - sc.scene_lds(flux, sd)
         if q is not None:
             # the planner grants q[0] slots or as many as fit (one wave a pixel: 6 of the CU's granules of 1280 B, less the scene and
             # the 96 B of the block's partial sums; an even count), and a queue of fewer than 64 + q[1] is no hit queue: the ray queue
             # runs.  The box scene's eighteen records leave 80 slots: (86, 22) gives it the ray queue, (66, 1) the hit queue.
-            slots = min(q[0], (6 * 1280 - _scene_lds(flux, sd) - 96) // SLOT & ~1)
+            slots = min(q[0], (6 * 1280 - sc.scene_lds(flux, sd) - 96) // SLOT & ~1)
             assert queue == (slots * SLOT if slots >= 64 + q[1] else RAY_QUEUE)
             assert queue == q[0] * SLOT or (case, q) == ("box_top_and_front_face", (86, 22))
             assert queue == 66 * SLOT or q != (66, 1)
@@ -163,11 +136,11 @@ def test_table_frame_changes_no_bit(flux, oracle_mod, demo2, switches, case, q):
     assert np.array_equal(got, general)
     assert gs == cs == es, (gs, cs, es)
     assert gs == rs == ss, (gs, rs, ss)
-    assert err_refill <= 1e-12
-    assert err_static <= 1e-12
+    assert err_refill <= TOL_ORDER
+    assert err_static <= TOL_ORDER
     if want is not None:
         assert {k: gs[k] for k in o_stats} == o_stats
-        assert err_oracle < 1e-4
+        assert err_oracle < TOL_ORACLE
 
 
 def test_the_cases_are_what_they_claim(flux, oracle_mod, demo2, switches):
@@ -175,7 +148,7 @@ def test_the_cases_are_what_they_claim(flux, oracle_mod, demo2, switches):
     none at all, the box case sees both faces (more Matte bounces than misses past its edge would leave: some primaries hit the front
     face, whose bounces leave towards -z), and a depth limit of 1 ends every path that would bounce."""
     switches()
-    st = {c: _references(flux, oracle_mod, demo2, c)[5][1] for c in CASES}
+    st = {c: _case(flux, oracle_mod, demo2, c)[5].stats for c in CASES}
     for c in ("floor_under_the_environment", "demo2", "plane_with_an_oblique_unit_normal", "ceiling_seen_from_below", "floor_as_a_disk",
               "box_top_and_front_face", "matte_plane_before_a_coincident_glossy_one", "depth_limit_2"):
         assert st[c]["matte_bounces"] > 0, c
@@ -186,9 +159,9 @@ def test_the_cases_are_what_they_claim(flux, oracle_mod, demo2, switches):
     assert st["depth_limit_1"]["segments"] == st["depth_limit_1"]["samples"] and st["depth_limit_1"]["depth_exhausted"] > 0
     # both faces of the box: its primaries' hits are all Matte, and a frame of the top face alone (the same slab, its front face
     # pushed out of view) has a different count
-    sd, depth = _references(flux, oracle_mod, demo2, "box_top_and_front_face")[:2]
+    sd, depth = _case(flux, oracle_mod, demo2, "box_top_and_front_face")[:2]
     top_only = copy.deepcopy(sd)
     box = next(s for s in top_only.shapes if isinstance(s, flux.BoxData))
     box.corner0 = (box.corner0[0], box.corner0[1], -1e3)
-    other = _render(flux, top_only, depth, flux.KERNEL_STATIC)[1]
+    other = sc.render(flux, top_only, N, depth, SEED, flux.KERNEL_STATIC).stats
     assert other["matte_bounces"] != st["box_top_and_front_face"]["matte_bounces"]

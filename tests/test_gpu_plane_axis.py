@@ -17,35 +17,17 @@ import copy
 import numpy as np
 import pytest
 
+import split_checks as sc
 from conftest import small_scene
+from split_checks import TOL_ORACLE
 from switches import switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 N, DEPTH, SEED = 128, 5, 4
-TURNS = {  # name -> where (x, y, z) goes; each takes the floor's normal (0, 1, 0) to the axis in the name
-    "floor_normal_plus_y": lambda v: (v[0], v[1], v[2]),
-    "floor_normal_minus_y": lambda v: (-v[0], -v[1], v[2]),
-    "floor_normal_plus_x": lambda v: (v[1], -v[0], v[2]),
-    "floor_normal_minus_x": lambda v: (-v[1], v[0], v[2]),
-    "floor_normal_plus_z": lambda v: (v[0], -v[2], v[1]),
-    "floor_normal_minus_z": lambda v: (v[0], v[2], -v[1]),
-}
-CASES = list(TURNS) + ["tilted_floor", "floor_then_tilted_wall", "tilted_wall_then_floor"]
+TURNED = {"floor_normal_" + name: turn for name, turn in sc.TURNS.items()}
+CASES = list(TURNED) + ["tilted_floor", "floor_then_tilted_wall", "tilted_wall_then_floor"]
 KERNELS = {"hit_queue": {}, "ray_queue": {"FLUX_SPLIT_HITQ_CAP": "0"}, "general_phase_a": {"FLUX_SPLIT_UNIFORM_A": "0"}}
-
-
-def _turned(flux, sd, turn):
-    sd = copy.deepcopy(sd)
-    for s in sd.shapes:
-        if isinstance(s, flux.SphereData):
-            s.center = turn(s.center)
-        else:
-            assert isinstance(s, flux.PlaneData)
-            s.point, s.normal = turn(s.point), turn(s.normal)
-    cs = sd.camera_settings
-    cs.eye, cs.look_at, cs.up = turn(cs.eye), turn(cs.look_at), turn(cs.up)
-    return sd
 
 
 def _cases(flux, demo2):
@@ -59,7 +41,7 @@ def _cases(flux, demo2):
         sd.shapes = copy.deepcopy(shapes)
         return sd
 
-    cases = {name: _turned(flux, base, turn) for name, turn in TURNS.items()}
+    cases = {name: sc.turned(flux, base, turn) for name, turn in TURNED.items()}
     for name, axis in (("plus_y", (0.0, 1.0, 0.0)), ("minus_y", (0.0, -1.0, 0.0)), ("plus_x", (1.0, 0.0, 0.0)), ("minus_x", (-1.0, 0.0, 0.0)),
                        ("plus_z", (0.0, 0.0, 1.0)), ("minus_z", (0.0, 0.0, -1.0))):
         plane = next(s for s in cases["floor_normal_" + name].shapes if isinstance(s, flux.PlaneData))
@@ -73,42 +55,21 @@ def _cases(flux, demo2):
     return cases
 
 
-_oracle = {}
-
-
-def _oracle_frame(flux, oracle_mod, sd, case):
-    """The oracle's frame and statistics of a case: computed once, read by every kernel."""
-    if case not in _oracle:
-        o = oracle_mod.Oracle(sd, flux.JobConfiguration(N, DEPTH, 50), seed=SEED)
-        o.stats(reset=True)
-        want = o.render_frame(threads=8)
-        want.setflags(write=False)
-        _oracle[case] = (want, o.stats())
-    return _oracle[case]
-
-
-def _render(flux, sd):
-    """The frame of the instantiation without statistics (the benchmark's), then frame and statistics of the one that counts."""
-    with flux.Renderer(sd, flux.JobConfiguration(N, DEPTH, 50), seed=SEED) as r:
-        r.set_kernel(flux.KERNEL_SPLIT)
-        plain = r.render_frame()
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return plain, img, r.stats(), r.launch_plan()
+_oracle = {}   # the oracle's frame and statistics of a case: read by every kernel
 
 
 @pytest.mark.parametrize("kernel", list(KERNELS))
 @pytest.mark.parametrize("case", CASES)
 def test_reduced_plane_test_changes_no_bit(flux, oracle_mod, demo2, switches, case, kernel):
     sd = _cases(flux, demo2)[case]
-    want, o_stats = _oracle_frame(flux, oracle_mod, sd, case)
+    want, o_stats = sc.references(_oracle, case, flux, oracle_mod, sd, N, DEPTH, SEED, kernels=())
     switches(**KERNELS[kernel])
-    plain, got, gs, plan = _render(flux, sd)
+    # (plain: the frame of the instantiation without statistics, the benchmark's, before the one that counts)
+    got, gs, plan, _, plain = sc.render(flux, sd, N, DEPTH, SEED, flux.KERNEL_SPLIT, plain=True)
     switches(FLUX_PLANE_AXIS="0", **KERNELS[kernel])
-    plain_general, general, es, plan_general = _render(flux, sd)
+    general, es, plan_general, _, plain_general = sc.render(flux, sd, N, DEPTH, SEED, flux.KERNEL_SPLIT, plain=True)
     switches(FLUX_SPLIT_HITQ_CAP="0")
-    ray_queue_lds = _render(flux, sd)[3]["lds"]
+    ray_queue_lds = sc.render(flux, sd, N, DEPTH, SEED, flux.KERNEL_SPLIT, plain=True).plan["lds"]
     switches()
     # which kernel ran: the split kernel, four waves a pixel; with the hit queue unless the case takes it away (the ray queue's 64
     # entries a wave are the smaller allocation)
@@ -122,4 +83,4 @@ def test_reduced_plane_test_changes_no_bit(flux, oracle_mod, demo2, switches, ca
     assert np.array_equal(plain, plain_general)
     assert gs == es, (gs, es)
     assert {k: gs[k] for k in o_stats} == o_stats
-    assert err < 1e-4
+    assert err < TOL_ORACLE

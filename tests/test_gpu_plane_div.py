@@ -24,20 +24,14 @@ import copy
 import numpy as np
 import pytest
 
+import split_checks as sc
 from conftest import small_scene
+from split_checks import TURNS
 from switches import switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 4
-TURNS = {  # name -> where (x, y, z) goes; each takes the floor's normal (0, 1, 0) to the axis in the name
-    "plus_y": lambda v: (v[0], v[1], v[2]),
-    "minus_y": lambda v: (-v[0], -v[1], v[2]),
-    "plus_x": lambda v: (v[1], -v[0], v[2]),
-    "minus_x": lambda v: (-v[1], v[0], v[2]),
-    "plus_z": lambda v: (v[0], -v[2], v[1]),
-    "minus_z": lambda v: (v[0], v[2], -v[1]),
-}
 JOBS = ((16, 5), (16, 1), (23, 5), (23, 1))  # (sample root, depth limit)
 KERNELS = [dict(FLUX_SPLIT_DEPTH_CUT=cut, **queue) for queue in ({}, {"FLUX_SPLIT_HITQ_CAP": "0"}) for cut in ("0", "1")]
 
@@ -112,19 +106,6 @@ def test_unscaled_division_and_votes_on_the_device(flux):
         assert np.all(np.abs(form[small]) < SMALL)
 
 
-def _turned(flux, sd, turn):
-    sd = copy.deepcopy(sd)
-    for s in sd.shapes:
-        if isinstance(s, flux.SphereData):
-            s.center = turn(s.center)
-        else:
-            assert isinstance(s, flux.PlaneData)
-            s.point, s.normal = turn(s.point), turn(s.normal)
-    cs = sd.camera_settings
-    cs.eye, cs.look_at, cs.up = turn(cs.eye), turn(cs.look_at), turn(cs.up)
-    return sd
-
-
 def _grazing(flux, base):
     """demo2 seen from a hair above the floor, looking along it."""
     sd = copy.deepcopy(base)
@@ -138,38 +119,17 @@ def _grazing(flux, base):
     return sd
 
 
-_oracle = {}
-
-
-def _oracle_frame(flux, oracle_mod, sd, key, root, depth):
-    """The oracle's frame and statistics of a case: computed once, read under every switch."""
-    if key not in _oracle:
-        o = oracle_mod.Oracle(sd, flux.JobConfiguration(root, depth, 50), seed=SEED)
-        o.stats(reset=True)
-        want = o.render_frame(threads=8)
-        want.setflags(write=False)
-        _oracle[key] = (want, o.stats())
-    return _oracle[key]
-
-
-def _render(flux, sd, root, depth):
-    """The frame of the instantiation without statistics (the benchmark's), then frame and statistics of the one that counts."""
-    with flux.Renderer(sd, flux.JobConfiguration(root, depth, 50), seed=SEED) as r:
-        r.set_kernel(flux.KERNEL_SPLIT)
-        plain = r.render_frame()
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return plain, img, r.stats(), r.launch_plan()
+_oracle = {}   # the oracle's frame and statistics of a case: read under every switch
 
 
 def _check(flux, oracle_mod, switches, sd, key, root, depth):
-    want, o_stats = _oracle_frame(flux, oracle_mod, sd, key, root, depth)
+    want, o_stats = sc.references(_oracle, key, flux, oracle_mod, sd, root, depth, SEED, kernels=())
     for env in KERNELS:
+        # (plain: the frame of the instantiation without statistics, the benchmark's, before the one that counts)
         switches(**env)
-        plain, got, gs, plan = _render(flux, sd, root, depth)
+        got, gs, plan, _, plain = sc.render(flux, sd, root, depth, SEED, flux.KERNEL_SPLIT, plain=True)
         switches(FLUX_PLANE_AXIS="0", **env)
-        plain_general, general, es, plan_general = _render(flux, sd, root, depth)
+        general, es, plan_general, _, plain_general = sc.render(flux, sd, root, depth, SEED, flux.KERNEL_SPLIT, plain=True)
         switches()
         assert plan == plan_general and plan["kernel"] == flux._lib.PLAN_SPLIT
         err = float(np.abs(got - want).max())
@@ -186,7 +146,7 @@ def _check(flux, oracle_mod, switches, sd, key, root, depth):
 @pytest.mark.parametrize("turn", list(TURNS))
 def test_frames_equal_the_general_form(flux, oracle_mod, demo2, switches, turn, job):
     root, depth = job
-    sd = _turned(flux, small_scene(demo2, 8, 6), TURNS[turn])
+    sd = sc.turned(flux, small_scene(demo2, 8, 6), TURNS[turn])
     plane = next(s for s in sd.shapes if isinstance(s, flux.PlaneData))
     assert sorted(abs(c) for c in plane.normal) == [0.0, 0.0, 1.0]
     _check(flux, oracle_mod, switches, sd, (turn, root, depth), root, depth)

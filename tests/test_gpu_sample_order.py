@@ -23,12 +23,13 @@ import numpy as np
 import pytest
 
 import sample_order_ref as ref
+import split_checks as sc
 import split_sweep as sw
+from split_checks import TOL_ORACLE, TOL_ORDER
 from switches import switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-TOL_ORACLE, TOL_ORDER = 1e-4, 1e-12
 JOBS = sw.JOBS + ((16, 5), (17, 5))
 SCENE_NAMES = ("floor", "glossy_no_floor", "no_environment")
 FRAMES = {"floor": (5, 3), "glossy_no_floor": (4, 3), "no_environment": (7, 3)}
@@ -54,44 +55,7 @@ def _scene(name):
     return sd, int(rng.integers(1, 1 << 30))
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle(name, root, depth):
-    import flux_amd as flux
-    from oracle import oracle
-    sd, seed = _scene(name)
-    o = oracle.Oracle(sd, flux.JobConfiguration(root, depth, 50), seed=seed)
-    o.stats(reset=True)
-    frame = o.render_frame(threads=8)
-    stats = o.stats()
-    o.close()
-    frame.setflags(write=False)
-    return frame, stats
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def _distance(a, b):
-    fa, fb = np.isfinite(a), np.isfinite(b)
-    assert np.array_equal(fa, fb), "finiteness patterns differ"
-    return float(np.abs(a[fa] - b[fa]).max()) if fa.any() else 0.0
-
-
-def _with_stats(flux, r, variant):
-    r.set_kernel(variant)
-    r.enable_stats(True)
-    r.stats(reset=True)
-    img = r.render_frame()
-    return img, r.stats()
-
-
-def _split(flux, r):
-    r.set_kernel(flux.KERNEL_SPLIT)
-    r.enable_stats(False)
-    plain = r.render_frame()
-    img, st = _with_stats(flux, r, flux.KERNEL_SPLIT)
-    return plain, img, st, r.launch_plan(flags=True)
+_oracle = {}   # the oracle's frame and statistics per scene and job
 
 
 # ---- (a) the table: before any render in this file ---------------------------------------------------------------------------------
@@ -136,22 +100,22 @@ def test_jobs_run_one_two_and_four_waves_a_pixel(flux, switches):
 
 @pytest.mark.parametrize("job", JOBS, ids=lambda j: f"root{j[0]}-depth{j[1]}")
 @pytest.mark.parametrize("name", SCENE_NAMES)
-def test_sorted_order_renders_the_same_samples(flux, switches, name, job):
+def test_sorted_order_renders_the_same_samples(flux, oracle_mod, switches, name, job):
     root, depth = job
     sd, seed = _scene(name)
     cfg = flux.JobConfiguration(root, depth, 50)
-    want, ost = _oracle(name, root, depth)
+    want, ost = sc.references(_oracle, (name, root, depth), flux, oracle_mod, sd, root, depth, seed, kernels=())
     for mode in MODES:
         tag = f"{name} root {root} depth {depth} {mode}"
         switches(**mode)
         try:
             with flux.Renderer(sd, cfg, seed=seed) as r:
-                static, ss = _with_stats(flux, r, flux.KERNEL_STATIC)
-                refill, rs = _with_stats(flux, r, flux.KERNEL_REFILL)
-                plain, got, gs, plan = _split(flux, r)
+                static, ss = sc.with_stats(flux, r, flux.KERNEL_STATIC)
+                refill, rs = sc.with_stats(flux, r, flux.KERNEL_REFILL)
+                plain, got, gs, plan = sc.split_run(flux, r)
             switches(FLUX_SAMPLE_ORDER="0", **mode)
             with flux.Renderer(sd, cfg, seed=seed) as r:
-                plain0, got0, gs0, plan0 = _split(flux, r)
+                plain0, got0, gs0, plan0 = sc.split_run(flux, r)
         finally:
             switches()
         assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == sw.waves_per_pixel(root), (tag, plan)
@@ -160,16 +124,16 @@ def test_sorted_order_renders_the_same_samples(flux, switches, name, job):
         if "FLUX_SPLIT_HITQ_CAP" in mode:
             assert not hitq, tag
         assert bool(plan["flags"] & flux._lib.PLAN_FLAG_UNIFORM_A) == ("FLUX_SPLIT_UNIFORM_A" not in mode), tag
-        err = dict(oracle=_distance(got, want), index_order=_distance(got, got0), static=_distance(got, static), refill=_distance(got, refill))
+        err = dict(oracle=sc.distance(got, want), index_order=sc.distance(got, got0), static=sc.distance(got, static), refill=sc.distance(got, refill))
         print(f"{tag}: hit queue {hitq}  " + "  ".join(f"|sorted - {k}| {v:.3e}" for k, v in err.items()) + f"  segments {gs['segments']}")
         differing = {k: (gs[k], gs0[k], ss[k], rs[k], ost[k]) for k in ost if not gs[k] == gs0[k] == ss[k] == rs[k] == ost[k]}
         assert len(ost) == 8 and not differing, f"{tag}: statistics (sorted, index order, static, refill, oracle) {differing}"
         assert gs == gs0 == ss == rs, (tag, gs, gs0, ss, rs)
         assert err["oracle"] < TOL_ORACLE, tag
         assert err["index_order"] <= TOL_ORDER and err["static"] <= TOL_ORDER and err["refill"] <= TOL_ORDER, tag
-        assert _distance(got0, want) < TOL_ORACLE, tag
-        assert _same_bits(plain, got), f"{tag}: the instantiation without statistics renders other bits"
-        assert _same_bits(plain0, got0), f"{tag}: (index order) the instantiation without statistics renders other bits"
+        assert sc.distance(got0, want) < TOL_ORACLE, tag
+        assert sc.same_bits(plain, got), f"{tag}: the instantiation without statistics renders other bits"
+        assert sc.same_bits(plain0, got0), f"{tag}: (index order) the instantiation without statistics renders other bits"
 
 
 @pytest.mark.parametrize("name", SCENE_NAMES)
@@ -182,4 +146,4 @@ def test_three_loopback_ranks_render_the_same_bits(flux, switches, name):
     for mode in (flux._lib.SHARD_SETS, flux._lib.SHARD_ROWS):
         with flux.MultiRenderer(sd, cfg, seed=seed, devices=[0] * 3, shard=mode | flux._lib.SHARD_LOOPBACK) as m:
             frame = m.render_frame()
-        assert _same_bits(np.ascontiguousarray(frame), want), f"{name}: three ranks, shard mode {mode}"
+        assert sc.same_bits(np.ascontiguousarray(frame), want), f"{name}: three ranks, shard mode {mode}"

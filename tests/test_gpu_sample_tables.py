@@ -11,14 +11,16 @@ import numpy as np
 import pytest
 
 import selftest
+import split_checks as sc
 from conftest import max_abs_diff, small_scene
+from split_checks import REC, SLOT, SPH, TOL_ORACLE
 from switches import queue, switches  # noqa: F401 (the fixture)
 from test_sample_table_slots import build_selftest
 
 pytestmark = pytest.mark.gpu
 
-TOL_IMAGE = 1e-4   # tests/test_gpu_parity.py
 TOL_TIGHT = 1e-9
+DEPTH, SEED = 5, 3
 
 # demo2's three exponents; one; five distinct ones (kGlossExpSlots = 4); exponent 0 beside another
 # "plane": the floor glossy too, with an exponent of its own -- a record past the spheres (scan order) whose slot is not the first
@@ -49,14 +51,6 @@ def _scene(flux, demo2, name, lens):
     return sd
 
 
-def _render(flux, sd, root, seed=3):
-    with flux.Renderer(sd, flux.JobConfiguration(root, 5, 50), seed=seed) as r:
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan(), r.device_bytes()
-
-
 @pytest.mark.parametrize("lens", [0.0, 0.3])
 @pytest.mark.parametrize("root", [16, 8, 4])
 @pytest.mark.parametrize("name", ["one", "three", "five", "zero", "plane"])
@@ -64,15 +58,15 @@ def test_frames_do_not_depend_on_the_table(flux, demo2, switches, name, root, le
     sd = _scene(flux, demo2, name, lens)
     q = queue((80, 16) if root == 16 else None)  # a one-wave block's LDS holds 88 slots for this scene: the plan takes the hit queue from H = 24 down
     switches(**q)
-    got, gs, gplan, gbytes = _render(flux, sd, root)
+    got, gs, gplan, gbytes = sc.render(flux, sd, root, DEPTH, SEED)[:4]
     switches(FLUX_SAMPLE_TABLES=0, **q)
-    want, ws, wplan, wbytes = _render(flux, sd, root)
+    want, ws, wplan, wbytes = sc.render(flux, sd, root, DEPTH, SEED)[:4]
     switches(**q)
     assert gplan["kernel"] == wplan["kernel"] == getattr(flux._lib, KERNEL_OF_ROOT[root])
     if root == 16:
         # the hit queue (68 B a slot), both times -- not the ray queue (5120 B a wave)
-        queues = gplan["lds"] - (len(sd.shapes) * 96 + sum(isinstance(s, flux.SphereData) for s in sd.shapes) * 32)
-        assert gplan["lds"] == wplan["lds"] and gplan["waves_per_pixel"] == 1 and queues == 80 * 68
+        queues = gplan["lds"] - (len(sd.shapes) * REC + sum(isinstance(s, flux.SphereData) for s in sd.shapes) * SPH)
+        assert gplan["lds"] == wplan["lds"] and gplan["waves_per_pixel"] == 1 and queues == 80 * SLOT
     assert gs["glossy_bounces"] > 0 and gs == ws
     assert np.array_equal(got, want)
     # the context reports the table by the memory it holds: one entry of 16 B per held sample and exponent, or nothing
@@ -85,49 +79,39 @@ def test_frames_do_not_depend_on_the_table(flux, demo2, switches, name, root, le
 def test_headline_plan_reads_the_table(flux, demo2, switches):
     """16384 spp, the plan's own hit queue (four waves a pixel, 110 slots of 68 B a wave for demo2's records), demo2 itself."""
     sd = small_scene(demo2, 8, 6)
-    got, gs, gplan, gbytes = _render(flux, sd, 128)
+    got, gs, gplan, gbytes = sc.render(flux, sd, 128, DEPTH, SEED)[:4]
     switches(FLUX_SAMPLE_TABLES=0)
-    want, ws, wplan, wbytes = _render(flux, sd, 128)
+    want, ws, wplan, wbytes = sc.render(flux, sd, 128, DEPTH, SEED)[:4]
     assert gplan["kernel"] == wplan["kernel"] == flux._lib.PLAN_SPLIT and gplan["waves_per_pixel"] == 4
     n_sph = sum(isinstance(s, flux.SphereData) for s in sd.shapes)
-    assert gplan["lds"] == wplan["lds"] == 110 * 68 * 4 + len(sd.shapes) * 96 + n_sph * 32
+    assert gplan["lds"] == wplan["lds"] == 110 * SLOT * 4 + len(sd.shapes) * REC + n_sph * SPH
     assert gs["glossy_bounces"] > 0 and gs == ws
     assert np.array_equal(got, want)
     assert gbytes - wbytes == 8 * 16384 * 48 + (len(sd.shapes) + 1) * 4
 
 
-@pytest.fixture(scope="module")
-def oracle_frames(flux, oracle_mod, demo2):
-    out = {}
-
-    def get(root, name="three"):
-        if (root, name) not in out:
-            sd = _scene(flux, demo2, name, 0.3)
-            o = oracle_mod.Oracle(sd, flux.JobConfiguration(root, 5, 50), seed=3)
-            o.stats(reset=True)
-            out[(root, name)] = (o.render_frame(threads=8), o.stats())
-            o.close()
-        return out[(root, name)]
-    return get
+_oracle = {}   # the oracle's frame and statistics per sample root and scene
 
 
 @pytest.mark.parametrize("root", [16, 8, 4])
-def test_against_the_oracle(flux, demo2, oracle_frames, switches, root):
+def test_against_the_oracle(flux, oracle_mod, demo2, switches, root):
+    sd = _scene(flux, demo2, "three", 0.3)
+    want, ost = sc.references(_oracle, (root, "three"), flux, oracle_mod, sd, root, DEPTH, SEED, kernels=())
     switches(**queue((80, 16) if root == 16 else None))  # the hit queue, as above
-    want, ost = oracle_frames(root)
-    got, gs, plan, _ = _render(flux, _scene(flux, demo2, "three", 0.3), root)
+    got, gs, plan = sc.render(flux, sd, root, DEPTH, SEED)[:3]
     assert plan["kernel"] == getattr(flux._lib, KERNEL_OF_ROOT[root])
     assert {k: gs[k] for k in ost} == ost
-    assert max_abs_diff(got, want) < TOL_IMAGE
+    assert max_abs_diff(got, want) < TOL_ORACLE
     assert np.percentile(np.abs(got - want), 99.9) < TOL_TIGHT
 
 
-def test_glossy_plane_against_the_oracle(flux, demo2, oracle_frames, switches):
+def test_glossy_plane_against_the_oracle(flux, oracle_mod, demo2, switches):
     """The glossy floor: most primary hits read the table through a record behind the spheres'."""
-    want, ost = oracle_frames(8, "plane")
-    got, gs, plan, _ = _render(flux, _scene(flux, demo2, "plane", 0.3), 8)
+    sd = _scene(flux, demo2, "plane", 0.3)
+    want, ost = sc.references(_oracle, (8, "plane"), flux, oracle_mod, sd, 8, DEPTH, SEED, kernels=())
+    got, gs = sc.render(flux, sd, 8, DEPTH, SEED)[:2]
     assert {k: gs[k] for k in ost} == ost
-    assert max_abs_diff(got, want) < TOL_IMAGE
+    assert max_abs_diff(got, want) < TOL_ORACLE
     assert np.percentile(np.abs(got - want), 99.9) < TOL_TIGHT
 
 

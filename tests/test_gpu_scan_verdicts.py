@@ -10,15 +10,17 @@ import copy
 import numpy as np
 import pytest
 
+import split_checks as sc
 import switches
 from switches import switches as env_switches  # noqa: F401 (the fixture)
 from conftest import small_scene
+from split_checks import Q_LARGEST, Q_SMALLEST, REC, SLOT, SPH, TOL_ORACLE, TOL_ORDER
 from test_gpu_parity import _env_cases
 
 pytestmark = pytest.mark.gpu
 
-SLOT, REC, SPH = 68, 96, 32   # bytes per hit-queue slot, DevHitRec, DevScanSphere
-QUEUES = [(86, 22), (66, 1), None]
+QUEUES = [Q_LARGEST, Q_SMALLEST, None]
+DEPTH = 5
 ENV_CASES = ["convex_first", "inverted_first", "nested_environments", "camera_outside_environment", "inside_convex_matte",
              "inside_convex_glossy", "inside_convex_reflective", "beyond_the_magnitude_guard", "plane_tangent_to_the_environment",
              "sphere_across_the_environment", "spheres_touching_the_environment"]
@@ -77,31 +79,13 @@ def _oracle_scene(flux, sd):
     return s
 
 
-def _render(flux, sd, n, kernel, seed):
-    with flux.Renderer(sd, flux.JobConfiguration(n, 5, 50), seed=seed) as r:
-        r.set_kernel(kernel)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan()
-
-
 _refs = {}
 
 
-def _references(flux, oracle_mod, demo2, case):
-    """The oracle's, the refill kernel's and the static kernel's frame and statistics of a case: computed once, read by every queue."""
-    if case not in _refs:
-        sd = (_own_cases(flux, demo2) if case in OWN_CASES else _env_cases(flux, demo2))[case]
-        o = oracle_mod.Oracle(_oracle_scene(flux, sd), flux.JobConfiguration(16, 5, 50), seed=4)
-        o.stats(reset=True)
-        want = o.render_frame(threads=8)
-        refill = _render(flux, sd, 16, flux.KERNEL_REFILL, 4)
-        static = _render(flux, sd, 16, flux.KERNEL_STATIC, 4)
-        for a in (want, refill[0], static[0]):
-            a.setflags(write=False)
-        _refs[case] = (sd, want, o.stats(), refill, static)
-    return _refs[case]
+def _case(flux, oracle_mod, demo2, case):
+    """scene, and the oracle's, the refill kernel's and the static kernel's frame and statistics: read by every queue"""
+    sd = (_own_cases(flux, demo2) if case in OWN_CASES else _env_cases(flux, demo2))[case]
+    return (sd,) + sc.references(_refs, case, flux, oracle_mod, sd, 16, DEPTH, 4, oracle_sd=_oracle_scene(flux, sd))
 
 
 @pytest.fixture
@@ -112,24 +96,24 @@ def queue(env_switches):
 @pytest.mark.parametrize("q", QUEUES)
 @pytest.mark.parametrize("case", OWN_CASES + ENV_CASES)
 def test_split_kernel_keeps_every_decision(flux, oracle_mod, demo2, queue, case, q):
-    sd, want, o_stats, (refill, rs, _), (static, ss, _) = _references(flux, oracle_mod, demo2, case)
+    sd, want, o_stats, (refill, rs, *_), (static, ss, *_) = _case(flux, oracle_mod, demo2, case)
     queue(q)
-    got, gs, plan = _render(flux, sd, 16, flux.KERNEL_SPLIT, 4)
+    got, gs, plan = sc.render(flux, sd, 16, DEPTH, 4, flux.KERNEL_SPLIT)[:3]
     queue(None)
     assert plan["kernel"] == flux._lib.PLAN_SPLIT
     if q is not None and case in OWN_CASES:  # the hit queue really ran: its LDS, not the ray queue's
         n_sph = sum(isinstance(s, flux.SphereData) for s in sd.shapes)
         assert plan["lds"] == q[0] * SLOT * plan["waves_per_pixel"] + len(sd.shapes) * REC + n_sph * SPH
     assert {k: gs[k] for k in o_stats} == o_stats
-    assert np.abs(got - want).max() < 1e-4
+    assert np.abs(got - want).max() < TOL_ORACLE
     assert gs == rs == ss, (gs, rs, ss)
-    assert np.abs(got - refill).max() <= 1e-12
-    assert np.abs(got - static).max() <= 1e-12
+    assert np.abs(got - refill).max() <= TOL_ORDER
+    assert np.abs(got - static).max() <= TOL_ORDER
 
 
-def test_back_faces_are_black(flux, oracle_mod, demo2):
+def test_back_faces_are_black(flux, oracle_mod, demo2, env_switches):
     """The case does what its name says, by the oracle's own frame: paths end on the emitter, and from inside it gives no light."""
-    _, inside, st, _, _ = _references(flux, oracle_mod, demo2, "camera_inside_convex_emitter")
+    _, inside, st, _, _ = _case(flux, oracle_mod, demo2, "camera_inside_convex_emitter")
     assert st["emissive_hits"] > 0 and float(np.abs(inside).max()) == 0.0
 
 
@@ -137,12 +121,12 @@ def test_back_faces_are_black(flux, oracle_mod, demo2):
 def test_headline_shapes(flux, demo2, n, waves):
     """demo2 at 16384 spp (K = 4, the plan's own 110-slot queue) and at 9216 spp (K = 2), 8 x 6 pixels."""
     sd = small_scene(demo2, 8, 6)
-    got, gs, plan = _render(flux, sd, n, flux.KERNEL_SPLIT, 1)
+    got, gs, plan = sc.render(flux, sd, n, DEPTH, 1, flux.KERNEL_SPLIT)[:3]
     assert plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == waves
     if n == 128:
         assert plan["lds"] == 110 * SLOT * 4 + len(sd.shapes) * REC + 12 * SPH
-    refill, rs, _ = _render(flux, sd, n, flux.KERNEL_REFILL, 1)
-    static, ss, _ = _render(flux, sd, n, flux.KERNEL_STATIC, 1)
+    refill, rs = sc.render(flux, sd, n, DEPTH, 1, flux.KERNEL_REFILL)[:2]
+    static, ss = sc.render(flux, sd, n, DEPTH, 1, flux.KERNEL_STATIC)[:2]
     assert gs == rs == ss, (gs, rs, ss)
-    assert np.abs(got - refill).max() <= 1e-12
-    assert np.abs(got - static).max() <= 1e-12
+    assert np.abs(got - refill).max() <= TOL_ORDER
+    assert np.abs(got - static).max() <= TOL_ORDER

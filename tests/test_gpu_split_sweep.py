@@ -37,48 +37,19 @@ mutant at its first -z ray.
 import numpy as np
 import pytest
 
+import split_checks as sc
 import split_sweep as sw
+from split_checks import TOL_ORACLE, TOL_ORDER
 from switches import switches  # noqa: F401 (the fixture)
 from test_gpu_ext_fuzz import check_run
 
 pytestmark = pytest.mark.gpu
 
-TOL_ORACLE, TOL_ORDER = 1e-4, 1e-12
 # switch -> (value, how the frame is held: "order" = within 1e-12 of the static and refill kernels, "cut" = within 1e-12 of the
 # plan's own frame, "bits" = that frame's bits)
 SWITCHES = {"FLUX_SPLIT_HITQ_CAP": ("0", "order"), "FLUX_SPLIT_HITQ_TAKE_AT": ("32", "order"), "FLUX_THROUGHPUT_TABLE": ("0", "bits"),
             "FLUX_SPLIT_DEPTH_CUT": ("0", "cut"), "FLUX_PLANE_AXIS": ("0", "bits"), "FLUX_SPLIT_UNIFORM_A": ("0", "bits"),
             "FLUX_SAMPLE_TABLES": ("0", "bits")}
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def _distance(a, b):
-    """max |a - b| over the pixels finite in both; the finiteness patterns must be equal"""
-    fa, fb = np.isfinite(a), np.isfinite(b)
-    assert np.array_equal(fa, fb), "finiteness patterns differ"
-    return float(np.abs(a[fa] - b[fa]).max()) if fa.any() else 0.0
-
-
-def _split(flux, r):
-    """the split kernel of the context as it stands: frame without statistics, frame with, statistics, plan"""
-    r.set_kernel(flux.KERNEL_SPLIT)
-    r.enable_stats(False)
-    plain = r.render_frame()
-    r.enable_stats(True)
-    r.stats(reset=True)
-    img = r.render_frame()
-    return plain, img, r.stats(), r.launch_plan(flags=True)
-
-
-def _with_stats(flux, r, variant):
-    r.set_kernel(variant)
-    r.enable_stats(True)
-    r.stats(reset=True)
-    img = r.render_frame()
-    return img, r.stats()
 
 
 def _check_plan(flux, plan, sd, root, depth, tag, env=None):
@@ -88,7 +59,7 @@ def _check_plan(flux, plan, sd, root, depth, tag, env=None):
     assert plan["math"] == flux.MATH_FAST and plan["route"] == flux._lib.ROUTE_NONE, (tag, plan)
     assert plan["flags"] == want, f"{tag}: the plan says {sw.describe(flux, plan['flags'])}, expected {sw.describe(flux, want)}"
     cap = sw.plan_hitq(flux, sd, root, depth, env)[0]
-    assert plan["lds"] == (cap * sw.SLOT if cap else 5120) * plan["waves_per_pixel"] + sw.scene_lds(flux, sd), (tag, plan)
+    assert plan["lds"] == (cap * sc.SLOT if cap else sc.RAY_QUEUE) * plan["waves_per_pixel"] + sc.scene_lds(flux, sd), (tag, plan)
 
 
 @pytest.mark.parametrize("index", range(sw.SCENES_PER_CLASS))
@@ -104,23 +75,23 @@ def test_split_kernel_on_a_generated_scene(flux, switches, cls, index):
                 r.set_kernel(flux.KERNEL_STATIC)
                 check_run(flux, r, sw.path_run(cls, index, draw, depth), f"{tag}: static kernel at 64 spp", True, {})
         with flux.Renderer(sd, flux.JobConfiguration(root, depth, 50), seed=seed) as r:
-            static, ss = _with_stats(flux, r, flux.KERNEL_STATIC)
-            refill, rs = _with_stats(flux, r, flux.KERNEL_REFILL)
-            plain, got, gs, plan = _split(flux, r)
+            static, ss = sc.with_stats(flux, r, flux.KERNEL_STATIC)
+            refill, rs = sc.with_stats(flux, r, flux.KERNEL_REFILL)
+            plain, got, gs, plan = sc.split_run(flux, r)
         _check_plan(flux, plan, sd, root, depth, tag)
-        err_static, err_refill = _distance(got, static), _distance(got, refill)
+        err_static, err_refill = sc.distance(got, static), sc.distance(got, refill)
         print(f"{tag}: |split - static| {err_static:.3e}  |split - refill| {err_refill:.3e}  segments {gs['segments']}  "
               f"depth_exhausted {gs['depth_exhausted']}")
         if cls in sw.ORACLE_CLASSES:
             want, ost, _ = sw.oracle_run(cls, index, draw, root, depth)
             differing = {k: (gs[k], ss[k], rs[k], ost[k]) for k in ost if not gs[k] == ss[k] == rs[k] == ost[k]}
             assert not differing, f"{tag}: statistics (split, static, refill, oracle) {differing}"
-            err_oracle = _distance(got, want)
+            err_oracle = sc.distance(got, want)
             print(f"{tag}: |split - oracle| {err_oracle:.3e}")
             assert err_oracle < TOL_ORACLE, tag
         assert gs == ss == rs, (tag, gs, ss, rs)
         assert err_static <= TOL_ORDER and err_refill <= TOL_ORDER, tag
-        assert _same_bits(plain, got), f"{tag}: the instantiation without statistics renders other bits"
+        assert sc.same_bits(plain, got), f"{tag}: the instantiation without statistics renders other bits"
         if (root, depth) == sw.HEADLINE_JOB:
             headline = dict(static=static, refill=refill, got=got, plain=plain, stats=gs)
 
@@ -132,24 +103,24 @@ def test_split_kernel_on_a_generated_scene(flux, switches, cls, index):
             switches(**{name: value})   # before the context: its tables are made at creation
             try:
                 with flux.Renderer(sd, cfg, seed=seed) as r:
-                    plain, img, st, plan = _split(flux, r)
+                    plain, img, st, plan = sc.split_run(flux, r)
             finally:
                 switches()
             _check_plan(flux, plan, sd, root, depth, tag, {name: value})
             assert st == headline["stats"], (tag, st, headline["stats"])
-            assert _same_bits(plain, img), tag
+            assert sc.same_bits(plain, img), tag
             if how == "bits":
-                assert _same_bits(img, headline["got"]) and _same_bits(plain, headline["plain"]), f"{tag}: the switch changes bits"
+                assert sc.same_bits(img, headline["got"]) and sc.same_bits(plain, headline["plain"]), f"{tag}: the switch changes bits"
             elif how == "cut":
-                err = _distance(img, headline["got"])
+                err = sc.distance(img, headline["got"])
                 print(f"{tag}: |uncut - cut| {err:.3e}")
                 assert err <= TOL_ORDER, tag
             else:
-                err = max(_distance(img, headline["static"]), _distance(img, headline["refill"]))
+                err = max(sc.distance(img, headline["static"]), sc.distance(img, headline["refill"]))
                 print(f"{tag}: |split - static or refill| {err:.3e}")
                 assert err <= TOL_ORDER, tag
     if index == 2:
         for mode in (flux._lib.SHARD_SETS, flux._lib.SHARD_ROWS):
             with flux.MultiRenderer(sd, cfg, seed=seed, devices=[0] * 3, shard=mode | flux._lib.SHARD_LOOPBACK) as m:
                 frame = m.render_frame()
-            assert _same_bits(np.ascontiguousarray(frame), headline["plain"]), f"{cls} {index}: three ranks, shard mode {mode}"
+            assert sc.same_bits(np.ascontiguousarray(frame), headline["plain"]), f"{cls} {index}: three ranks, shard mode {mode}"

@@ -18,14 +18,14 @@ import os
 import numpy as np
 import pytest
 
-import switches
+import split_checks as sc
 from switches import switches as env_switches  # noqa: F401 (the fixture)
 from conftest import SCENES, small_scene
+from split_checks import SLOT, TOL_ORDER
 
 pytestmark = pytest.mark.gpu
 
-W, H = 8, 6
-SLOT, REC, SPH = 68, 96, 32   # tests/test_gpu_split_hit_queue.py
+W, H, SEED = 8, 6, 1
 # scene, depth limit -> whether the context holds a table
 CASES = [("demo2", 5, True), ("demo2", 2, True), ("demo2", 3, True), ("records16", 5, True), ("records17", 5, False),
          ("box_room", 5, False), ("box_room", 3, True)]
@@ -51,52 +51,25 @@ def env(env_switches):
     return lambda take_at=None, tables=True: env_switches(FLUX_SPLIT_HITQ_TAKE_AT=take_at, FLUX_THROUGHPUT_TABLE=None if tables else 0)
 
 
-def _render(flux, sd, n, depth, kernel):
-    with flux.Renderer(sd, flux.JobConfiguration(n, depth, 50), seed=1) as r:
-        r.set_kernel(kernel)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan(), r.device_bytes()
-
-
-@pytest.fixture(scope="module")
-def references(flux, oracle_mod, scenes):
-    """Per scene, sample root and depth limit: the static kernel's frame and statistics and the oracle's statistics, made once."""
-    out = {}
-
-    def get(name, n, depth):
-        if (name, n, depth) not in out:
-            assert not any(n in os.environ for n in switches.NAMES)
-            img, st, _, _ = _render(flux, scenes[name], n, depth, flux.KERNEL_STATIC)
-            img.setflags(write=False)
-            ost = None
-            if name not in NOT_IN_THE_ORACLE:
-                o = oracle_mod.Oracle(scenes[name], flux.JobConfiguration(n, depth, 50), seed=1)
-                o.stats(reset=True)
-                o.render_frame(threads=8)
-                ost = o.stats()
-                o.close()
-            out[(name, n, depth)] = (img, st, ost)
-        return out[(name, n, depth)]
-    return get
+_refs = {}   # per scene, sample root and depth limit: the oracle's statistics and the static kernel's run
 
 
 @pytest.mark.parametrize("take_at", [None, 32])
 @pytest.mark.parametrize("n", sorted(ROOTS))
 @pytest.mark.parametrize("name,depth,has_table", CASES)
-def test_split_with_and_without_the_table(flux, scenes, references, env, name, depth, has_table, n, take_at):
+def test_split_with_and_without_the_table(flux, oracle_mod, scenes, env, name, depth, has_table, n, take_at):
     sd = scenes[name]
-    want, ws, ost = references(name, n, depth)
+    _, ost, (want, ws, *_) = sc.references(_refs, (name, n, depth), flux, oracle_mod, sd, n, depth, SEED, kernels=("STATIC",),
+                                           oracle_sd=None if name in NOT_IN_THE_ORACLE else sc.SAME)
     env(take_at, tables=True)
-    got, gs, plan, bytes_on = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    got, gs, plan, bytes_on = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:4]
     env(take_at, tables=False)
-    loop, ls, plan_off, bytes_off = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    loop, ls, plan_off, bytes_off = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:4]
     env()
     # the hit queue (C slots of 68 B a wave beside the scene's records), and the same plan with and without the table
     assert plan == plan_off and plan["kernel"] == flux._lib.PLAN_SPLIT and plan["waves_per_pixel"] == ROOTS[n]
     records = sum(6 if isinstance(s, flux.BoxData) else 1 for s in sd.shapes)  # a box: one record per face
-    queues = (plan["lds"] - records * REC - sum(isinstance(s, flux.SphereData) for s in sd.shapes) * SPH) // plan["waves_per_pixel"]
+    queues = (plan["lds"] - sc.scene_lds(flux, sd)) // plan["waves_per_pixel"]
     assert queues % SLOT == 0 and queues >= (64 + (take_at or 32)) * SLOT
     bits = (records - 1).bit_length()
     assert bits == (5 if name in ("records17", "box_room") else 4)
@@ -107,12 +80,12 @@ def test_split_with_and_without_the_table(flux, scenes, references, env, name, d
     if ost is not None:
         assert {k: ws[k] for k in ost} == ost and {k: gs[k] for k in ost} == ost
     assert gs["matte_bounces"] > 0
-    assert np.abs(got - want).max() <= 1e-12
+    assert np.abs(got - want).max() <= TOL_ORDER
 
 
 def test_every_record_is_in_some_list(flux, scenes):
     """records16 uses every value a 4-bit list entry can take: each of its three added spheres is hit, and bounced off, in the
     frame (their Matte bounces are the ones demo2 does not have)."""
-    a = _render(flux, scenes["demo2"], 128, 5, flux.KERNEL_SPLIT)[1]
-    b = _render(flux, scenes["records16"], 128, 5, flux.KERNEL_SPLIT)[1]
+    a = sc.render(flux, scenes["demo2"], 128, 5, SEED, flux.KERNEL_SPLIT).stats
+    b = sc.render(flux, scenes["records16"], 128, 5, SEED, flux.KERNEL_SPLIT).stats
     assert b["matte_bounces"] > a["matte_bounces"]

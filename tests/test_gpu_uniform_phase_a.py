@@ -15,12 +15,14 @@ import copy
 import numpy as np
 import pytest
 
+import split_checks as sc
 from conftest import small_scene
+from split_checks import QUEUES, TOL_ORACLE, TOL_ORDER
 from switches import queue, switches as env_switches  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-QUEUES = [None, (86, 22), (66, 1)]
+SEED = 4
 CASES = ["floor_under_the_environment", "demo2", "close_to_a_glossy_sphere", "close_to_a_reflective_sphere", "close_to_a_matte_sphere",
          "emissive_plane_lit_side", "emissive_plane_from_behind", "floor_as_a_disk", "floor_as_a_box", "floor_with_a_long_normal",
          "coincident_planes", "plane_coincident_with_a_disk", "outside_the_environment_looking_away", "partial_last_pass",
@@ -83,31 +85,14 @@ def _cases(flux, demo2):
     return cases
 
 
-def _render(flux, sd, n, depth, kernel, seed=4):
-    with flux.Renderer(sd, flux.JobConfiguration(n, depth, 50), seed=seed) as r:
-        r.set_kernel(kernel)
-        r.enable_stats(True)
-        r.stats(reset=True)
-        img = r.render_frame()
-        return img, r.stats(), r.launch_plan()
-
-
 _refs = {}
 
 
-def _references(flux, oracle_mod, demo2, case):
-    """The oracle's, the refill kernel's and the static kernel's frame and statistics of a case: computed once, read by every queue."""
-    if case not in _refs:
-        sd, oracle_sd, n, depth = _cases(flux, demo2)[case]
-        o = oracle_mod.Oracle(oracle_sd, flux.JobConfiguration(n, depth, 50), seed=4)
-        o.stats(reset=True)
-        want = o.render_frame(threads=8)
-        refill = _render(flux, sd, n, depth, flux.KERNEL_REFILL)
-        static = _render(flux, sd, n, depth, flux.KERNEL_STATIC)
-        for a in (want, refill[0], static[0]):
-            a.setflags(write=False)
-        _refs[case] = (sd, n, depth, want, o.stats(), refill, static)
-    return _refs[case]
+def _case(flux, oracle_mod, demo2, case):
+    """scene, sample root, depth limit, and the oracle's, the refill kernel's and the static kernel's frame and statistics: read by
+    every queue"""
+    sd, oracle_sd, n, depth = _cases(flux, demo2)[case]
+    return (sd, n, depth) + sc.references(_refs, case, flux, oracle_mod, sd, n, depth, SEED, oracle_sd=oracle_sd)
 
 
 @pytest.fixture
@@ -118,11 +103,11 @@ def switches(env_switches):
 @pytest.mark.parametrize("q", QUEUES)
 @pytest.mark.parametrize("case", CASES)
 def test_uniform_step_changes_no_bit(flux, oracle_mod, demo2, switches, case, q):
-    sd, n, depth, want, o_stats, (refill, rs, _), (static, ss, _) = _references(flux, oracle_mod, demo2, case)
+    sd, n, depth, want, o_stats, (refill, rs, *_), (static, ss, *_) = _case(flux, oracle_mod, demo2, case)
     switches(q, True)
-    got, gs, plan = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    got, gs, plan = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches(q, False)
-    general, es, plan_general = _render(flux, sd, n, depth, flux.KERNEL_SPLIT)
+    general, es, plan_general = sc.render(flux, sd, n, depth, SEED, flux.KERNEL_SPLIT)[:3]
     switches(None, True)
     # (a stored normal that is not unit routes the job to the STRICT arithmetic, which has no split kernel: the refill kernel runs,
     # with or without the switch)
@@ -132,21 +117,21 @@ def test_uniform_step_changes_no_bit(flux, oracle_mod, demo2, switches, case, q)
     print(f"{case} {q}: |split - oracle| {err_oracle:.3e}  |split - refill| {err_refill:.3e}  |split - static| {err_static:.3e}  "
           f"bits equal to the general step: {np.array_equal(got, general)}")
     assert gs == rs == ss, (gs, rs, ss)
-    assert err_refill <= 1e-12
-    assert err_static <= 1e-12
+    assert err_refill <= TOL_ORDER
+    assert err_static <= TOL_ORDER
     assert {k: gs[k] for k in o_stats} == o_stats
-    assert err_oracle < 1e-4
+    assert err_oracle < TOL_ORACLE
     assert np.array_equal(got, general)
     assert gs == es, (gs, es)
 
 
-def test_the_cases_are_what_they_claim(flux, oracle_mod, demo2):
+def test_the_cases_are_what_they_claim(flux, oracle_mod, demo2, env_switches):
     """By the oracle's own statistics: the all-miss scene only misses, the view from behind the emissive plane sees less light than
     the one from its lit side, and a depth limit of 1 ends every path that would bounce."""
-    st = {c: _references(flux, oracle_mod, demo2, c)[4] for c in ("outside_the_environment_looking_away", "depth_limit_1")}
+    st = {c: _case(flux, oracle_mod, demo2, c)[4] for c in ("outside_the_environment_looking_away", "depth_limit_1")}
     away = st["outside_the_environment_looking_away"]
     assert away["misses"] == away["samples"] == away["segments"] > 0
     assert st["depth_limit_1"]["segments"] == st["depth_limit_1"]["samples"] and st["depth_limit_1"]["depth_exhausted"] > 0
-    lit = _references(flux, oracle_mod, demo2, "emissive_plane_lit_side")[3]
-    behind = _references(flux, oracle_mod, demo2, "emissive_plane_from_behind")[3]
+    lit = _case(flux, oracle_mod, demo2, "emissive_plane_lit_side")[3]
+    behind = _case(flux, oracle_mod, demo2, "emissive_plane_from_behind")[3]
     assert float(lit.sum()) > float(behind.sum())
