@@ -132,6 +132,7 @@ SYMBOLS = {
     "flux_ctx_set_traversal": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_math": (C.c_int, [_P, C.c_int]),
     "flux_ctx_set_mesh_normals": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_double), C.c_uint64]),
+    "flux_ctx_set_mesh_colors": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_double), C.c_uint64]),
     "flux_debug_shade": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_double), C.c_uint64, C.c_uint64, C.c_uint64,
                                    C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "flux_sampler_grid": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double),

@@ -24,6 +24,7 @@
 #include "flux_math_coeffs.h"  // kExp2Poly -> RenderParams::exp2c
 
 #include "flux_ctx.h"
+#include "flux_color.h"
 #include "flux_smooth.h"
 #include "flux_switches.h"
 
@@ -195,6 +196,7 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     c->bvh = h.bvh;
     c->mesh_first = h.mesh_first;
     c->mesh_smooth.assign(h.mesh_first.empty() ? 0 : h.mesh_first.size() - 1, 0);
+    c->mesh_colored.assign(c->mesh_smooth.size(), 0);
     for (int a = 0; a < 3; a++) {
         c->U[a] = h.U[a];
         c->V[a] = h.V[a];
@@ -370,6 +372,48 @@ int upload(const HostScene &h, const flux_job_cfg &cfg, uint64_t seed, int devic
     for (int k = 0; k < FLUX_CREATE_TIMING_WORDS; k++) c->create_ms[k] = laps.ms[k];
     *out = c.release();
     return FLUX_OK;
+}
+
+// One per-triangle attribute of mesh m -- corner normals (V = double, flags = mesh_smooth) or corner colours (V = float, flags =
+// mesh_colored) --, checked and converted by the caller; an empty `values` clears it.  The table where the context has none yet, the
+// mesh's values staged in input order, and the device's own gather into leaf order, which leaves the other attribute alone.  Every
+// allocation precedes the first change.  The table is freed when no mesh has either attribute any more.
+template <class V>
+int set_mesh_attribute(flux_ctx *ctx, size_t m, const std::vector<V> &values, std::vector<unsigned char> &flags,
+                       hipError_t (*gather)(DevTri *, int, int, int, const V *, double *, hipStream_t)) {
+    const bool set = !values.empty();
+    const uint64_t own = ctx->mesh_first[m + 1] - ctx->mesh_first[m];
+    if (!set && !flags[m]) return (int)FLUX_OK;  // (a mesh without triangles, or nothing to clear)
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
+    const size_t table_bytes = (size_t)ctx->rp.n_tris * kTriNormalDoubles * sizeof(double);
+    DevBuf<double> fresh;
+    DevBuf<V> stage;
+    if (set && !ctx->d_tri_normals) {
+        HIP_TRY(fresh.alloc_bytes(table_bytes));
+        HIP_TRY(hipMemset(fresh, 0, table_bytes));
+    }
+    if (set) {
+        HIP_TRY(stage.alloc(values.size()));
+        HIP_TRY(hipMemcpy(stage, values.data(), values.size() * sizeof(V), hipMemcpyHostToDevice));
+    }
+    double *table = fresh ? fresh : ctx->d_tri_normals;
+    HIP_TRY(gather(ctx->d_tris, ctx->rp.n_tris, ctx->rp.n_shapes + (int)ctx->mesh_first[m], (int)own, stage, table, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (fresh) {
+        ctx->d_tri_normals = std::move(fresh);
+        ctx->device_bytes += table_bytes;
+    }
+    flags[m] = set ? 1 : 0;
+    bool any = false;
+    for (unsigned char f : ctx->mesh_smooth) any = any || f;
+    for (unsigned char f : ctx->mesh_colored) any = any || f;
+    if (!any && ctx->d_tri_normals) {  // the last attribute of the last mesh went: the context is as it was created
+        ctx->d_tri_normals.reset();
+        ctx->device_bytes -= table_bytes;
+    }
+    ctx->rp.tri_normals = ctx->d_tri_normals;
+    return (int)FLUX_OK;
 }
 
 }  // namespace flux
@@ -937,8 +981,7 @@ double flux_ctx_last_kernel_ms(flux_ctx *ctx) {
     return (double)ms;
 }
 
-// the checks and the normalisation (flux_smooth.h) before any device call; then the table where the context has none yet, the mesh's
-// normals staged in input order, and the device's own gather into leaf order.  Every allocation precedes the first change.
+// the checks and the normalisation (flux_smooth.h) before any device call; then set_mesh_attribute
 int flux_ctx_set_mesh_normals(flux_ctx *ctx, uint64_t mesh, const double *corner_normals, uint64_t num_triangles) {
     if (!ctx) return fail(FLUX_E_INVALID, "null context");
     return flux::no_throw([&] {
@@ -946,38 +989,19 @@ int flux_ctx_set_mesh_normals(flux_ctx *ctx, uint64_t mesh, const double *corner
         std::string error;
         if (!flux::normalize_corner_normals(ctx->mesh_first, mesh, corner_normals, num_triangles, normal, error))
             return fail(FLUX_E_INVALID, "%s", error.c_str());
-        const bool set = !normal.empty();
-        const size_t m = (size_t)mesh;
-        const uint64_t own = ctx->mesh_first[m + 1] - ctx->mesh_first[m];
-        if (!set && !ctx->mesh_smooth[m]) return (int)FLUX_OK;  // (a mesh without triangles, or nothing to clear)
-        DeviceGuard guard(ctx->device);
-        if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-        const size_t table_bytes = (size_t)ctx->rp.n_tris * flux::kTriNormalDoubles * sizeof(double);
-        flux::DevBuf<double> fresh, stage;
-        if (set && !ctx->d_tri_normals) {
-            HIP_TRY(fresh.alloc_bytes(table_bytes));
-            HIP_TRY(hipMemset(fresh, 0, table_bytes));
-        }
-        if (set) {
-            HIP_TRY(stage.alloc(normal.size()));
-            HIP_TRY(hipMemcpy(stage, normal.data(), normal.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        double *table = fresh ? fresh : ctx->d_tri_normals;
-        HIP_TRY(flux::gather_tri_normals(ctx->d_tris, ctx->rp.n_tris, ctx->rp.n_shapes + (int)ctx->mesh_first[m], (int)own, stage, table, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (fresh) {
-            ctx->d_tri_normals = std::move(fresh);
-            ctx->device_bytes += table_bytes;
-        }
-        ctx->mesh_smooth[m] = set ? 1 : 0;
-        bool any = false;
-        for (unsigned char f : ctx->mesh_smooth) any = any || f;
-        if (!any && ctx->d_tri_normals) {  // the last mesh went back to facet normals: the context is as it was created
-            ctx->d_tri_normals.reset();
-            ctx->device_bytes -= table_bytes;
-        }
-        ctx->rp.tri_normals = ctx->d_tri_normals;
-        return (int)FLUX_OK;
+        return flux::set_mesh_attribute(ctx, (size_t)mesh, normal, ctx->mesh_smooth, flux::gather_tri_normals);
+    });
+}
+
+// the checks and the f32 rounding (flux_color.h) before any device call; then set_mesh_attribute
+int flux_ctx_set_mesh_colors(flux_ctx *ctx, uint64_t mesh, const double *corner_colors, uint64_t num_triangles) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    return flux::no_throw([&] {
+        std::vector<float> color;
+        std::string error;
+        if (!flux::round_corner_colors(ctx->mesh_first, mesh, corner_colors, num_triangles, color, error))
+            return fail(FLUX_E_INVALID, "%s", error.c_str());
+        return flux::set_mesh_attribute(ctx, (size_t)mesh, color, ctx->mesh_colored, flux::gather_tri_colors);
     });
 }
 

@@ -9,13 +9,16 @@
 //           as stored, a box face's axis (negated for `invert`); a miss contributes 0;
 //   albedo  the material's bounce weight in its closed form -- kd colour for Matte, ks colour for Reflective / Glossy, transmit_color
 //           for a Dielectric: the records behind RenderParams::mats, which are a hit record's (fr, fg, fb) too --, for an Emissive
-//           power colour on the side it emits to (materials.rs:44) and 0 on the other; a miss contributes the background;
+//           power colour on the side it emits to (materials.rs:44) and 0 on the other; on a triangle with vertex colours (DESIGN.md
+//           section 5k) times the interpolated colour factor; a miss contributes the background;
 //   t, 1    the hit distance and a count of one; a miss contributes neither.
 // Values are not clamped.
 
 // the closed-form bounce weight of material `mat` (scene_build.cpp: 32 B a record behind the n_mats materials)
+constexpr uint32_t kMaterialWeightBytes = 32;
+__device__ __forceinline__ const char *material_weights(const RenderParams &P) { return reinterpret_cast<const char *>(P.mats + P.n_mats); }
 __device__ __forceinline__ V3 material_weight(const RenderParams &P, int mat) {
-    const double *w = reinterpret_cast<const double *>(P.mats + P.n_mats) + 4 * (size_t)mat;
+    const double *w = reinterpret_cast<const double *>(material_weights(P)) + 4 * (size_t)mat;
     return mk(w[0], w[1], w[2]);
 }
 
@@ -32,10 +35,8 @@ __device__ __forceinline__ void first_hit_fields(const RenderParams &P, const Ra
     if (is_tri) {
         const DevTri &T = P.tris[slot];
         const int mat = T.mat;
-        const V3 w = material_weight(P, mat);
-        const V3 tn = tri_shading_normal(P, r, slot);
+        const V3 tn = tri_shading_normal(P, r, slot, material_weights(P), kMaterialWeightBytes, mat, wr, wg, wb);  // (vertex colours: §5k)
         nx = tn.x; ny = tn.y; nz = tn.z;
-        wr = w.x; wg = w.y; wb = w.z;
         kind = P.mats[mat].kind;
     } else {
         const DevHitRec &R = *reinterpret_cast<const DevHitRec *>(reinterpret_cast<const char *>(P.frec) + (uint32_t)hit * (uint32_t)sizeof(DevHitRec));
@@ -51,8 +52,9 @@ __device__ __forceinline__ void first_hit_fields(const RenderParams &P, const Ra
 #else
     const DevShape *S = P.shapes + (is_tri ? 0 : hit);
     const int mat = is_tri ? P.tris[slot].mat : hit;
+    double wr = 0.0, wg = 0.0, wb = 0.0;  // a triangle's weight, times its colour factor where it has one (DESIGN.md section 5k)
     if (is_tri) {
-        n = tri_shading_normal(P, r, slot);
+        n = tri_shading_normal(P, r, slot, material_weights(P), kMaterialWeightBytes, mat, wr, wg, wb);
     } else if (S->kind == kShapeSphere) {
         const double inv = S->inv, rad = S->radius;
         n = mk(((r.ox - S->px) + t * d.x) * inv / rad, ((r.oy - S->py) + t * d.y) * inv / rad, ((r.oz - S->pz) + t * d.z) * inv / rad);
@@ -64,7 +66,8 @@ __device__ __forceinline__ void first_hit_fields(const RenderParams &P, const Ra
         n = mk(S->c0x, S->c0y, S->c0z);
     }
     kind = P.mats[mat].kind;
-    a = material_weight(P, mat);
+    // (three scalars, joined here: written through `a` in the branch, the compiler kept the triple in scratch)
+    a = is_tri ? mk(wr, wg, wb) : material_weight(P, mat);
 #endif
     if (kind == kMatEmissive) {  // materials.rs:41-50: black from behind
         const bool front = ((n.x * -1.0) * d.x + (n.y * -1.0) * d.y + (n.z * -1.0) * d.z) > 0.0;

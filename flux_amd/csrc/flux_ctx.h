@@ -174,6 +174,7 @@ struct flux_ctx {
     // normals in d_tri_normals (RenderParams::tri_normals), which is held while any mesh has
     std::vector<uint64_t> mesh_first;
     std::vector<unsigned char> mesh_smooth;
+    std::vector<unsigned char> mesh_colored;  // vertex colours (flux_ctx_set_mesh_colors): mesh m has corner colours in the same table
     flux::DevBuf<double> d_tri_normals;
     flux::BvhInfo bvh{};
     int traversal = FLUX_TRAVERSE_BVH;

@@ -38,9 +38,12 @@ hipError_t generate_glossx_table(const double *gloss, size_t count, const double
 hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *out, hipStream_t stream);
 // The corner-normal records (RenderParams::tri_normals) of ONE mesh, by the slot -> triangle map the device already holds (DevTri::id):
 // every slot s < n_tris whose triangle k = tris[s].id - first_id lies in [0, count) gets table[s] = stage[k] (nine doubles of
-// [count][3][3], the rest of the 128-B record zero) and DevTri::smooth = 1 -- or, with stage == nullptr, smooth = 0 and, where
-// `table` is not null, a zero record.  Other slots are not touched.  Asynchronous on `stream`.
+// [count][3][3], bytes 0..71 of the 128-B record) and DevTri::smooth = 1 -- or, with stage == nullptr, smooth = 0 and, where
+// `table` is not null, zeros in those bytes.  Other slots, and the record's other bytes, are not touched.  Asynchronous on `stream`.
 hipError_t gather_tri_normals(DevTri *tris, int n_tris, int first_id, int count, const double *stage, double *table, hipStream_t stream);
+// The same for the corner colours of ONE mesh (flux_ctx_set_mesh_colors): nine f32 of [count][3][3] into bytes 72..107 of the record
+// and DevTri::colored; the normals' bytes and DevTri::smooth are not touched.
+hipError_t gather_tri_colors(DevTri *tris, int n_tris, int first_id, int count, const float *stage, double *table, hipStream_t stream);
 hipError_t hemi_to_aos(size_t SD, size_t N, const double *in, double *out, hipStream_t stream);
 
 // The rows p names by the kernels of `pass` (flux_plan.h; not kPassAdaptive): Camera::render (trace.rs:53-97) for kPassRender --

@@ -241,24 +241,36 @@ hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *o
     return hipGetLastError();
 }
 
-// The corner-normal records of one mesh, gathered into leaf order (flux_tables.h gather_tri_normals): one thread per DevTri slot
-__global__ void gather_tri_normals_kernel(DevTri *__restrict__ tris, int n_tris, int first_id, int count, const double *__restrict__ stage,
-                                          double *__restrict__ table) {
+// One attribute of one mesh, gathered into leaf order (flux_tables.h gather_tri_normals, gather_tri_colors): one thread per DevTri
+// slot.  V = double: the nine corner-normal components at byte 0 of the slot's record and DevTri::smooth; V = float: the nine
+// corner-colour components at byte 72 and DevTri::colored.  The other attribute's bytes and flag are left alone.
+template <class V>
+__global__ void gather_tri_attribute_kernel(DevTri *__restrict__ tris, int n_tris, int first_id, int count, const V *__restrict__ stage,
+                                            double *__restrict__ table) {
+    constexpr bool kColors = sizeof(V) == sizeof(float);
     const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (s >= n_tris) return;
     const int k = tris[s].id - first_id;
     if (k < 0 || k >= count) return;
     if (table) {
-        double *o = table + (size_t)s * kTriNormalDoubles;
-        for (int j = 0; j < (int)kTriNormalDoubles; j++) o[j] = (stage && j < 9) ? stage[(size_t)k * 9 + j] : 0.0;
+        V *o = reinterpret_cast<V *>(table + (size_t)s * kTriNormalDoubles) + (kColors ? kTriColorFloat0 : 0);
+        for (int j = 0; j < 9; j++) o[j] = stage ? stage[(size_t)k * 9 + j] : (V)0;
     }
-    tris[s].smooth = stage ? 1 : 0;
+    if (kColors) tris[s].colored = stage ? 1 : 0;
+    else tris[s].smooth = stage ? 1 : 0;
 }
-hipError_t gather_tri_normals(DevTri *tris, int n_tris, int first_id, int count, const double *stage, double *table, hipStream_t stream) {
+template <class V>
+static hipError_t gather_tri_attribute(DevTri *tris, int n_tris, int first_id, int count, const V *stage, double *table, hipStream_t stream) {
     if (n_tris <= 0 || count <= 0) return hipSuccess;
     if (stage && !table) return hipErrorInvalidValue;
-    gather_tri_normals_kernel<<<dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, stream>>>(tris, n_tris, first_id, count, stage, table);
+    gather_tri_attribute_kernel<V><<<dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, stream>>>(tris, n_tris, first_id, count, stage, table);
     return hipGetLastError();
+}
+hipError_t gather_tri_normals(DevTri *tris, int n_tris, int first_id, int count, const double *stage, double *table, hipStream_t stream) {
+    return gather_tri_attribute<double>(tris, n_tris, first_id, count, stage, table, stream);
+}
+hipError_t gather_tri_colors(DevTri *tris, int n_tris, int first_id, int count, const float *stage, double *table, hipStream_t stream) {
+    return gather_tri_attribute<float>(tris, n_tris, first_id, count, stage, table, stream);
 }
 
 // The launcher of the <TRIS> kernels -- the per-pixel passes and flux_debug_shade, which every copy compiles both ways

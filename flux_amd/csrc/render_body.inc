@@ -290,45 +290,84 @@ __device__ __forceinline__ bool tri_hit(const DevTri &T, const Ray &r, double &t
     return tri_hit_v(mk(T.v0x, T.v0y, T.v0z), mk(T.e1x, T.e1y, T.e1z), mk(T.e2x, T.e2y, T.e2z), r, t);
 }
 
-// extension: smooth meshes (DESIGN.md section 5j; the spec: include/flux_abi.h flux_ctx_set_mesh_normals, tests/smooth_spec.py).
-// The shading normal of the hit of segment r on triangle `slot`: the stored facet normal, or -- for a triangle whose mesh has corner
-// normals -- their interpolation at the hit's barycentrics, recomputed here from the DevTri record with tri_hit_v's own expressions
-// (the traversal keeps no u, v: two registers less through its loop than carrying them would cost).  Every reader of a triangle's
-// normal calls this: the bounce and the facing test (shade_hit_fast, shade_hit), the feature buffers (first_hit_fields).
-// A context without a table (P.tri_normals == nullptr: a scalar branch) runs the stored normal's three loads as before.
-__device__ __forceinline__ V3 tri_shading_normal(const RenderParams &P, const Ray &r, int slot) {
+// extension: smooth meshes and vertex colours (DESIGN.md sections 5j and 5k; the spec: include/flux_abi.h flux_ctx_set_mesh_normals
+// and flux_ctx_set_mesh_colors, tests/smooth_spec.py, tests/color_spec.py).
+// The shading attributes of the hit of segment r on triangle `slot`.  Returned: the shading normal -- the stored facet normal, or,
+// for a triangle whose mesh has corner normals, their interpolation at the hit's barycentrics, recomputed here from the DevTri record
+// with tri_hit_v's own expressions (the traversal keeps no u, v: two registers less through its loop than carrying them would cost).
+// (fr, fg, fb): the material's triple as the caller would read it, the three doubles at `records + index * stride` (a
+// DevMaterial's fr, fg, fb, or the feature buffers' weight) -- times, for a triangle whose mesh has corner colours, their interpolation at the same barycentrics, clamped
+// below at 0.  One barycentric computation serves both attributes, and both lie in the slot's one 128-B record.  Every reader of a
+// triangle's normal or material colour calls this: the bounce and the facing test (shade_hit_fast, shade_hit), the feature buffers
+// (first_hit_fields).
+// The product sits inside the per-lane `colored` branch, with a read of the triple of its own, and every other lane reads the
+// triple as it is behind it -- the stored normal's pattern.  So a context without a table (P.tri_normals == nullptr: a scalar branch)
+// runs the stored normal's and the triple's loads and nothing else: no product, no select.  (Multiplied in the caller under
+// `P.tri_normals != nullptr`, the compiler ran three products and six selects for every triangle hit and waited for the triple
+// there: +1.6 % on configuration 5, which has no table.)  The coloured branch forms the triple's address from a copy of the index
+// the compiler cannot see through: with one address for both reads it was computed in front of the scalar branch, and the wait
+// for the triangle's material index with it -- ahead of the stored normal's loads instead of behind them.
+__device__ __forceinline__ V3 tri_shading_normal(const RenderParams &P, const Ray &r, int slot, const char *records, uint32_t stride,
+                                                 int index, double &fr, double &fg, double &fb) {
     const DevTri &T = P.tris[slot];
-    bool flat = true;
+    bool flat = true, plain = true;
     V3 n;
-    if (P.tri_normals != nullptr && T.smooth != 0) {
-        const V3 e1 = mk(T.e1x, T.e1y, T.e1z), e2 = mk(T.e2x, T.e2y, T.e2z);
-        const V3 d = mk(r.dx, r.dy, r.dz);
-        const V3 p = cross(d, e2);
-        const V3 s = mk(r.ox - T.v0x, r.oy - T.v0y, r.oz - T.v0z);
+    if (P.tri_normals != nullptr) {
+        const bool smooth = T.smooth != 0, colored = T.colored != 0;
+        if (smooth || colored) {
+            const V3 e1 = mk(T.e1x, T.e1y, T.e1z), e2 = mk(T.e2x, T.e2y, T.e2z);
+            const V3 d = mk(r.dx, r.dy, r.dz);
+            const V3 p = cross(d, e2);
+            const V3 s = mk(r.ox - T.v0x, r.oy - T.v0y, r.oz - T.v0z);
 #if FLUX_FAST
-        const double inv = fastmath::fdiv(1.0, dot(e1, p));
+            const double inv = fastmath::fdiv(1.0, dot(e1, p));
 #else
-        const double inv = 1.0 / dot(e1, p);
+            const double inv = 1.0 / dot(e1, p);
 #endif
-        const double u = dot(s, p) * inv;
-        const double v = dot(d, cross(s, e1)) * inv;
-        const double w = (1.0 - u) - v;
-        // uniform base + 32-bit byte offset (the slot count keeps slot * 128 below 2^32, as for the DevTri records)
-        const double *N = reinterpret_cast<const double *>(reinterpret_cast<const char *>(P.tri_normals) +
-                                                           (uint32_t)slot * (uint32_t)(kTriNormalDoubles * sizeof(double)));
-        const V3 m = mk((w * N[0] + u * N[3]) + v * N[6], (w * N[1] + u * N[4]) + v * N[7], (w * N[2] + u * N[5]) + v * N[8]);
-        const double l2 = (m.x * m.x + m.y * m.y) + m.z * m.z;
-        flat = !(l2 >= 1e-24);  // (true for a NaN too: opposed corner normals and a degenerate hit keep the facet normal)
+            const double u = dot(s, p) * inv;
+            const double v = dot(d, cross(s, e1)) * inv;
+            // uniform base + 32-bit byte offset (the slot count keeps slot * 128 below 2^32, as for the DevTri records)
+            const double *N = reinterpret_cast<const double *>(reinterpret_cast<const char *>(P.tri_normals) +
+                                                               (uint32_t)slot * (uint32_t)(kTriNormalDoubles * sizeof(double)));
+            if (smooth) {
+                const double w = (1.0 - u) - v;
+                const V3 m = mk((w * N[0] + u * N[3]) + v * N[6], (w * N[1] + u * N[4]) + v * N[7], (w * N[2] + u * N[5]) + v * N[8]);
+                const double l2 = (m.x * m.x + m.y * m.y) + m.z * m.z;
+                flat = !(l2 >= 1e-24);  // (true for a NaN too: opposed corner normals and a degenerate hit keep the facet normal)
 #if FLUX_FAST
-        const double il = fastmath::frsqrt(l2);
-        n = mk(m.x * il, m.y * il, m.z * il);
+                const double il = fastmath::frsqrt(l2);
+                n = mk(m.x * il, m.y * il, m.z * il);
 #else
-        const double len = sqrt(l2);
-        n = mk(m.x / len, m.y / len, m.z / len);
+                const double len = sqrt(l2);
+                n = mk(m.x / len, m.y / len, m.z / len);
 #endif
+            }
+            // (behind the normals: their eighteen registers are free again when the nine f32 colours arrive -- the same line)
+            if (colored) {
+                const float *K = reinterpret_cast<const float *>(N) + kTriColorFloat0;
+                const double k0r = (double)K[0], k0g = (double)K[1], k0b = (double)K[2];
+                // g1 = k1 - k0, g2 = k2 - k0, (k0 + u g1) + v g2, then maxNum against 0: a NaN and a rounding residue below 0 give 0
+                const V3 c = mk(fmax((k0r + u * ((double)K[3] - k0r)) + v * ((double)K[6] - k0r), 0.0),
+                                fmax((k0g + u * ((double)K[4] - k0g)) + v * ((double)K[7] - k0g), 0.0),
+                                fmax((k0b + u * ((double)K[5] - k0b)) + v * ((double)K[8] - k0b), 0.0));
+                int own = index;
+                asm("" : "+v"(own));
+                const double *triple = reinterpret_cast<const double *>(records + (uint32_t)own * stride);
+                fr = triple[0] * c.x;
+                fg = triple[1] * c.y;
+                fb = triple[2] * c.z;
+                plain = false;
+            }
+        }
     }
     // (the stored normal is read behind the interpolation, not in front of it: its six registers are not held across)
     if (flat) n = mk(T.nx, T.ny, T.nz);
+    if (plain) {
+        const double *triple = reinterpret_cast<const double *>(records + (uint32_t)index * stride);
+        fr = triple[0];
+        fg = triple[1];
+        fb = triple[2];
+    }
     return n;
 }
 
@@ -1574,9 +1613,9 @@ __device__ __forceinline__ bool shade_hit_fast(const RenderParams &P, Path &p, u
             const DevTri &T = P.tris[slot];
             const DevMaterial &Mt = P.mats[T.mat];
             p.mat = T.mat;
-            n = tri_shading_normal(P, p.r, slot);
+            n = tri_shading_normal(P, p.r, slot, reinterpret_cast<const char *>(P.mats), (uint32_t)sizeof(DevMaterial), T.mat, fr, fg, fb);
             kind = Mt.kind;
-            fr = Mt.fr; fg = Mt.fg; fb = Mt.fb; m_inv_e1 = Mt.inv_e1;
+            m_inv_e1 = Mt.inv_e1;
             ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
             az = kind == kMatMatte ? 0.0071 : 0.00764;
         } else {
@@ -1679,9 +1718,10 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
         const DevMaterial &Mt = LDS_SCENE ? *reinterpret_cast<const DevMaterial *>(mats_lds + (uint32_t)T.mat * (uint32_t)sizeof(DevMaterial))
                                           : P.mats[T.mat];
         p.mat = T.mat;
-        n = tri_shading_normal(P, p.r, slot);
+        n = tri_shading_normal(P, p.r, slot, LDS_SCENE ? mats_lds : reinterpret_cast<const char *>(P.mats), (uint32_t)sizeof(DevMaterial),
+                               T.mat, fr, fg, fb);
         kind = Mt.kind;
-        fr = Mt.fr; fg = Mt.fg; fb = Mt.fb; m_inv_e1 = Mt.inv_e1;
+        m_inv_e1 = Mt.inv_e1;
         ax = kind == kMatMatte ? 0.0034 : 0.00424;  // brdf.rs:22 / brdf.rs:58
         az = kind == kMatMatte ? 0.0071 : 0.00764;
     } else {
@@ -1710,8 +1750,10 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
 #else
     const DevShape *S = P.shapes + (is_tri ? 0 : hit);
     const DevMaterial *M = P.mats + (is_tri ? P.tris[slot].mat : hit);
+    double tfr = 0.0, tfg = 0.0, tfb = 0.0;  // a triangle's triple, times its colour factor where it has one (DESIGN.md section 5k)
     if (is_tri) {
-        n = tri_shading_normal(P, p.r, slot);
+        n = tri_shading_normal(P, p.r, slot, reinterpret_cast<const char *>(P.mats), (uint32_t)sizeof(DevMaterial), P.tris[slot].mat, tfr,
+                               tfg, tfb);
     } else if (S->kind == kShapeSphere) {
         const double inv = S->inv, rad = S->radius;
         n = mk(((p.r.ox - S->px) + t * d.x) * inv / rad, ((p.r.oy - S->py) + t * d.y) * inv / rad,
@@ -1728,12 +1770,12 @@ __device__ __forceinline__ bool shade_hit(const RenderParams &P, Path &p, uint32
     if (kind == kMatEmissive) {  // materials.rs:41-50
         if (STATS) st.c[5]++;
         const bool front = ((n.x * -1.0) * d.x + (n.y * -1.0) * d.y + (n.z * -1.0) * d.z) > 0.0;
-        Lr = front ? M->fr : 0.0;
-        Lg = front ? M->fg : 0.0;
-        Lb = front ? M->fb : 0.0;
+        Lr = front ? (is_tri ? tfr : M->fr) : 0.0;
+        Lg = front ? (is_tri ? tfg : M->fg) : 0.0;
+        Lb = front ? (is_tri ? tfb : M->fb) : 0.0;
         return false;
     }
-    double fr = M->fr, fg = M->fg, fb = M->fb;
+    double fr = is_tri ? tfr : M->fr, fg = is_tri ? tfg : M->fg, fb = is_tri ? tfb : M->fb;
     const double m_exponent = M->exponent, m_inv_e1 = M->inv_e1;
 #endif
 #if FLUX_FAST

@@ -40,11 +40,22 @@ def vertex_normals(vertices, triangles) -> np.ndarray:
     return n / length[:, None]
 
 
-def uv_sphere_mesh(segments: int, rings: int, center=(0.0, 0.0, 0.0), radius: float = 1.0, material=None, smooth: bool = True) -> MeshData:
+def elevation_colors(vertices, low_rgb, high_rgb) -> np.ndarray:
+    """Per-vertex colours, float64 [nv][3]: a linear ramp from `low_rgb` at the mesh's lowest y to `high_rgb` at its highest
+    (low + s (high - low), s = (y - y_min) / (y_max - y_min); a mesh of one height gets `low_rgb`)."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    lo, hi = np.asarray(low_rgb, dtype=np.float64), np.asarray(high_rgb, dtype=np.float64)
+    y0, y1 = (float(v[:, 1].min()), float(v[:, 1].max())) if len(v) else (0.0, 0.0)
+    s = (v[:, 1] - y0) / (y1 - y0) if y1 > y0 else np.zeros(len(v))
+    return lo + np.clip(s, 0.0, 1.0)[:, None] * (hi - lo)
+
+
+def uv_sphere_mesh(segments: int, rings: int, center=(0.0, 0.0, 0.0), radius: float = 1.0, material=None, smooth: bool = True,
+                   colors=None) -> MeshData:
     """A latitude / longitude sphere: `segments` around the y axis, `rings` from pole to pole, 2 segments (rings - 1) triangles --
     a fan of `segments` triangles at each pole and a quad (two triangles sharing their first vertex and an edge, facing outwards)
     per segment and inner ring.  Vertices: the north pole, (rings - 1) rows of `segments`, the south pole.  smooth: the exact
-    sphere normals (vertex - center) / radius as per-vertex `normals`."""
+    sphere normals (vertex - center) / radius as per-vertex `normals`.  colors: MeshData.colors, per vertex or per corner."""
     if segments < 3 or rings < 2:
         raise ValueError("uv_sphere_mesh: segments >= 3 and rings >= 2 required")
     c = np.asarray(center, dtype=np.float64)
@@ -70,10 +81,14 @@ def uv_sphere_mesh(segments: int, rings: int, center=(0.0, 0.0, 0.0), radius: fl
         tris.append((south, vid(rings - 2, s), vid(rings - 2, s + 1)))
     if material is None:
         material = MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0)
-    return MeshData(c + radius * unit, np.array(tris, dtype=np.uint32), material, unit.copy() if smooth else None)
+    return MeshData(c + radius * unit, np.array(tris, dtype=np.uint32), material, unit.copy() if smooth else None, colors)
 
 
-def heightfield_mesh(nx: int, nz: int, seed: int = 12345, smooth: bool = False) -> MeshData:
+# heightfield_mesh(colored=True): valley to crest
+ELEVATION_LOW, ELEVATION_HIGH = (0.25, 0.55, 0.2), (1.0, 0.95, 0.9)
+
+
+def heightfield_mesh(nx: int, nz: int, seed: int = 12345, smooth: bool = False, colored: bool = False) -> MeshData:
     i = np.arange(nx + 1, dtype=np.float64)
     j = np.arange(nz + 1, dtype=np.float64)
     x = -14.0 + 28.0 * i / nx
@@ -93,14 +108,16 @@ def heightfield_mesh(nx: int, nz: int, seed: int = 12345, smooth: bool = False) 
     tris[:, 0, 0], tris[:, 0, 1], tris[:, 0, 2] = v00, v01, v11
     tris[:, 1, 0], tris[:, 1, 1], tris[:, 1, 2] = v00, v11, v10
     tris = tris.reshape(-1, 3)
-    return MeshData(verts, tris, MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0), vertex_normals(verts, tris) if smooth else None)
+    return MeshData(verts, tris, MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0), vertex_normals(verts, tris) if smooth else None,
+                    elevation_colors(verts, ELEVATION_LOW, ELEVATION_HIGH) if colored else None)
 
 
-def heightfield_scene(nx: int = 1000, nz: int = 500, seed: int = 12345, base: SceneData = None, smooth: bool = False) -> SceneData:
+def heightfield_scene(nx: int = 1000, nz: int = 500, seed: int = 12345, base: SceneData = None, smooth: bool = False,
+                      colored: bool = False) -> SceneData:
     sd = copy.deepcopy(base) if base is not None else load_scene(os.path.join(_ROOT, "scenes", "demo2.yml"))
     sd.scene_name = f"heightfield_{nx}x{nz}"
     shapes = [s for s in sd.shapes if not isinstance(s, PlaneData)]
     shapes.append(PlaneData((0.0, -1.0, 0.0), (0.0, 1.0, 0.0), MatteData((0.5, 0.5, 0.5), (1.0, 1.0, 1.0), 1.0)))
-    shapes.append(heightfield_mesh(nx, nz, seed, smooth))
+    shapes.append(heightfield_mesh(nx, nz, seed, smooth, colored))
     sd.shapes = shapes
     return sd

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult, corner_normals, split_shapes
+from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult, corner_colors, corner_normals, split_shapes
 
 STAT_NAMES = ("samples", "segments", "matte_bounces", "glossy_bounces", "specular_bounces",
               "emissive_hits", "misses", "depth_exhausted", "bvh_nodes", "tris_tested",
@@ -37,6 +37,7 @@ class Renderer:
                                                  self.device, self.set_share[0], self.set_share[1], C.byref(h)))
         self._h = h
         _set_scene_normals(h, scene_data)
+        _set_scene_colors(h, scene_data)
         self._warn_if_routed()
 
     def _warn_if_routed(self):
@@ -314,6 +315,15 @@ class Renderer:
             normals = corner_normals(dataclasses.replace(meshes[mesh_index], normals=normals), f"mesh {mesh_index}")
         _set_mesh_normals(self._handle(), mesh_index, normals)
 
+    def set_mesh_colors(self, mesh_index: int, colors):
+        """Extension: vertex colours for mesh `mesh_index` (in the order of the scene's meshes) -- `colors` as MeshData.colors,
+        [vertices][3] or [triangles][3][3]; None: the material's colour alone again (flux_ctx_set_mesh_colors)."""
+        meshes = split_shapes(self.scene_data)[1]
+        if colors is not None and 0 <= mesh_index < len(meshes):
+            import dataclasses
+            colors = corner_colors(dataclasses.replace(meshes[mesh_index], colors=colors), f"mesh {mesh_index}")
+        _set_mesh_colors(self._handle(), mesh_index, colors)
+
     def bvh_info(self) -> dict:
         buf = (C.c_uint64 * _lib.BVH_INFO_WORDS)()
         _lib.check(_lib.lib.flux_ctx_bvh_info(self._handle(), buf, _lib.BVH_INFO_WORDS))
@@ -381,6 +391,25 @@ def _set_scene_normals(handle, scene_data):
             _set_mesh_normals(handle, i, corners)
 
 
+def _set_mesh_colors(handle, mesh_index, corners):
+    """flux_ctx_set_mesh_colors: `corners` [nt][3][3] float64, or None to clear"""
+    if mesh_index < 0:
+        raise _lib.FluxError(_lib.E_INVALID, f"mesh index {mesh_index} out of range")
+    if corners is None:
+        _lib.check(_lib.lib.flux_ctx_set_mesh_colors(handle, mesh_index, None, 0))
+        return
+    c = np.ascontiguousarray(corners, dtype=np.float64)
+    _lib.check(_lib.lib.flux_ctx_set_mesh_colors(handle, mesh_index, c.ctypes.data_as(C.POINTER(C.c_double)), c.size // 9))
+
+
+def _set_scene_colors(handle, scene_data):
+    """the colours of every mesh of the scene that has them, on one context"""
+    for i, m in enumerate(split_shapes(scene_data)[1]):
+        corners = corner_colors(m, f"mesh {i}")
+        if corners is not None and len(corners):
+            _set_mesh_colors(handle, i, corners)
+
+
 def _create_timing(handle) -> dict:
     buf = (C.c_double * _lib.CREATE_TIMING_WORDS)()
     _lib.check(_lib.lib.flux_ctx_create_timing(handle, buf))
@@ -408,6 +437,7 @@ class MultiRenderer:
             ctx = C.c_void_p()
             _lib.check(_lib.lib.flux_multi_ctx(h, rank, C.byref(ctx)))
             _set_scene_normals(ctx, scene_data)
+            _set_scene_colors(ctx, scene_data)   # vertex colours likewise (flux_ctx_set_mesh_colors)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -490,6 +520,8 @@ def render_frame_multi(scene_data: SceneData, config: JobConfiguration, seed: in
     for mesh normals (flux_ctx_set_mesh_normals works on a context), so a scene with a smooth mesh is refused: use MultiRenderer."""
     if any(m.normals is not None for m in split_shapes(scene_data)[1]):
         raise _lib.FluxError(_lib.E_INVALID, "render_frame_multi renders facet normals only; use MultiRenderer for a mesh with normals")
+    if any(m.colors is not None for m in split_shapes(scene_data)[1]):
+        raise _lib.FluxError(_lib.E_INVALID, "render_frame_multi has no place for vertex colours; use MultiRenderer for a mesh with colors")
     desc = SceneDesc(scene_data)
     cfg = _lib.FluxJobCfg(config.sample_root, config.max_trace_depth, config.rows_per_work_unit)
     out = np.empty((scene_data.output_settings.image_height, scene_data.output_settings.image_width, 3), dtype=np.float64)

@@ -406,11 +406,16 @@ class MeshData:
     Hit order: all Sphere/Plane shapes first (YAML order), then mesh triangles in YAML/index order.
     `normals` (optional; YAML `normals: [[x,y,z], ...]`, one per vertex): smooth shading -- [nv][3], one normal per vertex, or
     [nt][3][3], one per triangle corner.  The renderer interpolates them at the hit (include/flux_abi.h
-    flux_ctx_set_mesh_normals); None: the facet normals.  A Triangle stays flat."""
+    flux_ctx_set_mesh_normals); None: the facet normals.  A Triangle stays flat.
+    `colors` (optional; YAML `colors: [[r,g,b], ...]`, one per vertex): vertex colours -- [nv][3], one colour per vertex, or
+    [nt][3][3], one per triangle corner (sharp edges, a checker).  The renderer interpolates them at the hit and multiplies the
+    material's colour by the result (include/flux_abi.h flux_ctx_set_mesh_colors); None: the material's colour alone.
+    A Triangle stays plain."""
     vertices: object  # float64 ndarray [nv][3]
     triangles: object  # uint32 ndarray [nt][3]
     material: MaterialData
     normals: object = None  # float64 ndarray [nv][3] or [nt][3][3], or None
+    colors: object = None  # float64 ndarray [nv][3] or [nt][3][3], or None
 
 
 def mesh_from_yaml(tag, b, what):
@@ -437,6 +442,13 @@ def mesh_from_yaml(tag, b, what):
                              f"{len(nm) if isinstance(nm, list) else repr(nm)}")
         mesh.normals = np.array([_vec3(x, f"{w}.normals[{i}]") for i, x in enumerate(nm)], dtype=np.float64).reshape(-1, 3)
         corner_normals(mesh, w)  # (a zero or non-finite normal is refused where the scene is loaded)
+    if b.get("colors") is not None:
+        cl = b["colors"]
+        if not isinstance(cl, list) or len(cl) != len(v):
+            raise SceneError(f"{w}.colors: expected one [r,g,b] per vertex ({len(v)}), got "
+                             f"{len(cl) if isinstance(cl, list) else repr(cl)}")
+        mesh.colors = np.array([_vec3(x, f"{w}.colors[{i}]") for i, x in enumerate(cl)], dtype=np.float64).reshape(-1, 3)
+        corner_colors(mesh, w)  # (a component outside [0, FLT_MAX] is refused where the scene is loaded)
     return mesh
 
 
@@ -466,6 +478,34 @@ def corner_normals(mesh, what="mesh"):
     if bad.any():
         k, c = np.argwhere(bad)[0]
         raise SceneError(f"{what}.normals: triangle {k}, corner {c}: normal {tuple(float(x) for x in out[k, c])} must be finite with a finite length > 0")
+    return out
+
+
+def corner_colors(mesh, what="mesh"):
+    """`mesh.colors` in the layout of flux_ctx_set_mesh_colors, float64 [nt][3 corners][3 rgb] (per-vertex colours expanded through
+    `triangles`; not rounded to f32: the library does that), or None for a mesh without colours.  SceneError for a wrong shape, a
+    non-numeric entry, or a component outside [0, FLT_MAX] (a NaN included)."""
+    import numpy as np
+    if mesh.colors is None:
+        return None
+    t = np.asarray(mesh.triangles, dtype=np.int64).reshape(-1, 3)
+    nv = len(np.asarray(mesh.vertices).reshape(-1, 3))
+    try:
+        cl = np.asarray(mesh.colors, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SceneError(f"{what}.colors: expected numbers, got {mesh.colors!r}")
+    if cl.shape == (len(t), 3, 3):
+        out = cl
+    elif cl.shape == (nv, 3):
+        out = cl[t]
+    else:
+        raise SceneError(f"{what}.colors: expected [{nv}][3] (per vertex) or [{len(t)}][3][3] (per corner), got shape {cl.shape}")
+    out = np.ascontiguousarray(out, dtype=np.float64).reshape(len(t), 3, 3)
+    with np.errstate(invalid="ignore"):
+        bad = ~((out >= 0.0) & (out <= float(np.finfo(np.float32).max)))
+    if bad.any():
+        k, c, ch = np.argwhere(bad)[0]
+        raise SceneError(f"{what}.colors: triangle {k}, corner {c}, channel {ch}: component {float(out[k, c, ch])!r} must lie in [0, FLT_MAX]")
     return out
 
 

@@ -413,6 +413,36 @@ int flux_denoise_moments_device(int device, uint64_t width, uint64_t height, voi
  * scene, held while any mesh has normals. */
 int flux_ctx_set_mesh_normals(flux_ctx *ctx, uint64_t mesh, const double *corner_normals, uint64_t num_triangles);
 
+/* Vertex colours (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): three CORNER COLOURS per
+ * triangle of a mesh, interpolated at the hit and multiplied into the material's colour.  DESIGN.md section 5k;
+ * tests/color_spec.py states the same rule in numpy.  corner_colors is a host pointer laid out [num_triangles][3 corners][3 rgb], in
+ * the mesh's own triangle and corner order, and num_triangles must equal the mesh's count.  corner_colors == NULL with
+ * num_triangles == 0 clears the mesh's colours.
+ *   Host, when the call is made and before any device call: every component x must satisfy x >= 0 and x <= FLT_MAX (finite, and
+ *   rounding to a finite f32; -0.0 is accepted; a NaN, a negative value, an infinity and anything larger are refused).  Each
+ *   component is stored as (float)x, round-to-nearest-even: the stored corner colours k0, k1, k2.
+ *   Device, where a hit on a triangle with colours is shaded: u, v are exactly the barycentrics of flux_ctx_set_mesh_normals --
+ *   p = d x e2,  inv = 1 / (e1.p),  s = o - v0,  u = (s.p) inv,  q = s x e1,  v = (d.q) inv -- computed once when the triangle has
+ *   both normals and colours.  Per channel, with k* widened to f64 (exact):  g1 = k1 - k0,  g2 = k2 - k0,
+ *   c = (k0 + u g1) + v g2,  c = fmax(c, 0.0).  fmax is IEEE maxNum: a NaN gives 0, and so does a rounding residue below 0.
+ *   The material then acts as if its colour were colour (*) c, for all five materials: Matte diffuse_color, Reflective and Glossy
+ *   reflect_color, Dielectric transmit_color (the reflected branch's weight stays 1), Emissive color.  On the device this is one
+ *   multiply of the triple read from the material record (and of the albedo triple of both feature buffers) by c, at the place
+ *   where the triple is read.  STRICT performs exactly these operations; FAST may contract them and uses its fast division for
+ *   inv, as for the normals.  Equal corner colours k give c = k exactly for finite u, v; all-ones colours give the uncoloured
+ *   frame bit for bit.
+ *   Everything else about the hit -- the test, the BVH, ties, t, the normal -- is untouched, and a triangle of a mesh without
+ *   colours reads and computes what it did, also beside a mesh that has them.
+ * The colours share the 128-B per-triangle record of the corner normals (nine f32 in bytes 72..107): the table exists while any mesh
+ * has normals or colours, flux_ctx_device_bytes counts it once -- 128 B per triangle of the scene --, and clearing the last
+ * attribute of the last mesh frees it.
+ * The call is synchronous -- no render of the context may be in flight on a caller's stream --; colours set earlier for the mesh
+ * are replaced; a failed call leaves the context as it was.  FLUX_E_INVALID, before any device call, with a message naming the
+ * mesh and the first offending triangle, corner and channel: a null context, mesh >= the scene's num_meshes, a wrong count, a bad
+ * component.  Works on the contexts of flux_ctx_create and flux_ctx_create_sets and on the borrowed contexts of flux_multi_ctx: a
+ * flux_multi client sets the colours on EVERY rank.  The one-call flux_render_frame_multi has no place for them. */
+int flux_ctx_set_mesh_colors(flux_ctx *ctx, uint64_t mesh, const double *corner_colors, uint64_t num_triangles);
+
 /* Adaptive sampling (extension; FLUX_ABI_VERSION unchanged -- a client detects support by the symbol): further sample sets of
  * N = sample_root^2 samples for the pixels whose measured variance is still high, and only for those.  DESIGN.md section 5h;
  * tests/adaptive_spec.py states the same rule in numpy.  A call covers a list of h rows of W columns of a context that holds every
