@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "flux_amd", "csrc")
 HIP_SOURCES = ["abi.hip", "multi.hip", "tables.hip", "render.hip", "denoise.hip", "adaptive.hip", "bvh.cpp", "scene_build.cpp", "launch_plan.cpp"]
-HIP_HEADERS = ["flux_ctx.h", "flux_color.h", "flux_smooth.h", "flux_switches.h", "scene_build.h", "joining_thread.h", "flux_device.h", "flux_plan.h", "flux_rng.h", "flux_tables.h", "flux_bvh.h", "flux_math.h",
+HIP_HEADERS = ["flux_ctx.h", "flux_mesh_attr.h","flux_switches.h", "scene_build.h", "joining_thread.h", "flux_device.h", "flux_plan.h", "flux_rng.h", "flux_tables.h", "flux_bvh.h", "flux_math.h",
                "flux_math_coeffs.h", "flux_env_verdict.h", "flux_plane_axis.h", "flux_sample_order.h", "flux_moments.h", "render_body.inc", "aov_body.inc", "moments_body.inc", "adaptive_body.inc", "aov_chain_body.inc"]
 HIP_LIB = os.path.join(ROOT, "flux_amd", "libflux_hip.so")
 

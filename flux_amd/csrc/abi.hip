@@ -24,8 +24,7 @@
 #include "flux_math_coeffs.h"  // kExp2Poly -> RenderParams::exp2c
 
 #include "flux_ctx.h"
-#include "flux_color.h"
-#include "flux_smooth.h"
+#include "flux_mesh_attr.h"
 #include "flux_switches.h"
 
 namespace flux {
@@ -386,10 +385,10 @@ int set_mesh_attribute(flux_ctx *ctx, size_t m, const std::vector<V> &values, st
     if (!set && !flags[m]) return (int)FLUX_OK;  // (a mesh without triangles, or nothing to clear)
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return fail(FLUX_E_DEVICE, "hipSetDevice(%d) failed", ctx->device);
-    const size_t table_bytes = (size_t)ctx->rp.n_tris * kTriNormalDoubles * sizeof(double);
+    const size_t table_bytes = (size_t)ctx->rp.n_tris * kTriAttrDoubles * sizeof(double);
     DevBuf<double> fresh;
     DevBuf<V> stage;
-    if (set && !ctx->d_tri_normals) {
+    if (set && !ctx->d_tri_attrs) {
         HIP_TRY(fresh.alloc_bytes(table_bytes));
         HIP_TRY(hipMemset(fresh, 0, table_bytes));
     }
@@ -397,23 +396,39 @@ int set_mesh_attribute(flux_ctx *ctx, size_t m, const std::vector<V> &values, st
         HIP_TRY(stage.alloc(values.size()));
         HIP_TRY(hipMemcpy(stage, values.data(), values.size() * sizeof(V), hipMemcpyHostToDevice));
     }
-    double *table = fresh ? fresh : ctx->d_tri_normals;
+    double *table = fresh ? fresh : ctx->d_tri_attrs;
     HIP_TRY(gather(ctx->d_tris, ctx->rp.n_tris, ctx->rp.n_shapes + (int)ctx->mesh_first[m], (int)own, stage, table, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     if (fresh) {
-        ctx->d_tri_normals = std::move(fresh);
+        ctx->d_tri_attrs = std::move(fresh);
         ctx->device_bytes += table_bytes;
     }
     flags[m] = set ? 1 : 0;
     bool any = false;
     for (unsigned char f : ctx->mesh_smooth) any = any || f;
     for (unsigned char f : ctx->mesh_colored) any = any || f;
-    if (!any && ctx->d_tri_normals) {  // the last attribute of the last mesh went: the context is as it was created
-        ctx->d_tri_normals.reset();
+    if (!any && ctx->d_tri_attrs) {  // the last attribute of the last mesh went: the context is as it was created
+        ctx->d_tri_attrs.reset();
         ctx->device_bytes -= table_bytes;
     }
-    ctx->rp.tri_normals = ctx->d_tri_normals;
+    ctx->rp.tri_attrs = ctx->d_tri_attrs;
     return (int)FLUX_OK;
+}
+
+// flux_ctx_set_mesh_normals and flux_ctx_set_mesh_colors: the checks and the conversion (flux_mesh_attr.h) before any device call;
+// then set_mesh_attribute
+template <class V>
+int convert_and_set_mesh_attribute(flux_ctx *ctx, uint64_t mesh, const double *corners, uint64_t num_triangles,
+                                   bool (*convert)(const std::vector<uint64_t> &, uint64_t, const double *, uint64_t, std::vector<V> &, std::string &),
+                                   std::vector<unsigned char> flux_ctx::*flags,
+                                   hipError_t (*gather)(DevTri *, int, int, int, const V *, double *, hipStream_t)) {
+    if (!ctx) return fail(FLUX_E_INVALID, "null context");
+    return no_throw([&] {
+        std::vector<V> values;
+        std::string error;
+        if (!convert(ctx->mesh_first, mesh, corners, num_triangles, values, error)) return fail(FLUX_E_INVALID, "%s", error.c_str());
+        return set_mesh_attribute(ctx, (size_t)mesh, values, ctx->*flags, gather);
+    });
 }
 
 }  // namespace flux
@@ -981,28 +996,12 @@ double flux_ctx_last_kernel_ms(flux_ctx *ctx) {
     return (double)ms;
 }
 
-// the checks and the normalisation (flux_smooth.h) before any device call; then set_mesh_attribute
 int flux_ctx_set_mesh_normals(flux_ctx *ctx, uint64_t mesh, const double *corner_normals, uint64_t num_triangles) {
-    if (!ctx) return fail(FLUX_E_INVALID, "null context");
-    return flux::no_throw([&] {
-        std::vector<double> normal;
-        std::string error;
-        if (!flux::normalize_corner_normals(ctx->mesh_first, mesh, corner_normals, num_triangles, normal, error))
-            return fail(FLUX_E_INVALID, "%s", error.c_str());
-        return flux::set_mesh_attribute(ctx, (size_t)mesh, normal, ctx->mesh_smooth, flux::gather_tri_normals);
-    });
+    return flux::convert_and_set_mesh_attribute(ctx, mesh, corner_normals, num_triangles, flux::normalize_corner_normals, &flux_ctx::mesh_smooth, flux::gather_tri_normals);
 }
 
-// the checks and the f32 rounding (flux_color.h) before any device call; then set_mesh_attribute
 int flux_ctx_set_mesh_colors(flux_ctx *ctx, uint64_t mesh, const double *corner_colors, uint64_t num_triangles) {
-    if (!ctx) return fail(FLUX_E_INVALID, "null context");
-    return flux::no_throw([&] {
-        std::vector<float> color;
-        std::string error;
-        if (!flux::round_corner_colors(ctx->mesh_first, mesh, corner_colors, num_triangles, color, error))
-            return fail(FLUX_E_INVALID, "%s", error.c_str());
-        return flux::set_mesh_attribute(ctx, (size_t)mesh, color, ctx->mesh_colored, flux::gather_tri_colors);
-    });
+    return flux::convert_and_set_mesh_attribute(ctx, mesh, corner_colors, num_triangles, flux::round_corner_colors, &flux_ctx::mesh_colored, flux::gather_tri_colors);
 }
 
 int flux_ctx_enable_stats(flux_ctx *ctx, int on) {

@@ -15,7 +15,7 @@ struct DevTri {
     int32_t id;            // index in hit order: num_shapes + position in the input meshes.  Right behind the edges: the
     int32_t mat;           // intersection test then reads bytes 0..79 = five 16-B gathers.  mat: index into the materials
     double nx, ny, nz;     // normalize(e1 x e2), never flipped (read when shading only)
-    // The two flags of the slot's record of RenderParams::tri_normals.  Both are set and cleared on the device, with the table
+    // The two flags of the slot's record of RenderParams::tri_attrs.  Both are set and cleared on the device, with the table
     // (render.hip gather_tri_normals, gather_tri_colors); the host build leaves them 0.
     int32_t smooth;        // 1: the record holds corner normals (flux_ctx_set_mesh_normals)
     int32_t colored;       // 1: the record holds corner colours (flux_ctx_set_mesh_colors)

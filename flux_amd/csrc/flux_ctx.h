@@ -171,11 +171,11 @@ struct flux_ctx {
     flux::DevBuf<flux::DevNode4A> d_arena;  // the 4-wide tree of the FAST traversal kernel (RenderParams::nodes4), or empty
     flux::DevBuf<flux::DevNodeQ> d_nodesq;
     // extension: smooth meshes (flux_ctx_set_mesh_normals).  mesh_first: HostScene::mesh_first; mesh_smooth[m]: mesh m has corner
-    // normals in d_tri_normals (RenderParams::tri_normals), which is held while any mesh has
+    // normals in d_tri_attrs (RenderParams::tri_attrs), which is held while any mesh has
     std::vector<uint64_t> mesh_first;
     std::vector<unsigned char> mesh_smooth;
     std::vector<unsigned char> mesh_colored;  // vertex colours (flux_ctx_set_mesh_colors): mesh m has corner colours in the same table
-    flux::DevBuf<double> d_tri_normals;
+    flux::DevBuf<double> d_tri_attrs;
     flux::BvhInfo bvh{};
     int traversal = FLUX_TRAVERSE_BVH;
     int variant = FLUX_KERNEL_DEFAULT;

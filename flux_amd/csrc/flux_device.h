@@ -308,18 +308,18 @@ struct RenderParams {
     // depth was a load and its whole wait between the classification and the park, every pass.  (A copy, and the two fields where they
     // were: laying them side by side moved four other instantiations' scalar spills -- profiles/r16_plane_div/registers.txt.)
     alignas(8) int32_t depth_pair[2];
-    // extension: smooth meshes.  One record of kTriNormalDoubles doubles per DevTri slot, in leaf order as
+    // extension: smooth meshes.  One record of kTriAttrDoubles doubles per DevTri slot, in leaf order as
     // `tris`: the three corner normals {n0, n1, n2} of a triangle whose mesh has them (DevTri::smooth = 1), zeros otherwise.  nullptr:
     // no mesh of the context has normals -- no kernel then reads DevTri::smooth.  The shading step reads it (render_body.inc
     // tri_shading_normal), the traversal never.
     // extension: vertex colours.  The same record holds, in bytes 72..107, the three corner colours
     // {k0, k1, k2} as nine f32 of a triangle whose mesh has them (DevTri::colored = 1).  The table exists while any mesh has normals
     // or colours; a shaded hit on a triangle with either or both reads this one line.
-    const double *tri_normals;
+    const double *tri_attrs;
 };
-// doubles per record of RenderParams::tri_normals: nine used by the normals, nine f32 behind them by the colours, padded to one
+// doubles per record of RenderParams::tri_attrs: nine used by the normals, nine f32 behind them by the colours, padded to one
 // aligned 128-B line -- one more line per shaded hit
-constexpr size_t kTriNormalDoubles = 16;
+constexpr size_t kTriAttrDoubles = 16;
 // index of the first of the record's nine f32 corner colours, counted in floats: byte 72
 constexpr size_t kTriColorFloat0 = 18;
 // bytes per hit record of RenderParams::lobe_frame

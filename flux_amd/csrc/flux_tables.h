@@ -36,7 +36,7 @@ hipError_t generate_glossx_table(const double *gloss, size_t count, const double
 // The lobe frames of the scene's n_rec hit records (RenderParams::lobe_frame; `frec` on the device): out[k] = {b1, b2} of record k, zeros
 // for a sphere (render.hip: bit for bit the frame fast_bounce builds in the loop for a Matte hit of the record).  Asynchronous on `stream`.
 hipError_t generate_lobe_frame_table(const DevHitRec *frec, int n_rec, double *out, hipStream_t stream);
-// The corner-normal records (RenderParams::tri_normals) of ONE mesh, by the slot -> triangle map the device already holds (DevTri::id):
+// The corner-normal records (RenderParams::tri_attrs) of ONE mesh, by the slot -> triangle map the device already holds (DevTri::id):
 // every slot s < n_tris whose triangle k = tris[s].id - first_id lies in [0, count) gets table[s] = stage[k] (nine doubles of
 // [count][3][3], bytes 0..71 of the 128-B record) and DevTri::smooth = 1 -- or, with stage == nullptr, smooth = 0 and, where
 // `table` is not null, zeros in those bytes.  Other slots, and the record's other bytes, are not touched.  Asynchronous on `stream`.

@@ -253,7 +253,7 @@ __global__ void gather_tri_attribute_kernel(DevTri *__restrict__ tris, int n_tri
     const int k = tris[s].id - first_id;
     if (k < 0 || k >= count) return;
     if (table) {
-        V *o = reinterpret_cast<V *>(table + (size_t)s * kTriNormalDoubles) + (kColors ? kTriColorFloat0 : 0);
+        V *o = reinterpret_cast<V *>(table + (size_t)s * kTriAttrDoubles) + (kColors ? kTriColorFloat0 : 0);
         for (int j = 0; j < 9; j++) o[j] = stage ? stage[(size_t)k * 9 + j] : (V)0;
     }
     if (kColors) tris[s].colored = stage ? 1 : 0;

@@ -301,9 +301,9 @@ __device__ __forceinline__ bool tri_hit(const DevTri &T, const Ray &r, double &t
 // triangle's normal or material colour calls this: the bounce and the facing test (shade_hit_fast, shade_hit), the feature buffers
 // (first_hit_fields).
 // The product sits inside the per-lane `colored` branch, with a read of the triple of its own, and every other lane reads the
-// triple as it is behind it -- the stored normal's pattern.  So a context without a table (P.tri_normals == nullptr: a scalar branch)
+// triple as it is behind it -- the stored normal's pattern.  So a context without a table (P.tri_attrs == nullptr: a scalar branch)
 // runs the stored normal's and the triple's loads and nothing else: no product, no select.  (Multiplied in the caller under
-// `P.tri_normals != nullptr`, the compiler ran three products and six selects for every triangle hit and waited for the triple
+// `P.tri_attrs != nullptr`, the compiler ran three products and six selects for every triangle hit and waited for the triple
 // there: +1.6 % on configuration 5, which has no table.)  The coloured branch forms the triple's address from a copy of the index
 // the compiler cannot see through: with one address for both reads it was computed in front of the scalar branch, and the wait
 // for the triangle's material index with it -- ahead of the stored normal's loads instead of behind them.
@@ -312,7 +312,7 @@ __device__ __forceinline__ V3 tri_shading_normal(const RenderParams &P, const Ra
     const DevTri &T = P.tris[slot];
     bool flat = true, plain = true;
     V3 n;
-    if (P.tri_normals != nullptr) {
+    if (P.tri_attrs != nullptr) {
         const bool smooth = T.smooth != 0, colored = T.colored != 0;
         if (smooth || colored) {
             const V3 e1 = mk(T.e1x, T.e1y, T.e1z), e2 = mk(T.e2x, T.e2y, T.e2z);
@@ -327,8 +327,8 @@ __device__ __forceinline__ V3 tri_shading_normal(const RenderParams &P, const Ra
             const double u = dot(s, p) * inv;
             const double v = dot(d, cross(s, e1)) * inv;
             // uniform base + 32-bit byte offset (the slot count keeps slot * 128 below 2^32, as for the DevTri records)
-            const double *N = reinterpret_cast<const double *>(reinterpret_cast<const char *>(P.tri_normals) +
-                                                               (uint32_t)slot * (uint32_t)(kTriNormalDoubles * sizeof(double)));
+            const double *N = reinterpret_cast<const double *>(reinterpret_cast<const char *>(P.tri_attrs) +
+                                                               (uint32_t)slot * (uint32_t)(kTriAttrDoubles * sizeof(double)));
             if (smooth) {
                 const double w = (1.0 - u) - v;
                 const V3 m = mk((w * N[0] + u * N[3]) + v * N[6], (w * N[1] + u * N[4]) + v * N[7], (w * N[2] + u * N[5]) + v * N[8]);

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult, corner_colors, corner_normals, split_shapes
+from .scene import JobConfiguration, SceneData, SceneDesc, WorkUnit, WorkUnitResult, MESH_ATTRIBUTES, _corner_attribute, split_shapes
 
 STAT_NAMES = ("samples", "segments", "matte_bounces", "glossy_bounces", "specular_bounces",
               "emissive_hits", "misses", "depth_exhausted", "bvh_nodes", "tris_tested",
@@ -36,8 +36,7 @@ class Renderer:
         _lib.check(_lib.lib.flux_ctx_create_sets(C.byref(self._desc.desc), C.byref(cfg), C.c_uint64(self.seed),
                                                  self.device, self.set_share[0], self.set_share[1], C.byref(h)))
         self._h = h
-        _set_scene_normals(h, scene_data)
-        _set_scene_colors(h, scene_data)
+        _set_scene_attributes(h, scene_data)
         self._warn_if_routed()
 
     def _warn_if_routed(self):
@@ -107,11 +106,17 @@ class Renderer:
         rows = self.render_rows(unit.row_start, unit.row_end)
         return WorkUnitResult(work_unit=unit, rows=rows)
 
-    def render_rows(self, row_start: int, row_end: int) -> np.ndarray:
+    def _row_end(self, row_start, row_end):
+        """the last row of [row_start, row_end] inclusive (None: the frame's last), the range checked"""
+        if row_end is None:
+            row_end = self.height - 1
         if row_start < 0 or row_end < row_start:
             raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
-        n = row_end - row_start + 1
-        out = np.empty((n, self.width, 3), dtype=np.float64)
+        return row_end
+
+    def render_rows(self, row_start: int, row_end: int) -> np.ndarray:
+        row_end = self._row_end(row_start, row_end)
+        out = np.empty((row_end - row_start + 1, self.width, 3), dtype=np.float64)
         _lib.check(_lib.lib.flux_render_rows(self._handle(), row_start, row_end,
                                              out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
@@ -131,10 +136,7 @@ class Renderer:
     def render_aov(self, row_start: int = 0, row_end=None) -> np.ndarray:
         """Albedo, normal, depth and coverage of rows [row_start, row_end] inclusive (default: the frame), [rows, W, 8]:
         flux_render_aov_rows.  Channels: flux_amd.AOV_ALBEDO, AOV_NORMAL (slices), AOV_DEPTH, AOV_COVERAGE."""
-        if row_end is None:
-            row_end = self.height - 1
-        if row_start < 0 or row_end < row_start:
-            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        row_end = self._row_end(row_start, row_end)
         out = np.empty((row_end - row_start + 1, self.width, _lib.AOV_CHANNELS), dtype=np.float64)
         _lib.check(_lib.lib.flux_render_aov_rows(self._handle(), row_start, row_end, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
@@ -148,10 +150,7 @@ class Renderer:
     def render_aov_chain(self, max_chain: int = 0, row_start: int = 0, row_end=None) -> np.ndarray:
         """render_aov()'s buffers taken where each sample's chain of Reflective / Dielectric bounces ends, [rows, W, 8]:
         flux_render_aov_chain_rows.  max_chain: the most segments a chain has (0: max_trace_depth; 1 is render_aov() bit for bit)."""
-        if row_end is None:
-            row_end = self.height - 1
-        if row_start < 0 or row_end < row_start:
-            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        row_end = self._row_end(row_start, row_end)
         self._check_max_chain(max_chain)
         out = np.empty((row_end - row_start + 1, self.width, _lib.AOV_CHANNELS), dtype=np.float64)
         _lib.check(_lib.lib.flux_render_aov_chain_rows(self._handle(), row_start, row_end, max_chain,
@@ -175,10 +174,7 @@ class Renderer:
     def render_moments(self, row_start: int = 0, row_end=None) -> np.ndarray:
         """The frame and its measured variance for rows [row_start, row_end] inclusive (default: the frame), [rows, W, 8]:
         flux_render_moments_rows.  Channels: flux_amd.MOMENT_RGB (the frame), MOMENT_VAR, MOMENT_MEAN (unclamped), MOMENT_S2."""
-        if row_end is None:
-            row_end = self.height - 1
-        if row_start < 0 or row_end < row_start:
-            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        row_end = self._row_end(row_start, row_end)
         out = np.empty((row_end - row_start + 1, self.width, _lib.MOMENT_CHANNELS), dtype=np.float64)
         _lib.check(_lib.lib.flux_render_moments_rows(self._handle(), row_start, row_end, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
@@ -209,10 +205,7 @@ class Renderer:
         its mean and variance, so flux_amd.denoise_moments(moments, r.render_aov()) filters an adaptive frame with its per-pixel
         variance, and no further denoiser call exists.  With max_passes=1 the moments are render_moments() bit for bit.
         last_adaptive_info holds the call's rounds, pixel passes, samples and pixels that reached max_passes."""
-        if row_end is None:
-            row_end = self.height - 1
-        if row_start < 0 or row_end < row_start:
-            raise _lib.FluxError(_lib.E_INVALID, f"bad row range [{row_start},{row_end}]")
+        row_end = self._row_end(row_start, row_end)
         rows = row_end - row_start + 1
         mom = np.empty((rows, self.width, _lib.MOMENT_CHANNELS), dtype=np.float64)
         passes = np.empty((rows, self.width), dtype=np.uint32)
@@ -309,20 +302,19 @@ class Renderer:
     def set_mesh_normals(self, mesh_index: int, normals):
         """Extension: smooth shading for mesh `mesh_index` (in the order of the scene's meshes) -- `normals` as MeshData.normals,
         [vertices][3] or [triangles][3][3]; None: back to the facet normals (flux_ctx_set_mesh_normals)."""
-        meshes = split_shapes(self.scene_data)[1]
-        if normals is not None and 0 <= mesh_index < len(meshes):
-            import dataclasses
-            normals = corner_normals(dataclasses.replace(meshes[mesh_index], normals=normals), f"mesh {mesh_index}")
-        _set_mesh_normals(self._handle(), mesh_index, normals)
+        self._set_mesh_attribute("normals", mesh_index, normals)
 
     def set_mesh_colors(self, mesh_index: int, colors):
         """Extension: vertex colours for mesh `mesh_index` (in the order of the scene's meshes) -- `colors` as MeshData.colors,
         [vertices][3] or [triangles][3][3]; None: the material's colour alone again (flux_ctx_set_mesh_colors)."""
+        self._set_mesh_attribute("colors", mesh_index, colors)
+
+    def _set_mesh_attribute(self, attr, mesh_index, values):
         meshes = split_shapes(self.scene_data)[1]
-        if colors is not None and 0 <= mesh_index < len(meshes):
+        if values is not None and 0 <= mesh_index < len(meshes):
             import dataclasses
-            colors = corner_colors(dataclasses.replace(meshes[mesh_index], colors=colors), f"mesh {mesh_index}")
-        _set_mesh_colors(self._handle(), mesh_index, colors)
+            values = _corner_attribute(dataclasses.replace(meshes[mesh_index], **{attr: values}), attr, f"mesh {mesh_index}")
+        _set_mesh_attribute(self._handle(), attr, mesh_index, values)
 
     def bvh_info(self) -> dict:
         buf = (C.c_uint64 * _lib.BVH_INFO_WORDS)()
@@ -372,42 +364,25 @@ class Renderer:
         return _create_timing(self._handle())
 
 
-def _set_mesh_normals(handle, mesh_index, corners):
-    """flux_ctx_set_mesh_normals: `corners` [nt][3][3] float64, or None to clear"""
+def _set_mesh_attribute(handle, attr, mesh_index, corners):
+    """the attribute's call (MESH_ATTRIBUTES[attr].setter): `corners` [nt][3][3] float64, or None to clear"""
+    setter = getattr(_lib.lib, MESH_ATTRIBUTES[attr].setter)
     if mesh_index < 0:
         raise _lib.FluxError(_lib.E_INVALID, f"mesh index {mesh_index} out of range")
     if corners is None:
-        _lib.check(_lib.lib.flux_ctx_set_mesh_normals(handle, mesh_index, None, 0))
+        _lib.check(setter(handle, mesh_index, None, 0))
         return
     c = np.ascontiguousarray(corners, dtype=np.float64)
-    _lib.check(_lib.lib.flux_ctx_set_mesh_normals(handle, mesh_index, c.ctypes.data_as(C.POINTER(C.c_double)), c.size // 9))
+    _lib.check(setter(handle, mesh_index, c.ctypes.data_as(C.POINTER(C.c_double)), c.size // 9))
 
 
-def _set_scene_normals(handle, scene_data):
-    """the normals of every mesh of the scene that has them, on one context"""
-    for i, m in enumerate(split_shapes(scene_data)[1]):
-        corners = corner_normals(m, f"mesh {i}")
-        if corners is not None and len(corners):
-            _set_mesh_normals(handle, i, corners)
-
-
-def _set_mesh_colors(handle, mesh_index, corners):
-    """flux_ctx_set_mesh_colors: `corners` [nt][3][3] float64, or None to clear"""
-    if mesh_index < 0:
-        raise _lib.FluxError(_lib.E_INVALID, f"mesh index {mesh_index} out of range")
-    if corners is None:
-        _lib.check(_lib.lib.flux_ctx_set_mesh_colors(handle, mesh_index, None, 0))
-        return
-    c = np.ascontiguousarray(corners, dtype=np.float64)
-    _lib.check(_lib.lib.flux_ctx_set_mesh_colors(handle, mesh_index, c.ctypes.data_as(C.POINTER(C.c_double)), c.size // 9))
-
-
-def _set_scene_colors(handle, scene_data):
-    """the colours of every mesh of the scene that has them, on one context"""
-    for i, m in enumerate(split_shapes(scene_data)[1]):
-        corners = corner_colors(m, f"mesh {i}")
-        if corners is not None and len(corners):
-            _set_mesh_colors(handle, i, corners)
+def _set_scene_attributes(handle, scene_data):
+    """every attribute of every mesh of the scene that has it, on one context: the normals of all meshes, then the colours"""
+    for attr in MESH_ATTRIBUTES:
+        for i, m in enumerate(split_shapes(scene_data)[1]):
+            corners = _corner_attribute(m, attr, f"mesh {i}")
+            if corners is not None and len(corners):
+                _set_mesh_attribute(handle, attr, i, corners)
 
 
 def _create_timing(handle) -> dict:
@@ -433,11 +408,10 @@ class MultiRenderer:
         _lib.check(_lib.lib.flux_multi_create(C.byref(self._desc.desc), C.byref(cfg), C.c_uint64(self.seed), devs, len(self.devices),
                                               int(shard), C.byref(h)))
         self._h = h
-        for rank in range(len(self.devices)):  # smooth meshes: every rank's context gets the normals (flux_ctx_set_mesh_normals)
+        for rank in range(len(self.devices)):  # every rank's context gets the meshes' normals and colours
             ctx = C.c_void_p()
             _lib.check(_lib.lib.flux_multi_ctx(h, rank, C.byref(ctx)))
-            _set_scene_normals(ctx, scene_data)
-            _set_scene_colors(ctx, scene_data)   # vertex colours likewise (flux_ctx_set_mesh_colors)
+            _set_scene_attributes(ctx, scene_data)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -517,11 +491,10 @@ class _BorrowedRenderer(Renderer):
 def render_frame_multi(scene_data: SceneData, config: JobConfiguration, seed: int = 1, num_devices: int = 0,
                        shard: int = _lib.SHARD_AUTO) -> np.ndarray:
     """flux_render_frame_multi: create + render + destroy on the first `num_devices` devices (0 = all).  The one call has no place
-    for mesh normals (flux_ctx_set_mesh_normals works on a context), so a scene with a smooth mesh is refused: use MultiRenderer."""
-    if any(m.normals is not None for m in split_shapes(scene_data)[1]):
-        raise _lib.FluxError(_lib.E_INVALID, "render_frame_multi renders facet normals only; use MultiRenderer for a mesh with normals")
-    if any(m.colors is not None for m in split_shapes(scene_data)[1]):
-        raise _lib.FluxError(_lib.E_INVALID, "render_frame_multi has no place for vertex colours; use MultiRenderer for a mesh with colors")
+    for mesh attributes (their calls work on a context), so a scene with a smooth or coloured mesh is refused: use MultiRenderer."""
+    for attr, row in MESH_ATTRIBUTES.items():
+        if any(getattr(m, attr) is not None for m in split_shapes(scene_data)[1]):
+            raise _lib.FluxError(_lib.E_INVALID, row.multi_refusal)
     desc = SceneDesc(scene_data)
     cfg = _lib.FluxJobCfg(config.sample_root, config.max_trace_depth, config.rows_per_work_unit)
     out = np.empty((scene_data.output_settings.image_height, scene_data.output_settings.image_width, 3), dtype=np.float64)

@@ -435,78 +435,88 @@ def mesh_from_yaml(tag, b, what):
     if t.size and (t.min() < 0 or t.max() >= len(v)):
         raise SceneError(f"{w}: triangle index out of range (have {len(v)} vertices)")
     mesh = MeshData(v, t.astype(np.uint32), mat)
-    if b.get("normals") is not None:
-        nm = b["normals"]
-        if not isinstance(nm, list) or len(nm) != len(v):
-            raise SceneError(f"{w}.normals: expected one [x,y,z] per vertex ({len(v)}), got "
-                             f"{len(nm) if isinstance(nm, list) else repr(nm)}")
-        mesh.normals = np.array([_vec3(x, f"{w}.normals[{i}]") for i, x in enumerate(nm)], dtype=np.float64).reshape(-1, 3)
-        corner_normals(mesh, w)  # (a zero or non-finite normal is refused where the scene is loaded)
-    if b.get("colors") is not None:
-        cl = b["colors"]
-        if not isinstance(cl, list) or len(cl) != len(v):
-            raise SceneError(f"{w}.colors: expected one [r,g,b] per vertex ({len(v)}), got "
-                             f"{len(cl) if isinstance(cl, list) else repr(cl)}")
-        mesh.colors = np.array([_vec3(x, f"{w}.colors[{i}]") for i, x in enumerate(cl)], dtype=np.float64).reshape(-1, 3)
-        corner_colors(mesh, w)  # (a component outside [0, FLT_MAX] is refused where the scene is loaded)
+    for attr, row in MESH_ATTRIBUTES.items():
+        if b.get(attr) is not None:
+            x = b[attr]
+            if not isinstance(x, list) or len(x) != len(v):
+                raise SceneError(f"{w}.{attr}: expected one {row.entry} per vertex ({len(v)}), got "
+                                 f"{len(x) if isinstance(x, list) else repr(x)}")
+            setattr(mesh, attr, np.array([_vec3(e, f"{w}.{attr}[{i}]") for i, e in enumerate(x)], dtype=np.float64).reshape(-1, 3))
+            _corner_attribute(mesh, attr, w)  # (a value the library would refuse is refused where the scene is loaded)
     return mesh
 
 
-def corner_normals(mesh, what="mesh"):
-    """`mesh.normals` in the layout of flux_ctx_set_mesh_normals, float64 [nt][3 corners][3] (per-vertex normals expanded through
-    `triangles`; not normalised: the library does that), or None for a mesh without normals.  SceneError for a wrong count, a
-    non-numeric entry, or a normal that is not finite with a finite length > 0."""
+def _bad_normals(out):
     import numpy as np
-    if mesh.normals is None:
+    with np.errstate(over="ignore", invalid="ignore"):
+        nn = (out[..., 0] * out[..., 0] + out[..., 1] * out[..., 1]) + out[..., 2] * out[..., 2]
+    return ~(np.isfinite(out).all(axis=-1) & np.isfinite(nn) & (nn > 0.0))
+
+
+def _bad_colors(out):
+    import numpy as np
+    with np.errstate(invalid="ignore"):
+        return ~((out >= 0.0) & (out <= float(np.finfo(np.float32).max)))
+
+
+@dataclass(frozen=True)
+class _MeshAttribute:
+    setter: str  # the library's call (include/flux_abi.h)
+    entry: str  # one YAML entry
+    bad: object  # corners [nt][3][3] -> the mask of the refused corners [nt][3] or components [nt][3][3]
+    refusal: object  # (corners, the first refused index) -> the message behind "<what>.<field>: "
+    multi_refusal: str  # render_frame_multi's, which has no context to set the attribute on
+
+
+# The per-corner attributes of a mesh, by MeshData field = YAML key.  A third one adds a row.
+MESH_ATTRIBUTES = {
+    "normals": _MeshAttribute(
+        "flux_ctx_set_mesh_normals", "[x,y,z]", _bad_normals,
+        lambda out, i: f"triangle {i[0]}, corner {i[1]}: normal {tuple(float(x) for x in out[tuple(i)])} must be finite with a finite length > 0",
+        "render_frame_multi renders facet normals only; use MultiRenderer for a mesh with normals"),
+    "colors": _MeshAttribute(
+        "flux_ctx_set_mesh_colors", "[r,g,b]", _bad_colors,
+        lambda out, i: f"triangle {i[0]}, corner {i[1]}, channel {i[2]}: component {float(out[tuple(i)])!r} must lie in [0, FLT_MAX]",
+        "render_frame_multi has no place for vertex colours; use MultiRenderer for a mesh with colors"),
+}
+
+
+def _corner_attribute(mesh, attr, what):
+    """`mesh.<attr>` in the layout of the attribute's call, float64 [nt][3 corners][3] (per-vertex values expanded through `triangles`),
+    or None for a mesh without the attribute.  SceneError for a wrong shape, a non-numeric entry, or a value the call would refuse."""
+    import numpy as np
+    given = getattr(mesh, attr)
+    if given is None:
         return None
     t = np.asarray(mesh.triangles, dtype=np.int64).reshape(-1, 3)
     nv = len(np.asarray(mesh.vertices).reshape(-1, 3))
     try:
-        nm = np.asarray(mesh.normals, dtype=np.float64)
+        a = np.asarray(given, dtype=np.float64)
     except (TypeError, ValueError):
-        raise SceneError(f"{what}.normals: expected numbers, got {mesh.normals!r}")
-    if nm.shape == (len(t), 3, 3):
-        out = nm
-    elif nm.shape == (nv, 3):
-        out = nm[t]
+        raise SceneError(f"{what}.{attr}: expected numbers, got {given!r}")
+    if a.shape == (len(t), 3, 3):
+        out = a
+    elif a.shape == (nv, 3):
+        out = a[t]
     else:
-        raise SceneError(f"{what}.normals: expected [{nv}][3] (per vertex) or [{len(t)}][3][3] (per corner), got shape {nm.shape}")
+        raise SceneError(f"{what}.{attr}: expected [{nv}][3] (per vertex) or [{len(t)}][3][3] (per corner), got shape {a.shape}")
     out = np.ascontiguousarray(out, dtype=np.float64).reshape(len(t), 3, 3)
-    with np.errstate(over="ignore", invalid="ignore"):
-        nn = (out[..., 0] * out[..., 0] + out[..., 1] * out[..., 1]) + out[..., 2] * out[..., 2]
-    bad = ~(np.isfinite(out).all(axis=-1) & np.isfinite(nn) & (nn > 0.0))
+    bad = MESH_ATTRIBUTES[attr].bad(out)
     if bad.any():
-        k, c = np.argwhere(bad)[0]
-        raise SceneError(f"{what}.normals: triangle {k}, corner {c}: normal {tuple(float(x) for x in out[k, c])} must be finite with a finite length > 0")
+        raise SceneError(f"{what}.{attr}: " + MESH_ATTRIBUTES[attr].refusal(out, np.argwhere(bad)[0]))
     return out
+
+
+def corner_normals(mesh, what="mesh"):
+    """`mesh.normals` as _corner_attribute gives it (not normalised: the library does that); refused: a normal that is not finite
+    with a finite length > 0."""
+    return _corner_attribute(mesh, "normals", what)
 
 
 def corner_colors(mesh, what="mesh"):
-    """`mesh.colors` in the layout of flux_ctx_set_mesh_colors, float64 [nt][3 corners][3 rgb] (per-vertex colours expanded through
-    `triangles`; not rounded to f32: the library does that), or None for a mesh without colours.  SceneError for a wrong shape, a
-    non-numeric entry, or a component outside [0, FLT_MAX] (a NaN included)."""
-    import numpy as np
-    if mesh.colors is None:
-        return None
-    t = np.asarray(mesh.triangles, dtype=np.int64).reshape(-1, 3)
-    nv = len(np.asarray(mesh.vertices).reshape(-1, 3))
-    try:
-        cl = np.asarray(mesh.colors, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise SceneError(f"{what}.colors: expected numbers, got {mesh.colors!r}")
-    if cl.shape == (len(t), 3, 3):
-        out = cl
-    elif cl.shape == (nv, 3):
-        out = cl[t]
-    else:
-        raise SceneError(f"{what}.colors: expected [{nv}][3] (per vertex) or [{len(t)}][3][3] (per corner), got shape {cl.shape}")
-    out = np.ascontiguousarray(out, dtype=np.float64).reshape(len(t), 3, 3)
-    with np.errstate(invalid="ignore"):
-        bad = ~((out >= 0.0) & (out <= float(np.finfo(np.float32).max)))
-    if bad.any():
-        k, c, ch = np.argwhere(bad)[0]
-        raise SceneError(f"{what}.colors: triangle {k}, corner {c}, channel {ch}: component {float(out[k, c, ch])!r} must lie in [0, FLT_MAX]")
-    return out
+    """`mesh.colors` as _corner_attribute gives it (not rounded to f32: the library does that); refused: a component outside
+    [0, FLT_MAX] (a NaN included)."""
+    return _corner_attribute(mesh, "colors", what)
 
 
 def split_shapes(sd: SceneData):

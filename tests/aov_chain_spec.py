@@ -70,7 +70,8 @@ def _chain_quiet(spec, K):
     for k in range(1, K + 1):
         if not len(live):
             break
-        shape, t, n_hit, pt, _, _ = spec._nearest(o[live], d[live], margins)
+        shape, t, n_hit, pt, _, tri = spec._nearest(o[live], d[live], margins)
+        chosen = spec._materials(shape, o[live], d[live], tri, k)
         rays, fs, scales = [], [], []
         for j, ray in enumerate(live):
             length[ray] = k
@@ -78,7 +79,7 @@ def _chain_quiet(spec, K):
             if si < 0:
                 end[ray] = spec.background
                 continue
-            mat, n, dr = spec.sd.shapes[si].material, n_hit[j], d[ray]
+            mat, n, dr = chosen[j][0], n_hit[j], d[ray]
             if _kind(mat) in DELTA and k < K:
                 if _kind(mat) == "DielectricData":
                     u = spec._hemi[set_of[ray], k - 1, idx_of[ray], 2]
@@ -93,7 +94,7 @@ def _chain_quiet(spec, K):
                     wi, scale = wi[0], 1.0
                 else:  # materials.rs:56-72
                     out.mirror_bounces += 1
-                    mk, mp = spec._params[si]
+                    mk, mp = chosen[j][1]
                     wi, pdf, f = oracle_mod.sample_f(mk, mp, n, dr * -1.0, spec._hemi[set_of[ray], k - 1, idx_of[ray]],
                                                      spec._pixel[set_of[ray], idx_of[ray]])
                     scale = path_spec._dot(n, wi) / np.float64(pdf)

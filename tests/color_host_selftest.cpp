@@ -1,4 +1,4 @@
-// color_host_selftest.cpp -- the host half of flux_ctx_set_mesh_colors (flux_amd/csrc/flux_color.h), CPU only and linked against
+// color_host_selftest.cpp -- the host half of flux_ctx_set_mesh_colors (flux_amd/csrc/flux_mesh_attr.h), CPU only and linked against
 // nothing: the call's refusals, each with its message, and the f32 rounding of a fixed set of corner colours printed at full
 // precision; tests/test_vertex_colors.py recomputes the values with tests/color_spec.py.  Two meshes, of 3 and 2 triangles.
 #include <cfloat>
@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "../flux_amd/csrc/flux_color.h"
+#include "../flux_amd/csrc/flux_mesh_attr.h"
 
 #define CHECK(c)                                                       \
     do {                                                               \

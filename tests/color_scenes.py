@@ -93,33 +93,15 @@ def plain_twin(sd):
 
 
 def debug_rays(material):
-    """smooth_scenes.debug_rays' construction on this scene's meshes, with this file's seeds"""
+    """smooth_scenes.rays_at_meshes on this scene's meshes, with this file's seeds"""
     import flux_amd as flux
-    import smooth_spec
-    n = smooth_scenes.DEBUG_RAYS
-    sd = scene(flux, material)
-    rng = np.random.default_rng(RESEEDED.get((material, "rays"), SEED_BASE + 500 + MESH_MATERIALS.index(material)))
-    v0, e1, e2 = (np.concatenate(x) for x in zip(*[smooth_spec.mesh_triangles(s)[:3] for s in sd.shapes[3:]]))
-    k = rng.integers(0, len(v0), n)
-    u = rng.uniform(0.02, 0.98, n)
-    v = rng.uniform(0.02, 0.98, n) * (1.0 - u)
-    target = v0[k] + u[:, None] * e1[k] + v[:, None] * e2[k]
-    away = rng.normal(size=(n, 3))
-    away[:, 1] = np.abs(away[:, 1]) * 0.7 + 0.1
-    o = target + away / np.linalg.norm(away, axis=1)[:, None] * rng.uniform(4.0, 9.0, (n, 1))
-    d = target - o
-    return o, d / np.linalg.norm(d, axis=1)[:, None], int(rng.integers(0, WIDTH)), int(rng.integers(0, 4))
+    return smooth_scenes.rays_at_meshes(scene(flux, material), RESEEDED.get((material, "rays"), SEED_BASE + 500 + MESH_MATERIALS.index(material)))
 
 
 @functools.lru_cache(maxsize=None)
 def debug_reference(material):
-    """(o, d, set, index, radiance [m, 3], first-hit t [m] -- inf on a miss --, margins) of debug_rays through the root-2 job's
-    ColorPathSpec"""
-    _, _, spec = reference(material, 2)
-    o, d, set_index, index = debug_rays(material)
-    rad, _, margins, _, first = spec._trace(o, d, np.full(len(o), set_index), np.full(len(o), index))
-    t = np.where(first[0] >= 0, first[1], np.inf)
-    return o, d, set_index, index, rad, t, margins
+    """smooth_scenes.traced: debug_rays through the root-2 job's ColorPathSpec"""
+    return smooth_scenes.traced(reference(material, 2)[2], debug_rays(material))
 
 
 # the jobs the GPU tests render against the reference: every material at root 2, the Matte and the glass scene at every root

@@ -182,9 +182,15 @@ class PathSpec:
 
     # ---- Scene::shade ---------------------------------------------------------------------------------------------------------
 
+    def _materials(self, shape, o, d, tri, depth):
+        """Where the material of a hit is chosen, for this class and for the loops of aov_chain_spec: for the rays o, d [m, 3] of
+        segment `depth` with nearest hits `shape` [m] (`tri` [m]: on a triangle), per ray (the shape's material, its cached
+        material_params -- None for a Dielectric, which has none), or None for a miss.  A subclass may put another material on a hit."""
+        return [None if si < 0 else (self.sd.shapes[si].material, self._params.get(int(si))) for si in shape]
+
     def _trace(self, o, d, sets, idx):
         """The paths of primary rays o, d [k, 3] of sample sets `sets` and sample indices `idx`: (radiance [k, 3], statistics,
-        margins, classes, first hits)."""
+        margins, classes, first hits: shape, t, normal and _materials' choice)."""
         with np.errstate(all="ignore"):
             return self._trace_quiet(np.array(o, dtype=np.float64), np.array(d, dtype=np.float64), sets, idx)
 
@@ -205,8 +211,9 @@ class PathSpec:
                 break
             st["segments"] += len(live)
             shape, t, nrm, pt, face, tri = self._nearest(o[live], d[live], margins)
+            chosen = self._materials(shape, o[live], d[live], tri, depth)
             if depth == 1:
-                first = (shape.copy(), t.copy(), nrm.copy())
+                first = (shape.copy(), t.copy(), nrm.copy(), chosen)
             rays, fs, scales = [], [], []
             for j, ray in enumerate(live):
                 si = int(shape[j])
@@ -215,7 +222,7 @@ class PathSpec:
                     end[ray] = self.background
                     continue
                 s, n, dr = self.sd.shapes[si], nrm[j], d[ray]
-                mat = s.material
+                mat = chosen[j][0]
                 classes[_kind(s)[:-4] + "/" + _kind(mat)[:-4]] += 1
                 if face[j] >= 0:
                     classes[f"box face {int(face[j])}"] += 1
@@ -243,7 +250,7 @@ class PathSpec:
                         f = np.asarray(mat.transmit_color, dtype=np.float64)
                     wi, scale = wi[0], 1.0
                 else:  # materials.rs:18-34, 56-72
-                    mk, mp = self._params[si]
+                    mk, mp = chosen[j][1]
                     st[{oracle_mod.MAT_MATTE: "matte_bounces", oracle_mod.MAT_GLOSSY: "glossy_bounces",
                         oracle_mod.MAT_REFLECTIVE: "specular_bounces"}[mk]] += 1
                     sq = self._pixel[sets[ray], idx[ray]]
@@ -300,6 +307,7 @@ class PathSpec:
         self.sample_radiance = rad.reshape(H, W, N, 3)
         self.primary = (o, d, sets)
         self._first = (first[0].reshape(H, W, N), first[1].reshape(H, W, N), first[2].reshape(H, W, N, 3))
+        self._first_materials = first[3]
         with np.errstate(all="ignore"):
             color = np.zeros((H, W, 3))
             for i in range(N):
@@ -319,6 +327,11 @@ class PathSpec:
         self.frame()
         return self._first
 
+    def first_materials(self):
+        """Per sample, flat in [H, W, N] order: what _materials chose for the depth-1 hit, None for a miss."""
+        self.frame()
+        return self._first_materials
+
     def min_margin(self):
         self.frame()
         return min(self.margins.values())
@@ -328,6 +341,7 @@ def aov_buffers(spec):
     """The first-hit feature buffers of a PathSpec, built with aov_spec's albedo and _finish."""
     import aov_spec
     shape, t, nrm = spec.first_hits()
+    chosen = spec.first_materials()
     _, d, _ = spec.primary
     H, W, N = shape.shape
     alb, nsum, tsum, hits = np.zeros((H, W, 3)), np.zeros((H, W, 3)), np.zeros((H, W)), np.zeros((H, W))
@@ -338,7 +352,7 @@ def aov_buffers(spec):
                 if si < 0:
                     alb[r, c] += spec.background
                     continue
-                alb[r, c] += aov_spec.albedo(spec.sd.shapes[si].material, nrm[r, c, i], d[r, c, i])
+                alb[r, c] += aov_spec.albedo(chosen[(r * W + c) * N + i][0], nrm[r, c, i], d[r, c, i])
                 nsum[r, c] += nrm[r, c, i]
                 tsum[r, c] += t[r, c, i]
                 hits[r, c] += 1

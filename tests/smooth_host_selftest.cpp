@@ -1,4 +1,4 @@
-// smooth_host_selftest.cpp -- the host half of flux_ctx_set_mesh_normals (flux_amd/csrc/flux_smooth.h), CPU only and linked against
+// smooth_host_selftest.cpp -- the host half of flux_ctx_set_mesh_normals (flux_amd/csrc/flux_mesh_attr.h), CPU only and linked against
 // nothing: the call's refusals, each with its message, and the normalisation of a fixed set of corner normals printed at full
 // precision; tests/test_smooth_normals.py recomputes the values with tests/smooth_spec.py.  Two meshes, of 3 and 2 triangles.
 #include <cmath>
@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "../flux_amd/csrc/flux_smooth.h"
+#include "../flux_amd/csrc/flux_mesh_attr.h"
 
 #define CHECK(c)                                                       \
     do {                                                               \

@@ -103,13 +103,11 @@ def c_client_scene(flux):
 DEBUG_RAYS = 2000
 
 
-def debug_rays(material):
-    """DEBUG_RAYS unit rays from a shell around the scene towards random points of random triangles of the three meshes, and the
-    sample set and index their paths draw from"""
-    import flux_amd as flux
+def rays_at_meshes(sd, seed):
+    """DEBUG_RAYS unit rays from a shell around the scene towards random points of random triangles of the three meshes of `sd`, and
+    the sample set and index their paths draw from"""
     import smooth_spec
-    sd = scene(flux, material)
-    rng = np.random.default_rng(RESEEDED.get((material, "rays"), SEED_BASE + 500 + MESH_MATERIALS.index(material)))
+    rng = np.random.default_rng(seed)
     v0, e1, e2 = (np.concatenate(x) for x in zip(*[smooth_spec.mesh_triangles(s)[:3] for s in sd.shapes[3:]]))
     k = rng.integers(0, len(v0), DEBUG_RAYS)
     u = rng.uniform(0.02, 0.98, DEBUG_RAYS)
@@ -122,15 +120,23 @@ def debug_rays(material):
     return o, d / np.linalg.norm(d, axis=1)[:, None], int(rng.integers(0, WIDTH)), int(rng.integers(0, 4))
 
 
-@functools.lru_cache(maxsize=None)
-def debug_reference(material):
-    """(o, d, set, index, radiance [m, 3], first-hit t [m] -- inf on a miss --, margins) of debug_rays through the root-2 job's
-    SmoothPathSpec"""
-    _, _, spec = reference(material, 2)
-    o, d, set_index, index = debug_rays(material)
+def debug_rays(material):
+    import flux_amd as flux
+    return rays_at_meshes(scene(flux, material), RESEEDED.get((material, "rays"), SEED_BASE + 500 + MESH_MATERIALS.index(material)))
+
+
+def traced(spec, rays):
+    """(o, d, set, index, radiance [m, 3], first-hit t [m] -- inf on a miss --, margins) of `rays` (rays_at_meshes) through `spec`"""
+    o, d, set_index, index = rays
     rad, _, margins, _, first = spec._trace(o, d, np.full(len(o), set_index), np.full(len(o), index))
     t = np.where(first[0] >= 0, first[1], np.inf)
     return o, d, set_index, index, rad, t, margins
+
+
+@functools.lru_cache(maxsize=None)
+def debug_reference(material):
+    """traced: debug_rays through the root-2 job's SmoothPathSpec"""
+    return traced(reference(material, 2)[2], debug_rays(material))
 
 
 # the jobs the GPU tests render against the reference: every material at root 2, the Matte and the glass scene at every root

@@ -5,42 +5,32 @@ with normals (quads that fuse into two-triangle leaf records, pole triangles tha
 WITHOUT normals, an analytic sphere and plane, an inverted Emissive environment; sample roots 2, 8 and 16.
 tests/test_smooth_path_spec.py shows that no decision of these scenes lies within 1e-9 of its threshold, so nothing is excluded."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import aov_chain_spec
 import aov_spec
-import extension_checks
+import mesh_attr_checks as checks
 import path_spec
 import smooth_scenes
 import test_gpu_ext_fuzz as fuzz
-from conftest import ROOT
+from mesh_attr_checks import configurations as _configurations, everything as _everything, traversals as _traversals
 
 pytestmark = pytest.mark.gpu
 
 NORMAL_TOL = 1e-12   # the issue's: a few ulp per sample over at most 256 samples; a swapped or dropped corner moves a sample by > 0.1
-
-
-def _traversals(flux):
-    return (flux._lib.TRAVERSE_BVH, flux._lib.TRAVERSE_BRUTE, flux._lib.TRAVERSE_BVH_BINARY)
+TIGHT = ((aov_spec.NORMAL, NORMAL_TOL),)
 
 
 def _renderer(flux, sd, root, seed):
-    return flux.Renderer(sd, flux.JobConfiguration(root, smooth_scenes.DEPTH, 50), seed=seed)
+    return checks.renderer(flux, sd, root, seed, smooth_scenes.DEPTH)
 
 
 # ---- 1. the feature buffers -----------------------------------------------------------------------------------------------------
 
 def _assert_aov(got, want, label):
-    err = aov_spec.channel_errors(got, want)
-    print(f"smooth aov {label}: max |gpu - spec| per channel = " + " ".join(f"{e:.2e}" for e in err))
-    assert got.shape == want.shape
-    assert np.all(err[aov_spec.NORMAL] <= NORMAL_TOL), (label, err)
-    assert np.all(err <= aov_spec.TOL), (label, err)
-    assert np.array_equal(got[..., aov_spec.COVERAGE], want[..., aov_spec.COVERAGE]), label
+    checks.assert_aov(got, want, f"smooth aov {label}", TIGHT)
 
 
 @pytest.mark.parametrize("material,root", [("Matte", 2), ("Matte", 8), ("Matte", 16), ("Dielectric", 2), ("Emissive", 2)])
@@ -61,17 +51,10 @@ def test_feature_buffers(flux, material, root):
 
 # ---- 2. the paths ---------------------------------------------------------------------------------------------------------------
 
-def _configurations(flux):
-    return list(itertools.product((flux.MATH_FAST, flux.MATH_STRICT), (flux.KERNEL_DEFAULT, flux.KERNEL_STATIC, flux.KERNEL_REFILL),
-                                  _traversals(flux)))
-
-
 def _frames(flux, r):
     out = {}
     for math, kernel, trav in _configurations(flux):
-        r.set_math(math)
-        r.set_kernel(kernel)
-        r.set_traversal(trav)
+        checks.configure(r, math, kernel, trav)
         out[(math, kernel, trav)] = r.render_frame()
     return out
 
@@ -84,9 +67,7 @@ def test_frames_against_the_path_reference(flux, material, root):
     worst, smooth = {}, {}
     with _renderer(flux, sd, root, seed) as r:
         for math, kernel, trav in _configurations(flux):
-            r.set_math(math)
-            r.set_kernel(kernel)
-            r.set_traversal(trav)
+            checks.configure(r, math, kernel, trav)
             smooth[(math, kernel, trav)], _ = fuzz.check_run(flux, r, spec, f"{material} root {root} math {math} kernel {kernel} traversal {trav}",
                                                              True, worst)
     print(f"smooth {material} root {root}: max |gpu - reference| " + ", ".join(f"{k} {v:.3e}" for k, v in sorted(worst.items())))
@@ -105,29 +86,10 @@ def test_frames_against_the_path_reference(flux, material, root):
 def test_debug_shade_against_the_path_reference(flux, material):
     """2 000 rays per material (10^4 in all) aimed at points of the three meshes: radiance within check_run's tolerances, t equal to
     rounding."""
-    sd, seed, _ = smooth_scenes.reference(material, 2)
-    o, d, set_index, index, rad, t_ref, _ = smooth_scenes.debug_reference(material)
-    with _renderer(flux, sd, 2, seed) as r:
-        for math, trav in itertools.product((flux.MATH_FAST, flux.MATH_STRICT), _traversals(flux)):
-            r.set_math(math)
-            r.set_traversal(trav)
-            rgb, hit, t = r.debug_shade(o, d, 1, set_index, index)
-            assert np.array_equal(hit >= 0, np.isfinite(t_ref))
-            on = hit >= 0
-            assert np.max(np.abs(t[on] - t_ref[on]) / t_ref[on]) <= 1e-12
-            err = np.abs(rgb - rad)
-            print(f"smooth debug_shade {material} math {math} traversal {trav}: max {err.max():.3e}, 99.9th percentile {np.percentile(err, 99.9):.3e}")
-            assert np.isfinite(rgb).all() and err.max() < fuzz.TOL and np.percentile(err, 99.9) < fuzz.TOL_TIGHT
+    checks.debug_shade(flux, smooth_scenes, "smooth", material)
 
 
 # ---- 3. the flat path is untouched ------------------------------------------------------------------------------------------------
-
-def _everything(r):
-    r.enable_stats(True)
-    r.stats(reset=True)
-    frame = r.render_frame()
-    return frame, r.stats(), r.render_aov(), r.render_aov_chain(), r.render_moments()
-
 
 @pytest.mark.parametrize("root", [2, 8])
 def test_set_and_cleared_equals_never_set(flux, root):
@@ -186,89 +148,33 @@ def test_flat_mesh_pixels_do_not_see_the_other_meshes_normals(flux):
 
 @pytest.mark.parametrize("root", [2, 8])
 def test_every_consumer_sees_the_new_normal(flux, root):
-    sd, seed, _ = smooth_scenes.reference("Matte", 2)
-    with _renderer(flux, sd, root, seed) as r:
-        r.set_kernel(flux.KERNEL_STATIC)   # channels 0..2 are the static kernel's frame bit for bit (tests/test_gpu_moments.py)
-        frame, mom = r.render_frame(), r.render_moments()
-        assert mom[..., :3].tobytes() == frame.tobytes()
-        r.set_kernel(flux.KERNEL_DEFAULT)
-        got, passes = r.render_adaptive(threshold=0.0, max_passes=1)
-        assert got.tobytes() == mom.tobytes() and np.all(passes == 1)
-        assert np.array_equal(r.render_denoised(variance="measured"), flux.denoise_moments(mom, r.render_aov()), equal_nan=True)
-        smooth_aov = r.render_aov()
-    if root == 2:
-        with _renderer(flux, smooth_scenes.flat_twin(sd), root, seed) as f:
-            flat_aov = f.render_aov()
-        ball = np.zeros((smooth_scenes.HEIGHT, smooth_scenes.WIDTH), bool)
-        shape, _, _ = smooth_scenes.reference("Matte", 2)[2].first_hits()
-        ball |= (shape == 3).all(axis=2)
-        assert ball.any()
-        delta = np.abs(smooth_aov[..., aov_spec.NORMAL] - flat_aov[..., aov_spec.NORMAL])[ball]
-        print(f"smooth against flat normal buffer on the sphere: max {delta.max():.3f}")
-        assert delta.max() > 0.05   # the guides really change
+    checks.every_consumer(flux, smooth_scenes, smooth_scenes.flat_twin, root, aov_spec.NORMAL, 3, 0.05,
+                          "smooth against flat normal buffer on the sphere")
 
 
 # ---- 5. shares ------------------------------------------------------------------------------------------------------------------
 
 def test_shares_give_the_renderers_frame(flux):
-    sd, seed, _ = smooth_scenes.reference("Glossy", 2)
-    cfg = flux.JobConfiguration(8, smooth_scenes.DEPTH, 50)
-    with flux.Renderer(sd, cfg, seed=seed) as r:
-        frame = r.render_frame()
-        for world in (2, 3):
-            assert np.array_equal(extension_checks.set_sharded_frame(flux, r, world).numpy(), frame)
-        for step in (1, 4):
-            assert np.array_equal(extension_checks.row_tiles(r, step), frame)
-    for G, mode, got in extension_checks.loopback_frames(flux, sd, cfg, seed, (2, 3), (flux.SHARD_SETS, flux.SHARD_ROWS)):
-        assert np.array_equal(got, frame), (G, mode)
-    with flux.Renderer(smooth_scenes.flat_twin(sd), cfg, seed=seed) as f:
-        assert not np.array_equal(f.render_frame(), frame)
+    checks.shares(flux, smooth_scenes, smooth_scenes.flat_twin)
 
 
 # ---- 6. the C ABI from plain C --------------------------------------------------------------------------------------------------
 
-def _fnv1a(data):
-    h = 1469598103934665603
-    for b in data:
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
 def test_c_client_sets_normals_and_is_refused_as_the_header_says(flux, tmp_path):
-    exe = str(tmp_path / "smooth_c_client")
-    subprocess.run(["gcc", "-std=c99", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "smooth_c_client.c"), "-o", exe, "-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-lm",
-                    "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"), "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    p = subprocess.run([exe, "8", "11"], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stderr + p.stdout
-    lines = dict(line.split(" ", 1) for line in p.stdout.splitlines())
-    assert lines["refusals"] == "ok"
-    sd = smooth_scenes.c_client_scene(flux)
-    with flux.Renderer(sd, flux.JobConfiguration(8, 4, 50), seed=11) as r:
-        smooth = r.render_frame()
-    with flux.Renderer(smooth_scenes.flat_twin(sd), flux.JobConfiguration(8, 4, 50), seed=11) as r:
-        flat = r.render_frame()
-    assert lines["smooth"] == f"{_fnv1a(smooth.tobytes()):016x}"
-    assert lines["flat"] == lines["cleared"] == f"{_fnv1a(flat.tobytes()):016x}"
-    assert lines["smooth"] != lines["flat"]
+    checks.c_client(flux, tmp_path, "smooth_c_client", smooth_scenes, smooth_scenes.flat_twin, "flat", "smooth")
 
 
 def test_refusals_on_a_live_context_leave_it_unchanged(flux):
     sd, seed, _ = smooth_scenes.reference("Matte", 2)
-    lib, E = flux._lib.lib, flux._lib.E_INVALID
     with _renderer(flux, sd, 2, seed) as r:
         frame, aov, size = r.render_frame(), r.render_aov(), r.device_bytes()
         good = np.tile(np.array([0.0, 1.0, 0.0]), (80, 3, 1))
-        ptr = lambda a: a.ctypes.data_as(flux._lib.C.POINTER(flux._lib.C.c_double))  # noqa: E731
-        for mesh, arr, count, needle in ((3, good, 80, "mesh 3 out of range (3 meshes)"), (0, good, 79, "mesh 0 has 80 triangles, got normals for 79"),
-                                         (1, good, 80, "mesh 1 has 2 triangles"), (0, None, 80, "null pointer")):
-            assert lib.flux_ctx_set_mesh_normals(r._handle(), mesh, None if arr is None else ptr(arr), count) == E
-            assert needle in flux._lib.last_error(), flux._lib.last_error()
+        refusal = checks.common_refusals(flux, r, "normals", good)
         for value, where in ((0.0, (17, 2)), (np.nan, (0, 0)), (np.inf, (79, 1))):
             bad = good.copy()
             bad[where] = value
-            assert lib.flux_ctx_set_mesh_normals(r._handle(), 0, ptr(bad), 80) == E
-            assert f"mesh 0, triangle {where[0]}, corner {where[1]}" in flux._lib.last_error(), flux._lib.last_error()
+            message = refusal(0, bad, 80)
+            assert f"mesh 0, triangle {where[0]}, corner {where[1]}" in message, message
         with pytest.raises(flux.SceneError):
             r.set_mesh_normals(0, np.zeros((42, 3)))
         with pytest.raises(flux.FluxError):
@@ -289,9 +195,7 @@ def test_launch_plan_and_device_bytes(flux, root):
     with _renderer(flux, sd, root, seed) as r, _renderer(flux, smooth_scenes.flat_twin(sd), root, seed) as f:
         for math, kernel, trav in _configurations(flux):
             for x in (r, f):
-                x.set_math(math)
-                x.set_kernel(kernel)
-                x.set_traversal(trav)
+                checks.configure(x, math, kernel, trav)
             # words 0-6 equal; word 7 too: no instantiation of its own (a wave-uniform branch on the table pointer), so no flag bit
             assert r.launch_plan(flags=True) == f.launch_plan(flags=True)
         assert r.device_bytes() == f.device_bytes() + 84 * 128   # one 128-B record per triangle of the scene

@@ -5,8 +5,6 @@ the refusals.  The scenes are tests/color_scenes.py's: tests/smooth_scenes.py's 
 colours, whose floor has a per-corner checker and no normals, whose wall has neither; sample roots 2, 8 and 16.
 tests/test_color_path_spec.py shows that no decision of these scenes lies within 1e-9 of its threshold, so nothing is excluded."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,60 +12,27 @@ import pytest
 import aov_spec
 import color_path_spec
 import color_scenes
-import extension_checks
-import smooth_scenes
+import mesh_attr_checks as checks
 import test_gpu_ext_fuzz as fuzz
-from conftest import ROOT
+from mesh_attr_checks import (assert_same as _assert_same, configurations as _configurations, configure as _configure,
+                              everything as _everything, traversals as _traversals)
 
 pytestmark = pytest.mark.gpu
 
 ALBEDO_TOL = 1e-12   # the issue's: a few ulp per sample over at most 256 samples of values <= 1; a wrong corner moves a pixel mean by >= 1e-3
 NORMAL_TOL = 1e-12   # the smooth suite's
 TRIANGLES = 84       # 80 + 2 + 2: the table holds a record for every triangle of the scene
-
-
-def _traversals(flux):
-    return (flux._lib.TRAVERSE_BVH, flux._lib.TRAVERSE_BRUTE, flux._lib.TRAVERSE_BVH_BINARY)
-
-
-def _configurations(flux):
-    return list(itertools.product((flux.MATH_FAST, flux.MATH_STRICT), (flux.KERNEL_DEFAULT, flux.KERNEL_STATIC, flux.KERNEL_REFILL),
-                                  _traversals(flux)))
-
-
-def _configure(r, math, kernel, trav):
-    r.set_math(math)
-    r.set_kernel(kernel)
-    r.set_traversal(trav)
+TIGHT = ((aov_spec.ALBEDO, ALBEDO_TOL), (aov_spec.NORMAL, NORMAL_TOL))
 
 
 def _renderer(flux, sd, root, seed):
-    return flux.Renderer(sd, flux.JobConfiguration(root, color_scenes.DEPTH, 50), seed=seed)
-
-
-def _everything(r):
-    """the five quantities two contexts are compared in: frame, statistics, feature buffers, chain buffers, moments"""
-    r.enable_stats(True)
-    r.stats(reset=True)
-    frame = r.render_frame()
-    return frame, r.stats(), r.render_aov(), r.render_aov_chain(), r.render_moments()
-
-
-def _assert_same(got, want, label):
-    for k, (a, b) in enumerate(zip(got, want)):
-        assert a == b if isinstance(a, dict) else np.array_equal(a, b, equal_nan=True), (label, k)
+    return checks.renderer(flux, sd, root, seed, color_scenes.DEPTH)
 
 
 # ---- 1. the feature buffers -----------------------------------------------------------------------------------------------------
 
 def _assert_aov(got, want, label):
-    err = aov_spec.channel_errors(got, want)
-    print(f"colour aov {label}: max |gpu - spec| per channel = " + " ".join(f"{e:.2e}" for e in err))
-    assert got.shape == want.shape
-    assert np.all(err[aov_spec.ALBEDO] <= ALBEDO_TOL), (label, err)
-    assert np.all(err[aov_spec.NORMAL] <= NORMAL_TOL), (label, err)
-    assert np.all(err <= aov_spec.TOL), (label, err)
-    assert np.array_equal(got[..., aov_spec.COVERAGE], want[..., aov_spec.COVERAGE]), label
+    checks.assert_aov(got, want, f"colour aov {label}", TIGHT)
 
 
 @pytest.mark.parametrize("material,root", [("Matte", 2), ("Matte", 8), ("Matte", 16), ("Dielectric", 2), ("Reflective", 2), ("Emissive", 2)])
@@ -102,20 +67,7 @@ def test_frames_against_the_path_reference(flux, material, root):
 
 @pytest.mark.parametrize("material", color_scenes.MESH_MATERIALS)
 def test_debug_shade_against_the_path_reference(flux, material):
-    sd, seed, _ = color_scenes.reference(material, 2)
-    o, d, set_index, index, rad, t_ref, _ = color_scenes.debug_reference(material)
-    assert len(o) == smooth_scenes.DEBUG_RAYS
-    with _renderer(flux, sd, 2, seed) as r:
-        for math, trav in itertools.product((flux.MATH_FAST, flux.MATH_STRICT), _traversals(flux)):
-            r.set_math(math)
-            r.set_traversal(trav)
-            rgb, hit, t = r.debug_shade(o, d, 1, set_index, index)
-            assert np.array_equal(hit >= 0, np.isfinite(t_ref))
-            on = hit >= 0
-            assert np.max(np.abs(t[on] - t_ref[on]) / t_ref[on]) <= 1e-12
-            err = np.abs(rgb - rad)
-            print(f"colour debug_shade {material} math {math} traversal {trav}: max {err.max():.3e}, 99.9th percentile {np.percentile(err, 99.9):.3e}")
-            assert np.isfinite(rgb).all() and err.max() < fuzz.TOL and np.percentile(err, 99.9) < fuzz.TOL_TIGHT
+    checks.debug_shade(flux, color_scenes, "colour", material)
 
 
 # ---- 4. all-ones colours ----------------------------------------------------------------------------------------------------------
@@ -206,94 +158,35 @@ def test_wall_pixels_do_not_see_the_other_meshes_colours(flux):
 
 @pytest.mark.parametrize("root", [2, 8])
 def test_every_consumer_sees_the_colours(flux, root):
-    sd, seed, _ = color_scenes.reference("Matte", 2)
-    with _renderer(flux, sd, root, seed) as r:
-        r.set_kernel(flux.KERNEL_STATIC)   # channels 0..2 are the static kernel's frame bit for bit (tests/test_gpu_moments.py)
-        frame, mom = r.render_frame(), r.render_moments()
-        assert mom[..., :3].tobytes() == frame.tobytes()
-        r.set_kernel(flux.KERNEL_DEFAULT)
-        got, passes = r.render_adaptive(threshold=0.0, max_passes=1)
-        assert got.tobytes() == mom.tobytes() and np.all(passes == 1)
-        aov = r.render_aov()
-        assert np.array_equal(r.render_denoised(variance="measured"), flux.denoise_moments(mom, aov), equal_nan=True)
-        assert np.array_equal(r.render_denoised(), flux.denoise(r.render_frame(), aov), equal_nan=True)
-        assert np.array_equal(r.render_denoised(guides="chain"), flux.denoise(r.render_frame(), r.render_aov_chain()), equal_nan=True)
-    if root == 2:
-        with _renderer(flux, color_scenes.plain_twin(sd), root, seed) as f:
-            plain_aov = f.render_aov()
-        shape, _, _ = color_scenes.reference("Matte", 2)[2].first_hits()
-        floor = (shape == 4).all(axis=2)
-        assert floor.any()
-        delta = np.abs(aov[..., aov_spec.ALBEDO] - plain_aov[..., aov_spec.ALBEDO])[floor]
-        print(f"coloured against plain albedo buffer on the checker floor: max {delta.max():.3f}")
-        assert delta.max() > 0.2   # the guides really change
+    checks.every_consumer(flux, color_scenes, color_scenes.plain_twin, root, aov_spec.ALBEDO, 4, 0.2,
+                          "coloured against plain albedo buffer on the checker floor")
 
 
 # ---- 8. shares ------------------------------------------------------------------------------------------------------------------
 
 def test_shares_give_the_renderers_frame(flux):
-    sd, seed, _ = color_scenes.reference("Glossy", 2)
-    cfg = flux.JobConfiguration(8, color_scenes.DEPTH, 50)
-    with flux.Renderer(sd, cfg, seed=seed) as r:
-        frame = r.render_frame()
-        for world in (2, 3):
-            assert np.array_equal(extension_checks.set_sharded_frame(flux, r, world).numpy(), frame)
-        for step in (1, 4):
-            assert np.array_equal(extension_checks.row_tiles(r, step), frame)
-    for G, mode, got in extension_checks.loopback_frames(flux, sd, cfg, seed, (2, 3), (flux.SHARD_SETS, flux.SHARD_ROWS)):
-        assert np.array_equal(got, frame), (G, mode)
-    with flux.Renderer(color_scenes.plain_twin(sd), cfg, seed=seed) as f:
-        assert not np.array_equal(f.render_frame(), frame)
-    with pytest.raises(flux.FluxError):
-        flux.render_frame_multi(sd, cfg, seed=seed, num_devices=1)   # the one call refuses a coloured mesh
+    checks.shares(flux, color_scenes, color_scenes.plain_twin)   # (the one call refuses a coloured mesh)
 
 
 # ---- 9. the C ABI from plain C --------------------------------------------------------------------------------------------------
 
-def _fnv1a(data):
-    h = 1469598103934665603
-    for b in data:
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
 def test_c_client_sets_colours_and_is_refused_as_the_header_says(flux, tmp_path):
-    exe = str(tmp_path / "color_c_client")
-    subprocess.run(["gcc", "-std=c99", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "color_c_client.c"), "-o", exe, "-L" + os.path.join(ROOT, "flux_amd"), "-lflux_hip", "-lm",
-                    "-Wl,-rpath," + os.path.join(ROOT, "flux_amd"), "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    p = subprocess.run([exe, "8", "11"], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stderr + p.stdout
-    lines = dict(line.split(" ", 1) for line in p.stdout.splitlines())
-    assert lines["refusals"] == "ok"
-    sd = color_scenes.c_client_scene(flux)
-    with flux.Renderer(sd, flux.JobConfiguration(8, 4, 50), seed=11) as r:
-        colored = r.render_frame()
-    with flux.Renderer(color_scenes.plain_twin(sd), flux.JobConfiguration(8, 4, 50), seed=11) as r:
-        plain = r.render_frame()
-    assert lines["colored"] == f"{_fnv1a(colored.tobytes()):016x}"
-    assert lines["plain"] == lines["cleared"] == f"{_fnv1a(plain.tobytes()):016x}"
-    assert lines["colored"] != lines["plain"]
+    checks.c_client(flux, tmp_path, "color_c_client", color_scenes, color_scenes.plain_twin, "plain", "colored")
 
 
 # ---- 10. refusals ---------------------------------------------------------------------------------------------------------------
 
 def test_refusals_on_a_live_context_leave_it_unchanged(flux):
     sd, seed, _ = color_scenes.reference("Matte", 2)
-    lib, E = flux._lib.lib, flux._lib.E_INVALID
     with _renderer(flux, sd, 2, seed) as r:
         frame, aov, size = r.render_frame(), r.render_aov(), r.device_bytes()
         good = np.tile(np.array([0.5, 1.0, 0.25]), (80, 3, 1))
-        ptr = lambda a: a.ctypes.data_as(flux._lib.C.POINTER(flux._lib.C.c_double))  # noqa: E731
-        for mesh, arr, count, needle in ((3, good, 80, "mesh 3 out of range (3 meshes)"), (0, good, 79, "mesh 0 has 80 triangles, got colors for 79"),
-                                         (1, good, 80, "mesh 1 has 2 triangles"), (0, None, 80, "null pointer")):
-            assert lib.flux_ctx_set_mesh_colors(r._handle(), mesh, None if arr is None else ptr(arr), count) == E
-            assert needle in flux._lib.last_error(), flux._lib.last_error()
+        refusal = checks.common_refusals(flux, r, "colors", good)
         for value, where in ((-1e-9, (17, 2, 1)), (np.nan, (0, 0, 0)), (np.inf, (79, 1, 2)), (-np.inf, (40, 0, 1)), (3.5e38, (3, 2, 0))):
             bad = good.copy()
             bad[where] = value
-            assert lib.flux_ctx_set_mesh_colors(r._handle(), 0, ptr(bad), 80) == E
-            assert f"mesh 0, triangle {where[0]}, corner {where[1]}, channel {where[2]}" in flux._lib.last_error(), flux._lib.last_error()
+            message = refusal(0, bad, 80)
+            assert f"mesh 0, triangle {where[0]}, corner {where[1]}, channel {where[2]}" in message, message
         with pytest.raises(flux.SceneError):
             r.set_mesh_colors(0, np.zeros((42, 2)))
         with pytest.raises(flux.SceneError):

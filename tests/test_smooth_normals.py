@@ -1,13 +1,12 @@
 """Smooth meshes without a GPU: the numpy statement of the rule (tests/smooth_spec.py) against its own
 properties, the loader and the procedural meshes, the entry point's checks that need no device, and the host half of the call
-(flux_amd/csrc/flux_smooth.h) as a stand-alone program, plain and under the sanitizers."""
-import ctypes as C
+(flux_amd/csrc/flux_mesh_attr.h) as a stand-alone program, plain and under the sanitizers."""
 import os
 
 import numpy as np
 import pytest
 
-import selftest
+import mesh_attr_checks as checks
 import smooth_spec
 from conftest import SCENES
 
@@ -109,24 +108,7 @@ def test_barycentrics_equal_a_numpy_moller_trumbore_on_random_hits():
 
 # ---- the loader, the procedural meshes ------------------------------------------------------------------------------------------
 
-MESH_YAML = """
-scene_name: t
-camera_settings: {eye: [0, 1, -5], look_at: [0, 0, 0], up: [0, 1, 0]}
-camera_data: {zoom_factor: 1.0, view_plane_distance: 500.0, focal_distance: 5.0, lens_radius: 0.0}
-output_settings: {image_width: 4, image_height: 3, pixel_size: 50.0}
-background: [0, 0, 0]
-shapes:
-  - Mesh:
-      vertices: [[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]]
-      triangles: [[0, 1, 2], [0, 2, 3]]
-      NORMALS
-      material: {Matte: {diffuse_color: [1, 1, 1], ambient_color: [0, 0, 0], diffuse_coefficient: 1.0}}
-"""
-
-
-def _load(flux, normals_line):
-    import yaml
-    return flux.scene.scene_from_dict(yaml.safe_load(MESH_YAML.replace("NORMALS", normals_line)))
+_load = checks.load
 
 
 def test_normals_round_trip_into_the_calls_layout(flux):
@@ -160,22 +142,11 @@ def test_normals_round_trip_into_the_calls_layout(flux):
     ("normals: [[0, 0, 1], [0, 0, 1], [0, 0, 1], [0, .nan, 1]]", "triangle 1, corner 2"),
 ])
 def test_loader_refusals(flux, line, message):
-    with pytest.raises(flux.SceneError) as e:
-        _load(flux, line)
-    assert message in str(e.value), str(e.value)
+    checks.loader_refusal(flux, line, message)
 
 
 def test_meshdata_refusals(flux):
-    import dataclasses
-    from flux_amd.scene import corner_normals
-    mesh = _load(flux, "").shapes[0]
-    for bad, message in ((np.zeros((5, 3)), "expected [4][3] (per vertex) or [2][3][3] (per corner), got shape (5, 3)"),
-                         (np.ones((3, 3, 3)), "got shape (3, 3, 3)"),
-                         ([["a", 0, 1]] * 4, "expected numbers"),
-                         (np.full((4, 3), 1e200), "triangle 0, corner 0")):   # a length that overflows
-        with pytest.raises(flux.SceneError) as e:
-            corner_normals(dataclasses.replace(mesh, normals=bad), "mesh 0")
-        assert message in str(e.value), str(e.value)
+    checks.meshdata_refusals(flux, "normals", np.full((4, 3), 1e200), "triangle 0, corner 0")   # a length that overflows
 
 
 def test_procedural_meshes(flux):
@@ -223,11 +194,7 @@ def test_demo_scene_loads(flux):
 # ---- the entry point without a device, the host half stand-alone ------------------------------------------------------------------
 
 def test_null_context_is_refused_without_a_device(flux):
-    lib = flux._lib.lib
-    n = (C.c_double * 9)(0, 0, 1, 0, 0, 1, 0, 0, 1)
-    assert lib.flux_ctx_set_mesh_normals(None, 0, n, 1) == flux._lib.E_INVALID
-    assert "null context" in flux._lib.last_error()
-    assert lib.flux_ctx_set_mesh_normals(None, 0, None, 0) == flux._lib.E_INVALID
+    checks.null_context_refused(flux, "normals")
 
 
 def _check_selftest_output(out):
@@ -239,10 +206,8 @@ def _check_selftest_output(out):
 
 
 def test_host_half_equals_the_spec(tmp_path):
-    exe = selftest.build(str(tmp_path / "smooth_host_selftest"), "smooth_host_selftest.cpp")
-    _check_selftest_output(selftest.run(exe))
+    checks.host_selftest(tmp_path, "smooth_host_selftest", _check_selftest_output, sanitized=False)
 
 
 def test_host_half_under_asan_and_ubsan(tmp_path):
-    exe = selftest.build(str(tmp_path / "smooth_host_selftest_san"), "smooth_host_selftest.cpp", flags=selftest.SANITIZE)
-    _check_selftest_output(selftest.run(exe, env=selftest.sanitize_env()))
+    checks.host_selftest(tmp_path, "smooth_host_selftest", _check_selftest_output, sanitized=True)

@@ -1,7 +1,6 @@
 """Vertex colours without a GPU: the numpy statement of the rule (tests/color_spec.py) against its own properties,
 the loader and the procedural meshes, the entry point's checks that need no device, and the host half of the call
-(flux_amd/csrc/flux_color.h) as a stand-alone program, plain and under the sanitizers."""
-import ctypes as C
+(flux_amd/csrc/flux_mesh_attr.h) as a stand-alone program, plain and under the sanitizers."""
 import dataclasses
 import os
 
@@ -9,7 +8,7 @@ import numpy as np
 import pytest
 
 import color_spec
-import selftest
+import mesh_attr_checks as checks
 from conftest import SCENES
 
 FLT_MAX = color_spec.FLT_MAX
@@ -98,24 +97,7 @@ def test_checks_and_rounding():
 
 # ---- the loader, the procedural meshes ------------------------------------------------------------------------------------------
 
-MESH_YAML = """
-scene_name: t
-camera_settings: {eye: [0, 1, -5], look_at: [0, 0, 0], up: [0, 1, 0]}
-camera_data: {zoom_factor: 1.0, view_plane_distance: 500.0, focal_distance: 5.0, lens_radius: 0.0}
-output_settings: {image_width: 4, image_height: 3, pixel_size: 50.0}
-background: [0, 0, 0]
-shapes:
-  - Mesh:
-      vertices: [[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]]
-      triangles: [[0, 1, 2], [0, 2, 3]]
-      COLORS
-      material: {Matte: {diffuse_color: [1, 1, 1], ambient_color: [0, 0, 0], diffuse_coefficient: 1.0}}
-"""
-
-
-def _load(flux, colors_line):
-    import yaml
-    return flux.scene.scene_from_dict(yaml.safe_load(MESH_YAML.replace("COLORS", colors_line)))
+_load = checks.load
 
 
 def test_colours_round_trip_into_the_calls_layout(flux):
@@ -154,21 +136,12 @@ def test_colours_round_trip_into_the_calls_layout(flux):
     ("colors: [[0, 0, 1], [0, 0, 1], [1.0e+39, 0, 1], [0, 1, 1]]", "triangle 0, corner 2, channel 0"),
 ])
 def test_loader_refusals(flux, line, message):
-    with pytest.raises(flux.SceneError) as e:
-        _load(flux, line)
-    assert message in str(e.value), str(e.value)
+    checks.loader_refusal(flux, line, message)
 
 
 def test_meshdata_refusals(flux):
     from flux_amd.scene import corner_colors
-    mesh = _load(flux, "").shapes[0]
-    for bad, message in ((np.zeros((5, 3)), "expected [4][3] (per vertex) or [2][3][3] (per corner), got shape (5, 3)"),
-                         (np.ones((3, 3, 3)), "got shape (3, 3, 3)"),
-                         ([["a", 0, 1]] * 4, "expected numbers"),
-                         (np.full((4, 3), -1e-300), "mesh 0.colors: triangle 0, corner 0, channel 0")):
-        with pytest.raises(flux.SceneError) as e:
-            corner_colors(dataclasses.replace(mesh, colors=bad), "mesh 0")
-        assert message in str(e.value), str(e.value)
+    mesh = checks.meshdata_refusals(flux, "colors", np.full((4, 3), -1e-300), "mesh 0.colors: triangle 0, corner 0, channel 0")
     # the loader's verdict is the spec's, offender for offender
     rng = np.random.default_rng(5)
     for _ in range(20):
@@ -221,11 +194,7 @@ def test_render_frame_multi_refuses_a_coloured_mesh(flux):
 # ---- the entry point without a device, the host half stand-alone ------------------------------------------------------------------
 
 def test_null_context_is_refused_without_a_device(flux):
-    lib = flux._lib.lib
-    n = (C.c_double * 9)(0, 0, 1, 0, 0, 1, 0, 0, 1)
-    assert lib.flux_ctx_set_mesh_colors(None, 0, n, 1) == flux._lib.E_INVALID
-    assert "null context" in flux._lib.last_error()
-    assert lib.flux_ctx_set_mesh_colors(None, 0, None, 0) == flux._lib.E_INVALID
+    checks.null_context_refused(flux, "colors")
 
 
 def _check_selftest_output(out):
@@ -238,10 +207,8 @@ def _check_selftest_output(out):
 
 
 def test_host_half_equals_the_spec(tmp_path):
-    exe = selftest.build(str(tmp_path / "color_host_selftest"), "color_host_selftest.cpp")
-    _check_selftest_output(selftest.run(exe))
+    checks.host_selftest(tmp_path, "color_host_selftest", _check_selftest_output, sanitized=False)
 
 
 def test_host_half_under_asan_and_ubsan(tmp_path):
-    exe = selftest.build(str(tmp_path / "color_host_selftest_san"), "color_host_selftest.cpp", flags=selftest.SANITIZE)
-    _check_selftest_output(selftest.run(exe, env=selftest.sanitize_env()))
+    checks.host_selftest(tmp_path, "color_host_selftest", _check_selftest_output, sanitized=True)
